@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- encode Msamples/s of the SLA LPC+residual hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5] [--seconds S]
+    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5] [--seconds S] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (sla_hip_analyze_device: prepass -> partition search -> block LPC +
 quantiser -> PARCOR lattice -> long-term + LMS + Rice parameter) over one batch of synthetic PCM that is already
 resident in HBM when the timed region starts.
 
 N = 1: the largest single-GPU configuration of BASELINE.json, C3 (48 kHz 24-bit stereo, 60 min, order 32) unless --config
-says otherwise; the same JSON line carries `summary` ({config: [Msamples/s, ms per step, roofline.frac, 1-core CPU
+says otherwise.  A plain run sets up, warms up, times the K steps, verifies the last one (below) and prints the line.
+With --full the same JSON line also carries `summary` ({config: [Msamples/s, ms per step, roofline.frac, 1-core CPU
 Msamples/s]} for all four, among the first keys and again at the end of the line) and `other_configs` -- C2 and C5 at
-their FULL length and the C4 clip batch -- each with its own roofline, verification and CPU baseline.
+their FULL length and the C4 clip batch -- each with its own roofline, verification and CPU baseline, and for every
+configuration the end-to-end and decode legs, the audit of the block certificate and the steps with nothing kept.
+
+--dump-outputs DIR writes what the last timed step handed its caller -- residual planes, block table, per-block
+parameters -- as float64 .npy files (fixed, seeded samples of the big arrays, 64 MB at most): the input is seeded, so two
+builds can be compared output for output.
 
 N > 1, one rank per GPU -- launched by torch.distributed.run, or by this script itself: `python bench.py --gpus N`
 without WORLD_SIZE in the environment starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a
@@ -107,6 +113,36 @@ def synth_device(torch, nch, n_total, bits, rate, lo, hi, seed=12345):
             out[ch, c0:c0 + m] = (q << (32 - bits)).to(torch.int32)
             del a, pw, geo, s, noise, t, x, q
     return out
+
+
+DUMP_RESIDUALS = 1 << 20         # residual values per plane (sampled positions x channels) that --dump-outputs writes
+DUMP_BLOCKS = 2048               # blocks whose parameters it writes (the block table itself is written whole)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(torch, enc, d_lat, d_fin, nch, n_valid, column, out_dir, seed=2024):
+    """--dump-outputs: the residual planes of the last analysis (device) at a fixed, seeded sample of the n_valid analysed
+    sample positions (column() maps a position to its plane column), the whole block table and the per-block parameters
+    of a fixed, seeded sample of blocks (sla_hip_get_trace), each as DIR/<name>.npy in float64 (exact for every int32)"""
+    rng = np.random.default_rng(seed)
+    pos = np.unique(rng.integers(0, n_valid, size=min(n_valid, DUMP_RESIDUALS // nch)))
+    cols = torch.from_numpy(column(pos)).cuda()
+    arrays = {"residual_positions": pos,
+              "residual_final": d_fin.index_select(1, cols).cpu().numpy(),
+              "residual_lattice": d_lat.index_select(1, cols).cpu().numpy()}
+    tr = enc.trace(want_residuals=False)
+    nb = tr.num_blocks
+    blocks = np.sort(rng.choice(nb, size=min(nb, DUMP_BLOCKS), replace=False))
+    arrays.update({"block_start": tr.blk_start[:nb], "block_nsmpl": tr.blk_nsmpl[:nb], "block_type": tr.blk_type[:nb],
+                   "offset_lshift": np.array([tr.offset_lshift]), "sampled_blocks": blocks})
+    for name in ("parcor", "code", "kint", "parcor_exact", "rshift", "pitch", "ltm_coef", "rice_init"):
+        arrays["block_" + name] = getattr(tr, name)[blocks]
+    total = sum(a.size * 8 for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def upload_bytes_per_sample(bits):
@@ -412,6 +448,13 @@ def run_config(torch, sla_amd, S, cfg, args, rank, world, primary, cpu_results=N
     if rank != 0:
         enc.close()
         return out
+    if primary and args.dump_outputs:
+        b = (state["step"] - 1) % nbuf
+        if batch is not None:
+            n_valid, column = n_own, (lambda pos: pos // clip_n * pitch + pos % clip_n)
+        else:
+            n_valid, column = n_last, (lambda pos: pos)
+        dump_outputs(torch, enc, d_lat[b], d_fin[b], nch, n_valid, column, args.dump_outputs)
 
     # ---- roofline of the dominant kernel (HIP-event durations measured inside the library, on the stream the
     #      kernels run on) ----------------------------------------------------------------------------------
@@ -630,7 +673,7 @@ def run_config(torch, sla_amd, S, cfg, args, rank, world, primary, cpu_results=N
     #      on the guess that the file looks like the last one.  `value` is that warm, same-shape steady state (the contract's
     #      K steps after W warm-ups); beside it: the same steps with nothing kept (every step builds and uploads its tables and
     #      waits for its prepass, as files of varying length do) and the first call on the fresh handle (`cold_call_ms`)
-    if world == 1 and not dist_on and cert_on:
+    if args.full and world == 1 and not dist_on and cert_on:
         # the standing audit of the block certificate: the same analysis once more with every 16th certified
         # (block, channel) pair re-analysed by the exact reference-order kernels, which compare codes, lattice coefficients and
         # the RAW side with what the certified run stored; a difference fails the call (and this bench)
@@ -642,7 +685,7 @@ def run_config(torch, sla_amd, S, cfg, args, rank, world, primary, cpu_results=N
         out["block_certificate"]["audit"] = {"every": 16, "pairs_audited_equal": int(aud[0]), "pairs_different": int(aud[1])}
         if aud[1] != 0:
             raise SystemExit(3)
-    if world == 1 and not dist_on:
+    if args.full and world == 1 and not dist_on:
         ex = enc.last_expand()
         out["per_handle_shortcuts"] = {"analyses_served_from_kept_search_tables": int(ex[2]), "searches_launched_on_a_wrong_guess": int(ex[3]),
                                        "chunks_from_device_tables": int(ex[0]), "chunks": int(ex[1])}
@@ -658,7 +701,7 @@ def run_config(torch, sla_amd, S, cfg, args, rank, world, primary, cpu_results=N
         enc.set_option("table_cache", 1)
 
     # ---- end-to-end .sla encode from host PCM (PCIe + bit-pack included); never `value` -------------------------
-    if not args.no_e2e and world == 1 and batch is not None:
+    if args.full and not args.no_e2e and world == 1 and batch is not None:
         enc2 = sla_amd.Encoder(*cap)
         enc2.set_wave_format(nch, bits, rate)
         enc2.set_encode_parameter(order, ltm, lms, ms, win, maxb)
@@ -703,7 +746,7 @@ def run_config(torch, sla_amd, S, cfg, args, rank, world, primary, cpu_results=N
         out["end_to_end"]["one_clip_per_call_msamples_s"] = round(one.shape[0] * one.shape[1] / per_clip / 1e6, 3)
         out["end_to_end"]["one_clip_per_call_ms"] = round(per_clip * 1e3, 3)
         enc2.close()
-    if not args.no_e2e and world == 1 and batch is None:
+    if args.full and not args.no_e2e and world == 1 and batch is None:
         if host_pcm is None:
             host_pcm = np.ascontiguousarray(d_pcm[:, :n_file].cpu().numpy())
         enc2 = sla_amd.Encoder(*cap)
@@ -825,7 +868,14 @@ def main():
                          "exchange, bounds, shard analyse, all-gather of the residual planes), so that the RCCL calls execute on a one-GPU box")
     ap.add_argument("--launch-check", action="store_true",
                     help="only bring the ranks up (process group of --backend, no GPU work) and print the line's launch fields")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, seeded samples, 64 MB at most)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, the other configurations, the end-to-end and decode legs, the audit of the "
+                         "block certificate and the steps with nothing kept (the --no-* options trim this)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as the driver may run it: this process has not touched the GPU (no torch import yet)
@@ -853,10 +903,10 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
-    want_others = (world == 1 and not args.no_other_configs and args.seconds is None)
+    want_others = (args.full and world == 1 and not args.no_other_configs and args.seconds is None)
     # ---- CPU legs first, while this process has not touched the GPU (they start worker processes) ---------------
     cpu_results = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_results = {args.config: cpu_baseline(S, args.config, args.cpu_seconds, args.cpu_seconds / 3)}
         if want_others:
             for cfg in sorted(CONFIGS):

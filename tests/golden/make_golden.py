@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 import slalibs as S          # noqa: E402
 import waveforms as W        # noqa: E402
 
-A_WAV = "/root/reference/test/a.wav"
+A_WAV = os.path.join(HERE, "a.wav")          # the reference's test/a.wav, stored verbatim
 
 CASES = {
     # name: (input recipe, params kwargs)

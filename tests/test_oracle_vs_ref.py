@@ -6,13 +6,18 @@ Mirrors the reference's own suites: test_SLAPredictor.c (autocorrelation :1010-1
 :75-209, predict/synth identity :437-552, Dijkstra known answers :807-990), test_SLACoder.c
 (put/get identity :25-278), test_SLAUtility.c (CRC16 known answers :41-72) and
 test_SLAEncodeDecode.c (round-trip matrix :558-1172)."""
+import os
+
 import numpy as np
 import pytest
 
 import slalibs as S
 import waveforms as W
 
-A_WAV = "/root/reference/test/a.wav"
+# the reference's own test fixtures (test/a.wav, test/PriChanIcon.png), stored verbatim
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+A_WAV = os.path.join(GOLD, "a.wav")
+PNG = os.path.join(GOLD, "PriChanIcon.png")
 
 
 def bits_equal(a, b):
@@ -126,7 +131,7 @@ def test_crc16_known_answers(oracle, ref):
     assert oracle.crc16(b"") == 0
     data = open(A_WAV, "rb").read()
     assert oracle.crc16(data) == 0xA611 == ref.crc16(data)
-    png = open("/root/reference/test/PriChanIcon.png", "rb").read()
+    png = open(PNG, "rb").read()
     assert oracle.crc16(png) == 0xEA63
 
 
@@ -233,7 +238,7 @@ def test_rice_coder(oracle, ref, name, nch, bits):
 
 def test_rice_coder_byte_stream(oracle, ref):
     """reference test_SLACoder.c:25-278 codes the bytes of PriChanIcon.png"""
-    png = np.frombuffer(open("/root/reference/test/PriChanIcon.png", "rb").read(), np.uint8)
+    png = np.frombuffer(open(PNG, "rb").read(), np.uint8)
     res = (png.astype(np.int32) - 128)[None, :65536]
     a, b = oracle.code_residual(res, 16), ref.code_residual(res, 16)
     assert a == b
