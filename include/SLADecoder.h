@@ -147,7 +147,8 @@ SLAStreamingDecoder_Decode(struct SLAStreamingDecoder* decoder,
                            uint32_t*                   num_output_samples);
 
 /* Wall time [ms] of the last DecodeWhole, 6 floats: upload, block walk, kernels (device, stream events),
- * download, total, number of kernel batches (1 unless a block's size field disagreed with its contents). */
+ * download, total, number of kernel batches (1 unless a block's size field disagreed with its contents).
+ * After sla_hip_decode_batch (include/sla_hip.h): the same split for the batch, [5] = the number of passes. */
 int sla_hip_decoder_last_timing(const struct SLADecoder* decoder, float* timing_ms);
 
 /* The same decode on an image that already lives in device memory, planes left on the device:

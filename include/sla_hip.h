@@ -466,6 +466,17 @@ int sla_hip_launch_dec_bits(const uint32_t* d_image, uint64_t image_bytes,
                             uint32_t want_crc, int32_t* d_planes, uint64_t plane_stride,
                             sla_hip_dec_info* d_info, sla_hip_dec_chan* d_chan, int32_t* d_kint,
                             sla_hip_stream_t stream);
+/* dec_bits over blocks of several files concatenated in one image: d_block_end[b] (device, one per block) is the byte
+ * end of block b's file in the image, and the block's reader treats it as the end of the stream -- zeros past it, the
+ * same give-up limit -- so that it decodes exactly as its file would on its own.  NULL: every block is bounded by
+ * image_bytes (sla_hip_launch_dec_bits). */
+int sla_hip_launch_dec_bits_x(const uint32_t* d_image, uint64_t image_bytes,
+                              const sla_hip_dec_block* d_blocks, uint32_t num_blocks,
+                              uint32_t num_channels, uint32_t bits_per_sample, uint32_t offset_lshift,
+                              uint32_t mid_side, uint32_t parcor_order, uint32_t longterm_order,
+                              uint32_t want_crc, int32_t* d_planes, uint64_t plane_stride,
+                              sla_hip_dec_info* d_info, sla_hip_dec_chan* d_chan, int32_t* d_kint,
+                              sla_hip_stream_t stream, const uint64_t* d_block_end);
 int sla_hip_launch_dec_lms(int32_t* d_planes, uint64_t plane_stride, const sla_hip_dec_block* d_blocks,
                            const sla_hip_dec_info* d_info, uint32_t num_blocks, uint32_t num_channels,
                            uint32_t lms_order, sla_hip_stream_t stream);
@@ -481,6 +492,42 @@ int sla_hip_launch_dec_deemphasis(int32_t* d_data, uint32_t num_samples, int32_t
                                   sla_hip_stream_t stream);
 int sla_hip_launch_dec_finish(int32_t* d_planes, uint64_t plane_stride, uint32_t num_channels,
                               uint32_t num_samples, uint32_t mid_side, uint32_t shift, sla_hip_stream_t stream);
+/* dec_finish for the files of a batch pass, out of place: file f's region of the planes starts at plane_off, and its
+ * num_samples finished samples per channel go to d_out[out_off + ch * num_samples + i] (packed [file][ch][n]).
+ * max_samples: the largest num_samples of the table (sizes the grid). */
+typedef struct sla_hip_dec_file {
+  uint64_t plane_off;       /* first sample of the file's region in every plane */
+  uint64_t out_off;         /* first element of the file's [C][num_samples] block in d_out */
+  uint32_t num_samples;     /* samples per channel to finish */
+  uint32_t mid_side;        /* 1: planes 0 / 1 are mid / side (two channels only) */
+  uint32_t shift;           /* left shift of the left-justification: 32 - bits_per_sample + offset_lshift */
+  uint32_t reserved;
+} sla_hip_dec_file;
+int sla_hip_launch_dec_finish_batch(const int32_t* d_planes, uint64_t plane_stride, uint32_t num_channels,
+                                    const sla_hip_dec_file* d_files, uint32_t num_files, uint32_t max_samples,
+                                    int32_t* d_out, sla_hip_stream_t stream);
+
+/* Many .sla files decoded in one call, the decode-side counterpart of sla_hip_encode_batch.  Every item gets exactly
+ * what SLADecoder_DecodeWhole of that file alone on this handle would give: result, output_num_samples and the samples
+ * (those before a failing block included).  Files are grouped by the header fields the kernels are launched with
+ * (channels, bits, mid/side, PARCOR / long-term / LMS order, offset_lshift); a group goes through the kernels in passes
+ * of at most SLA_HIP_DEC_BATCH_PASS sample-channels (a single larger file is a pass of its own), each pass with one
+ * upload of the images, one of the block table, one launch per kernel and one download of the samples.  A file whose
+ * block body does not end where its size field says (the reference then resyncs where its reader stopped) is decoded
+ * again on its own.  Afterwards the handle's wave format and encode parameter are those DecodeWhole of the items, in
+ * order, would have left; sla_hip_decoder_last_timing holds the batch's split, [5] = the number of passes.
+ * Returns 0 when the batch ran, SLA_APIRESULT_INVALID_ARGUMENT for a NULL decoder or NULL items with num_items > 0. */
+#define SLA_HIP_DEC_BATCH_PASS (1u << 28)
+struct SLADecoder;
+typedef struct sla_hip_decode_item {
+  const uint8_t* data;            /* in : a whole .sla stream (header + blocks) */
+  uint32_t data_size;             /* in  */
+  uint32_t buffer_num_samples;    /* in : capacity of every buffer[ch] */
+  int32_t** buffer;               /* in : one plane per channel of this file, receives left-justified PCM */
+  uint32_t output_num_samples;    /* out */
+  int32_t  result;                /* out: SLAApiResult */
+} sla_hip_decode_item;            /* 32 bytes */
+int sla_hip_decode_batch(struct SLADecoder* decoder, sla_hip_decode_item* items, uint32_t num_items);
 
 /* ---- (2) whole-file driver ---------------------------------------------- */
 

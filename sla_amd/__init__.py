@@ -85,6 +85,12 @@ class BatchItem(C.Structure):
                 ("data", u8p), ("output_size", C.c_uint32), ("result", C.c_int32)]
 
 
+class DecodeItem(C.Structure):
+    """sla_hip_decode_item (include/sla_hip.h): one file of sla_hip_decode_batch"""
+    _fields_ = [("data", u8p), ("data_size", C.c_uint32), ("buffer_num_samples", C.c_uint32),
+                ("buffer", C.POINTER(i32p)), ("output_num_samples", C.c_uint32), ("result", C.c_int32)]
+
+
 class SlaError(RuntimeError):
     def __init__(self, code, where):
         name = API_RESULT[code] if 0 <= code < len(API_RESULT) else ("hipError %d" % (-code))
@@ -168,6 +174,12 @@ def lib():
         L.SLAStreamingDecoder_CollectDataFragment.argtypes = [C.c_void_p, C.POINTER(u8p), u32p]
         L.SLAStreamingDecoder_Decode.argtypes = [C.c_void_p, C.POINTER(i32p), C.c_uint32, u32p]
         L.sla_hip_decode_device.argtypes = [C.c_void_p, u8p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, u32p]
+        L.sla_hip_decode_batch.argtypes = [C.c_void_p, C.POINTER(DecodeItem), C.c_uint32]
+        L.sla_hip_launch_dec_bits_x.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sla_hip_launch_dec_finish_batch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                      C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -210,6 +222,8 @@ EXPORTED_SYMBOLS = [
     # decode side of include/SLAPredictor.h
     "SLALPCSynthesizer_SynthesizeByParcorCoefInt32", "SLALongTermSynthesizer_SynthesizeInt32", "SLALMSFilter_SynthesizeInt32",
     "SLAEmphasisFilter_DeEmphasisInt32", "sla_hip_launch_dec_deemphasis",
+    # batch decode (include/sla_hip.h)
+    "sla_hip_decode_batch", "sla_hip_launch_dec_bits_x", "sla_hip_launch_dec_finish_batch",
 ]
 
 
@@ -534,6 +548,36 @@ class Decoder:
         rc = self._lib.SLADecoder_DecodeWhole(self._h, buf.ctypes.data_as(u8p), len(buf), ptrs, capacity, C.byref(n))
         return rc, out[:, :n.value]
 
+    def decode_batch(self, datas, capacities=None, outs=None):
+        """many .sla files in one call (sla_hip_decode_batch) -> list of (result code, planar left-justified int32
+        [C][n]), each exactly what decode_whole of that file alone returns.  The channel count comes from each header,
+        the default capacity is its num_samples.  `outs`: optional preallocated int32 arrays [>= C][>= capacity], one
+        per file (views of them are returned)"""
+        items = (DecodeItem * len(datas))()
+        keep = []
+        for i, data in enumerate(datas):
+            buf = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
+            nch = int(buf[14]) if len(buf) > 14 else 1
+            if capacities is not None:
+                cap = int(capacities[i])
+            else:
+                cap = int.from_bytes(bytes(buf[15:19]), "big") if len(buf) >= 19 else 0
+            out = outs[i] if outs is not None else np.empty((max(nch, 1), max(cap, 1)), np.int32)
+            if out.shape[0] < nch or out.shape[1] < cap or out.dtype != np.int32 or not out[0].flags.c_contiguous:
+                raise ValueError("output %d: need int32 rows of at least [%d][%d]" % (i, nch, cap))
+            ptrs = (i32p * out.shape[0])(*[out[c].ctypes.data_as(i32p) for c in range(out.shape[0])])
+            keep.append((buf, out, ptrs))
+            items[i].data = buf.ctypes.data_as(u8p)
+            items[i].data_size = len(buf)
+            items[i].buffer_num_samples = cap
+            items[i].buffer = ptrs
+        self._check(self._lib.sla_hip_decode_batch(self._h, items, len(datas)), "sla_hip_decode_batch")
+        return [(int(items[i].result), keep[i][1][:, :items[i].output_num_samples]) for i in range(len(datas))]
+
+    def _check(self, rc, where):
+        if rc != 0:
+            raise SlaError(rc, where)
+
     def decode_device(self, data, image_ptr, planes_ptr, plane_stride):
         """decode an image that already lives in device memory into device planes; returns (rc, samples)"""
         buf = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data
@@ -543,7 +587,8 @@ class Decoder:
         return rc, n.value
 
     def last_timing(self):
-        """[ms] upload, block walk, kernels (stream events), download, total; number of kernel batches"""
+        """[ms] upload, block walk, kernels (stream events), download, total; number of kernel batches
+        (after decode_batch: of passes)"""
         t = (C.c_float * 6)()
         self._lib.sla_hip_decoder_last_timing(self._h, t)
         return list(t)

@@ -16,6 +16,7 @@
 //   k_dec_lattice        src/SLAPredictor.c:610-740 (SLALPCSynthesizer_SynthesizeByParcorCoefInt32),
 //                        :1768-1791 (SLAEmphasisFilter_DeEmphasisInt32)
 //   k_dec_finish         src/SLAUtility.c:415-433 (mid/side -> left/right), src/SLADecoder.c:540-547 (left-justify)
+//   k_dec_finish_batch   the same for every file of a batch pass, packed [file][ch][n] for one copy home
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -119,16 +120,24 @@ struct bit_reader {
 };
 
 // the wave moves every owner lane's window to its read position and loads the words from there on
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, uint32_t src)
+{
+  return ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src) << 32) | (uint32_t)__shfl((int)(uint32_t)v, (int)src);
+}
+// BOUNDED: every lane's reader has an end of its own (blocks of several files in one image), so the words of an
+// owner's window are bounded by that owner's end, not by the loading lane's
+template <bool BOUNDED = false>
 __device__ __forceinline__ void fill_windows(bit_reader& rd, uint32_t* s_win, uint32_t row_words, uint32_t win_words,
                                              uint32_t owners, uint32_t lane)
 {
   __syncthreads();
   rd.base += rd.rp >> 5; rd.rp &= 31;
   for (uint32_t o = 0; o < owners; o++) {
-    const uint64_t base = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(rd.base >> 32), (int)o) << 32) | (uint32_t)__shfl((int)(uint32_t)rd.base, (int)o);
+    const uint64_t base = shfl_u64(rd.base, o);
+    const uint64_t words = BOUNDED ? shfl_u64(rd.words, o) : rd.words;
     for (uint32_t k = lane; k < win_words; k += 64) {
       const uint64_t i = base + k;
-      s_win[o * row_words + k] = (i < rd.words) ? __builtin_bswap32(rd.img[i]) : 0u;
+      s_win[o * row_words + k] = (i < words) ? __builtin_bswap32(rd.img[i]) : 0u;
     }
   }
   rd.win_words = (lane < owners) ? win_words : 0u;
@@ -171,6 +180,7 @@ void k_dec_crc(const uint8_t* __restrict__ bytes, const sla_hip_dec_block* __res
 // ---------------------------------------------------------------------------------------------
 struct dec_bits_args {
   const uint32_t* image; uint64_t image_bytes;
+  const uint64_t* block_end;   // BOUNDED: byte end of each block's file in the image (its reader's end of stream)
   const sla_hip_dec_block* blocks; uint32_t num_blocks;
   uint32_t bps, lshift, mid_side, order, ntaps, lanes;
   int32_t* planes; uint64_t stride;
@@ -181,7 +191,7 @@ struct dec_bits_args {
 #define DEC_ROW  (DEC_TILE + 1)
 #define DEC_WIN  128         // words of stream per channel a lane finds in LDS per tile (64 bits per sample)
 
-template <int C>
+template <int C, bool BOUNDED>
 __global__ __launch_bounds__(64)
 void k_dec_bits(const dec_bits_args a)
 {
@@ -199,9 +209,12 @@ void k_dec_bits(const dec_bits_args a)
   sla_hip_dec_block b;
   b.byte_off = 0; b.byte_len = 0; b.smp_off = 0; b.num_samples = 0; b.flags = 0;
   if (mine) { b = a.blocks[j]; }
+  // the end of this block's stream: bytes past it read as zero and the give-up limit counts from it, exactly as
+  // for the file decoded on its own
+  const uint64_t end = (BOUNDED && mine) ? a.block_end[j] : a.image_bytes;
   bit_reader rd;
-  rd.open(a.image, a.image_bytes, b.byte_off, s_win + (mine ? lane : 0u) * WROW);
-  fill_windows(rd, s_win, WROW, WIN, a.lanes, lane);       // helper lanes have no row of their own: they only carry words
+  rd.open(a.image, end, b.byte_off, s_win + (mine ? lane : 0u) * WROW);
+  fill_windows<BOUNDED>(rd, s_win, WROW, WIN, a.lanes, lane);       // helper lanes have no row of their own: they only carry words
   (void)rd.get(16);                                        // sync code          src/SLADecoder.c:330-334
   (void)rd.get(32);                                        // size field         (the host walked these)
   (void)rd.get(16);                                        // CRC16
@@ -257,7 +270,7 @@ void k_dec_bits(const dec_bits_args a)
 
   for (uint32_t s0 = 0; s0 < nmax; s0 += DEC_TILE) {
     const uint32_t cnt = (s0 < n) ? ((n - s0 < DEC_TILE) ? (n - s0) : (uint32_t)DEC_TILE) : 0u;
-    fill_windows(rd, s_win, WROW, WIN, a.lanes, lane);
+    fill_windows<BOUNDED>(rd, s_win, WROW, WIN, a.lanes, lane);
     if (type == 1) {
       for (uint32_t u = 0; u < cnt; u++) {
 #pragma unroll
@@ -333,7 +346,7 @@ void k_dec_bits(const dec_bits_args a)
     sla_hip_dec_info* io = a.info + j;
     io->type = type;
     io->used_bytes = (uint32_t)((rd.pos() >> 3) - b.byte_off);
-    io->overrun = (rd.dead || (rd.pos() >> 3) > a.image_bytes) ? 1u : 0u;
+    io->overrun = (rd.dead || (rd.pos() >> 3) > end) ? 1u : 0u;
   }
 }
 
@@ -614,6 +627,33 @@ void k_dec_finish(int32_t* __restrict__ planes, uint64_t stride, uint32_t num_ch
   }
 }
 
+// k_dec_finish_batch: k_dec_finish for every file of a batch pass, out of place: the finished samples of file f go
+// to out[files[f].out_off + c * n + i] (packed [file][ch][n], so that the pass comes home in one copy).  blockIdx.y
+// walks the files, the x dimension their samples: loads and stores of consecutive lanes are consecutive words.
+__global__ __launch_bounds__(256)
+void k_dec_finish_batch(const int32_t* __restrict__ planes, uint64_t stride, uint32_t num_channels,
+                        const sla_hip_dec_file* __restrict__ files, uint32_t num_files, int32_t* __restrict__ out)
+{
+  for (uint32_t f = blockIdx.y; f < num_files; f += gridDim.y) {
+    const sla_hip_dec_file fi = files[f];
+    const int32_t* src = planes + fi.plane_off;
+    int32_t* dst = out + fi.out_off;
+    const uint32_t n = fi.num_samples, shift = fi.shift;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+      uint32_t c = 0;
+      if (fi.mid_side && num_channels == 2) {
+        const int32_t side = src[stride + i];
+        const int32_t mid = (int32_t)(((uint32_t)src[i] << 1) | ((uint32_t)side & 1u));
+        const int32_t l = (int32_t)((uint32_t)mid + (uint32_t)side) >> 1, r = (int32_t)((uint32_t)mid - (uint32_t)side) >> 1;
+        dst[i] = (int32_t)((uint32_t)l << shift);
+        dst[(uint64_t)n + i] = (int32_t)((uint32_t)r << shift);
+        c = 2;
+      }
+      for (; c < num_channels; c++) { dst[(uint64_t)c * n + i] = (int32_t)((uint32_t)src[(uint64_t)c * stride + i] << shift); }
+    }
+  }
+}
+
 // De-emphasis as a pass of its own (per-call API): y[n] = x[n] + ((y[n-1] * (2^s - 1)) >> s), y[-1] = previous.
 // A one-tap recurrence through a truncating shift: strictly serial, one lane.
 __global__ __launch_bounds__(64)
@@ -641,6 +681,19 @@ extern "C" int sla_hip_launch_dec_bits(const uint32_t* d_image, uint64_t image_b
                                        sla_hip_dec_info* d_info, sla_hip_dec_chan* d_chan, int32_t* d_kint,
                                        sla_hip_stream_t stream)
 {
+  return sla_hip_launch_dec_bits_x(d_image, image_bytes, d_blocks, num_blocks, num_channels, bits_per_sample, offset_lshift,
+                                   mid_side, parcor_order, longterm_order, want_crc, d_planes, plane_stride, d_info, d_chan,
+                                   d_kint, stream, nullptr);
+}
+
+extern "C" int sla_hip_launch_dec_bits_x(const uint32_t* d_image, uint64_t image_bytes,
+                                         const sla_hip_dec_block* d_blocks, uint32_t num_blocks,
+                                         uint32_t num_channels, uint32_t bits_per_sample, uint32_t offset_lshift,
+                                         uint32_t mid_side, uint32_t parcor_order, uint32_t longterm_order,
+                                         uint32_t want_crc, int32_t* d_planes, uint64_t plane_stride,
+                                         sla_hip_dec_info* d_info, sla_hip_dec_chan* d_chan, int32_t* d_kint,
+                                         sla_hip_stream_t stream, const uint64_t* d_block_end)
+{
   if (d_image == nullptr || d_blocks == nullptr || d_planes == nullptr || d_info == nullptr || d_chan == nullptr || d_kint == nullptr) {
     return SLA_APIRESULT_INVALID_ARGUMENT;
   }
@@ -654,7 +707,7 @@ extern "C" int sla_hip_launch_dec_bits(const uint32_t* d_image, uint64_t image_b
     if (e != hipSuccess) { return hip_rc(e); }
   }
   dec_bits_args a;
-  a.image = d_image; a.image_bytes = image_bytes; a.blocks = d_blocks; a.num_blocks = num_blocks;
+  a.image = d_image; a.image_bytes = image_bytes; a.block_end = d_block_end; a.blocks = d_blocks; a.num_blocks = num_blocks;
   a.bps = bits_per_sample; a.lshift = offset_lshift; a.mid_side = mid_side; a.order = parcor_order; a.ntaps = longterm_order;
   // enough waves for every SIMD of the chip before a wave takes a second block
   uint32_t lanes = (num_blocks + 1023) / 1024;
@@ -664,16 +717,19 @@ extern "C" int sla_hip_launch_dec_bits(const uint32_t* d_image, uint64_t image_b
   a.planes = d_planes; a.stride = plane_stride; a.info = d_info; a.chan = d_chan; a.kint = d_kint;
   const dim3 grid((num_blocks + lanes - 1) / lanes), block(64);
   const size_t lds = sizeof(uint32_t) * ((size_t)lanes * num_channels * DEC_ROW + (size_t)lanes * (DEC_WIN * num_channels + 1));
-  switch (num_channels) {
-    case 1: hipLaunchKernelGGL(k_dec_bits<1>, grid, block, lds, st, a); break;
-    case 2: hipLaunchKernelGGL(k_dec_bits<2>, grid, block, lds, st, a); break;
-    case 3: hipLaunchKernelGGL(k_dec_bits<3>, grid, block, lds, st, a); break;
-    case 4: hipLaunchKernelGGL(k_dec_bits<4>, grid, block, lds, st, a); break;
-    case 5: hipLaunchKernelGGL(k_dec_bits<5>, grid, block, lds, st, a); break;
-    case 6: hipLaunchKernelGGL(k_dec_bits<6>, grid, block, lds, st, a); break;
-    case 7: hipLaunchKernelGGL(k_dec_bits<7>, grid, block, lds, st, a); break;
-    default: hipLaunchKernelGGL(k_dec_bits<8>, grid, block, lds, st, a); break;
+#define SLA_DEC_BITS(B)                                                                \
+  switch (num_channels) {                                                              \
+    case 1: hipLaunchKernelGGL((k_dec_bits<1, B>), grid, block, lds, st, a); break;    \
+    case 2: hipLaunchKernelGGL((k_dec_bits<2, B>), grid, block, lds, st, a); break;    \
+    case 3: hipLaunchKernelGGL((k_dec_bits<3, B>), grid, block, lds, st, a); break;    \
+    case 4: hipLaunchKernelGGL((k_dec_bits<4, B>), grid, block, lds, st, a); break;    \
+    case 5: hipLaunchKernelGGL((k_dec_bits<5, B>), grid, block, lds, st, a); break;    \
+    case 6: hipLaunchKernelGGL((k_dec_bits<6, B>), grid, block, lds, st, a); break;    \
+    case 7: hipLaunchKernelGGL((k_dec_bits<7, B>), grid, block, lds, st, a); break;    \
+    default: hipLaunchKernelGGL((k_dec_bits<8, B>), grid, block, lds, st, a); break;   \
   }
+  if (d_block_end != nullptr) { SLA_DEC_BITS(true) } else { SLA_DEC_BITS(false) }
+#undef SLA_DEC_BITS
   return hip_rc(hipGetLastError());
 }
 
@@ -747,6 +803,22 @@ extern "C" int sla_hip_launch_dec_finish(int32_t* d_planes, uint64_t plane_strid
   if (num_samples == 0) { return 0; }
   hipLaunchKernelGGL(k_dec_finish, dim3((num_samples + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_planes, plane_stride,
                      num_channels, num_samples, mid_side, shift);
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_dec_finish_batch(const int32_t* d_planes, uint64_t plane_stride, uint32_t num_channels,
+                                               const sla_hip_dec_file* d_files, uint32_t num_files, uint32_t max_samples,
+                                               int32_t* d_out, sla_hip_stream_t stream)
+{
+  if (d_planes == nullptr || d_files == nullptr || d_out == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_channels == 0 || num_channels > 8) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_files == 0 || max_samples == 0) { return 0; }
+  // enough workgroups to fill the chip for one long file; short files of a big pass get a workgroup row each
+  uint32_t gx = (max_samples + 255) / 256;
+  if (gx > 1024) { gx = 1024; }
+  const uint32_t gy = (num_files < 65535u) ? num_files : 65535u;
+  hipLaunchKernelGGL(k_dec_finish_batch, dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, d_planes, plane_stride, num_channels,
+                     d_files, num_files, d_out);
   return hip_rc(hipGetLastError());
 }
 

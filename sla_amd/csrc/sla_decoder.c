@@ -11,6 +11,7 @@
 #include "SLADecoder.h"
 
 #include <math.h>
+#include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -22,6 +23,7 @@
 #define STATUS_ENCODE_PARAM   2u
 
 typedef struct { void* ptr; size_t cap; } dbuf_t;
+typedef struct { void* ptr; size_t cap; } hbuf_t;
 
 struct SLADecoder {
   struct SLADecoderConfig   cfg;
@@ -31,6 +33,8 @@ struct SLADecoder {
   hipStream_t               stream;
   hipEvent_t                ev[2];
   dbuf_t                    d_image, d_planes, d_blocks, d_info, d_chan, d_kint;
+  dbuf_t                    d_ftab, d_out;              /* sla_hip_decode_batch: file table, packed samples */
+  hbuf_t                    h_img, h_ptab, h_out;       /* sla_hip_decode_batch: page-locked staging */
   sla_hip_dec_block*        h_blocks;
   sla_hip_dec_info*         h_info;
   uint32_t                  h_cap;
@@ -54,6 +58,16 @@ static int dbuf_reserve(dbuf_t* b, size_t bytes)
   return 0;
 }
 static void dbuf_free(dbuf_t* b) { if (b->ptr != NULL) { (void)hipFree(b->ptr); } b->ptr = NULL; b->cap = 0; }
+static int hbuf_reserve(hbuf_t* b, size_t bytes)
+{
+  if (bytes <= b->cap) { return 0; }
+  if (b->ptr != NULL) { (void)hipHostFree(b->ptr); b->ptr = NULL; b->cap = 0; }
+  bytes += bytes / 4 + 256;
+  if (hipHostMalloc(&b->ptr, bytes, hipHostMallocDefault) != hipSuccess) { b->ptr = NULL; return -1; }
+  b->cap = bytes;
+  return 0;
+}
+static void hbuf_free(hbuf_t* b) { if (b->ptr != NULL) { (void)hipHostFree(b->ptr); } b->ptr = NULL; b->cap = 0; }
 
 static uint32_t rd_be16(const uint8_t* p) { return ((uint32_t)p[0] << 8) | p[1]; }
 static uint32_t rd_be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
@@ -114,6 +128,8 @@ void SLADecoder_Destroy(struct SLADecoder* d)
   (void)hipStreamSynchronize(d->stream);
   dbuf_free(&d->d_image); dbuf_free(&d->d_planes); dbuf_free(&d->d_blocks);
   dbuf_free(&d->d_info); dbuf_free(&d->d_chan); dbuf_free(&d->d_kint);
+  dbuf_free(&d->d_ftab); dbuf_free(&d->d_out);
+  hbuf_free(&d->h_img); hbuf_free(&d->h_ptab); hbuf_free(&d->h_out);
   if (d->h_blocks != NULL) { (void)hipHostFree(d->h_blocks); }
   if (d->h_info != NULL) { (void)hipHostFree(d->h_info); }
   (void)hipEventDestroy(d->ev[0]); (void)hipEventDestroy(d->ev[1]);
@@ -160,6 +176,101 @@ static int host_tables_reserve(struct SLADecoder* d, uint32_t blocks)
 #define HIPCHK(call) do { if ((call) != hipSuccess) { return SLA_APIRESULT_NG; } } while (0)
 #define RCCHK(call)  do { const int rc_ = (call); if (rc_ != 0) { return (rc_ > 0) ? (SLAApiResult)rc_ : SLA_APIRESULT_NG; } } while (0)
 
+/* Walk a file's block chain from byte `off`, sample `pos` (positions in the file) and append the blocks to
+ * d->h_blocks[*nb ...]; *walk_err says why the walk stopped short of `total` samples.    src/SLADecoder.c:696-722
+ * Returns -1 when the host table could not grow. */
+static int walk_chain(struct SLADecoder* d, const uint8_t* data, uint32_t data_size, uint32_t off, uint32_t pos,
+                      uint32_t total, uint32_t buffer_num_samples, uint32_t* nb, SLAApiResult* walk_err)
+{
+  const uint32_t cap_n = d->cfg.max_num_block_samples;
+  *walk_err = SLA_APIRESULT_OK;
+  while (pos < total) {
+    const uint8_t* p;
+    uint32_t left, bsize, n, flags = 0;
+    if (off > data_size) { *walk_err = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE; break; }
+    left = data_size - off;
+    if (left < DEC_MIN_BLOCK_HEADER) { *walk_err = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE; break; }
+    p = data + off;
+    if (rd_be16(p) != SLAI_SYNC_CODE) { *walk_err = SLA_APIRESULT_FAILED_TO_FIND_SYNC_CODE; break; }
+    bsize = rd_be32(p + 2) + 6u;
+    n = rd_be16(p + 8);
+    if (bsize > left || bsize < SLAI_BLK_CRC_START) { *walk_err = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE; break; }   /* no CRC check on a clipped block (:343) */
+    if (n > buffer_num_samples - pos || n > cap_n) {
+      /* the CRC of this block is still checked first (:343-352 precede :633-636): keep it, header only */
+      *walk_err = SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE;
+      if (d->cfg.enable_crc_check != 1) { break; }
+      flags = SLA_HIP_DEC_HEADER_ONLY;
+    }
+    if (host_tables_reserve(d, *nb + 1) != 0) { return -1; }
+    d->h_blocks[*nb].byte_off = off; d->h_blocks[*nb].byte_len = bsize; d->h_blocks[*nb].smp_off = pos;
+    d->h_blocks[*nb].num_samples = n; d->h_blocks[*nb].flags = flags;
+    (*nb)++;
+    if (flags != 0) { break; }
+    off += bsize; pos += n;
+  }
+  return 0;
+}
+
+/* Examine the decoded blocks of one file in file order: the first failure decides (*result), *done_samples counts the
+ * samples of the blocks before it.  Table positions are the file's own (byte offsets into `data`).  Returns 1 when a
+ * block's body did not end where its size field says: the reference continues from where its reader stopped (:715),
+ * so the walk resumes at (*off, *pos). */
+static int examine_blocks(const struct SLADecoder* d, const uint8_t* data, const sla_hip_dec_block* blocks,
+                          const sla_hip_dec_info* info, uint32_t nb, int lms_ok, SLAApiResult walk_err,
+                          uint32_t* one_block_size, uint32_t* done_samples, uint32_t* off, uint32_t* pos, SLAApiResult* result)
+{
+  uint32_t i;
+  *result = SLA_APIRESULT_OK;
+  for (i = 0; i < nb; i++) {
+    const sla_hip_dec_block* b = &blocks[i];
+    const sla_hip_dec_info* in = &info[i];
+    if (d->cfg.enable_crc_check == 1 && in->crc != rd_be16(data + b->byte_off + 6)) { *result = SLA_APIRESULT_DETECT_DATA_CORRUPTION; return 0; }
+    if (b->flags & SLA_HIP_DEC_HEADER_ONLY) { *result = walk_err; return 0; }
+    if (in->type > 2) { *result = SLA_APIRESULT_INVALID_HEADER_FORMAT; return 0; }
+    if (in->type == 0 && !lms_ok) { *result = SLA_APIRESULT_FAILED_TO_SYNTHESIZE; return 0; }
+    *done_samples = b->smp_off + b->num_samples;
+    if (one_block_size != NULL) { *one_block_size = in->used_bytes; return 0; }     /* src/SLADecoder.c:651 */
+    if (in->used_bytes != b->byte_len) {
+      *off = (uint32_t)b->byte_off + in->used_bytes; *pos = *done_samples;
+      return 1;
+    }
+  }
+  *result = walk_err;
+  return 0;
+}
+
+/* The kernel launch parameters of a file, from its header; SLA_APIRESULT_OK when the kernels can run on it.  Sets the
+ * handle's wave format and encode parameter as it goes, as the reference's DecodeWhole does. */
+typedef struct {
+  uint32_t C, total, bps, lshift, order, ntaps, lms, ms;
+} dec_format_t;
+
+static SLAApiResult file_format(struct SLADecoder* d, const uint8_t* data, uint32_t data_size, dec_format_t* f)
+{
+  struct SLAHeaderInfo header;
+  SLAApiResult ret;
+  if ((ret = SLADecoder_DecodeHeader(data, data_size, &header)) != SLA_APIRESULT_OK) { return ret; }
+  if ((ret = SLADecoder_SetWaveFormat(d, &header.wave_format)) != SLA_APIRESULT_OK) { return ret; }
+  if ((ret = SLADecoder_SetEncodeParameter(d, &header.encode_param)) != SLA_APIRESULT_OK) { return ret; }
+  f->C = header.wave_format.num_channels; f->total = header.num_samples;
+  f->bps = header.wave_format.bit_per_sample; f->lshift = header.wave_format.offset_lshift;
+  f->order = header.encode_param.parcor_order; f->ntaps = header.encode_param.longterm_order;
+  f->lms = header.encode_param.lms_order_per_filter;
+  f->ms = (header.encode_param.ch_process_method == SLA_CHPROCESSMETHOD_STEREO_MS) ? 1u : 0u;
+  return SLA_APIRESULT_OK;
+}
+
+/* what a file with a valid header but nothing the kernels can run on returns (SLA_APIRESULT_OK and no samples for an
+ * empty file), or -1 when the kernels are to run */
+static int format_verdict(const dec_format_t* f)
+{
+  if (f->total == 0) { return SLA_APIRESULT_OK; }
+  if (f->ms && f->C != 2) { return SLA_APIRESULT_INVAILD_CHPROCESSMETHOD; }                   /* src/SLADecoder.c:605-613 */
+  if (f->C == 0 || f->bps == 0 || f->lshift >= f->bps) { return SLA_APIRESULT_INVALID_HEADER_FORMAT; }   /* the reference asserts (src/SLADecoder.c:541-542) */
+  return -1;
+}
+static int lms_order_ok(uint32_t lms) { return (lms == 4 || lms == 8 || lms == 16 || lms == 32); }
+
 /* The decode proper.  `host_data` is always the stream in host memory (the walk reads it); the image in device
  * memory is either uploaded from it or supplied by the caller, the planes likewise are the handle's or the caller's. */
 static SLAApiResult decode_run(struct SLADecoder* d, const uint8_t* data, uint32_t data_size, const uint32_t* d_image_user,
@@ -169,40 +280,33 @@ static SLAApiResult decode_run(struct SLADecoder* d, const uint8_t* data, uint32
   /* one_block_size == NULL: a whole file (header, then blocks until header.num_samples samples are out);
    * otherwise `data` starts at a block's sync code and exactly that block is decoded with the handle's current
    * format / parameters (the streaming decoder's unit; reference SLADecoder_DecodeBlock, src/SLADecoder.c:583-657) */
-  struct SLAHeaderInfo header;
+  dec_format_t f;
   SLAApiResult ret, result = SLA_APIRESULT_OK;
   uint32_t C, total, order, ntaps, lms, ms, bps, lshift, cap_n;
   uint32_t off = SLA_HEADER_SIZE, pos = 0, done_samples = 0, batches = 0, ch;
   uint64_t stride;
   const uint32_t* d_image;
   int32_t* d_planes;
-  int lms_ok;
+  int lms_ok, verdict;
   float kernel_ms = 0.0f;
   double t0 = now_ms(), t_up = 0.0, t_walk = 0.0, t1;
 
   memset(d->timing, 0, sizeof(d->timing));
   if (one_block_size == NULL) {
-    if ((ret = SLADecoder_DecodeHeader(data, data_size, &header)) != SLA_APIRESULT_OK) { return ret; }
-    if ((ret = SLADecoder_SetWaveFormat(d, &header.wave_format)) != SLA_APIRESULT_OK) { return ret; }
-    if ((ret = SLADecoder_SetEncodeParameter(d, &header.encode_param)) != SLA_APIRESULT_OK) { return ret; }
+    if ((ret = file_format(d, data, data_size, &f)) != SLA_APIRESULT_OK) { return ret; }
   } else {
     if (!(d->status_flag & STATUS_WAVE_FORMAT) || !(d->status_flag & STATUS_ENCODE_PARAM)) { return SLA_APIRESULT_PARAMETER_NOT_SET; }
-    memset(&header, 0, sizeof(header));
-    header.wave_format = d->wave_format; header.encode_param = d->encode_param;
-    header.num_samples = 1;               /* the walk stops behind the first block */
+    f.C = d->wave_format.num_channels; f.bps = d->wave_format.bit_per_sample; f.lshift = d->wave_format.offset_lshift;
+    f.order = d->encode_param.parcor_order; f.ntaps = d->encode_param.longterm_order; f.lms = d->encode_param.lms_order_per_filter;
+    f.ms = (d->encode_param.ch_process_method == SLA_CHPROCESSMETHOD_STEREO_MS) ? 1u : 0u;
+    f.total = 1;                          /* the walk stops behind the first block */
     off = 0; *one_block_size = 0;
   }
-  C = header.wave_format.num_channels; total = header.num_samples;
-  bps = header.wave_format.bit_per_sample; lshift = header.wave_format.offset_lshift;
-  order = header.encode_param.parcor_order; ntaps = header.encode_param.longterm_order;
-  lms = header.encode_param.lms_order_per_filter;
-  ms = (header.encode_param.ch_process_method == SLA_CHPROCESSMETHOD_STEREO_MS) ? 1u : 0u;
+  C = f.C; total = f.total; bps = f.bps; lshift = f.lshift; order = f.order; ntaps = f.ntaps; lms = f.lms; ms = f.ms;
   cap_n = d->cfg.max_num_block_samples;
   *output_num_samples = 0;
-  if (total == 0) { return SLA_APIRESULT_OK; }
-  if (ms && C != 2) { return SLA_APIRESULT_INVAILD_CHPROCESSMETHOD; }            /* src/SLADecoder.c:605-613 */
-  if (C == 0 || bps == 0 || lshift >= bps) { return SLA_APIRESULT_INVALID_HEADER_FORMAT; }   /* the reference asserts (src/SLADecoder.c:541-542) */
-  lms_ok = (lms == 4 || lms == 8 || lms == 16 || lms == 32);
+  if ((verdict = format_verdict(&f)) >= 0) { return (SLAApiResult)verdict; }
+  lms_ok = lms_order_ok(lms);
 
   /* the stream image on the device */
   if (d_image_user != NULL) { d_image = d_image_user; }
@@ -224,34 +328,10 @@ static SLAApiResult decode_run(struct SLADecoder* d, const uint8_t* data, uint32
   t_up = now_ms() - t0;
 
   for (;;) {
-    uint32_t nb = 0, i, resync = 0, batch_off = off, batch_pos = pos;
-    SLAApiResult walk_err = SLA_APIRESULT_OK;
+    uint32_t nb = 0;
+    SLAApiResult walk_err;
     double tw = now_ms();
-    /* ---- walk the chain from (off, pos)                                  src/SLADecoder.c:696-722 */
-    while (batch_pos < total) {
-      const uint8_t* p;
-      uint32_t left, bsize, n, flags = 0;
-      if (batch_off > data_size) { walk_err = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE; break; }
-      left = data_size - batch_off;
-      if (left < DEC_MIN_BLOCK_HEADER) { walk_err = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE; break; }
-      p = data + batch_off;
-      if (rd_be16(p) != SLAI_SYNC_CODE) { walk_err = SLA_APIRESULT_FAILED_TO_FIND_SYNC_CODE; break; }
-      bsize = rd_be32(p + 2) + 6u;
-      n = rd_be16(p + 8);
-      if (bsize > left || bsize < SLAI_BLK_CRC_START) { walk_err = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE; break; }   /* no CRC check on a clipped block (:343) */
-      if (n > buffer_num_samples - batch_pos || n > cap_n) {
-        /* the CRC of this block is still checked first (:343-352 precede :633-636): keep it, header only */
-        walk_err = SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE;
-        if (d->cfg.enable_crc_check != 1) { break; }
-        flags = SLA_HIP_DEC_HEADER_ONLY;
-      }
-      if (host_tables_reserve(d, nb + 1) != 0) { return SLA_APIRESULT_NG; }
-      d->h_blocks[nb].byte_off = batch_off; d->h_blocks[nb].byte_len = bsize; d->h_blocks[nb].smp_off = batch_pos;
-      d->h_blocks[nb].num_samples = n; d->h_blocks[nb].flags = flags;
-      nb++;
-      if (flags != 0) { break; }
-      batch_off += bsize; batch_pos += n;
-    }
+    if (walk_chain(d, data, data_size, off, pos, total, buffer_num_samples, &nb, &walk_err) != 0) { return SLA_APIRESULT_NG; }
     t_walk += now_ms() - tw;
     batches++;
 
@@ -282,25 +362,7 @@ static SLAApiResult decode_run(struct SLADecoder* d, const uint8_t* data, uint32
     }
 
     /* ---- examine the blocks in file order: the first failure decides */
-    result = SLA_APIRESULT_OK;
-    for (i = 0; i < nb; i++) {
-      const sla_hip_dec_block* b = &d->h_blocks[i];
-      const sla_hip_dec_info* in = &d->h_info[i];
-      if (d->cfg.enable_crc_check == 1 && in->crc != rd_be16(data + b->byte_off + 6)) { result = SLA_APIRESULT_DETECT_DATA_CORRUPTION; break; }
-      if (b->flags & SLA_HIP_DEC_HEADER_ONLY) { result = walk_err; break; }
-      if (in->type > 2) { result = SLA_APIRESULT_INVALID_HEADER_FORMAT; break; }
-      if (in->type == 0 && !lms_ok) { result = SLA_APIRESULT_FAILED_TO_SYNTHESIZE; break; }
-      done_samples = b->smp_off + b->num_samples;
-      if (one_block_size != NULL) { *one_block_size = in->used_bytes; break; }     /* src/SLADecoder.c:651 */
-      if (in->used_bytes != b->byte_len) {
-        /* the body did not end where the size field says: the reference continues from where its reader stopped (:715) */
-        off = (uint32_t)b->byte_off + in->used_bytes; pos = done_samples; resync = 1;
-        break;
-      }
-    }
-    if (resync) { continue; }
-    if (i == nb && result == SLA_APIRESULT_OK) { result = walk_err; }
-    break;
+    if (!examine_blocks(d, data, d->h_blocks, d->h_info, nb, lms_ok, walk_err, one_block_size, &done_samples, &off, &pos, &result)) { break; }
   }
 
   /* ---- mid/side, left-justification, copy-out of everything before the failing block */
@@ -339,6 +401,318 @@ SLAApiResult sla_hip_decode_device(struct SLADecoder* decoder, const uint8_t* ho
   if (decoder == NULL || host_data == NULL || d_image == NULL || d_planes == NULL || output_num_samples == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   return decode_run(decoder, host_data, data_size, d_image, d_planes, plane_stride, NULL,
                     (plane_stride > 0xFFFFFFFFull) ? 0xFFFFFFFFu : (uint32_t)plane_stride, output_num_samples, NULL);
+}
+
+/* ------------------------------------------------------------------------------------------------------------
+ * sla_hip_decode_batch (include/sla_hip.h): the blocks of many files through the kernels together.  The headers and
+ * the block walk are those of decode_run, file by file; files that share the kernels' launch parameters share a pass;
+ * a pass uploads its images (concatenated at 4-byte offsets, each block's reader bounded by the end of its own file:
+ * sla_hip_launch_dec_bits_x) and its block table once, runs each kernel once over one set of planes in which every
+ * file has a region of its own, and brings the finished samples of all its files home in one copy
+ * (sla_hip_launch_dec_finish_batch).  The results are then examined file by file with decode_run's code.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DEC_BATCH_PASS_BYTES (1ull << 30)    /* stream bytes of one pass (staging and device image) */
+#define DEC_BATCH_ALIGN      64u             /* samples: every file's plane region starts on a 256-byte boundary */
+#define DEC_COPY_THREADS     4u              /* host threads of a staging copy, the caller's own among them */
+#define DEC_COPY_PIECE       ((size_t)4 << 20)
+
+typedef struct { void* dst; const void* src; size_t bytes; } copy_job_t;
+typedef struct { copy_job_t* v; uint32_t n, cap, next; size_t bytes; } copy_list_t;
+
+static int copy_add(copy_list_t* l, void* dst, const void* src, size_t bytes)
+{
+  while (bytes > 0) {
+    const size_t take = (bytes < DEC_COPY_PIECE) ? bytes : DEC_COPY_PIECE;
+    if (l->n == l->cap) {
+      const uint32_t cap = l->cap * 2 + 64;
+      copy_job_t* v = (copy_job_t*)realloc(l->v, sizeof(*v) * cap);
+      if (v == NULL) { return -1; }
+      l->v = v; l->cap = cap;
+    }
+    l->v[l->n].dst = dst; l->v[l->n].src = src; l->v[l->n].bytes = take;
+    l->n++; l->bytes += take;
+    dst = (uint8_t*)dst + take; src = (const uint8_t*)src + take; bytes -= take;
+  }
+  return 0;
+}
+
+static void* copy_worker(void* arg)
+{
+  copy_list_t* l = (copy_list_t*)arg;
+  for (;;) {
+    const uint32_t k = __atomic_fetch_add(&l->next, 1u, __ATOMIC_RELAXED);
+    if (k >= l->n) { return NULL; }
+    memcpy(l->v[k].dst, l->v[k].src, l->v[k].bytes);
+  }
+}
+
+/* the listed copies on at most DEC_COPY_THREADS threads; small lists stay on the caller's thread */
+static void copy_run(copy_list_t* l)
+{
+  pthread_t tid[DEC_COPY_THREADS - 1];
+  uint32_t nt = 0, t, want = (l->bytes >= 2 * DEC_COPY_PIECE) ? DEC_COPY_THREADS : 1u;
+  if (want > l->n) { want = l->n; }
+  l->next = 0;
+  for (t = 1; t < want; t++) { if (pthread_create(&tid[nt], NULL, copy_worker, l) == 0) { nt++; } }
+  (void)copy_worker(l);
+  for (t = 0; t < nt; t++) { pthread_join(tid[t], NULL); }
+  l->n = 0; l->bytes = 0;
+}
+
+typedef struct {
+  uint32_t     item;        /* index into the caller's items */
+  dec_format_t f;
+  uint32_t     first, nb;   /* its blocks: d->h_blocks[first, first + nb), positions in the file */
+  SLAApiResult walk_err;
+  uint32_t     extent;      /* samples per channel its blocks write */
+  int          alone;       /* decoded on its own through decode_run */
+  uint64_t     img_off;     /* its image in the pass image */
+  uint64_t     plane_off;   /* its region in the pass planes */
+} bfile_t;
+
+static int bfile_cmp(const void* pa, const void* pb)
+{
+  const bfile_t* a = (const bfile_t*)pa;
+  const bfile_t* b = (const bfile_t*)pb;
+  const uint32_t ka[8] = { a->alone, a->f.C, a->f.bps, a->f.ms, a->f.order, a->f.ntaps, a->f.lms, a->f.lshift };
+  const uint32_t kb[8] = { b->alone, b->f.C, b->f.bps, b->f.ms, b->f.order, b->f.ntaps, b->f.lms, b->f.lshift };
+  int k;
+  for (k = 0; k < 8; k++) { if (ka[k] != kb[k]) { return (ka[k] < kb[k]) ? -1 : 1; } }
+  return (a->item < b->item) ? -1 : (a->item > b->item);
+}
+static int same_launch(const dec_format_t* a, const dec_format_t* b)
+{
+  return a->C == b->C && a->bps == b->bps && a->ms == b->ms && a->order == b->order && a->ntaps == b->ntaps
+         && a->lms == b->lms && a->lshift == b->lshift;
+}
+
+#define BCHK(call) do { if ((call) != hipSuccess) { return -1; } } while (0)
+#define BRC(call)  do { if ((call) != 0) { return -1; } } while (0)
+
+/* One pass: files[0, nf), all with the same launch parameters, blocks d->h_blocks[files[0].first ...] contiguous.
+ * Returns -1 on a device or allocation failure. */
+static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t* files, uint32_t nf, copy_list_t* cl,
+                      double* t_up, double* t_down, float* kernel_ms)
+{
+  const dec_format_t* f = &files[0].f;
+  const uint32_t C = f->C, first = files[0].first, cap_n = d->cfg.max_num_block_samples;
+  const int lms_ok = lms_order_ok(f->lms);
+  uint64_t img_bytes = 0, span = 0, out_elems = 0;
+  uint32_t nb = 0, i, k, nfin = 0, max_done = 0;
+  uint32_t* done;
+  sla_hip_dec_block* tb;
+  uint64_t* tend;
+  sla_hip_dec_file* ft;
+  float ms_k = 0.0f;
+  double t;
+
+  for (i = 0; i < nf; i++) {
+    files[i].img_off = img_bytes; img_bytes += ((uint64_t)items[files[i].item].data_size + 3) & ~(uint64_t)3;
+    files[i].plane_off = span; span += ((uint64_t)files[i].extent + DEC_BATCH_ALIGN - 1) / DEC_BATCH_ALIGN * DEC_BATCH_ALIGN;
+    nb += files[i].nb;
+  }
+  if (span == 0) { span = 1; }
+
+  /* ---- images into staging (the bytes after each file up to its 4-byte boundary are zero) and over in one copy,
+   *      the block table -- positions in the pass, then every block's end of stream -- likewise */
+  t = now_ms();
+  if (hbuf_reserve(&d->h_img, img_bytes + 16) != 0 || dbuf_reserve(&d->d_image, img_bytes + 16) != 0
+      || hbuf_reserve(&d->h_ptab, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb + sizeof(sla_hip_dec_file) * nf) != 0
+      || dbuf_reserve(&d->d_blocks, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb) != 0
+      || dbuf_reserve(&d->d_info, sizeof(sla_hip_dec_info) * nb) != 0
+      || dbuf_reserve(&d->d_chan, sizeof(sla_hip_dec_chan) * (size_t)nb * C) != 0
+      || dbuf_reserve(&d->d_kint, sizeof(int32_t) * (size_t)nb * C * (f->order + 1)) != 0
+      || dbuf_reserve(&d->d_planes, sizeof(int32_t) * (size_t)span * C) != 0
+      || dbuf_reserve(&d->d_ftab, sizeof(sla_hip_dec_file) * nf) != 0) { return -1; }
+  for (i = 0; i < nf; i++) {
+    const sla_hip_decode_item* it = &items[files[i].item];
+    uint8_t* dst = (uint8_t*)d->h_img.ptr + files[i].img_off;
+    const uint32_t pad = (uint32_t)(((uint64_t)it->data_size + 3) & ~(uint64_t)3) - it->data_size;
+    if (pad != 0) { memset(dst + it->data_size, 0, pad); }
+    if (copy_add(cl, dst, it->data, it->data_size) != 0) { return -1; }
+  }
+  copy_run(cl);
+  tb = (sla_hip_dec_block*)d->h_ptab.ptr;
+  tend = (uint64_t*)(tb + nb);
+  for (i = 0, k = 0; i < nf; i++) {
+    const uint64_t end = files[i].img_off + items[files[i].item].data_size;
+    uint32_t b;
+    for (b = 0; b < files[i].nb; b++, k++) {
+      tb[k] = d->h_blocks[files[i].first + b];
+      tb[k].byte_off += files[i].img_off;
+      tb[k].smp_off += (uint32_t)files[i].plane_off;
+      tend[k] = end;
+    }
+  }
+  BCHK(hipMemcpyAsync(d->d_image.ptr, d->h_img.ptr, img_bytes, hipMemcpyHostToDevice, d->stream));
+  BCHK(hipMemcpyAsync(d->d_blocks.ptr, tb, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb, hipMemcpyHostToDevice, d->stream));
+  BCHK(hipMemsetAsync(d->d_info.ptr, 0, sizeof(sla_hip_dec_info) * nb, d->stream));
+  BCHK(hipStreamSynchronize(d->stream));
+  *t_up += now_ms() - t;
+
+  /* ---- the kernels, once each over all blocks of the pass */
+  if (nb > 0) {
+    const sla_hip_dec_block* db = (const sla_hip_dec_block*)d->d_blocks.ptr;
+    const sla_hip_dec_info* di = (const sla_hip_dec_info*)d->d_info.ptr;
+    int32_t* planes = (int32_t*)d->d_planes.ptr;
+    BCHK(hipEventRecord(d->ev[0], d->stream));
+    BRC(sla_hip_launch_dec_bits_x((const uint32_t*)d->d_image.ptr, img_bytes, db, nb, C, f->bps, f->lshift, f->ms, f->order, f->ntaps,
+                                  d->cfg.enable_crc_check == 1, planes, span, (sla_hip_dec_info*)d->d_info.ptr,
+                                  (sla_hip_dec_chan*)d->d_chan.ptr, (int32_t*)d->d_kint.ptr, d->stream,
+                                  (const uint64_t*)(db + nb)));
+    BCHK(hipMemcpyAsync(d->h_info + first, d->d_info.ptr, sizeof(sla_hip_dec_info) * nb, hipMemcpyDeviceToHost, d->stream));
+    if (lms_ok) {
+      BRC(sla_hip_launch_dec_lms(planes, span, db, di, nb, C, f->lms, d->stream));
+      BRC(sla_hip_launch_dec_ltm(planes, span, db, di, (const sla_hip_dec_chan*)d->d_chan.ptr, nb, C, f->ntaps, cap_n, d->stream));
+      BRC(sla_hip_launch_dec_lattice(planes, span, db, di, nb, C, (const int32_t*)d->d_kint.ptr, f->order, 1, d->stream));
+    }
+    BCHK(hipEventRecord(d->ev[1], d->stream));
+    BCHK(hipStreamSynchronize(d->stream));
+    if (hipEventElapsedTime(&ms_k, d->ev[0], d->ev[1]) == hipSuccess) { *kernel_ms += ms_k; }
+  }
+
+  /* ---- every file examined on its own, in file order, with decode_run's code */
+  done = (uint32_t*)calloc(nf, sizeof(uint32_t));
+  if (done == NULL) { return -1; }
+  ft = (sla_hip_dec_file*)(tend + nb);
+  for (i = 0; i < nf; i++) {
+    sla_hip_decode_item* it = &items[files[i].item];
+    uint32_t off = SLA_HEADER_SIZE, pos = 0;
+    SLAApiResult result;
+    if (examine_blocks(d, it->data, d->h_blocks + files[i].first, d->h_info + files[i].first, files[i].nb, lms_ok,
+                       files[i].walk_err, NULL, &done[i], &off, &pos, &result)) {
+      /* a block body that does not end where its size field says: the walk would resume where the reader stopped.
+       * Rare (damaged or hand-made streams) -- the file is decoded again on its own, which is exact by construction. */
+      files[i].alone = 1; done[i] = 0;
+      continue;
+    }
+    it->result = result;
+    if (done[i] > 0) {
+      ft[nfin].plane_off = files[i].plane_off; ft[nfin].out_off = out_elems; ft[nfin].num_samples = done[i];
+      ft[nfin].mid_side = f->ms; ft[nfin].shift = 32u - f->bps + f->lshift; ft[nfin].reserved = 0;
+      out_elems += (uint64_t)done[i] * C;
+      if (done[i] > max_done) { max_done = done[i]; }
+      nfin++;
+    }
+  }
+
+  /* ---- mid/side and left-justification of every file, packed, home in one copy, into the caller's planes */
+  t = now_ms();
+  if (nfin > 0) {
+    uint64_t o = 0;
+    if (dbuf_reserve(&d->d_out, sizeof(int32_t) * out_elems) != 0 || hbuf_reserve(&d->h_out, sizeof(int32_t) * out_elems) != 0) { free(done); return -1; }
+    if (hipMemcpyAsync(d->d_ftab.ptr, ft, sizeof(sla_hip_dec_file) * nfin, hipMemcpyHostToDevice, d->stream) != hipSuccess
+        || hipEventRecord(d->ev[0], d->stream) != hipSuccess
+        || sla_hip_launch_dec_finish_batch((const int32_t*)d->d_planes.ptr, span, C, (const sla_hip_dec_file*)d->d_ftab.ptr, nfin,
+                                           max_done, (int32_t*)d->d_out.ptr, d->stream) != 0
+        || hipEventRecord(d->ev[1], d->stream) != hipSuccess
+        || hipMemcpyAsync(d->h_out.ptr, d->d_out.ptr, sizeof(int32_t) * out_elems, hipMemcpyDeviceToHost, d->stream) != hipSuccess
+        || hipStreamSynchronize(d->stream) != hipSuccess) { free(done); return -1; }
+    if (hipEventElapsedTime(&ms_k, d->ev[0], d->ev[1]) == hipSuccess) { *kernel_ms += ms_k; }
+    for (i = 0; i < nf; i++) {
+      sla_hip_decode_item* it = &items[files[i].item];
+      uint32_t c;
+      if (files[i].alone || done[i] == 0) { continue; }
+      for (c = 0; c < C; c++) {
+        if (copy_add(cl, it->buffer[c], (const int32_t*)d->h_out.ptr + o + (uint64_t)c * done[i], sizeof(int32_t) * (size_t)done[i]) != 0) {
+          free(done); return -1;
+        }
+      }
+      o += (uint64_t)done[i] * C;
+    }
+    copy_run(cl);
+  }
+  for (i = 0; i < nf; i++) { if (!files[i].alone) { items[files[i].item].output_num_samples = done[i]; } }
+  free(done);
+  *t_down += now_ms() - t;
+  return 0;
+}
+
+int sla_hip_decode_batch(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t num_items)
+{
+  bfile_t* files;
+  copy_list_t cl;
+  struct SLAWaveFormat wf_after;
+  struct SLAEncodeParameter ep_after;
+  uint32_t flag_after, nf = 0, nblocks = 0, passes = 0, i, p0;
+  int rc = 0;
+  float kernel_ms = 0.0f;
+  double t0 = now_ms(), t_walk = 0.0, t_up = 0.0, t_down = 0.0, t;
+
+  if (d == NULL || (items == NULL && num_items > 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  memset(d->timing, 0, sizeof(d->timing));
+  if (num_items == 0) { return 0; }
+  files = (bfile_t*)calloc(num_items, sizeof(*files));
+  if (files == NULL) { return SLA_APIRESULT_NG; }
+  memset(&cl, 0, sizeof(cl));
+
+  /* ---- headers in item order: the handle's format moves exactly as under DecodeWhole of one item after the other */
+  t = now_ms();
+  for (i = 0; i < num_items; i++) {
+    sla_hip_decode_item* it = &items[i];
+    dec_format_t f;
+    SLAApiResult ret;
+    int verdict;
+    uint32_t c;
+    it->output_num_samples = 0;
+    if (it->data == NULL || it->buffer == NULL) { it->result = SLA_APIRESULT_INVALID_ARGUMENT; continue; }
+    if ((ret = file_format(d, it->data, it->data_size, &f)) != SLA_APIRESULT_OK) { it->result = ret; continue; }
+    if ((verdict = format_verdict(&f)) >= 0) { it->result = verdict; continue; }
+    it->result = SLA_APIRESULT_OK;
+    files[nf].item = i; files[nf].f = f;
+    for (c = 0; c < f.C; c++) { if (it->buffer[c] == NULL) { files[nf].alone = 1; } }     /* fails there as DecodeWhole does */
+    nf++;
+  }
+  wf_after = d->wave_format; ep_after = d->encode_param; flag_after = d->status_flag;
+
+  /* ---- files that share the launch parameters next to each other, each one's block chain walked */
+  qsort(files, nf, sizeof(*files), bfile_cmp);
+  for (i = 0; i < nf; i++) {
+    const sla_hip_decode_item* it = &items[files[i].item];
+    uint32_t b;
+    if (files[i].alone) { continue; }
+    files[i].first = nblocks;
+    if (walk_chain(d, it->data, it->data_size, SLA_HEADER_SIZE, 0, files[i].f.total, it->buffer_num_samples, &nblocks, &files[i].walk_err) != 0) {
+      rc = SLA_APIRESULT_NG; goto out;
+    }
+    files[i].nb = nblocks - files[i].first;
+    for (b = files[i].first; b < nblocks; b++) {
+      const sla_hip_dec_block* bl = &d->h_blocks[b];
+      const uint32_t e = bl->smp_off + ((bl->flags & SLA_HIP_DEC_HEADER_ONLY) ? 0u : bl->num_samples);
+      if (e > files[i].extent) { files[i].extent = e; }
+    }
+  }
+  t_walk += now_ms() - t;
+
+  /* ---- passes: runs of equal launch parameters, cut at SLA_HIP_DEC_BATCH_PASS sample-channels / DEC_BATCH_PASS_BYTES */
+  for (p0 = 0; p0 < nf && !files[p0].alone; ) {
+    uint64_t smp = 0, bytes = 0;
+    uint32_t p1 = p0;
+    while (p1 < nf && !files[p1].alone && same_launch(&files[p1].f, &files[p0].f)) {
+      const uint64_t s1 = ((uint64_t)files[p1].extent + DEC_BATCH_ALIGN) * files[p1].f.C;
+      const uint64_t b1 = (uint64_t)items[files[p1].item].data_size + 4;
+      if (p1 > p0 && (smp + s1 > SLA_HIP_DEC_BATCH_PASS || bytes + b1 > DEC_BATCH_PASS_BYTES)) { break; }
+      smp += s1; bytes += b1; p1++;
+    }
+    if (batch_pass(d, items, files + p0, p1 - p0, &cl, &t_up, &t_down, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+    passes++;
+    p0 = p1;
+  }
+
+  /* ---- files decoded on their own */
+  for (i = 0; i < nf; i++) {
+    sla_hip_decode_item* it = &items[files[i].item];
+    if (!files[i].alone) { continue; }
+    it->result = decode_run(d, it->data, it->data_size, NULL, NULL, 0, it->buffer, it->buffer_num_samples, &it->output_num_samples, NULL);
+  }
+
+out:
+  d->wave_format = wf_after; d->encode_param = ep_after; d->status_flag = flag_after;
+  d->timing[0] = (float)t_up; d->timing[1] = (float)t_walk; d->timing[2] = kernel_ms; d->timing[3] = (float)t_down;
+  d->timing[4] = (float)(now_ms() - t0); d->timing[5] = (float)passes;
+  free(cl.v);
+  free(files);
+  return rc;
 }
 
 int sla_hip_decoder_last_timing(const struct SLADecoder* decoder, float* timing_ms)
