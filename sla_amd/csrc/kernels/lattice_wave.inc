@@ -139,7 +139,7 @@ __device__ __forceinline__ uint32_t lat_pad(uint32_t p) { return p; }
                  [F8] "+v"(F[8]), [F9] "+v"(F[9]), [F10] "+v"(F[10]), [F11] "+v"(F[11]), [F12] "+v"(F[12]), [F13] "+v"(F[13]), [F14] "+v"(F[14]), [F15] "+v"(F[15]), [F16] "+v"(F[16]), \
                  [B0] "+v"(B[0]), [B1] "+v"(B[1]), [B2] "+v"(B[2]), [B3] "+v"(B[3]), [B4] "+v"(B[4]), [B5] "+v"(B[5]), [B6] "+v"(B[6]), [B7] "+v"(B[7]), [B8] "+v"(B[8]), \
                  [B9] "+v"(B[9]), [B10] "+v"(B[10]), [B11] "+v"(B[11]), [B12] "+v"(B[12]), [B13] "+v"(B[13]), [B14] "+v"(B[14]), [B15] "+v"(B[15]), [B16] "+v"(B[16]), [B17] "+v"(B[17])
-#define LAT_INS [k] "v"(k), [k2] "v"(k * 2), [k17] "v"((int32_t)((uint32_t)k << 17)), [c] "s"(0x4000), [c2] "s"(0x8000), [c31] "s"(0x80000000ll), [form] "s"(form)
+#define LAT_INS [k] "v"(k), [k2] "v"((int32_t)((uint32_t)k << 1)), [k17] "v"((int32_t)((uint32_t)k << 17)), [c] "s"(0x4000), [c2] "s"(0x8000), [c31] "s"(0x80000000ll), [form] "s"(form)
 #define LAT_CLOBBERS "scc", "vcc", "v60", "v61", "v62", "v63"
 static_assert(LAT_T == 17, "the stage blocks are written for 17 samples per lane");
 

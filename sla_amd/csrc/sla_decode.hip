@@ -94,10 +94,15 @@ struct bit_reader {
     rp += n;
     return v;
   }
-  // any width: the low 32 bits of the number (reference reads up to 64 bits and the callers truncate)
+  // any width: the low 32 bits of the number (reference reads up to 64 bits and the callers truncate); the bits above
+  // them come first and are skipped
   __device__ __forceinline__ uint32_t get_wide(uint32_t n)
   {
-    while (n > 32) { (void)get(32); n -= 32; }
+    while (n > 32) {
+      const uint32_t skip = (n - 32 < 32) ? (n - 32) : 32u;
+      (void)get(skip);
+      n -= skip;
+    }
     return get(n);
   }
   // zeros before the next 1 bit; the 1 is consumed

@@ -180,3 +180,20 @@ def test_lattice_ragged_blocks_and_shift(oracle, hip):
             for plain in (False, True):
                 got, _ = run_lattice(hip, x, kint, order, False, plain, shift=8)
                 assert np.array_equal(got, want), (order, n, plain)
+
+
+def test_lattice_with_coefficients_beyond_2_30(oracle, hip):
+    """the raw launcher takes caller-supplied coefficients (SLALPCSynthesizer_PredictByParcorCoefInt32): |k| >= 2^30,
+    up to INT32_MIN, on full-range input, plain and certified forms (the products wrap; oracle pinned to the reference
+    for such k in tests/test_oracle_vs_ref.py::test_lattice_wraparound)"""
+    rng = np.random.default_rng(2030)
+    n = 3000
+    x = rng.integers(-2 ** 31, 2 ** 31, n, dtype=np.int64).astype(np.int32)
+    x[:4] = [-2 ** 31, 2 ** 31 - 1, -1, 0]
+    for order, ks in [(1, [-2 ** 31]), (2, [2 ** 30, -2 ** 30]), (5, [2 ** 31 - 1, -2 ** 31, 2 ** 30 + 1, -(2 ** 30) - 7, 3]),
+                      (16, list(rng.integers(-2 ** 31, 2 ** 31, 16)))]:
+        kint = np.array([0] + [int(k) for k in ks], np.int64).astype(np.int32)
+        want = oracle.lattice_predict(x, kint)
+        for plain in (False, True):
+            got, _ = run_lattice(hip, x, kint, order, True, plain)
+            assert np.array_equal(got, want), (order, plain, int(np.argmax(got != want)))

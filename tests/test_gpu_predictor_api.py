@@ -232,3 +232,44 @@ def test_deemphasis_inverts_preemphasis_across_calls(oracle, L):
     assert np.array_equal(got, x)
     assert L.SLAEmphasisFilter_DeEmphasisInt32(C.c_void_p(h), None, 10, 5) == 2
     L.SLAEmphasisFilter_Destroy(C.c_void_p(h))
+
+
+def test_synthesis_entry_points_on_extreme_operands(oracle, L):
+    """full-range int32 inputs, PARCOR coefficients up to +-2^15 and beyond, long-term taps at +-2^31, every LMS order:
+    outputs wrap, and must wrap exactly like the oracle (the per-call long-term API takes odd tap counts only; pinned to the reference for such operands in
+    tests/test_oracle_vs_ref.py::test_unit_synthesis_on_extreme_operands)"""
+    rng = np.random.default_rng(31)
+    n = 3000
+    x = rng.integers(-2 ** 31, 2 ** 31, n, dtype=np.int64).astype(np.int32)
+    x[:6] = [-2 ** 31, 2 ** 31 - 1, -1, 0, 1, -2 ** 31]
+    h = L.SLALPCSynthesizer_Create(255)
+    for kint in (np.array([0, -32768, 32767, -32768, 32767, -32768], np.int32),
+                 np.array([0, 2 ** 31 - 1, -2 ** 31, 2 ** 30, 5], np.int32),
+                 rng.integers(-2 ** 31, 2 ** 31, 33, dtype=np.int64).astype(np.int32)):
+        kint[0] = 0
+        out = np.zeros(n, np.int32)
+        assert L.SLALPCSynthesizer_Reset(C.c_void_p(h)) == 0
+        assert L.SLALPCSynthesizer_SynthesizeByParcorCoefInt32(C.c_void_p(h), p(x, i32p), n, p(kint, i32p), len(kint) - 1, p(out, i32p)) == 0
+        assert np.array_equal(out, oracle.lattice_synth(x, kint)), kint[:4]
+    L.SLALPCSynthesizer_Destroy(C.c_void_p(h))
+    h = L.SLALongTermSynthesizer_Create(5, 256)
+    for pitch, coef in [(3, [-2 ** 31]), (255, [-2 ** 31, 0x7FFF0000, -2 ** 31]), (100, [0x7FFF0000, -2 ** 31, 0x7FFF0000]),
+                        (7, [-2 ** 31, -2 ** 31, 0x7FFF0000, -2 ** 31, 0x7FFF0000])]:
+        coef = np.array(coef, np.int64).astype(np.int32)
+        out = np.zeros(n, np.int32)
+        assert L.SLALongTermSynthesizer_Reset(C.c_void_p(h)) == 0
+        assert L.SLALongTermSynthesizer_SynthesizeInt32(C.c_void_p(h), p(x, i32p), n, pitch, p(coef, i32p), len(coef), p(out, i32p)) == 0
+        assert np.array_equal(out, oracle.ltm_synth(x, pitch, coef)), (pitch, len(coef))
+    L.SLALongTermSynthesizer_Destroy(C.c_void_p(h))
+    h = L.SLALMSFilter_Create(32)
+    for order in (4, 8, 16, 32):
+        out = np.zeros(n, np.int32)
+        assert L.SLALMSFilter_Reset(C.c_void_p(h)) == 0
+        assert L.SLALMSFilter_SynthesizeInt32(C.c_void_p(h), order, p(x, i32p), n, p(out, i32p)) == 0
+        assert np.array_equal(out, oracle.lms_synth(x, order)), order
+    L.SLALMSFilter_Destroy(C.c_void_p(h))
+    h = L.SLAEmphasisFilter_Create()
+    got = x.copy()
+    assert L.SLAEmphasisFilter_DeEmphasisInt32(C.c_void_p(h), p(got, i32p), n, 5) == 0
+    assert np.array_equal(got, oracle.deemph_i32(x))
+    L.SLAEmphasisFilter_Destroy(C.c_void_p(h))

@@ -97,6 +97,30 @@ def test_lattice_wraparound(oracle, ref):
     kint = rng.integers(-32768, 32767, 33, dtype=np.int64).astype(np.int32)
     kint[0] = 0
     assert np.array_equal(oracle.lattice_predict(x, kint), ref.lattice_predict(x, kint))
+    # caller-supplied coefficients of any int32 value (the per-call predictor API), |k| >= 2^30 included
+    for ks in ([-2 ** 31], [2 ** 30, -2 ** 30], [2 ** 31 - 1, -2 ** 31, 2 ** 30 + 1, -(2 ** 30) - 7, 3],
+               list(rng.integers(-2 ** 31, 2 ** 31, 16))):
+        kint = np.array([0] + [int(k) for k in ks], np.int64).astype(np.int32)
+        a = oracle.lattice_predict(x, kint)
+        assert np.array_equal(a, ref.lattice_predict(x, kint))
+        assert np.array_equal(oracle.lattice_synth(a, kint), ref.lattice_synth(a, kint))
+
+
+def test_unit_synthesis_on_extreme_operands(oracle, ref):
+    """the synthesis functions the decoder chains, on full-range int32 input with coefficients at the ends of int32
+    (the operands of tests/test_gpu_predictor_api.py::test_synthesis_entry_points_on_extreme_operands)"""
+    rng = np.random.default_rng(31)
+    x = rng.integers(-2 ** 31, 2 ** 31, 3000, dtype=np.int64).astype(np.int32)
+    x[:6] = [-2 ** 31, 2 ** 31 - 1, -1, 0, 1, -2 ** 31]
+    for kint in (np.array([0, -32768, 32767, -32768, 32767, -32768], np.int32), np.array([0, 2 ** 31 - 1, -2 ** 31, 2 ** 30, 5], np.int32)):
+        assert np.array_equal(oracle.lattice_synth(x, kint), ref.lattice_synth(x, kint))
+    for pitch, coef in [(3, [-2 ** 31]), (255, [-2 ** 31, 0x7FFF0000, -2 ** 31]), (100, [0x7FFF0000, -2 ** 31, 0x7FFF0000]),
+                        (7, [-2 ** 31, -2 ** 31, 0x7FFF0000, -2 ** 31, 0x7FFF0000])]:
+        coef = np.array(coef, np.int64).astype(np.int32)
+        assert np.array_equal(oracle.ltm_synth(x, pitch, coef), ref.ltm_synth(x, pitch, coef)), (pitch, len(coef))
+    for order in (4, 8, 16, 32):
+        assert np.array_equal(oracle.lms_synth(x, order), ref.lms_synth(x, order)), order
+    assert np.array_equal(oracle.deemph_i32(x), ref.deemph_i32(x))
 
 
 @pytest.mark.parametrize("name", W.NAMES)
