@@ -529,6 +529,60 @@ typedef struct sla_hip_decode_item {
 } sla_hip_decode_item;            /* 32 bytes */
 int sla_hip_decode_batch(struct SLADecoder* decoder, sla_hip_decode_item* items, uint32_t num_items);
 
+/* Many .sla files in host memory decoded into caller-owned DEVICE memory, in the sample format a tensor consumer wants.
+ * The decode is sla_hip_decode_batch's (same header pass, walk, grouping and passes): every item gets the result and
+ * output_num_samples that sla_hip_decode_batch gives the same file with buffer_num_samples = capacity, and its samples
+ * [0, output_num_samples) are that call's, converted as sample_format says.  Instead of a download, a kernel
+ * (sla_hip_launch_dec_emit_batch) writes every file's samples straight from the decode planes to its destination:
+ * sample i of channel c goes to element c * channel_stride + i * sample_stride of dst.  Nothing outside that region
+ * ([0, C) x [0, capacity), C from the file's header) is written; without SLA_HIP_DEC_ZERO_FILL nothing past
+ * output_num_samples either, with it every channel's [output_num_samples, capacity) is written zero for every item
+ * whose header gave a channel count, failed items included.
+ * Per item, before any device work on it, INVALID_ARGUMENT (and nothing written) for: NULL data or dst,
+ * sample_stride == 0, channel_stride == 0 on a file of more than one channel, dst not aligned to the element size, a
+ * region whose byte extent overflows, a dst that is not device memory, a region outside dst's allocation.
+ * The handle's stream waits on an event recorded on `stream` (NULL: the null stream) before the first write; the call
+ * returns when every write has completed.  Overlapping destinations are undefined.  sla_hip_decoder_last_timing holds
+ * sla_hip_decode_batch's split with [3] = the emit / zero-fill stage.
+ * Returns 0 when the batch ran; INVALID_ARGUMENT for a NULL decoder, NULL items with num_items > 0, an unknown format
+ * or unknown flag bits (then no item is touched). */
+#define SLA_HIP_PCM_S32_LEFT  0u   /* int32, left-justified: exactly what sla_hip_decode_batch writes */
+#define SLA_HIP_PCM_S32       1u   /* int32, the sample as a bit_per_sample-bit integer: left >> (32 - bps) */
+#define SLA_HIP_PCM_S16       2u   /* int16: left >> 16 (arithmetic; exact for files of <= 16 bits) */
+#define SLA_HIP_PCM_F32       3u   /* float: (float)left * 2^-31, int -> float rounded to nearest even */
+#define SLA_HIP_DEC_ZERO_FILL 1u   /* flag: also write zeros to [output_num_samples, capacity) of each channel */
+typedef struct sla_hip_decode_device_item {
+  const uint8_t* data;            /* in : a whole .sla stream in host memory */
+  void*    dst;                   /* in : device memory */
+  uint64_t channel_stride;        /* in : elements */
+  uint64_t sample_stride;         /* in : elements (>= 1) */
+  uint32_t data_size;             /* in  */
+  uint32_t capacity;              /* in : samples per channel (buffer_num_samples of sla_hip_decode_batch) */
+  uint32_t output_num_samples;    /* out */
+  int32_t  result;                /* out: SLAApiResult */
+} sla_hip_decode_device_item;     /* 48 bytes */
+int sla_hip_decode_batch_device(struct SLADecoder* decoder, sla_hip_decode_device_item* items, uint32_t num_items,
+                                uint32_t sample_format, uint32_t flags, sla_hip_stream_t stream);
+
+/* The emit kernel of sla_hip_decode_batch_device: for every file of the table, mid/side and left-justification of its
+ * region of the planes (as dec_finish_batch), the conversion to sample_format and the store to its own destination;
+ * [done, fill_end) of every channel is written zero in the same launch.  A file with mid_side = 0 and shift = 0 emits
+ * planes that are already finished.  max_samples: the largest max(done, fill_end) of the table (sizes the grid). */
+typedef struct sla_hip_dec_emit {
+  uint64_t plane_off;             /* first sample of the file's region in every plane */
+  uint64_t channel_stride;        /* elements of dst */
+  uint64_t sample_stride;         /* elements of dst */
+  void*    dst;                   /* device */
+  uint32_t done;                  /* samples per channel decoded (read from the planes) */
+  uint32_t fill_end;              /* [done, fill_end) is written zero; <= done: nothing */
+  uint32_t num_channels;          /* of the file; <= 8 unless done == 0 */
+  uint32_t mid_side;              /* 1: planes 0 / 1 are mid / side (two channels only) */
+  uint32_t shift;                 /* left shift of the left-justification: 32 - bits_per_sample + offset_lshift */
+  uint32_t bits_per_sample;       /* SLA_HIP_PCM_S32 shifts the left-justified sample right by 32 - bits_per_sample */
+} sla_hip_dec_emit;               /* 56 bytes */
+int sla_hip_launch_dec_emit_batch(const int32_t* d_planes, uint64_t plane_stride, const sla_hip_dec_emit* d_files,
+                                  uint32_t num_files, uint32_t max_samples, uint32_t sample_format, sla_hip_stream_t stream);
+
 /* ---- (2) whole-file driver ---------------------------------------------- */
 
 /* Per-block results of the last analyze call, copied into caller arrays

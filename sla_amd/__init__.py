@@ -91,6 +91,18 @@ class DecodeItem(C.Structure):
                 ("buffer", C.POINTER(i32p)), ("output_num_samples", C.c_uint32), ("result", C.c_int32)]
 
 
+class DecodeDeviceItem(C.Structure):
+    """sla_hip_decode_device_item (include/sla_hip.h): one file of sla_hip_decode_batch_device"""
+    _fields_ = [("data", u8p), ("dst", C.c_void_p), ("channel_stride", C.c_uint64), ("sample_stride", C.c_uint64),
+                ("data_size", C.c_uint32), ("capacity", C.c_uint32), ("output_num_samples", C.c_uint32),
+                ("result", C.c_int32)]
+
+
+# sample formats and flags of sla_hip_decode_batch_device
+PCM_S32_LEFT, PCM_S32, PCM_S16, PCM_F32 = range(4)
+DEC_ZERO_FILL = 1
+
+
 class SlaError(RuntimeError):
     def __init__(self, code, where):
         name = API_RESULT[code] if 0 <= code < len(API_RESULT) else ("hipError %d" % (-code))
@@ -175,6 +187,10 @@ def lib():
         L.SLAStreamingDecoder_Decode.argtypes = [C.c_void_p, C.POINTER(i32p), C.c_uint32, u32p]
         L.sla_hip_decode_device.argtypes = [C.c_void_p, u8p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, u32p]
         L.sla_hip_decode_batch.argtypes = [C.c_void_p, C.POINTER(DecodeItem), C.c_uint32]
+        L.sla_hip_decode_batch_device.argtypes = [C.c_void_p, C.POINTER(DecodeDeviceItem), C.c_uint32, C.c_uint32,
+                                                  C.c_uint32, C.c_void_p]
+        L.sla_hip_launch_dec_emit_batch.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                    C.c_uint32, C.c_void_p]
         L.sla_hip_launch_dec_bits_x.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                                 C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                                 C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -224,6 +240,8 @@ EXPORTED_SYMBOLS = [
     "SLAEmphasisFilter_DeEmphasisInt32", "sla_hip_launch_dec_deemphasis",
     # batch decode (include/sla_hip.h)
     "sla_hip_decode_batch", "sla_hip_launch_dec_bits_x", "sla_hip_launch_dec_finish_batch",
+    # batch decode into device memory (include/sla_hip.h)
+    "sla_hip_decode_batch_device", "sla_hip_launch_dec_emit_batch",
 ]
 
 
@@ -525,6 +543,9 @@ class Decoder:
         if not self._h:
             raise RuntimeError("SLADecoder_Create failed: no usable HIP device or unsupported capacity "
                                "(libsla_hip has no CPU fallback)")
+        dev = C.c_int(0)
+        self._lib.hipGetDevice(C.byref(dev))
+        self.device_index = dev.value             # the handle's stream lives on the device current at creation
 
     def close(self):
         if getattr(self, "_h", None):
@@ -578,6 +599,100 @@ class Decoder:
         if rc != 0:
             raise SlaError(rc, where)
 
+    _FORMAT_DTYPE = {PCM_S32_LEFT: "int32", PCM_S32: "int32", PCM_S16: "int16", PCM_F32: "float32"}
+
+    def decode_batch_into(self, datas, outs, sample_format, zero_fill=True, stream=None):
+        """many .sla files in host memory -> caller-owned device tensors (sla_hip_decode_batch_device); returns
+        [(result code, samples)], each what decode_batch gives that file with capacity = the tensor's length.
+        outs[i] is a 2-D torch tensor indexed [channel][sample] on the handle's device, with at least as many rows as
+        the file's header has channels; its strides become the item's (an interleaved [n][C] buffer is passed as its
+        transpose .T), its length is the capacity.  Its dtype must match sample_format: int32 for PCM_S32_LEFT and
+        PCM_S32, int16 for PCM_S16, float32 for PCM_F32.  zero_fill: [n, capacity) of every channel is written zero.
+        stream: a torch.cuda.Stream, default the current one; the call is synchronous."""
+        import torch
+        if sample_format not in self._FORMAT_DTYPE:
+            raise ValueError("unknown sample format %r" % (sample_format,))
+        if len(outs) != len(datas):
+            raise ValueError("%d outputs for %d files" % (len(outs), len(datas)))
+        want = getattr(torch, self._FORMAT_DTYPE[sample_format])
+        items = (DecodeDeviceItem * len(datas))()
+        keep = []
+        for i, (data, out) in enumerate(zip(datas, outs)):
+            buf = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
+            if not isinstance(out, torch.Tensor) or out.dim() != 2:
+                raise ValueError("output %d: need a 2-D torch tensor [channel][sample]" % i)
+            if out.dtype != want:
+                raise ValueError("output %d: dtype %s, the format wants %s" % (i, out.dtype, want))
+            if out.device.type != "cuda" or out.device.index != self.device_index:
+                raise ValueError("output %d: on %s, the decoder's device is cuda:%d" % (i, out.device, self.device_index))
+            rc, h = decode_header(buf[:43])         # the header alone: no copy of the stream
+            nch = h.wave_format.num_channels if rc in (0, 11) else 0
+            if out.shape[0] < nch:
+                raise ValueError("output %d: %d rows for a file of %d channels" % (i, out.shape[0], nch))
+            if out.shape[1] > 0xFFFFFFFF or min(out.stride()) < 0 or (out.shape[1] > 1 and out.stride(1) == 0) \
+                    or (nch > 1 and out.stride(0) == 0):
+                raise ValueError("output %d: unsupported shape %s / strides %s" % (i, tuple(out.shape), out.stride()))
+            keep.append(buf)
+            items[i].data = buf.ctypes.data_as(u8p)
+            items[i].data_size = len(buf)
+            items[i].dst = out.data_ptr() or None
+            items[i].channel_stride = out.stride(0)
+            items[i].sample_stride = max(out.stride(1), 1)
+            items[i].capacity = out.shape[1]
+        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        rc = self._lib.sla_hip_decode_batch_device(self._h, items, len(datas), sample_format,
+                                                   DEC_ZERO_FILL if zero_fill else 0, C.c_void_p(st.cuda_stream))
+        self._check(rc, "sla_hip_decode_batch_device")
+        return [(int(items[i].result), int(items[i].output_num_samples)) for i in range(len(datas))]
+
+    def decode_batch_tensor(self, datas, dtype=None, layout="planar", length=None, right_justify=False):
+        """many .sla files -> one padded device tensor on the handle's device: [B][C][L] (planar) or [B][L][C]
+        (interleaved), C the largest channel count among the headers, L `length` or the largest header num_samples.
+        dtype float32 (default; sample * 2^-31), int16 (left-justified >> 16) or int32 (left-justified, or with
+        right_justify the bit_per_sample-bit integer).  Returns (tensor, lengths, results); everything past a file's
+        length, rows past its channel count and files that gave nothing are zero."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype == torch.float32:
+            fmt = PCM_F32
+        elif dtype == torch.int16:
+            fmt = PCM_S16
+        elif dtype == torch.int32:
+            fmt = PCM_S32 if right_justify else PCM_S32_LEFT
+        else:
+            raise ValueError("dtype must be float32, int16 or int32, not %s" % (dtype,))
+        if layout not in ("planar", "interleaved"):
+            raise ValueError("layout must be 'planar' or 'interleaved', not %r" % (layout,))
+        bufs = [d if isinstance(d, np.ndarray) else np.frombuffer(bytes(d), np.uint8) for d in datas]
+        nchs, nsmp = [], []
+        for buf in bufs:
+            rc, h = decode_header(buf[:43])         # the header alone: no copy of the stream
+            given = rc in (0, 11)                      # OK, or a header CRC failure: the fields are delivered
+            nchs.append(h.wave_format.num_channels if given else 0)
+            nsmp.append(h.num_samples if given else 0)
+        B, Cn = len(bufs), max(nchs, default=0)
+        L = int(length) if length is not None else max(nsmp, default=0)
+        if L < 0 or L > 0xFFFFFFFF:
+            raise ValueError("length %d out of range" % L)
+        dev = torch.device("cuda", self.device_index)
+        shape = (B, Cn, L) if layout == "planar" else (B, L, Cn)
+        out = torch.empty(shape, dtype=dtype, device=dev)
+        if out.numel() == 0:
+            # nothing can be written: a one-element stand-in keeps the per-item pointers valid, the results are real
+            scratch = torch.empty(1, dtype=dtype, device=dev)
+            outs = [scratch.as_strided((Cn, L), (1, 1)) for _ in range(B)]
+        else:
+            outs = [out[b] if layout == "planar" else out[b].t() for b in range(B)]
+        got = self.decode_batch_into(bufs, outs, fmt, zero_fill=True)
+        # the zero fill covers [n, L) of the rows a header gave; what no header covers is zeroed here
+        for b in range(B):
+            if nchs[b] < Cn:
+                if layout == "planar":
+                    out[b, nchs[b]:].zero_()
+                else:
+                    out[b, :, nchs[b]:].zero_()
+        return out, [n for _, n in got], [rc for rc, _ in got]
+
     def decode_device(self, data, image_ptr, planes_ptr, plane_stride):
         """decode an image that already lives in device memory into device planes; returns (rc, samples)"""
         buf = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data
@@ -588,7 +703,7 @@ class Decoder:
 
     def last_timing(self):
         """[ms] upload, block walk, kernels (stream events), download, total; number of kernel batches
-        (after decode_batch: of passes)"""
+        (after decode_batch: of passes; after decode_batch_into: [3] is the emit and zero-fill stage)"""
         t = (C.c_float * 6)()
         self._lib.sla_hip_decoder_last_timing(self._h, t)
         return list(t)

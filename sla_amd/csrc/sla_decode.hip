@@ -17,6 +17,7 @@
 //                        :1768-1791 (SLAEmphasisFilter_DeEmphasisInt32)
 //   k_dec_finish         src/SLAUtility.c:415-433 (mid/side -> left/right), src/SLADecoder.c:540-547 (left-justify)
 //   k_dec_finish_batch   the same for every file of a batch pass, packed [file][ch][n] for one copy home
+//   k_dec_emit_batch     the same, converted and stored to every file's own device destination
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -659,6 +660,127 @@ void k_dec_finish_batch(const int32_t* __restrict__ planes, uint64_t stride, uin
   }
 }
 
+// k_dec_emit_batch: k_dec_finish_batch's mid/side and left-justification, then the conversion to the caller's sample
+// format and the store to every file's own destination (sla_hip_decode_batch_device), with [done, fill_end) of every
+// channel written zero in the same pass.  blockIdx.y walks the files, the x dimension their samples.  Three store
+// shapes, chosen per file (wave-uniform): planar (sample_stride 1), a lane takes 4 consecutive samples of each channel,
+// one 16-byte plane load and one 16-byte (int16: 8-byte) store; interleaved stereo (channel_stride 1, sample_stride 2),
+// a lane takes one sample, its two elements in one store; any other strides one element per store.
+template <uint32_t FMT> struct emit_type { typedef int32_t T; };
+template <> struct emit_type<SLA_HIP_PCM_S16> { typedef int16_t T; };
+template <> struct emit_type<SLA_HIP_PCM_F32> { typedef float T; };
+
+template <uint32_t FMT>
+__device__ __forceinline__ typename emit_type<FMT>::T emit_cvt(int32_t left, uint32_t bps)
+{
+  if constexpr (FMT == SLA_HIP_PCM_S32) { return left >> ((32u - bps) & 31u); }
+  else if constexpr (FMT == SLA_HIP_PCM_S16) { return (int16_t)(left >> 16); }
+  else if constexpr (FMT == SLA_HIP_PCM_F32) { return (float)left * 0x1p-31f; }     // exact scaling of the rounded int
+  else { return left; }
+}
+
+// left / right of mid / side, left-justified (src/SLAUtility.c:415-433, as k_dec_finish)
+__device__ __forceinline__ void emit_lr(int32_t m, int32_t side, uint32_t shift, int32_t& l, int32_t& r)
+{
+  const int32_t mid = (int32_t)(((uint32_t)m << 1) | ((uint32_t)side & 1u));
+  l = (int32_t)((uint32_t)((int32_t)((uint32_t)mid + (uint32_t)side) >> 1) << shift);
+  r = (int32_t)((uint32_t)((int32_t)((uint32_t)mid - (uint32_t)side) >> 1) << shift);
+}
+
+// 4 consecutive plane samples from g; those at or past `done` read as zero
+__device__ __forceinline__ void emit_load4(const int32_t* p, uint64_t g, uint32_t done, bool vload, int32_t v[4])
+{
+  typedef int32_t i4 __attribute__((ext_vector_type(4)));
+  if (vload && g + 4 <= done) {
+    const i4 q = *(const i4*)(p + g);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++) { v[k] = (g + k < done) ? p[g + k] : 0; }
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void emit_store4(T* p, uint64_t g, uint64_t lim, const T v[4])
+{
+  typedef T t4 __attribute__((ext_vector_type(4)));
+  if (g + 4 <= lim) {
+    t4 q; q.x = v[0]; q.y = v[1]; q.z = v[2]; q.w = v[3];
+    *(t4*)(p + g) = q;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++) { if (g + k < lim) { p[g + k] = v[k]; } }
+  }
+}
+
+template <uint32_t FMT>
+__global__ __launch_bounds__(256)
+void k_dec_emit_batch(const int32_t* __restrict__ planes, uint64_t stride, const sla_hip_dec_emit* __restrict__ files,
+                      uint32_t num_files)
+{
+  typedef typename emit_type<FMT>::T T;
+  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (uint64_t)gridDim.x * blockDim.x;
+  for (uint32_t f = blockIdx.y; f < num_files; f += gridDim.y) {
+    const sla_hip_dec_emit e = files[f];
+    const int32_t* src = planes + e.plane_off;
+    T* dst = (T*)e.dst;
+    const uint32_t done = e.done, C = e.num_channels, shift = e.shift, bps = e.bits_per_sample;
+    const uint64_t lim = (e.fill_end > done) ? e.fill_end : done, cs = e.channel_stride, ss = e.sample_stride;
+    const bool ms = e.mid_side != 0 && C == 2;
+    if (ss == 1 && (C == 1 || cs % 4 == 0) && ((uintptr_t)dst % (4 * sizeof(T))) == 0) {
+      const bool vload = ((e.plane_off | stride) & 3u) == 0;
+      for (uint64_t g = tid * 4; g < lim; g += nt * 4) {
+        int32_t a[4], b[4];
+        T o[4];
+        if (ms) {
+          emit_load4(src, g, done, vload, a);
+          emit_load4(src + stride, g, done, vload, b);
+#pragma unroll
+          for (int k = 0; k < 4; k++) { int32_t l = 0, r = 0; if (g + k < done) { emit_lr(a[k], b[k], shift, l, r); } a[k] = l; b[k] = r; }
+#pragma unroll
+          for (int k = 0; k < 4; k++) { o[k] = emit_cvt<FMT>(a[k], bps); }
+          emit_store4(dst, g, lim, o);
+#pragma unroll
+          for (int k = 0; k < 4; k++) { o[k] = emit_cvt<FMT>(b[k], bps); }
+          emit_store4(dst + cs, g, lim, o);
+        } else {
+          for (uint32_t c = 0; c < C; c++) {
+            emit_load4(src + (uint64_t)c * stride, g, done, vload, a);
+#pragma unroll
+            for (int k = 0; k < 4; k++) { o[k] = emit_cvt<FMT>((int32_t)((uint32_t)a[k] << shift), bps); }
+            emit_store4(dst + (uint64_t)c * cs, g, lim, o);
+          }
+        }
+      }
+    } else if (C == 2 && cs == 1 && ss == 2 && ((uintptr_t)dst % (2 * sizeof(T))) == 0) {
+      typedef T t2 __attribute__((ext_vector_type(2)));
+      for (uint64_t i = tid; i < lim; i += nt) {
+        int32_t l = 0, r = 0;
+        if (i < done) {
+          if (ms) { emit_lr(src[i], src[stride + i], shift, l, r); }
+          else { l = (int32_t)((uint32_t)src[i] << shift); r = (int32_t)((uint32_t)src[stride + i] << shift); }
+        }
+        t2 q; q.x = emit_cvt<FMT>(l, bps); q.y = emit_cvt<FMT>(r, bps);
+        *(t2*)(dst + 2 * i) = q;
+      }
+    } else {
+      for (uint64_t i = tid; i < lim; i += nt) {
+        if (ms && i < done) {
+          int32_t l, r;
+          emit_lr(src[i], src[stride + i], shift, l, r);
+          dst[i * ss] = emit_cvt<FMT>(l, bps);
+          dst[cs + i * ss] = emit_cvt<FMT>(r, bps);
+        } else {
+          for (uint32_t c = 0; c < C; c++) {
+            const int32_t left = (i < done) ? (int32_t)((uint32_t)src[(uint64_t)c * stride + i] << shift) : 0;
+            dst[(uint64_t)c * cs + i * ss] = emit_cvt<FMT>(left, bps);
+          }
+        }
+      }
+    }
+  }
+}
+
 // De-emphasis as a pass of its own (per-call API): y[n] = x[n] + ((y[n-1] * (2^s - 1)) >> s), y[-1] = previous.
 // A one-tap recurrence through a truncating shift: strictly serial, one lane.
 __global__ __launch_bounds__(64)
@@ -824,6 +946,25 @@ extern "C" int sla_hip_launch_dec_finish_batch(const int32_t* d_planes, uint64_t
   const uint32_t gy = (num_files < 65535u) ? num_files : 65535u;
   hipLaunchKernelGGL(k_dec_finish_batch, dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, d_planes, plane_stride, num_channels,
                      d_files, num_files, d_out);
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_dec_emit_batch(const int32_t* d_planes, uint64_t plane_stride, const sla_hip_dec_emit* d_files,
+                                             uint32_t num_files, uint32_t max_samples, uint32_t sample_format, sla_hip_stream_t stream)
+{
+  if (d_planes == nullptr || d_files == nullptr || sample_format > SLA_HIP_PCM_F32) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_files == 0 || max_samples == 0) { return 0; }
+  // a workgroup row covers 1024 samples of a planar file (256 lanes x 4); longer files and the other shapes grid-stride
+  uint32_t gx = (max_samples + 1023) / 1024;
+  if (gx > 1024) { gx = 1024; }
+  const dim3 grid(gx, (num_files < 65535u) ? num_files : 65535u), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  switch (sample_format) {
+    case SLA_HIP_PCM_S32_LEFT: hipLaunchKernelGGL(k_dec_emit_batch<SLA_HIP_PCM_S32_LEFT>, grid, block, 0, st, d_planes, plane_stride, d_files, num_files); break;
+    case SLA_HIP_PCM_S32:      hipLaunchKernelGGL(k_dec_emit_batch<SLA_HIP_PCM_S32>, grid, block, 0, st, d_planes, plane_stride, d_files, num_files); break;
+    case SLA_HIP_PCM_S16:      hipLaunchKernelGGL(k_dec_emit_batch<SLA_HIP_PCM_S16>, grid, block, 0, st, d_planes, plane_stride, d_files, num_files); break;
+    default:                   hipLaunchKernelGGL(k_dec_emit_batch<SLA_HIP_PCM_F32>, grid, block, 0, st, d_planes, plane_stride, d_files, num_files); break;
+  }
   return hip_rc(hipGetLastError());
 }
 

@@ -32,6 +32,7 @@ struct SLADecoder {
   uint32_t                  status_flag;
   hipStream_t               stream;
   hipEvent_t                ev[2];
+  hipEvent_t                ev_order;                   /* sla_hip_decode_batch_device: the caller's stream, recorded */
   dbuf_t                    d_image, d_planes, d_blocks, d_info, d_chan, d_kint;
   dbuf_t                    d_ftab, d_out;              /* sla_hip_decode_batch: file table, packed samples */
   hbuf_t                    h_img, h_ptab, h_out;       /* sla_hip_decode_batch: page-locked staging */
@@ -133,6 +134,7 @@ void SLADecoder_Destroy(struct SLADecoder* d)
   if (d->h_blocks != NULL) { (void)hipHostFree(d->h_blocks); }
   if (d->h_info != NULL) { (void)hipHostFree(d->h_info); }
   (void)hipEventDestroy(d->ev[0]); (void)hipEventDestroy(d->ev[1]);
+  if (d->ev_order != NULL) { (void)hipEventDestroy(d->ev_order); }
   (void)hipStreamDestroy(d->stream);
   free(d);
 }
@@ -271,6 +273,14 @@ static int format_verdict(const dec_format_t* f)
 }
 static int lms_order_ok(uint32_t lms) { return (lms == 4 || lms == 8 || lms == 16 || lms == 32); }
 
+/* the plane stride decode_run gives the handle's own planes */
+static uint64_t run_plane_stride(uint32_t total, uint32_t buffer_num_samples)
+{
+  const uint64_t want = (uint64_t)total + 65535u;
+  const uint64_t stride = (buffer_num_samples < want) ? buffer_num_samples : want;
+  return (stride == 0) ? 1 : stride;
+}
+
 /* The decode proper.  `host_data` is always the stream in host memory (the walk reads it); the image in device
  * memory is either uploaded from it or supplied by the caller, the planes likewise are the handle's or the caller's. */
 static SLAApiResult decode_run(struct SLADecoder* d, const uint8_t* data, uint32_t data_size, const uint32_t* d_image_user,
@@ -319,9 +329,7 @@ static SLAApiResult decode_run(struct SLADecoder* d, const uint8_t* data, uint32
   }
   if (d_planes_user != NULL) { d_planes = d_planes_user; stride = stride_user; }
   else {
-    const uint64_t want = (uint64_t)total + 65535u;
-    stride = (buffer_num_samples < want) ? buffer_num_samples : want;
-    if (stride == 0) { stride = 1; }
+    stride = run_plane_stride(total, buffer_num_samples);
     if (dbuf_reserve(&d->d_planes, (size_t)stride * C * sizeof(int32_t)) != 0) { return SLA_APIRESULT_NG; }
     d_planes = (int32_t*)d->d_planes.ptr;
   }
@@ -489,10 +497,56 @@ static int same_launch(const dec_format_t* a, const dec_format_t* b)
 #define BCHK(call) do { if ((call) != hipSuccess) { return -1; } } while (0)
 #define BRC(call)  do { if ((call) != 0) { return -1; } } while (0)
 
+/* sla_hip_decode_batch_device: where the samples go.  The internal items (sla_hip_decode_item, buffer NULL) are the
+ * caller's device items one to one. */
+#define DEV_PENDING 0u     /* not (yet) in a pass: a failed header gets the zero fill alone */
+#define DEV_REFUSED 1u     /* refused before its header: nothing written */
+#define DEV_DECODED 2u     /* in a pass or decoded on its own: emitted there */
+typedef struct {
+  const sla_hip_decode_device_item* items;
+  uint32_t  format, zero_fill;
+  uint8_t*  state;          /* DEV_* per item */
+  uint32_t* chans;          /* per item: the channel count its header gave, 0 when none */
+} dev_out_t;
+
+/* one emit table entry for item `it` (0 when there is nothing to write) */
+static uint32_t emit_entry(sla_hip_dec_emit* e, const sla_hip_decode_device_item* it, uint32_t zero_fill, uint64_t plane_off,
+                           uint32_t done, uint32_t C, uint32_t ms, uint32_t shift, uint32_t bps, uint32_t* max_lim)
+{
+  const uint32_t fill_end = zero_fill ? it->capacity : 0, lim = (fill_end > done) ? fill_end : done;
+  if (lim == 0 || C == 0) { return 0; }
+  e->plane_off = plane_off; e->channel_stride = it->channel_stride; e->sample_stride = it->sample_stride; e->dst = it->dst;
+  e->done = done; e->fill_end = fill_end; e->num_channels = C; e->mid_side = ms; e->shift = shift; e->bits_per_sample = bps;
+  if (lim > *max_lim) { *max_lim = lim; }
+  return 1;
+}
+
+/* the emit table over in one copy and the emit kernel over it, on the handle's stream, waited for; its kernel time is
+ * added to *kernel_ms */
+static int emit_run(struct SLADecoder* d, const int32_t* planes, uint64_t stride, const sla_hip_dec_emit* et, uint32_t ne,
+                    uint32_t max_lim, uint32_t format, float* kernel_ms)
+{
+  float ms = 0.0f;
+  if (ne == 0) { return 0; }
+  if (dbuf_reserve(&d->d_ftab, sizeof(*et) * ne) != 0) { return -1; }
+  if (planes == NULL) {               /* a table of zero fills only: the kernel reads no plane, but takes a valid pointer */
+    if (dbuf_reserve(&d->d_planes, 256) != 0) { return -1; }
+    planes = (const int32_t*)d->d_planes.ptr;
+  }
+  BCHK(hipMemcpyAsync(d->d_ftab.ptr, et, sizeof(*et) * ne, hipMemcpyHostToDevice, d->stream));
+  BCHK(hipEventRecord(d->ev[0], d->stream));
+  BRC(sla_hip_launch_dec_emit_batch(planes, stride, (const sla_hip_dec_emit*)d->d_ftab.ptr, ne, max_lim, format, d->stream));
+  BCHK(hipEventRecord(d->ev[1], d->stream));
+  BCHK(hipStreamSynchronize(d->stream));
+  if (hipEventElapsedTime(&ms, d->ev[0], d->ev[1]) == hipSuccess) { *kernel_ms += ms; }
+  return 0;
+}
+
 /* One pass: files[0, nf), all with the same launch parameters, blocks d->h_blocks[files[0].first ...] contiguous.
+ * dev != NULL: the samples go to the caller's device destinations through the emit kernel, nothing comes home.
  * Returns -1 on a device or allocation failure. */
 static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t* files, uint32_t nf, copy_list_t* cl,
-                      double* t_up, double* t_down, float* kernel_ms)
+                      const dev_out_t* dev, double* t_up, double* t_down, float* kernel_ms)
 {
   const dec_format_t* f = &files[0].f;
   const uint32_t C = f->C, first = files[0].first, cap_n = d->cfg.max_num_block_samples;
@@ -517,7 +571,7 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
    *      the block table -- positions in the pass, then every block's end of stream -- likewise */
   t = now_ms();
   if (hbuf_reserve(&d->h_img, img_bytes + 16) != 0 || dbuf_reserve(&d->d_image, img_bytes + 16) != 0
-      || hbuf_reserve(&d->h_ptab, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb + sizeof(sla_hip_dec_file) * nf) != 0
+      || hbuf_reserve(&d->h_ptab, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb + sizeof(sla_hip_dec_emit) * nf) != 0
       || dbuf_reserve(&d->d_blocks, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb) != 0
       || dbuf_reserve(&d->d_info, sizeof(sla_hip_dec_info) * nb) != 0
       || dbuf_reserve(&d->d_chan, sizeof(sla_hip_dec_chan) * (size_t)nb * C) != 0
@@ -587,7 +641,7 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
       continue;
     }
     it->result = result;
-    if (done[i] > 0) {
+    if (done[i] > 0 && dev == NULL) {
       ft[nfin].plane_off = files[i].plane_off; ft[nfin].out_off = out_elems; ft[nfin].num_samples = done[i];
       ft[nfin].mid_side = f->ms; ft[nfin].shift = 32u - f->bps + f->lshift; ft[nfin].reserved = 0;
       out_elems += (uint64_t)done[i] * C;
@@ -596,9 +650,19 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
     }
   }
 
-  /* ---- mid/side and left-justification of every file, packed, home in one copy, into the caller's planes */
+  /* ---- mid/side and left-justification of every file, packed, home in one copy, into the caller's planes; or, for
+   *      device destinations, converted and stored there by the emit kernel, zero fill included */
   t = now_ms();
-  if (nfin > 0) {
+  if (dev != NULL) {
+    sla_hip_dec_emit* et = (sla_hip_dec_emit*)(tend + nb);
+    uint32_t ne = 0, max_lim = 0;
+    for (i = 0; i < nf; i++) {
+      if (files[i].alone) { continue; }
+      ne += emit_entry(et + ne, &dev->items[files[i].item], dev->zero_fill, files[i].plane_off, done[i], C, f->ms,
+                       32u - f->bps + f->lshift, f->bps, &max_lim);
+    }
+    if (emit_run(d, (const int32_t*)d->d_planes.ptr, span, et, ne, max_lim, dev->format, kernel_ms) != 0) { free(done); return -1; }
+  } else if (nfin > 0) {
     uint64_t o = 0;
     if (dbuf_reserve(&d->d_out, sizeof(int32_t) * out_elems) != 0 || hbuf_reserve(&d->h_out, sizeof(int32_t) * out_elems) != 0) { free(done); return -1; }
     if (hipMemcpyAsync(d->d_ftab.ptr, ft, sizeof(sla_hip_dec_file) * nfin, hipMemcpyHostToDevice, d->stream) != hipSuccess
@@ -628,7 +692,7 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
   return 0;
 }
 
-int sla_hip_decode_batch(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t num_items)
+static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t num_items, const dev_out_t* dev)
 {
   bfile_t* files;
   copy_list_t cl;
@@ -639,7 +703,6 @@ int sla_hip_decode_batch(struct SLADecoder* d, sla_hip_decode_item* items, uint3
   float kernel_ms = 0.0f;
   double t0 = now_ms(), t_walk = 0.0, t_up = 0.0, t_down = 0.0, t;
 
-  if (d == NULL || (items == NULL && num_items > 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   memset(d->timing, 0, sizeof(d->timing));
   if (num_items == 0) { return 0; }
   files = (bfile_t*)calloc(num_items, sizeof(*files));
@@ -655,12 +718,13 @@ int sla_hip_decode_batch(struct SLADecoder* d, sla_hip_decode_item* items, uint3
     int verdict;
     uint32_t c;
     it->output_num_samples = 0;
-    if (it->data == NULL || it->buffer == NULL) { it->result = SLA_APIRESULT_INVALID_ARGUMENT; continue; }
+    if (dev != NULL ? dev->state[i] == DEV_REFUSED : (it->data == NULL || it->buffer == NULL)) { it->result = SLA_APIRESULT_INVALID_ARGUMENT; continue; }
     if ((ret = file_format(d, it->data, it->data_size, &f)) != SLA_APIRESULT_OK) { it->result = ret; continue; }
     if ((verdict = format_verdict(&f)) >= 0) { it->result = verdict; continue; }
     it->result = SLA_APIRESULT_OK;
     files[nf].item = i; files[nf].f = f;
-    for (c = 0; c < f.C; c++) { if (it->buffer[c] == NULL) { files[nf].alone = 1; } }     /* fails there as DecodeWhole does */
+    if (dev != NULL) { dev->state[i] = DEV_DECODED; }
+    else { for (c = 0; c < f.C; c++) { if (it->buffer[c] == NULL) { files[nf].alone = 1; } } }     /* fails there as DecodeWhole does */
     nf++;
   }
   wf_after = d->wave_format; ep_after = d->encode_param; flag_after = d->status_flag;
@@ -694,16 +758,40 @@ int sla_hip_decode_batch(struct SLADecoder* d, sla_hip_decode_item* items, uint3
       if (p1 > p0 && (smp + s1 > SLA_HIP_DEC_BATCH_PASS || bytes + b1 > DEC_BATCH_PASS_BYTES)) { break; }
       smp += s1; bytes += b1; p1++;
     }
-    if (batch_pass(d, items, files + p0, p1 - p0, &cl, &t_up, &t_down, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+    if (batch_pass(d, items, files + p0, p1 - p0, &cl, dev, &t_up, &t_down, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; goto out; }
     passes++;
     p0 = p1;
   }
 
-  /* ---- files decoded on their own */
+  /* ---- files decoded on their own; for device destinations decode_run leaves the finished planes in the handle's
+   *      scratch and the emit kernel takes them from there */
   for (i = 0; i < nf; i++) {
     sla_hip_decode_item* it = &items[files[i].item];
     if (!files[i].alone) { continue; }
     it->result = decode_run(d, it->data, it->data_size, NULL, NULL, 0, it->buffer, it->buffer_num_samples, &it->output_num_samples, NULL);
+    if (dev != NULL) {
+      sla_hip_dec_emit e;
+      uint32_t max_lim = 0, ne;
+      t = now_ms();
+      ne = emit_entry(&e, &dev->items[files[i].item], dev->zero_fill, 0, it->output_num_samples, files[i].f.C, 0, 0, files[i].f.bps, &max_lim);
+      if (emit_run(d, (const int32_t*)d->d_planes.ptr, run_plane_stride(files[i].f.total, it->buffer_num_samples), &e, ne, max_lim,
+                   dev->format, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+      t_down += now_ms() - t;
+    }
+  }
+
+  /* ---- device destinations of items whose header gave a channel count but that were not decoded: the zero fill */
+  if (dev != NULL && dev->zero_fill) {
+    sla_hip_dec_emit* et = (sla_hip_dec_emit*)calloc(num_items, sizeof(*et));
+    uint32_t ne = 0, max_lim = 0;
+    if (et == NULL) { rc = SLA_APIRESULT_NG; goto out; }
+    t = now_ms();
+    for (i = 0; i < num_items; i++) {
+      if (dev->state[i] == DEV_PENDING) { ne += emit_entry(et + ne, &dev->items[i], 1, 0, 0, dev->chans[i], 0, 0, 32, &max_lim); }
+    }
+    if (emit_run(d, NULL, 1, et, ne, max_lim, dev->format, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; }
+    free(et);
+    t_down += now_ms() - t;
   }
 
 out:
@@ -712,6 +800,82 @@ out:
   d->timing[4] = (float)(now_ms() - t0); d->timing[5] = (float)passes;
   free(cl.v);
   free(files);
+  return rc;
+}
+
+int sla_hip_decode_batch(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t num_items)
+{
+  if (d == NULL || (items == NULL && num_items > 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  return batch_run(d, items, num_items, NULL);
+}
+
+/* the channel count a file's header gives (its fields are delivered also when only the header CRC fails), 0 when none */
+static uint32_t header_channels(const uint8_t* data, uint32_t data_size)
+{
+  struct SLAHeaderInfo h;
+  SLAApiResult r;
+  if (data == NULL) { return 0; }
+  r = SLADecoder_DecodeHeader(data, data_size, &h);
+  return (r == SLA_APIRESULT_OK || r == SLA_APIRESULT_DETECT_DATA_CORRUPTION) ? h.wave_format.num_channels : 0;
+}
+
+/* 1 when item `it` may be written: the argument checks of sla_hip_decode_batch_device, before any device work.  C is
+ * the header's channel count; the region is [0, C) x [0, capacity) of elements of esize bytes.  A host pointer never
+ * passes: the runtime must report dst as device memory, and the region must lie inside dst's allocation. */
+static int dst_region_ok(const sla_hip_decode_device_item* it, uint32_t C, uint64_t esize)
+{
+  hipPointerAttribute_t at;
+  hipDeviceptr_t base = NULL;
+  size_t size = 0;
+  uint64_t bytes = 0, a, b, last, end;
+  if (it->data == NULL || it->dst == NULL || it->sample_stride == 0 || (C > 1 && it->channel_stride == 0)) { return 0; }
+  if ((uintptr_t)it->dst % esize != 0) { return 0; }
+  if (C > 0 && it->capacity > 0) {
+    if (__builtin_mul_overflow((uint64_t)(C - 1), it->channel_stride, &a) || __builtin_mul_overflow((uint64_t)(it->capacity - 1), it->sample_stride, &b)
+        || __builtin_add_overflow(a, b, &last) || __builtin_add_overflow(last, (uint64_t)1, &last) || __builtin_mul_overflow(last, esize, &bytes)
+        || __builtin_add_overflow((uint64_t)(uintptr_t)it->dst, bytes, &end)) { return 0; }
+  }
+  memset(&at, 0, sizeof(at));
+  if (hipPointerGetAttributes(&at, it->dst) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  if (at.type != hipMemoryTypeDevice) { return 0; }
+  if (bytes > 0) {
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)it->dst) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if ((uintptr_t)it->dst < (uintptr_t)base || end > (uint64_t)(uintptr_t)base + size) { return 0; }
+  }
+  return 1;
+}
+
+int sla_hip_decode_batch_device(struct SLADecoder* d, sla_hip_decode_device_item* items, uint32_t num_items,
+                                uint32_t sample_format, uint32_t flags, sla_hip_stream_t stream)
+{
+  sla_hip_decode_item* bi;
+  dev_out_t dev;
+  uint32_t i;
+  int rc = 0;
+  if (d == NULL || (items == NULL && num_items > 0) || sample_format > SLA_HIP_PCM_F32 || (flags & ~SLA_HIP_DEC_ZERO_FILL) != 0) {
+    return SLA_APIRESULT_INVALID_ARGUMENT;
+  }
+  if (num_items == 0) { memset(d->timing, 0, sizeof(d->timing)); return 0; }
+  bi = (sla_hip_decode_item*)calloc(num_items, sizeof(*bi));
+  dev.items = items; dev.format = sample_format; dev.zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u;
+  dev.state = (uint8_t*)calloc(num_items, 1);
+  dev.chans = (uint32_t*)calloc(num_items, sizeof(uint32_t));
+  if (bi == NULL || dev.state == NULL || dev.chans == NULL) { rc = SLA_APIRESULT_NG; goto out; }
+  for (i = 0; i < num_items; i++) {
+    const sla_hip_decode_device_item* it = &items[i];
+    bi[i].data = it->data; bi[i].data_size = it->data_size; bi[i].buffer_num_samples = it->capacity; bi[i].buffer = NULL;
+    dev.chans[i] = header_channels(it->data, it->data_size);
+    if (!dst_region_ok(it, dev.chans[i], (sample_format == SLA_HIP_PCM_S16) ? 2u : 4u)) { dev.state[i] = DEV_REFUSED; }
+  }
+  /* nothing is written before the caller's stream has reached this call */
+  if (d->ev_order == NULL && hipEventCreateWithFlags(&d->ev_order, hipEventDisableTiming) != hipSuccess) { d->ev_order = NULL; rc = SLA_APIRESULT_NG; goto out; }
+  if (hipEventRecord(d->ev_order, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(d->stream, d->ev_order, 0) != hipSuccess) {
+    rc = SLA_APIRESULT_NG; goto out;
+  }
+  rc = batch_run(d, bi, num_items, &dev);
+  for (i = 0; i < num_items; i++) { items[i].result = bi[i].result; items[i].output_num_samples = bi[i].output_num_samples; }
+out:
+  free(bi); free(dev.state); free(dev.chans);
   return rc;
 }
 
