@@ -645,6 +645,67 @@ int sla_hip_analyze_batch_device(struct SLAEncoder* encoder, const int32_t* d_pc
                                  const uint32_t* file_start, const uint32_t* file_samples, uint32_t num_files,
                                  uint32_t* file_lshift, float* timing_ms);
 
+/* Many files whose PCM already lives in caller-owned DEVICE memory, encoded to .sla bytes in host memory: the encode-side
+ * mirror of sla_hip_decode_batch_device.  Sample i of channel c of an item is the element c * channel_stride +
+ * i * sample_stride of src, for c < C (the handle's channel count) and i < num_samples.  With bps the handle's
+ * bit_per_sample, sample_format turns the element v into the left-justified word L of the file's plane:
+ *   SLA_HIP_PCM_S32_LEFT  int32  L = v
+ *   SLA_HIP_PCM_S32       int32  L = (uint32)v << (32 - bps); any v outside [-2^(bps-1), 2^(bps-1) - 1] refuses the item
+ *   SLA_HIP_PCM_S16       int16  L = (uint32)v << 16
+ *   SLA_HIP_PCM_F32       float  L = q << (32 - bps), q = rint(v * 2^(bps-1)) (ties to even) saturated to
+ *                                [-2^(bps-1), 2^(bps-1) - 1], +-inf saturate; any NaN refuses the item
+ * Every item gets exactly the result, output_size and bytes that sla_hip_encode_batch on this handle gives for host planes
+ * holding those L words: low bits below bps give INVALID_ARGUMENT, a buffer too small INSUFFICIENT_BUFFER_SIZE, an empty
+ * file the 43-byte header, and every file has its own offset_lshift.  A refused item gets INVALID_ARGUMENT, output_size 0
+ * and nothing in its data.  Round trips are exact: the SLA_HIP_PCM_S32_LEFT or SLA_HIP_PCM_S32 output of
+ * sla_hip_decode_batch_device fed back in the same format, its SLA_HIP_PCM_S16 output when bps <= 16, its SLA_HIP_PCM_F32
+ * output when bps <= 24.
+ * Per item, on the host before any device work (nothing is then read from its src), INVALID_ARGUMENT for: NULL data, NULL
+ * src with num_samples > 0, sample_stride == 0, channel_stride == 0 with more than one channel, src not aligned to the
+ * element size, a region whose byte extent overflows, a src the runtime does not report as device memory of the handle's
+ * device (host and page-locked host memory included), a region outside src's allocation.
+ * Passes are those of sla_hip_encode_batch (files back to back on SLA_HIP_PREPASS_TILE starts, at most 2^28 samples per
+ * channel, a larger file in a pass of its own), run in one piece -- no worker lanes: they overlap host uploads, and there
+ * are none -- with one sla_hip_launch_enc_ingest_batch per pass in place of the staging and upload.  The handle's stream
+ * waits on an event recorded on `stream` (NULL: the null stream) before the first read; the call returns when every byte
+ * is in the host buffers and no kernel reads src any more.  src is never written.  Afterwards the handle is where
+ * sla_hip_encode_batch leaves it: no analysis to trace or pack, offset_lshift of the last pass.
+ * Returns 0 when the batch ran; INVALID_ARGUMENT for a NULL encoder, NULL items with num_items > 0 or an unknown format,
+ * the code sla_hip_encode_batch gives for parameters that are not set, EXCEED_HANDLE_CAPACITY for a num_samples above the
+ * pass cap -- then no item is touched. */
+typedef struct sla_hip_encode_device_item {
+  const void* src;                /* in : device memory */
+  uint64_t channel_stride;        /* in : elements */
+  uint64_t sample_stride;         /* in : elements (>= 1) */
+  uint8_t* data;                  /* in : HOST buffer that receives the .sla bytes */
+  uint32_t num_samples;           /* in : samples per channel */
+  uint32_t data_size;             /* in : capacity of data */
+  uint32_t output_size;           /* out */
+  int32_t  result;                /* out: SLAApiResult */
+} sla_hip_encode_device_item;     /* 48 bytes */
+int sla_hip_encode_batch_device(struct SLAEncoder* encoder, sla_hip_encode_device_item* items, uint32_t num_items,
+                                uint32_t sample_format, sla_hip_stream_t stream);
+
+/* The ingest kernel of sla_hip_encode_batch_device: for every file of the table, its num_samples samples of each of
+ * num_channels channels are read from src, converted as sample_format says (bits_per_sample = bps of the table above) and
+ * stored to d_planes[c * plane_stride + plane_off + i]; [num_samples, fill_end) of every plane is written zero in the same
+ * launch.  Refusals only the samples can show are ORed into d_error[file] (zeroed by the caller): 1 = an SLA_HIP_PCM_S32
+ * element out of range, 2 = an SLA_HIP_PCM_F32 NaN.  plane_off, plane_stride and d_planes aligned to 4 words give 16-byte
+ * plane stores.  max_samples: the largest max(num_samples, fill_end) of the table (sizes the grid). */
+typedef struct sla_hip_enc_ingest {
+  uint64_t plane_off;             /* first sample of the file's region in every plane */
+  uint64_t channel_stride;        /* elements of src */
+  uint64_t sample_stride;         /* elements of src */
+  const void* src;                /* device */
+  uint32_t num_samples;           /* samples per channel read from src */
+  uint32_t fill_end;              /* [num_samples, fill_end) is written zero; <= num_samples: nothing */
+  uint32_t bits_per_sample;
+  uint32_t reserved;
+} sla_hip_enc_ingest;             /* 48 bytes */
+int sla_hip_launch_enc_ingest_batch(const sla_hip_enc_ingest* d_files, uint32_t num_files, uint32_t max_samples,
+                                    uint32_t num_channels, uint32_t sample_format, int32_t* d_planes, uint64_t plane_stride,
+                                    uint32_t* d_error, sla_hip_stream_t stream);
+
 /* ---- one file, several GPUs ------------------------------------------------------------------------------
  * Blocks are independent (every filter and the coder reset per block, src/SLAEncoder.c:594-659), so the super-frames
  * of ONE file shard over the GPUs of a node, one process and one encoder handle per GPU.  Three facts of the whole

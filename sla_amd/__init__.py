@@ -98,7 +98,13 @@ class DecodeDeviceItem(C.Structure):
                 ("result", C.c_int32)]
 
 
-# sample formats and flags of sla_hip_decode_batch_device
+class EncodeDeviceItem(C.Structure):
+    """sla_hip_encode_device_item (include/sla_hip.h): one file of sla_hip_encode_batch_device"""
+    _fields_ = [("src", C.c_void_p), ("channel_stride", C.c_uint64), ("sample_stride", C.c_uint64), ("data", u8p),
+                ("num_samples", C.c_uint32), ("data_size", C.c_uint32), ("output_size", C.c_uint32), ("result", C.c_int32)]
+
+
+# sample formats of sla_hip_decode_batch_device / sla_hip_encode_batch_device, flag of the former
 PCM_S32_LEFT, PCM_S32, PCM_S16, PCM_F32 = range(4)
 DEC_ZERO_FILL = 1
 
@@ -164,6 +170,9 @@ def lib():
         L.sla_hip_encode_batch.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_uint32]
         L.sla_hip_analyze_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, u32p, u32p, C.c_uint32,
                                                    u32p, C.POINTER(C.c_float)]
+        L.sla_hip_encode_batch_device.argtypes = [C.c_void_p, C.POINTER(EncodeDeviceItem), C.c_uint32, C.c_uint32, C.c_void_p]
+        L.sla_hip_launch_enc_ingest_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                      C.c_uint64, C.c_void_p, C.c_void_p]
         L.SLADecoder_Create.restype = C.c_void_p
         L.SLADecoder_Create.argtypes = [C.POINTER(SLADecoderConfig)]
         L.SLADecoder_Destroy.argtypes = [C.c_void_p]
@@ -242,6 +251,8 @@ EXPORTED_SYMBOLS = [
     "sla_hip_decode_batch", "sla_hip_launch_dec_bits_x", "sla_hip_launch_dec_finish_batch",
     # batch decode into device memory (include/sla_hip.h)
     "sla_hip_decode_batch_device", "sla_hip_launch_dec_emit_batch",
+    # batch encode from device memory (include/sla_hip.h)
+    "sla_hip_encode_batch_device", "sla_hip_launch_enc_ingest_batch",
 ]
 
 
@@ -297,6 +308,9 @@ class Encoder:
         self._h = self._lib.SLAEncoder_Create(C.byref(cfg))
         if not self._h:
             raise RuntimeError("SLAEncoder_Create failed: no usable HIP device (libsla_hip has no CPU fallback)")
+        dev = C.c_int(0)
+        self._lib.hipGetDevice(C.byref(dev))
+        self.device_index = dev.value             # the handle's stream lives on the device current at creation
         self.num_channels = 0
         self.order = 0
         self.ltm_order = 0
@@ -376,6 +390,83 @@ class Encoder:
         if outs is not None:
             return [(int(items[i].result), keep[i][2][:items[i].output_size]) for i in range(len(pcms))]
         return [(int(items[i].result), keep[i][2][:items[i].output_size].tobytes()) for i in range(len(pcms))]
+
+    def encode_batch_from(self, srcs, sample_format, capacities=None, outs=None, stream=None):
+        """many files whose PCM already lives in device tensors -> .sla bytes (sla_hip_encode_batch_device); returns
+        [(result code, bytes)], each what encode_batch gives for the left-justified words the format's conversion makes
+        (include/sla_hip.h).  srcs[i] is a 2-D torch tensor [channel][sample] on the handle's device with at least as many
+        rows as the handle has channels; its strides become the item's (an interleaved [n][C] buffer is passed as its
+        transpose .T), its length is the file's.  Its dtype must match sample_format: int32 for PCM_S32_LEFT and PCM_S32,
+        int16 for PCM_S16, float32 for PCM_F32.  capacities / outs as in encode_batch.  stream: a torch.cuda.Stream, default
+        the current one; the call is synchronous and never writes the tensors."""
+        import torch
+        if sample_format not in Decoder._FORMAT_DTYPE:
+            raise ValueError("unknown sample format %r" % (sample_format,))
+        if outs is not None and len(outs) != len(srcs):
+            raise ValueError("%d outputs for %d files" % (len(outs), len(srcs)))
+        want = getattr(torch, Decoder._FORMAT_DTYPE[sample_format])
+        items = (EncodeDeviceItem * len(srcs))()
+        bufs = []
+        for i, x in enumerate(srcs):
+            if not isinstance(x, torch.Tensor) or x.dim() != 2:
+                raise ValueError("source %d: need a 2-D torch tensor [channel][sample]" % i)
+            if x.dtype != want:
+                raise ValueError("source %d: dtype %s, the format wants %s" % (i, x.dtype, want))
+            if x.device.type != "cuda" or x.device.index != self.device_index:
+                raise ValueError("source %d: on %s, the encoder's device is cuda:%d" % (i, x.device, self.device_index))
+            if x.shape[0] < self.num_channels:
+                raise ValueError("source %d: %d rows for %d channels" % (i, x.shape[0], self.num_channels))
+            n = x.shape[1]
+            if n > 0xFFFFFFFF or min(x.stride()) < 0:
+                raise ValueError("source %d: unsupported shape %s / strides %s" % (i, tuple(x.shape), x.stride()))
+            if outs is not None:
+                buf, cap = outs[i], min(len(outs[i]), 0xFFFFFFFF)
+            else:
+                cap = capacities[i] if capacities is not None else 8 * self.num_channels * n + 65536
+                buf = np.empty(cap, np.uint8)
+            bufs.append(buf)
+            cs, ss = x.stride(0), x.stride(1)
+            if n <= 1:                                  # strides that are never stepped along: any valid value
+                ss = max(ss, 1)
+                cs = max(cs, 1) if n == 0 else cs
+            items[i].src = x.data_ptr() or None
+            items[i].channel_stride = cs
+            items[i].sample_stride = ss
+            items[i].num_samples = n
+            items[i].data = buf.ctypes.data_as(u8p)
+            items[i].data_size = cap
+        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        self._check(self._lib.sla_hip_encode_batch_device(self._h, items, len(srcs), sample_format, C.c_void_p(st.cuda_stream)),
+                    "sla_hip_encode_batch_device")
+        if outs is not None:
+            return [(int(items[i].result), bufs[i][:items[i].output_size]) for i in range(len(srcs))]
+        return [(int(items[i].result), bufs[i][:items[i].output_size].tobytes()) for i in range(len(srcs))]
+
+    def encode_batch_tensor(self, x, lengths=None, layout="planar", right_justify=False):
+        """a padded batch in one device tensor -> .sla bytes, the mirror of Decoder.decode_batch_tensor: x is [B][C][L]
+        (planar) or [B][L][C] (interleaved) on the handle's device, file b its first lengths[b] <= L samples (default L).
+        The dtype picks the format: float32 -> PCM_F32, int16 -> PCM_S16, int32 -> PCM_S32_LEFT, or PCM_S32 with
+        right_justify.  Returns encode_batch_from's [(result code, bytes)];
+        enc.encode_batch_tensor(*dec.decode_batch_tensor(datas)[:2]) gives the files back."""
+        import torch
+        if not isinstance(x, torch.Tensor) or x.dim() != 3:
+            raise ValueError("need a 3-D torch tensor [B][C][L] or [B][L][C]")
+        if x.dtype == torch.float32:
+            fmt = PCM_F32
+        elif x.dtype == torch.int16:
+            fmt = PCM_S16
+        elif x.dtype == torch.int32:
+            fmt = PCM_S32 if right_justify else PCM_S32_LEFT
+        else:
+            raise ValueError("dtype must be float32, int16 or int32, not %s" % (x.dtype,))
+        if layout not in ("planar", "interleaved"):
+            raise ValueError("layout must be 'planar' or 'interleaved', not %r" % (layout,))
+        B, L = x.shape[0], (x.shape[2] if layout == "planar" else x.shape[1])
+        lengths = [L] * B if lengths is None else [int(n) for n in lengths]
+        if len(lengths) != B or any(n < 0 or n > L for n in lengths):
+            raise ValueError("need %d lengths in [0, %d]" % (B, L))
+        srcs = [(x[b] if layout == "planar" else x[b].t())[:, :lengths[b]] for b in range(B)]
+        return self.encode_batch_from(srcs, fmt)
 
     def encode_block(self, pcm, capacity=None):
         pcm, ptrs = self._planes(pcm)

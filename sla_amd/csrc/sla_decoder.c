@@ -819,30 +819,38 @@ static uint32_t header_channels(const uint8_t* data, uint32_t data_size)
   return (r == SLA_APIRESULT_OK || r == SLA_APIRESULT_DETECT_DATA_CORRUPTION) ? h.wave_format.num_channels : 0;
 }
 
-/* 1 when item `it` may be written: the argument checks of sla_hip_decode_batch_device, before any device work.  C is
- * the header's channel count; the region is [0, C) x [0, capacity) of elements of esize bytes.  A host pointer never
- * passes: the runtime must report dst as device memory, and the region must lie inside dst's allocation. */
-static int dst_region_ok(const sla_hip_decode_device_item* it, uint32_t C, uint64_t esize)
+/* sla_internal.h: the region [0, C) x [0, n) of elements of esize bytes at p, element (c, i) at c * channel_stride +
+ * i * sample_stride, may be accessed by a kernel.  A host pointer never passes: the runtime must report p as device memory
+ * (of `device` when >= 0), and the region must lie inside p's allocation. */
+int slai_device_region_ok(const void* p, uint32_t C, uint32_t n, uint64_t channel_stride, uint64_t sample_stride, uint64_t esize,
+                          int device)
 {
   hipPointerAttribute_t at;
   hipDeviceptr_t base = NULL;
   size_t size = 0;
   uint64_t bytes = 0, a, b, last, end;
-  if (it->data == NULL || it->dst == NULL || it->sample_stride == 0 || (C > 1 && it->channel_stride == 0)) { return 0; }
-  if ((uintptr_t)it->dst % esize != 0) { return 0; }
-  if (C > 0 && it->capacity > 0) {
-    if (__builtin_mul_overflow((uint64_t)(C - 1), it->channel_stride, &a) || __builtin_mul_overflow((uint64_t)(it->capacity - 1), it->sample_stride, &b)
+  if ((uintptr_t)p % esize != 0) { return 0; }
+  if (C > 0 && n > 0) {
+    if (__builtin_mul_overflow((uint64_t)(C - 1), channel_stride, &a) || __builtin_mul_overflow((uint64_t)(n - 1), sample_stride, &b)
         || __builtin_add_overflow(a, b, &last) || __builtin_add_overflow(last, (uint64_t)1, &last) || __builtin_mul_overflow(last, esize, &bytes)
-        || __builtin_add_overflow((uint64_t)(uintptr_t)it->dst, bytes, &end)) { return 0; }
+        || __builtin_add_overflow((uint64_t)(uintptr_t)p, bytes, &end)) { return 0; }
   }
   memset(&at, 0, sizeof(at));
-  if (hipPointerGetAttributes(&at, it->dst) != hipSuccess) { (void)hipGetLastError(); return 0; }
-  if (at.type != hipMemoryTypeDevice) { return 0; }
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  if (at.type != hipMemoryTypeDevice || (device >= 0 && at.device != device)) { return 0; }
   if (bytes > 0) {
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)it->dst) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    if ((uintptr_t)it->dst < (uintptr_t)base || end > (uint64_t)(uintptr_t)base + size) { return 0; }
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if ((uintptr_t)p < (uintptr_t)base || end > (uint64_t)(uintptr_t)base + size) { return 0; }
   }
   return 1;
+}
+
+/* 1 when item `it` may be written: the argument checks of sla_hip_decode_batch_device, before any device work.  C is
+ * the header's channel count; the region is [0, C) x [0, capacity) of elements of esize bytes. */
+static int dst_region_ok(const sla_hip_decode_device_item* it, uint32_t C, uint64_t esize)
+{
+  if (it->data == NULL || it->dst == NULL || it->sample_stride == 0 || (C > 1 && it->channel_stride == 0)) { return 0; }
+  return slai_device_region_ok(it->dst, C, it->capacity, it->channel_stride, it->sample_stride, esize, -1);
 }
 
 int sla_hip_decode_batch_device(struct SLADecoder* d, sla_hip_decode_device_item* items, uint32_t num_items,

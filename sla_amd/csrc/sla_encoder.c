@@ -145,7 +145,10 @@ struct SLAEncoder {
   uint32_t nsegs; const uint32_t* seg_start; const uint32_t* seg_len;
   uint32_t batch_lshift, batch_or;
   devbuf_t d_tile_or; pinbuf_t h_tile_or;
-  devbuf_t d_binfo; pinbuf_t h_binfo;            /* batch: file starts | lengths | k_batch_scan's three words per file */
+  devbuf_t d_binfo; pinbuf_t h_binfo;            /* batch: file starts | lengths | k_batch_scan's three words per file
+                                                    (| the ingest kernel's error word, sla_hip_encode_batch_device) */
+  devbuf_t d_ingest; pinbuf_t h_ingest;          /* sla_hip_encode_batch_device: the ingest kernel's file table */
+  hipEvent_t ev_order;                           /* sla_hip_encode_batch_device: the caller's stream, recorded */
   int      batch_silence;                        /* the batch has an all-zero mask word or a silent file tail: whole mask on the host, host tables */
   int      mask_absent;                          /* the mask stayed on the device (nothing in it can make a block SILENT): readers take "all ones" */
   uint32_t* tab_segs; uint32_t tab_nsegs;        /* kept search tables of a batch: the file layout they were built for */
@@ -453,6 +456,9 @@ void SLAEncoder_Destroy(struct SLAEncoder* e)
   if (e->h_tile_or.ptr != NULL) { (void)hipHostFree(e->h_tile_or.ptr); }
   if (e->d_binfo.ptr != NULL) { (void)hipFree(e->d_binfo.ptr); }
   if (e->h_binfo.ptr != NULL) { (void)hipHostFree(e->h_binfo.ptr); }
+  if (e->d_ingest.ptr != NULL) { (void)hipFree(e->d_ingest.ptr); }
+  if (e->h_ingest.ptr != NULL) { (void)hipHostFree(e->h_ingest.ptr); }
+  if (e->ev_order != NULL) { (void)hipEventDestroy(e->ev_order); }
   free(e->tab_segs);
   for (i = 0; i < 2; i++) {
     if (e->h_stage[i].ptr != NULL) { (void)hipHostFree(e->h_stage[i].ptr); }
@@ -3343,20 +3349,22 @@ static int upload_batch_pass(struct SLAEncoder* e, const sla_hip_batch_item* ite
 
 /* Prepass over planes that hold `count` files back to back: the silence mask of everything on the host, and per file
  * the OR of its samples (from the 1024-sample tiles) and its offset_lshift (src/SLAEncoder.c:425-455; 0xFFFFFFFF:
- * samples wider than the declared depth). */
+ * samples wider than the declared depth).  err (NULL: none) receives the error words k_enc_ingest_batch left behind the
+ * summary in d_binfo, in the same download. */
 static int batch_prepass(struct SLAEncoder* e, uint64_t span, const uint32_t* start, const uint32_t* len, uint32_t count,
-                         uint32_t* lsh, uint32_t* orv)
+                         uint32_t* lsh, uint32_t* orv, uint32_t* err)
 {
   const uint32_t C = e->wave_format.num_channels, bps = e->wave_format.bit_per_sample;
   const uint32_t ms = (e->encode_param.ch_process_method == SLA_CHPROCESSMETHOD_STEREO_MS);
   const uint64_t nwords = (span + 63) / 64;
   const uint32_t ntiles = (uint32_t)((span + 4 * SLA_HIP_PREPASS_TILE - 1) / (4 * SLA_HIP_PREPASS_TILE) * 4);
+  const uint32_t words = (err != NULL) ? 6u : 5u;          /* per file in d_binfo */
   uint32_t i;
   RCCHK(dev_reserve(&e->d_or, 64));
   RCCHK(dev_reserve(&e->d_nz, (size_t)(nwords + 2) * 8));
   RCCHK(dev_reserve(&e->d_tile_or, sizeof(uint32_t) * ((size_t)ntiles + 4)));
-  RCCHK(dev_reserve(&e->d_binfo, sizeof(uint32_t) * 5 * (size_t)count + 64));
-  RCCHK(pin_reserve(&e->h_binfo, sizeof(uint32_t) * 5 * (size_t)count + 64));
+  RCCHK(dev_reserve(&e->d_binfo, sizeof(uint32_t) * words * (size_t)count + 64));
+  RCCHK(pin_reserve(&e->h_binfo, sizeof(uint32_t) * words * (size_t)count + 64));
   {
     /* the files' positions go up behind nothing, the prepass and the per-file summary (k_batch_scan) follow, and what
      * comes home is 12 bytes per file: its OR word, its all-zero mask words, "its last super-frame is silent".  Only a
@@ -3373,9 +3381,10 @@ static int batch_prepass(struct SLAEncoder* e, uint64_t span, const uint32_t* st
     RCCHK(sla_hip_launch_batch_scan((const uint64_t*)e->d_nz.ptr, (const uint32_t*)e->d_tile_or.ptr, (const uint32_t*)e->d_binfo.ptr,
                                     (const uint32_t*)e->d_binfo.ptr + count, count, e->encode_param.max_num_block_samples,
                                     (uint32_t*)e->d_binfo.ptr + 2 * (size_t)count, e->stream));
-    HIPCHK(hipMemcpyAsync(hb + 2 * (size_t)count, (uint32_t*)e->d_binfo.ptr + 2 * (size_t)count, sizeof(uint32_t) * 3 * (size_t)count,
+    HIPCHK(hipMemcpyAsync(hb + 2 * (size_t)count, (uint32_t*)e->d_binfo.ptr + 2 * (size_t)count, sizeof(uint32_t) * (words - 2) * (size_t)count,
                           hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    if (err != NULL) { memcpy(err, hb + 5 * (size_t)count, sizeof(uint32_t) * count); }
     for (i = 0; i < count; i++) { if (info[3 * i + 1] != 0 || info[3 * i + 2] != 0) { silence = 1; } }
     e->batch_silence = silence;
     if (silence) {
@@ -3397,20 +3406,61 @@ static int batch_prepass(struct SLAEncoder* e, uint64_t span, const uint32_t* st
   return 0;
 }
 
-/* items [first, first + count): one upload, one prepass, one pipeline pass per distinct offset_lshift */
-static int encode_batch_pass(struct SLAEncoder* e, sla_hip_batch_item* items, uint32_t first, uint32_t count)
+/* Where the samples of a pass come from when they are not host planes: the items of sla_hip_encode_batch_device (the
+ * pass's sla_hip_batch_item copies carry their sizes and buffers, a refused item with no samples and no buffer). */
+typedef struct { const sla_hip_encode_device_item* items; uint32_t format; } ingest_src_t;
+
+/* The upload leg of a pass of device items, queued on the handle's stream (which already waits for the caller's): the
+ * files' error words zeroed, the file table up, one k_enc_ingest_batch writing every file's planes and the zero gap
+ * behind it.  batch_prepass brings the error words home with its per-file summary. */
+static int ingest_batch_pass(struct SLAEncoder* e, const ingest_src_t* dev, const sla_hip_batch_item* items, const uint32_t* start,
+                             uint32_t first, uint32_t count, uint64_t stride)
+{
+  const uint32_t C = e->wave_format.num_channels;
+  sla_hip_enc_ingest* t;
+  uint32_t i, max_fill = 0;
+  RCCHK(dev_reserve(&e->d_binfo, sizeof(uint32_t) * 6 * (size_t)count + 64));      /* (batch_prepass's size with error words) */
+  RCCHK(dev_reserve(&e->d_ingest, sizeof(sla_hip_enc_ingest) * (size_t)count));
+  RCCHK(pin_reserve(&e->h_ingest, sizeof(sla_hip_enc_ingest) * (size_t)count));
+  t = (sla_hip_enc_ingest*)e->h_ingest.ptr;
+  for (i = 0; i < count; i++) {
+    const sla_hip_encode_device_item* it = &dev->items[first + i];
+    const uint32_t n = items[first + i].num_samples;
+    memset(&t[i], 0, sizeof(t[i]));
+    t[i].plane_off = start[i];
+    t[i].src = (n > 0) ? it->src : NULL;
+    t[i].channel_stride = it->channel_stride; t[i].sample_stride = it->sample_stride;
+    t[i].num_samples = n;
+    t[i].fill_end = (n + SLA_HIP_PREPASS_TILE - 1) / SLA_HIP_PREPASS_TILE * SLA_HIP_PREPASS_TILE;
+    t[i].bits_per_sample = e->wave_format.bit_per_sample;
+    if (t[i].fill_end > max_fill) { max_fill = t[i].fill_end; }
+  }
+  HIPCHK(hipMemsetAsync((uint32_t*)e->d_binfo.ptr + 5 * (size_t)count, 0, sizeof(uint32_t) * count, e->stream));
+  if (max_fill == 0) {                    /* no file has a sample: the one tile the pass still spans is zero */
+    HIPCHK(hipMemsetAsync(e->d_pcm.ptr, 0, sizeof(int32_t) * (size_t)C * stride, e->stream));
+    return 0;
+  }
+  HIPCHK(hipMemcpyAsync(e->d_ingest.ptr, t, sizeof(sla_hip_enc_ingest) * (size_t)count, hipMemcpyHostToDevice, e->stream));
+  return sla_hip_launch_enc_ingest_batch((const sla_hip_enc_ingest*)e->d_ingest.ptr, count, max_fill, C, dev->format,
+                                         (int32_t*)e->d_pcm.ptr, stride, (uint32_t*)e->d_binfo.ptr + 5 * (size_t)count, e->stream);
+}
+
+/* items [first, first + count): one upload (host planes, dev == NULL) or one ingest (dev), one prepass, one pipeline pass
+ * per distinct offset_lshift */
+static int encode_batch_pass(struct SLAEncoder* e, sla_hip_batch_item* items, uint32_t first, uint32_t count, const ingest_src_t* dev)
 {
   const uint32_t C = e->wave_format.num_channels, bps = e->wave_format.bit_per_sample;
-  uint32_t *start, *lsh, *seg_start, *seg_len, *seg_item, *orv;
+  uint32_t *start, *lsh, *seg_start, *seg_len, *seg_item, *orv, *err;
   pack_seg_t* segs;
   uint32_t i, lowbits = 0;
   uint64_t span = 0, stride;
   int mode16 = (bps <= 16), rc = 0;
 
-  start = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)count * 6 + 64);
+  start = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)count * 7 + 64);
   segs = (pack_seg_t*)malloc(sizeof(pack_seg_t) * ((size_t)count + 1));
   if (start == NULL || segs == NULL) { free(start); free(segs); return SLA_APIRESULT_NG; }
   lsh = start + count; seg_start = lsh + count; seg_len = seg_start + count; seg_item = seg_len + count; orv = seg_item + count;
+  err = orv + count;
   for (i = 0; i < count; i++) {
     start[i] = (uint32_t)span;
     span += ((uint64_t)items[first + i].num_samples + SLA_HIP_PREPASS_TILE - 1) / SLA_HIP_PREPASS_TILE * SLA_HIP_PREPASS_TILE;
@@ -3420,22 +3470,30 @@ static int encode_batch_pass(struct SLAEncoder* e, sla_hip_batch_item* items, ui
 #define BATCH_CHK(call) do { rc = (call); if (rc != 0) { goto done; } } while (0)
 #define BATCH_HIP(call) do { if ((call) != hipSuccess) { rc = SLA_APIRESULT_NG; goto done; } } while (0)
   BATCH_CHK(dev_reserve(&e->d_pcm, sizeof(int32_t) * (size_t)C * (stride + 64)));
-  for (i = 0; i < 2; i++) { BATCH_CHK(pin_reserve(&e->h_stage[i], XFER_SLOT_BYTES)); BATCH_CHK(dev_reserve(&e->d_stage[i], XFER_SLOT_BYTES)); }
-  if (e->upload_gate != NULL) { pthread_mutex_lock(e->upload_gate); }
-  e->batch_stamp[0] = now_ms();
-  rc = upload_batch_pass(e, items, start, first, count, (size_t)span, stride, mode16, &lowbits);
-  if (rc == 0 && mode16 && lowbits != 0) { rc = upload_batch_pass(e, items, start, first, count, (size_t)span, stride, 0, &lowbits); }
-  e->batch_stamp[1] = now_ms();
-  if (e->upload_gate != NULL) { pthread_mutex_unlock(e->upload_gate); }
+  if (dev != NULL) {
+    e->batch_stamp[0] = now_ms();
+    rc = ingest_batch_pass(e, dev, items, start, first, count, stride);
+  } else {
+    for (i = 0; i < 2; i++) { BATCH_CHK(pin_reserve(&e->h_stage[i], XFER_SLOT_BYTES)); BATCH_CHK(dev_reserve(&e->d_stage[i], XFER_SLOT_BYTES)); }
+    if (e->upload_gate != NULL) { pthread_mutex_lock(e->upload_gate); }
+    e->batch_stamp[0] = now_ms();
+    rc = upload_batch_pass(e, items, start, first, count, (size_t)span, stride, mode16, &lowbits);
+    if (rc == 0 && mode16 && lowbits != 0) { rc = upload_batch_pass(e, items, start, first, count, (size_t)span, stride, 0, &lowbits); }
+    e->batch_stamp[1] = now_ms();
+    if (e->upload_gate != NULL) { pthread_mutex_unlock(e->upload_gate); }
+  }
   if (rc != 0) { goto done; }
   e->pcm_dev = (const int32_t*)e->d_pcm.ptr; e->stride = stride; e->num_samples = (uint32_t)span;
 
-  /* prepass over everything: silence mask, offset_lshift per file */
+  /* prepass over everything: silence mask, offset_lshift per file (and the ingest's error words) */
   for (i = 0; i < count; i++) { seg_len[i] = items[first + i].num_samples; }
-  BATCH_CHK(batch_prepass(e, span, start, seg_len, count, lsh, orv));
+  BATCH_CHK(batch_prepass(e, span, start, seg_len, count, lsh, orv, (dev != NULL) ? err : NULL));
+  if (dev != NULL) { e->batch_stamp[1] = e->batch_stamp[2] = now_ms(); }      /* (ingest and prepass: the first wait on the device) */
   for (i = 0; i < count; i++) {
     items[first + i].result = SLA_APIRESULT_OK; items[first + i].output_size = 0;
-    if (lsh[i] == 0xFFFFFFFFu) { items[first + i].result = SLA_APIRESULT_INVALID_ARGUMENT; continue; }
+    if (lsh[i] == 0xFFFFFFFFu || (dev != NULL && err[i] != 0)) {        /* (an ingest refusal joins no pass) */
+      items[first + i].result = SLA_APIRESULT_INVALID_ARGUMENT; lsh[i] = 0xFFFFFFFFu; continue;
+    }
     if (items[first + i].data == NULL || items[first + i].data_size < SLA_HEADER_SIZE) {
       items[first + i].result = (items[first + i].data == NULL) ? SLA_APIRESULT_INVALID_ARGUMENT : SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE;
       lsh[i] = 0xFFFFFFFFu;
@@ -3506,7 +3564,7 @@ int sla_hip_analyze_batch_device(struct SLAEncoder* e, const int32_t* d_pcm, uin
   orv = lsh + num_files; seg_start = orv + num_files; seg_len = seg_start + num_files;
   e->pcm_dev = d_pcm; e->stride = plane_stride; e->num_samples = span;
   memset(acc, 0, sizeof(acc));
-  rc = batch_prepass(e, span, file_start, file_samples, num_files, lsh, orv);
+  rc = batch_prepass(e, span, file_start, file_samples, num_files, lsh, orv, NULL);
   for (i = 0; rc == 0 && i < num_files; i++) {
     if (file_lshift != NULL) { file_lshift[i] = lsh[i]; }
     if (lsh[i] == 0xFFFFFFFFu) { rc = SLA_APIRESULT_INVALID_ARGUMENT; }
@@ -3655,10 +3713,71 @@ int sla_hip_encode_batch(struct SLAEncoder* e, sla_hip_batch_item* items, uint32
       if (count > 0 && span + add > BATCH_MAX_SPAN) { break; }
       span += add; count++;
     }
-    rc = encode_batch_pass(e, items, first, count);
+    rc = encode_batch_pass(e, items, first, count, NULL);
     if (rc != 0) { return (rc > 0) ? rc : SLA_APIRESULT_NG; }
     first += count;
   }
+  return 0;
+}
+
+/* Many files from caller-owned device memory (include/sla_hip.h).  The items become sla_hip_batch_item copies -- sizes and
+ * buffers; a refused item gets no samples and no buffer, so the pass answers it INVALID_ARGUMENT without reading or writing
+ * anything of it -- and go through encode_batch_pass with the ingest kernel as the upload leg, passes grouped exactly as in
+ * sla_hip_encode_batch.  No worker lanes: they exist to overlap host uploads, and there are none here. */
+int sla_hip_encode_batch_device(struct SLAEncoder* e, sla_hip_encode_device_item* items, uint32_t num_items,
+                                uint32_t sample_format, sla_hip_stream_t stream)
+{
+  sla_hip_batch_item* bi;
+  ingest_src_t dev;
+  uint32_t first = 0, i, C;
+  uint64_t esize;
+  int rc;
+  if (e == NULL || (items == NULL && num_items != 0) || sample_format > SLA_HIP_PCM_F32) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if ((rc = check_ready(e)) != 0) { return rc; }
+  for (i = 0; i < num_items; i++) {
+    if (items[i].num_samples > BATCH_MAX_SPAN - SLA_HIP_PREPASS_TILE) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
+  }
+  if (num_items == 0) { return 0; }
+  RCCHK(enter(e));
+  C = e->wave_format.num_channels;
+  esize = (sample_format == SLA_HIP_PCM_S16) ? 2u : 4u;
+  bi = (sla_hip_batch_item*)calloc(num_items, sizeof(*bi));
+  if (bi == NULL) { return SLA_APIRESULT_NG; }
+  for (i = 0; i < num_items; i++) {
+    const sla_hip_encode_device_item* it = &items[i];
+    int ok = (it->data != NULL && it->sample_stride != 0 && (C <= 1 || it->channel_stride != 0));
+    if (ok) {
+      ok = (it->src == NULL) ? (it->num_samples == 0)
+                             : slai_device_region_ok(it->src, C, it->num_samples, it->channel_stride, it->sample_stride, esize, e->device);
+    }
+    bi[i].num_samples = ok ? it->num_samples : 0;
+    bi[i].data = ok ? it->data : NULL;
+    bi[i].data_size = it->data_size;
+  }
+  /* nothing is read before the caller's stream has reached this call */
+  if (e->ev_order == NULL && hipEventCreateWithFlags(&e->ev_order, hipEventDisableTiming) != hipSuccess) { e->ev_order = NULL; free(bi); return SLA_APIRESULT_NG; }
+  if (hipEventRecord(e->ev_order, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(e->stream, e->ev_order, 0) != hipSuccess) {
+    free(bi); return SLA_APIRESULT_NG;
+  }
+  dev.items = items; dev.format = sample_format;
+  while (first < num_items) {
+    uint64_t span = 0;
+    uint32_t count = 0;
+    while (first + count < num_items) {
+      const uint64_t add = ((uint64_t)bi[first + count].num_samples + SLA_HIP_PREPASS_TILE - 1) / SLA_HIP_PREPASS_TILE * SLA_HIP_PREPASS_TILE;
+      if (count > 0 && span + add > BATCH_MAX_SPAN) { break; }
+      span += add; count++;
+    }
+    rc = encode_batch_pass(e, bi, first, count, &dev);
+    if (rc != 0) { free(bi); return (rc > 0) ? rc : SLA_APIRESULT_NG; }
+    if (e->trace) {
+      fprintf(stderr, "[sla_hip] encode_batch_device pass of %u files: ingest + prepass %.3f ms, analysis %.3f ms, pack + download %.3f ms\n", count,
+              e->batch_stamp[1] - e->batch_stamp[0], e->batch_stamp[2] - e->batch_stamp[1], e->batch_stamp[3] - e->batch_stamp[2]);
+    }
+    for (i = first; i < first + count; i++) { items[i].result = bi[i].result; items[i].output_size = bi[i].output_size; }
+    first += count;
+  }
+  free(bi);
   return 0;
 }
 

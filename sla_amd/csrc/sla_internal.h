@@ -78,4 +78,11 @@ void     slai_coding_mode(const uint32_t* rice_init, uint32_t num_channels, uint
 uint32_t slai_crc16(const uint8_t* data, size_t n);
 int      slai_write_header(const struct SLAHeaderInfo* h, uint8_t* data, uint32_t data_size);
 
+/* ---- sla_decoder.c: caller-owned device memory of the batch calls --------- */
+/* 1 when [0, C) x [0, n) of esize-byte elements at p (element (c, i) at c * channel_stride + i * sample_stride) is aligned,
+ * its byte extent does not overflow, the runtime reports p as device memory (of `device` when >= 0) and the region lies
+ * inside p's allocation.  NULL p, zero strides: the caller's checks. */
+int      slai_device_region_ok(const void* p, uint32_t C, uint32_t n, uint64_t channel_stride, uint64_t sample_stride,
+                               uint64_t esize, int device);
+
 #endif

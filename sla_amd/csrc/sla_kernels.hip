@@ -27,6 +27,7 @@
 //                                         src/SLACoder.c:361-385 (mean of folded residual)
 //   k_rice_k/_k2/_bits/_write,            src/SLACoder.c:45-83,120-139,165-271,388-467 (Golomb, gamma, recursive Rice, PutDataArray),
 //   k_block_crc, k_unpack16/24 (pack)     src/SLAEncoder.c:682-798 (block assembly), src/SLAUtility.c:321-339 (CRC16)
+//   k_enc_ingest_batch (ingest)           no counterpart: caller-owned device PCM into the planes of a batch pass
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <float.h>
@@ -100,3 +101,4 @@ __device__ __forceinline__ uint32_t umax_wave(uint32_t v)
 #include "kernels/longterm.inc"
 #include "kernels/launchers.inc"
 #include "kernels/pack.inc"
+#include "kernels/ingest.inc"
