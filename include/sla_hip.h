@@ -395,6 +395,33 @@ int sla_hip_launch_ltm_acf_x(const int32_t* d_residual, uint64_t plane_stride,
 int sla_hip_launch_ltm_solve(const double* d_acf_records, const sla_hip_lpc_group* d_groups, uint32_t num_jobs,
                              uint32_t longterm_order, sla_hip_tail_job* d_jobs, sla_hip_stream_t stream);
 
+/* The certified long-term stage: the same job table as above, but the autocorrelation comes from an any-order FMA
+ * transform of half the reference's size or less (k_ltm_acf_fast) and carries an error bound
+ *     |r'[j] - r_ref[j]| <= eps = safety * SLA_HIP_LTM_CERT_C * 2^-53 * log2(fft_size) * r'[0]       (j <= 261)
+ * that covers the fast transform's error and the reference's own (first order; DESIGN section 2 has the derivation and
+ * the measured errors).  A job whose every decision -- pitch scan, arg-max, the solver's branches, sum|coef| >= 1, the
+ * 15-bit tap quantiser -- is safe under +-eps gets the pitch and taps of sla_hip_launch_ltm_solve by proof; every other
+ * job is recomputed by the exact kernels from a device-resident list, in the same call and on the same stream.
+ *   d_fast_twiddles  SLA_HIP_FAST_TWIDDLE_DOUBLES(fft_size) doubles from sla_hip_ltm_fast_twiddles
+ *   d_eps            num_jobs doubles (work area: the bound of every job, < 0 = pick not certified)
+ *   d_list           num_jobs words (work area), d_counters: 4 words, ZERO before the call; afterwards {list entries,
+ *                    uncertified jobs, audited jobs found equal, audited jobs found different} (tuning cert_audit = N
+ *                    sends every N-th certified job through the exact kernels as well and compares pitch and taps)
+ *   safety           >= SLA_HIP_LTM_CERT_SAFETY_MIN
+ * fft_size (the reference's: roundup2(2 * capacity)) must satisfy sla_hip_ltm_cert_supported. */
+#define SLA_HIP_LTM_CERT_C 64.0
+#define SLA_HIP_LTM_CERT_SAFETY_MIN 16.0
+#define SLA_HIP_FAST_TWIDDLE_DOUBLES(fft_size) (6u * (size_t)(fft_size))      /* (an upper bound: the sizes below fft_size / 2 add up to less) */
+int    sla_hip_ltm_cert_supported(uint32_t fft_size);
+double sla_hip_ltm_cert_eps_rel(uint32_t fft_size, double safety);
+int    sla_hip_ltm_fast_twiddles(uint32_t fft_size, double* out);
+int sla_hip_launch_ltm_cert_x(const int32_t* d_residual, uint64_t plane_stride, const sla_hip_acf_job* d_acf_jobs,
+                              const sla_hip_lpc_group* d_groups, uint32_t num_jobs, uint32_t fft_size,
+                              const double* d_twiddles, const double* d_fast_twiddles, double* d_scratch, uint32_t scratch_slots,
+                              double* d_acf_records, double* d_eps, uint32_t longterm_order, double safety,
+                              sla_hip_tail_job* d_jobs, uint32_t* d_list, uint32_t* d_counters,
+                              sla_hip_stream_t stream, const sla_hip_launch_extra* extra);
+
 /* Long-term filter + sign-log LMS + folded-residual sum, one lane per job.
  * d_res_in/d_res_out are channel planes with the same stride as the PCM. */
 int sla_hip_launch_tail(const int32_t* d_res_in, int32_t* d_res_out, uint64_t plane_stride,
@@ -815,6 +842,13 @@ int sla_hip_last_block_cert(const struct SLAEncoder* encoder, uint32_t* counters
 /* 2 counters of the last analysis under option "cert_audit": certified pairs the exact kernels re-analysed and found equal;
  * pairs they found DIFFERENT (the analysis that saw one returned SLA_APIRESULT_NG). */
 int sla_hip_last_cert_audit(const struct SLAEncoder* encoder, uint32_t* counters);
+/* 5 words of the last analysis' certified long-term stage (option ltm_cert, default 1; device_ltm = 1 only): jobs,
+ * certified, sent through the exact kernels (fallback), audited jobs found equal / different (cert_audit; also summed
+ * into sla_hip_last_cert_audit, and like there an analysis that saw a different one returns SLA_APIRESULT_NG).  All zero
+ * when the stage ran the exact route.  A batch dealt out to worker lanes sums its lanes' counters into this handle; the
+ * pieces of a streamed file (option stream) run on lanes whose counters are not collected: the counters then describe the
+ * handle's own last analysis only. */
+int sla_hip_last_ltm_cert(const struct SLAEncoder* encoder, uint32_t* counters);
 
 /* 4 counters: pipeline chunks of the last analysis whose block stage was launched from device-written tables
  * (sla_hip_launch_expand; option "device_expand"), its pipeline chunks in all; since the handle was created: the analyses

@@ -158,6 +158,11 @@ def lib():
         L.sla_hip_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.sla_hip_last_block_cert.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.sla_hip_last_cert_audit.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        if hasattr(L, "sla_hip_last_ltm_cert"):              # (SLA_HIP_LIB may name an older build in an A/B run)
+            L.sla_hip_last_ltm_cert.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+            L.sla_hip_ltm_cert_eps_rel.restype = C.c_double
+            L.sla_hip_ltm_cert_eps_rel.argtypes = [C.c_uint32, C.c_double]
+            L.sla_hip_ltm_cert_supported.argtypes = [C.c_uint32]
         L.sla_hip_last_expand.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.sla_hip_search_exact_lags.restype = C.c_uint32
         L.sla_hip_encoder_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
@@ -222,6 +227,7 @@ EXPORTED_SYMBOLS = [
     "sla_hip_launch_lpc_x", "sla_hip_launch_ltm_acf_x", "sla_hip_launch_search_exact_x", "sla_hip_launch_tail_x", "sla_hip_last_expand", "sla_hip_launch_expand", "sla_hip_launch_expand_masked",
     "sla_hip_launch_lpc_f64", "sla_hip_launch_lattice_raw", "sla_hip_launch_tail_stages", "sla_hip_launch_emphasis_i32",
     "sla_hip_launch_emphasis_f64", "sla_hip_use_tuning", "sla_hip_launch_lattice_groups", "sla_hip_launch_ltm_solve",
+    "sla_hip_launch_ltm_cert_x", "sla_hip_ltm_fast_twiddles", "sla_hip_ltm_cert_eps_rel", "sla_hip_ltm_cert_supported", "sla_hip_last_ltm_cert",
     "sla_hip_encoder_set_option", "sla_hip_shard_scan", "sla_hip_shard_scan_counts", "sla_hip_shard_bounds", "sla_hip_shard_analyze", "sla_hip_shard_analyze_no_silence", "sla_hip_shard_header",
     # include/SLAPredictor.h, include/SLACoder.h (per-call API of the reference, encode side)
     "SLALPCCalculator_Create", "SLALPCCalculator_Destroy", "SLALPCCalculator_CalculatePARCORCoefDouble",
@@ -562,6 +568,12 @@ class Encoder:
         """option cert_audit: (certified pairs the exact kernels re-analysed and found equal, pairs they found different)"""
         c = (C.c_uint32 * 2)()
         self._check(self._lib.sla_hip_last_cert_audit(self._h, c), "sla_hip_last_cert_audit")
+        return tuple(c)
+
+    def last_ltm_cert(self):
+        """certified long-term stage (option ltm_cert) in the last analysis: (jobs, certified, fallback, audit_ok, audit_bad)"""
+        c = (C.c_uint32 * 5)()
+        self._check(self._lib.sla_hip_last_ltm_cert(self._h, c), "sla_hip_last_ltm_cert")
         return tuple(c)
 
     def bind_residual_planes(self, lattice_ptr, final_ptr, plane_stride):

@@ -680,12 +680,12 @@ extern "C" int sla_hip_launch_ltm_acf_x(const int32_t* d_residual, uint64_t plan
     hipError_t e = ensure_dynamic_lds((const void*)k_ltm_acf<true>, lds);
     if (e != hipSuccess) { return hip_rc(e); }
     hipLaunchKernelGGL(k_ltm_acf<true>, dim3(num_jobs), dim3(ACF_THREADS), lds, st, d_residual, plane_stride, d_jobs, num_jobs,
-                       log2F, d_twiddles, (double*)nullptr, d_acf_head, head, span);
+                       log2F, d_twiddles, (double*)nullptr, d_acf_head, head, span, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
   } else {
     if (d_scratch == nullptr || scratch_slots == 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
     uint32_t grid = (num_jobs < scratch_slots) ? num_jobs : scratch_slots;
     hipLaunchKernelGGL(k_ltm_acf<false>, dim3(grid), dim3(ACF_THREADS), 0, st, d_residual, plane_stride, d_jobs, num_jobs,
-                       log2F, d_twiddles, d_scratch, d_acf_head, head, span);
+                       log2F, d_twiddles, d_scratch, d_acf_head, head, span, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
   }
   return hip_rc(hipGetLastError());
 }
@@ -708,5 +708,71 @@ extern "C" int sla_hip_launch_ltm_solve(const double* d_acf_records, const sla_h
   if (longterm_order == 1) { hipLaunchKernelGGL(k_ltm_solve<1>, grid, block, 0, (hipStream_t)stream, d_acf_records, d_groups, num_jobs, d_jobs); }
   else if (longterm_order == 3) { hipLaunchKernelGGL(k_ltm_solve<3>, grid, block, 0, (hipStream_t)stream, d_acf_records, d_groups, num_jobs, d_jobs); }
   else { hipLaunchKernelGGL(k_ltm_solve<5>, grid, block, 0, (hipStream_t)stream, d_acf_records, d_groups, num_jobs, d_jobs); }
+  return hip_rc(hipGetLastError());
+}
+
+// The certified long-term stage (k_ltm_acf_fast -> k_ltm_solve_cert -> exact kernels over the fallback list), all on one
+// stream.  The list kernels run on a fixed small grid and read the list's length on the device: an empty list costs two
+// near-empty launches.  d_counters (4 words, zero before the call): list entries, uncertified jobs, audit ok, audit bad.
+#define LIST_LTM_GRID 64u
+extern "C" int sla_hip_ltm_cert_supported(uint32_t fft_size)
+{
+  return (fft_size == 4096 || fft_size == 8192 || fft_size == 16384 || fft_size == 32768) ? 1 : 0;
+}
+
+extern "C" int sla_hip_launch_ltm_cert_x(const int32_t* d_residual, uint64_t plane_stride, const sla_hip_acf_job* d_acf_jobs,
+                                       const sla_hip_lpc_group* d_groups, uint32_t num_jobs, uint32_t fft_size,
+                                       const double* d_twiddles, const double* d_fast_twiddles, double* d_scratch, uint32_t scratch_slots,
+                                       double* d_acf_records, double* d_eps, uint32_t longterm_order, double safety,
+                                       sla_hip_tail_job* d_jobs, uint32_t* d_list, uint32_t* d_counters,
+                                       sla_hip_stream_t stream, const sla_hip_launch_extra* extra)
+{
+  if (d_residual == nullptr || d_acf_jobs == nullptr || d_groups == nullptr || d_twiddles == nullptr || d_fast_twiddles == nullptr
+      || d_acf_records == nullptr || d_eps == nullptr || d_jobs == nullptr || d_list == nullptr || d_counters == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (!sla_hip_ltm_cert_supported(fft_size)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (longterm_order == 0 || longterm_order > LTM_NT || (longterm_order & 1u) == 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (!(safety >= SLA_HIP_LTM_CERT_SAFETY_MIN)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_jobs == 0) { return 0; }
+  uint32_t log2F = 0;
+  while ((1u << log2F) < fft_size) { log2F++; }
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* span = span_of(extra);
+  const double eps_rel = sla_hip_ltm_cert_eps_rel(fft_size, safety);
+  const uint32_t audit_every = tuning().cert_audit;
+  hipError_t e = hipSuccess;
+  // the transform is at most half the reference's: 16 bytes * 2^(log2F - 2) of LDS
+#define SLA_ACFF(LTOP, TT) do { \
+    const size_t lds = sizeof(double2) * ((size_t)1 << (LTOP)); \
+    e = ensure_dynamic_lds((const void*)k_ltm_acf_fast<LTOP, TT>, lds); \
+    if (e != hipSuccess) { return hip_rc(e); } \
+    hipLaunchKernelGGL((k_ltm_acf_fast<LTOP, TT>), dim3(num_jobs), dim3(TT), lds, st, d_residual, plane_stride, d_acf_jobs, num_jobs, d_fast_twiddles, d_acf_records, d_eps, eps_rel, span); } while (0)
+  if (log2F == 12) { SLA_ACFF(10, 128); }
+  else if (log2F == 13) { SLA_ACFF(11, 256); }
+  else if (log2F == 14) { SLA_ACFF(12, 512); }
+  else { SLA_ACFF(13, 1024); }
+#undef SLA_ACFF
+  const dim3 grid((num_jobs + 63) / 64), block(64);
+#define SLA_SOLVEC(D) hipLaunchKernelGGL(k_ltm_solve_cert<D>, grid, block, 0, st, d_acf_records, d_eps, d_groups, num_jobs, d_jobs, d_list, d_counters, audit_every)
+  if (longterm_order == 1) { SLA_SOLVEC(1); } else if (longterm_order == 3) { SLA_SOLVEC(3); } else { SLA_SOLVEC(5); }
+#undef SLA_SOLVEC
+  // the exact route over whatever was not certified (and over the audited jobs)
+  const size_t lds = sizeof(double) * (size_t)fft_size;
+  if (lds <= SLA_HIP_LDS_BUDGET) {
+#define SLA_ACF2L(LL, TT) do { \
+      e = ensure_dynamic_lds((const void*)k_ltm_acf2_list<LL, TT>, lds); \
+      if (e != hipSuccess) { return hip_rc(e); } \
+      hipLaunchKernelGGL((k_ltm_acf2_list<LL, TT>), dim3(LIST_LTM_GRID), dim3(TT), lds, st, d_residual, plane_stride, d_acf_jobs, d_list, d_counters, d_twiddles, d_acf_records, span); } while (0)
+    if (log2F == 12) { SLA_ACF2L(11, 512); } else if (log2F == 13) { SLA_ACF2L(12, 512); } else { SLA_ACF2L(13, 1024); }
+#undef SLA_ACF2L
+  } else {
+    if (d_scratch == nullptr || scratch_slots == 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+    const uint32_t grid_l = (LIST_LTM_GRID < scratch_slots) ? LIST_LTM_GRID : scratch_slots;
+    hipLaunchKernelGGL(k_ltm_acf<false>, dim3(grid_l), dim3(ACF_THREADS), 0, st, d_residual, plane_stride, d_acf_jobs, 0u,
+                       log2F, d_twiddles, d_scratch, d_acf_records, SLA_HIP_ACF_RECORD, span, (const uint32_t*)d_list, (const uint32_t*)d_counters);
+  }
+  const dim3 grid_s(LIST_LTM_GRID);
+#define SLA_SOLVEL(D) hipLaunchKernelGGL(k_ltm_solve_list<D>, grid_s, block, 0, st, d_acf_records, d_groups, d_list, d_counters, d_jobs)
+  if (longterm_order == 1) { SLA_SOLVEL(1); } else if (longterm_order == 3) { SLA_SOLVEL(3); } else { SLA_SOLVEL(5); }
+#undef SLA_SOLVEL
   return hip_rc(hipGetLastError());
 }

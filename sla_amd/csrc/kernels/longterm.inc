@@ -49,6 +49,21 @@ __device__ __forceinline__ void acf_bfly(double2& zi, double2& zq, double wr, do
   zi = make_double2(zi.x + tr, zi.y + ti);
 }
 
+// The same butterfly for the certified route (k_ltm_acf_fast): products fused into the sums, 8 FP64 issues instead of 10.
+// Not the reference's rounding: whoever uses it carries an error bound (acf_emit_cert, k_ltm_solve_cert).
+__device__ __forceinline__ void acf_bfly_fma(double2& zi, double2& zq, double wr, double wi)
+{
+  const double tr = fma(wr, zq.x, -(wi * zq.y));
+  const double ti = fma(wr, zq.y, wi * zq.x);
+  zq = make_double2(zi.x - tr, zi.y - ti);
+  zi = make_double2(zi.x + tr, zi.y + ti);
+}
+template <bool FAST>
+__device__ __forceinline__ void acf_bfly_sel(double2& zi, double2& zq, double wr, double wi)
+{
+  if constexpr (FAST) { acf_bfly_fma(zi, zq, wr, wi); } else { acf_bfly(zi, zq, wr, wi); }
+}
+
 // R consecutive radix-2 stages (half-spans h, 2h, .., h<<(R-1)) on the 2^R points ci + m*h that only
 // exchange data among themselves: one LDS round trip and one barrier instead of R, 2^R - 1 twiddles instead
 // of R * 2^(R-1).  Every butterfly is the radix-2 one above on the same operands, so the results are the
@@ -259,7 +274,8 @@ template <bool IN_LDS>
 __global__ __launch_bounds__(ACF_THREADS)
 void k_ltm_acf(const int32_t* __restrict__ res, uint64_t stride, const sla_hip_acf_job* __restrict__ jobs,
                uint32_t njobs, uint32_t log2F, const double* __restrict__ tw, double* __restrict__ scratch,
-               double* __restrict__ out, uint32_t head, unsigned long long* span)
+               double* __restrict__ out, uint32_t head, unsigned long long* span,
+               const uint32_t* __restrict__ list, const uint32_t* __restrict__ list_count)
 {
   extern __shared__ double2 lds2[];
   span_begin(span);
@@ -273,7 +289,10 @@ void k_ltm_acf(const int32_t* __restrict__ res, uint64_t stride, const sla_hip_a
   const double* rtr_i = rti_f + (F >> 2); const double* rti_i = rtr_i + (F >> 2);
   const double scale = 4.656612873077392578125e-10;   // 2^-31
 
-  for (uint32_t job = blockIdx.x; job < njobs; job += gridDim.x) {
+  // list != nullptr: the jobs list[0 .. *list_count) instead of 0 .. njobs (the certified route's fallback; bit 31 = audited)
+  if (list != nullptr) { njobs = *list_count; }
+  for (uint32_t it = blockIdx.x; it < njobs; it += gridDim.x) {
+    const uint32_t job = (list != nullptr) ? (list[it] & 0x7FFFFFFFu) : it;
     const sla_hip_acf_job jb = jobs[job];
     const int32_t* src = res + (uint64_t)jb.channel * stride + jb.blk_off;
     const uint32_t n = jb.blk_len;
@@ -347,7 +366,7 @@ __device__ __forceinline__ double2 acf2_tw(__amdgpu_buffer_rsrc_t rsrc, uint32_t
 
 #define ACF2_NEED 162u        // complex slots that hold lags 0 .. 323: what acf_emit reads for the compact record
 
-template <int R, int L, int THREADS>
+template <int R, int L, int THREADS, bool FAST = false>
 __device__ __forceinline__ void acf2_first_pass(double2* z, const int32_t* __restrict__ src, uint32_t n,
                                                 const double* __restrict__ twr, const double* __restrict__ twi)
 {
@@ -382,7 +401,7 @@ __device__ __forceinline__ void acf2_first_pass(double2* z, const int32_t* __res
       for (uint32_t m = 1; m < P; m += 2) {
         const uint32_t c = t + (__brev(m) >> (32 - R)) * ngroups;
         v[m] = make_double2((2 * c < n) ? (double)src[2 * c] * scale : 0.0, (2 * c + 1 < n) ? (double)src[2 * c + 1] * scale : 0.0);
-        acf_bfly(v[m - 1], v[m], twr[0], twi[0]);
+        acf_bfly_sel<FAST>(v[m - 1], v[m], twr[0], twi[0]);
       }
     }
 #pragma unroll
@@ -393,7 +412,7 @@ __device__ __forceinline__ void acf2_first_pass(double2* z, const int32_t* __res
       for (uint32_t m = 0; m < P; m++) {
         if ((m >> st) & 1u) { continue; }
         const uint32_t k = m & ((1u << st) - 1u);
-        acf_bfly(v[m], v[m + (1u << st)], twr[hs - 1 + k], twi[hs - 1 + k]);      // the same twiddle in every lane: scalar loads
+        acf_bfly_sel<FAST>(v[m], v[m + (1u << st)], twr[hs - 1 + k], twi[hs - 1 + k]);      // the same twiddle in every lane: scalar loads
       }
     }
     const uint32_t a0 = acf_sw(P * b);                                    // (m < 8 is its own swizzle)
@@ -411,7 +430,7 @@ __device__ __forceinline__ void acf2_first_pass(double2* z, const int32_t* __res
 //   * PRUNE (the compact record only needs the slots [0, ACF2_NEED) of the inverse transform): after this pass the
 //     remaining stages only combine points whose positions agree modulo H = h << R, so only the positions p with
 //     (p mod H) < need matter: groups beyond them are skipped, points beyond them not stored.
-template <int R, int LOG2H, int L, int THREADS, bool INV, bool PRUNE>
+template <int R, int LOG2H, int L, int THREADS, bool INV, bool PRUNE, bool FAST = false>
 __device__ __forceinline__ void acf2_pass(double2* z, __amdgpu_buffer_rsrc_t tw2)
 {
   constexpr uint32_t P = 1u << R, h = 1u << LOG2H, H = h << R, npts = 1u << L, groups = npts >> R;
@@ -451,7 +470,7 @@ __device__ __forceinline__ void acf2_pass(double2* z, __amdgpu_buffer_rsrc_t tw2
         if ((m >> st) & 1u) { continue; }
         // twiddle hs - 1 + low + (m mod 2^st) * h of this direction's table
         const double2 w = acf2_tw(tw2, low << 4, (tw_base + hs - 1 + (m & ((1u << st) - 1u)) * h) << 4);
-        acf_bfly(v[m], v[m + (1u << st)], w.x, w.y);
+        acf_bfly_sel<FAST>(v[m], v[m + (1u << st)], w.x, w.y);
       }
     }
 #pragma unroll
@@ -461,18 +480,18 @@ __device__ __forceinline__ void acf2_pass(double2* z, __amdgpu_buffer_rsrc_t tw2
 }
 
 // the stage schedule of one direction from half-span 2^LOG2H on: passes of three stages, the tail as 2 + 2 or 2
-template <int LOG2H, int L, int THREADS, bool INV, bool PRUNE>
+template <int LOG2H, int L, int THREADS, bool INV, bool PRUNE, bool FAST = false>
 __device__ __forceinline__ void acf2_stages(double2* z, __amdgpu_buffer_rsrc_t tw2)
 {
   constexpr int left = L - LOG2H;
   if constexpr (left >= 3 && left != 4) {
-    acf2_pass<3, LOG2H, L, THREADS, INV, PRUNE>(z, tw2);
-    acf2_stages<LOG2H + 3, L, THREADS, INV, PRUNE>(z, tw2);
+    acf2_pass<3, LOG2H, L, THREADS, INV, PRUNE, FAST>(z, tw2);
+    acf2_stages<LOG2H + 3, L, THREADS, INV, PRUNE, FAST>(z, tw2);
   } else if constexpr (left >= 2) {
-    acf2_pass<2, LOG2H, L, THREADS, INV, PRUNE>(z, tw2);
-    acf2_stages<LOG2H + 2, L, THREADS, INV, PRUNE>(z, tw2);
+    acf2_pass<2, LOG2H, L, THREADS, INV, PRUNE, FAST>(z, tw2);
+    acf2_stages<LOG2H + 2, L, THREADS, INV, PRUNE, FAST>(z, tw2);
   } else if constexpr (left == 1) {
-    acf2_pass<1, LOG2H, L, THREADS, INV, PRUNE>(z, tw2);
+    acf2_pass<1, LOG2H, L, THREADS, INV, PRUNE, FAST>(z, tw2);
   }
 }
 
@@ -489,7 +508,19 @@ __device__ __forceinline__ void acf2_recombine(double2& A, double2& B, double c2
   B = make_double2(h1r - wr * h2r + wi * h2i, -h1i + wr * h2i + wi * h2r);
 }
 
-template <int L, int THREADS>
+// (the certified route's form: the same expressions with the products fused into the sums)
+__device__ __forceinline__ void acf2_recombine_fma(double2& A, double2& B, double c2, double wr, double wi)
+{
+  const double h1r = 0.5 * (A.x + B.x);
+  const double h1i = 0.5 * (A.y - B.y);
+  const double h2r = -c2 * (A.y + B.y);
+  const double h2i = c2 * (A.x - B.x);
+  const double pr = fma(wr, h2r, -(wi * h2i)), pi = fma(wr, h2i, wi * h2r);
+  A = make_double2(h1r + pr, h1i + pi);
+  B = make_double2(h1r - pr, pi - h1i);
+}
+
+template <int L, int THREADS, bool FAST = false>
 __device__ __forceinline__ void acf2_middle(double2* z, __amdgpu_buffer_rsrc_t tw2)
 {
   // Thread tid takes the pairs (A = slot c, B = slot npts - c), c = tid + k THREADS in 1 .. npts/2 - 1 (c = 0: the DC / Nyquist
@@ -522,10 +553,17 @@ __device__ __forceinline__ void acf2_middle(double2* z, __amdgpu_buffer_rsrc_t t
       // recombination twiddles: pairs [2 npts, 2 npts + npts/2) forward, the next npts/2 inverse; entry c - 1 of either
       const double2 wf = acf2_tw(tw2, tid << 4, (2u * npts + k * THREADS - 1u) << 4);
       const double2 wi = acf2_tw(tw2, tid << 4, (2u * npts + half + k * THREADS - 1u) << 4);
-      acf2_recombine(A[k], B[k], -0.5, wf.x, wf.y);
-      A[k] = make_double2(A[k].x * A[k].x + A[k].y * A[k].y, 0.0);       // power spectrum  src/SLAPredictor.c:844-851
-      B[k] = make_double2(B[k].x * B[k].x + B[k].y * B[k].y, 0.0);
-      acf2_recombine(A[k], B[k], 0.5, wi.x, wi.y);
+      if constexpr (FAST) {
+        acf2_recombine_fma(A[k], B[k], -0.5, wf.x, wf.y);
+        A[k] = make_double2(fma(A[k].x, A[k].x, A[k].y * A[k].y), 0.0);
+        B[k] = make_double2(fma(B[k].x, B[k].x, B[k].y * B[k].y), 0.0);
+        acf2_recombine_fma(A[k], B[k], 0.5, wi.x, wi.y);
+      } else {
+        acf2_recombine(A[k], B[k], -0.5, wf.x, wf.y);
+        A[k] = make_double2(A[k].x * A[k].x + A[k].y * A[k].y, 0.0);       // power spectrum  src/SLAPredictor.c:844-851
+        B[k] = make_double2(B[k].x * B[k].x + B[k].y * B[k].y, 0.0);
+        acf2_recombine(A[k], B[k], 0.5, wi.x, wi.y);
+      }
     }
     __builtin_amdgcn_sched_barrier(0);          // one pair at a time: hoisting every pair's twiddles and temporaries costs spills
   }
@@ -573,6 +611,252 @@ void k_ltm_acf2(const int32_t* __restrict__ res, uint64_t stride, const sla_hip_
     acf2_middle<L, ACF2_THREADS>(z, tw2);
     acf2_stages<0, L, ACF2_THREADS, true, RECORD>(z, tw2);
     acf_emit<ACF2_THREADS>(z, job, out, head, s_acf, s_mask);
+    __syncthreads();
+  }
+  span_end(span);
+}
+
+// k_ltm_acf2 over a device-resident list of jobs (the certified route's fallback and its audit): a fixed small grid walks
+// list[0 .. *count); bit 31 of an entry marks an audited job (k_ltm_solve_list compares instead of replacing).
+#define LTM_LIST_AUDIT 0x80000000u
+template <int L, int ACF2_THREADS>
+__global__ __launch_bounds__(ACF2_THREADS, 4)
+void k_ltm_acf2_list(const int32_t* __restrict__ res, uint64_t stride, const sla_hip_acf_job* __restrict__ jobs,
+                     const uint32_t* __restrict__ list, const uint32_t* __restrict__ count, const double* __restrict__ tw,
+                     double* __restrict__ out, unsigned long long* span)
+{
+  extern __shared__ double2 lds2[];
+  __shared__ double s_acf[ACF_PICK_LAGS];
+  __shared__ unsigned long long s_mask[3][ACF_PICK_LAGS / 64];
+  constexpr uint32_t npts = 1u << L, F = npts << 1;
+  double2* z = lds2;
+  const uint32_t n_list = *count;
+  if (n_list == 0) { return; }                           // (the usual case: nothing recorded in the span either)
+  const __amdgpu_buffer_rsrc_t tw2 = __builtin_amdgcn_make_buffer_rsrc((void*)(tw + 3 * (size_t)F), 0, (int)(3u * F * sizeof(double)), 0x00020000);
+  for (uint32_t i = blockIdx.x; i < n_list; i += gridDim.x) {
+    const uint32_t job = list[i] & ~LTM_LIST_AUDIT;
+    const sla_hip_acf_job jb = jobs[job];
+    const int32_t* src = res + (uint64_t)jb.channel * stride + jb.blk_off;
+    acf2_first_pass<3, L, ACF2_THREADS>(z, src, jb.blk_len, tw, tw + (F >> 1));
+    acf2_stages<3, L, ACF2_THREADS, false, false>(z, tw2);
+    acf2_middle<L, ACF2_THREADS>(z, tw2);
+    acf2_stages<0, L, ACF2_THREADS, true, true>(z, tw2);
+    acf_emit<ACF2_THREADS>(z, job, out, SLA_HIP_ACF_RECORD, s_acf, s_mask);
+    __syncthreads();
+  }
+  span_end(span);
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_ltm_acf_fast: the certified route's autocorrelation.  Nothing downstream reads the reference's bits: the record only
+// feeds decisions (sign and neighbour comparisons of the pitch scan, an arg-max, a small Toeplitz solve, a 15-bit
+// quantiser), so the transform may run in any order with fused multiply-adds as long as every decision is proven to come
+// out as the reference's -- acf_emit_cert and k_ltm_solve_cert prove it under |r' - r_ref| <= eps, and what they cannot
+// prove goes through k_ltm_acf2_list / k_ltm_solve_list.
+//   * Transform size: H = 2^(l+1) >= blk_len real points instead of the reference's F = roundup2(2 * capacity).  The
+//     circular autocorrelation of size H differs from the linear one by the wrap term
+//         r[k] = c[k] - sum_{m < k - (H - n)} x[H - k + m] x[m]          (at most k terms, only when n > H - k)
+//     which the workgroup adds up from the block's first and last ACF_WRAP_LAGS samples (four lags per thread).  A block shorter than
+//     H - ACF_WRAP_LAGS has no wrap term at all (the smallest H is 2048, so every short last block).
+//   * Twiddles: a table of its own per size (slai_fft_fast_export: cos / sin evaluated in double, the layout of the exact
+//     table), the passes and the LDS swizzle of k_ltm_acf2 with FMA butterflies.
+//   * The result is scaled to the reference's: its inverse transform is unnormalised, r_ref[k] = F/2 * sum x x.
+// The workgroup picks l from blk_len: a workgroup-uniform branch over the instantiated sizes.
+// ---------------------------------------------------------------------------------------------
+#define ACF_WRAP_LAGS 264u          // lags the record can touch: pitch <= 257, + 2 taps, + the neighbour the scan compares with
+#define ACF_FAST_LAGS 324u          // lags the pruned inverse leaves valid (ACF2_NEED slots)
+#define ACF_FAST_TW_OFFSET(l, lmin) (12u * ((size_t)(1u << (l)) - (size_t)(1u << (lmin))))     // tables of the smaller sizes in front: 6 * 2^(q+1) doubles each
+
+template <int L, int THREADS>
+__device__ __forceinline__ void acf_fast_transform(double2* z, const int32_t* __restrict__ src, uint32_t n, const double* __restrict__ tw)
+{
+  constexpr uint32_t F = 2u << L;
+  const __amdgpu_buffer_rsrc_t tw2 = __builtin_amdgcn_make_buffer_rsrc((void*)(tw + 3 * (size_t)F), 0, (int)(3u * F * sizeof(double)), 0x00020000);
+  acf2_first_pass<3, L, THREADS, true>(z, src, n, tw, tw + (F >> 1));
+  acf2_stages<3, L, THREADS, false, false, true>(z, tw2);
+  acf2_middle<L, THREADS, true>(z, tw2);
+  acf2_stages<0, L, THREADS, true, true, true>(z, tw2);
+}
+
+// acf_emit with the certificate: s_r holds r'[0 .. ACF_FAST_LAGS), eps = eps_rel * r'[0] bounds |r' - r_ref| at every lag.
+// The record is certified (eps_out >= 0) only if every predicate the scan can evaluate is safe: |r'[j]| > eps for the
+// lags 0 .. 258 (signs), |r'[j] - r'[j-1]| > 2 eps for 1 .. 258 (neighbour comparisons), the winning peak above every
+// other candidate by more than 2 eps, r'[0] - eps > FLT_MIN.  An all-zero block is exact (r'[0] == 0: silent).
+template <int THREADS>
+__device__ __forceinline__ void acf_emit_cert(const double* s_r, uint32_t job, double* __restrict__ out, double* __restrict__ eps_out,
+                                              double eps_rel, bool size_ok, unsigned long long (*s_mask)[ACF_PICK_LAGS / 64])
+{
+  const double eps = eps_rel * s_r[0];
+  for (uint32_t j = threadIdx.x; j < ACF_PICK_LAGS; j += THREADS) {             // (whole waves: 320 = 5 x 64)
+    const double vc = s_r[j], vm = (j >= 1) ? s_r[j - 1] : 0.0, vp = s_r[j + 1];
+    const unsigned long long bu = __ballot(j >= 1 && j < 256 && vm < 0.0 && vc > 0.0);
+    const unsigned long long bd = __ballot(j >= 1 && j < 256 && vc > 0.0 && vp < 0.0);
+    const unsigned long long bl = __ballot(j >= 1 && j <= 257 && vc > vm && vc > vp && vc > 0.0);
+    // (negated comparisons: a NaN or an infinity anywhere is unsafe)
+    const unsigned long long bx = __ballot(j <= 258 && (!(fabs(vc) > eps) || (j >= 1 && !(fabs(vc - vm) > 2.0 * eps))));
+    if ((j & 63) == 0) { s_mask[0][j >> 6] = bu; s_mask[1][j >> 6] = bd; s_mask[2][j >> 6] = bl; s_mask[3][j >> 6] = bx; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t w = lane >> 4, sh = (lane & 15u) * 4;
+    const uint32_t up = (uint32_t)(s_mask[0][w] >> sh) & 15u, dn = (uint32_t)(s_mask[1][w] >> sh) & 15u;
+    const uint32_t lm = (uint32_t)(s_mask[2][w] >> sh) & 15u;
+    const uint32_t lm_hi = (uint32_t)s_mask[2][4] & 3u;
+    bool unsafe = ((s_mask[3][0] | s_mask[3][1] | s_mask[3][2] | s_mask[3][3] | s_mask[3][4]) != 0ull) || !size_ok;
+    uint32_t f = 0;
+#pragma unroll
+    for (uint32_t s0 = 0; s0 < 2; s0++) {
+      uint32_t st = s0;
+#pragma unroll
+      for (uint32_t q = 0; q < 4; q++) { st = st ? (((dn >> q) & 1u) ^ 1u) : ((up >> q) & 1u); }
+      f |= st << s0;
+    }
+    uint32_t g = f;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+      const uint32_t below = (uint32_t)__shfl_up((int)g, d);
+      if (lane >= d) { g = ((g >> (below & 1u)) & 1u) | (((g >> ((below >> 1) & 1u)) & 1u) << 1); }
+    }
+    const uint32_t incl = g & 1u;
+    uint32_t st = (uint32_t)__shfl_up((int)incl, 1);
+    if (lane == 0) { st = 0; }
+    const uint32_t s255 = (uint32_t)__shfl((int)incl, 63);
+    double best = 0.0;
+    uint32_t arg = 0, cand = 0, s_before_last = 0;      // cand: bits 0..3 this lane's lags, bit 4 lag 256 + lane
+#pragma unroll
+    for (uint32_t q = 0; q < 4; q++) {
+      const uint32_t lag = lane * 4 + q;
+      const uint32_t prev = st;
+      if (q == 3) { s_before_last = prev; }
+      st = prev ? (((dn >> q) & 1u) ^ 1u) : ((up >> q) & 1u);
+      if ((prev | st) && ((lm >> q) & 1u)) {
+        const double v = s_r[lag];
+        cand |= 1u << q;
+        if (v > best) { best = v; arg = lag; }
+      }
+    }
+    const uint32_t s254 = (uint32_t)__shfl((int)s_before_last, 63);
+    if (lane < 2) {
+      const uint32_t lag = 256 + lane;
+      const bool open = (s255 != 0) && lane == 0;
+      const bool pseudo = (s255 == 0 && s254 == 0);
+      if ((open || pseudo) && ((lm_hi >> lane) & 1u)) {
+        const double v = s_r[lag];
+        cand |= 16u;
+        if (v > best) { best = v; arg = lag; }
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const double ov = __shfl_xor(best, off);
+      const uint32_t oa = (uint32_t)__shfl_xor((int)arg, off);
+      if (ov > best || (ov == best && ov > 0.0 && oa < arg)) { best = ov; arg = oa; }
+    }
+    // the winner must stand clear of every other candidate: a tie, or anything within 2 eps of it, is not decided here
+    bool close = false;
+#pragma unroll
+    for (uint32_t q = 0; q < 5; q++) {
+      const uint32_t lag = (q < 4) ? lane * 4 + q : 256 + lane;
+      if (((cand >> q) & 1u) && lag != arg && !(s_r[lag] < best - 2.0 * eps)) { close = true; }
+    }
+    if (__ballot(close) != 0ull) { unsafe = true; }
+    const double r0 = s_r[0];
+    const bool silent = (r0 == 0.0);                                         // exact: every sample of the block is zero
+    const bool live = fabs(r0) > (double)FLT_MIN;
+    if (!silent && !(r0 - eps > 2.0 * (double)FLT_MIN)) { unsafe = true; }
+    const uint32_t chosen = live ? arg : 0u;
+    double* o = out + (uint64_t)job * SLA_HIP_ACF_RECORD;
+    if (lane == 0) {
+      o[0] = !live ? 0.0 : ((best > 0.0) ? 1.0 : 2.0); o[1] = (double)chosen;
+      eps_out[job] = (silent || !unsafe) ? eps : -1.0;
+    }
+    if (lane < 5) { o[2 + lane] = s_r[lane]; }
+    if (lane >= 8 && lane < 13) { const uint32_t k = lane - 8; o[7 + k] = (chosen + k >= 2) ? s_r[chosen + k - 2] : 0.0; }
+  }
+}
+
+template <int LTOP, int THREADS>
+__global__ __launch_bounds__(THREADS, 4)
+void k_ltm_acf_fast(const int32_t* __restrict__ res, uint64_t stride, const sla_hip_acf_job* __restrict__ jobs,
+                    uint32_t njobs, const double* __restrict__ tw_fast, double* __restrict__ out, double* __restrict__ eps_out,
+                    double eps_rel, unsigned long long* span)
+{
+  extern __shared__ double2 lds2[];
+  span_begin(span);
+  // THREADS = 2^(LTOP - 3): one radix-8 group per thread in the largest transform's passes (with more, half the workgroup
+  // idles in every pass of a half-size transform and the kernel, bound by the latency of its passes, gains nothing)
+  static_assert(THREADS == (1 << (LTOP - 3)), "threads per workgroup");
+  constexpr int LMIN = (THREADS == 1024) ? 11 : 10;      // acf2_middle: at least one pair per thread; H >= 2048: a short last block has no wrap term
+  static_assert(LTOP >= LMIN && LTOP <= LMIN + 2, "sizes instantiated below");
+  __shared__ double s_r[ACF_FAST_LAGS + 4];
+  __shared__ double s_head[ACF_WRAP_LAGS], s_tail[ACF_WRAP_LAGS + 8];
+  __shared__ unsigned long long s_mask[4][ACF_PICK_LAGS / 64];
+  double2* z = lds2;
+  const double scale = 4.656612873077392578125e-10;   // 2^-31
+  for (uint32_t job = blockIdx.x; job < njobs; job += gridDim.x) {
+    const sla_hip_acf_job jb = jobs[job];
+    const int32_t* src = res + (uint64_t)jb.channel * stride + jb.blk_off;
+    const uint32_t n = jb.blk_len;
+    uint32_t l = LMIN;
+    while ((2u << l) < n && l < (uint32_t)LTOP) { l++; }
+    const uint32_t H = 2u << l;
+    const bool size_ok = (n <= H);                         // (a block beyond the capacity the kernel was built for: never certified)
+    const double* tw = tw_fast + ACF_FAST_TW_OFFSET(l, LMIN);
+    if (l == (uint32_t)LMIN) { acf_fast_transform<LMIN, THREADS>(z, src, n, tw); }
+    else if constexpr (LTOP >= LMIN + 1) {
+      if (l == (uint32_t)LMIN + 1) { acf_fast_transform<LMIN + 1, THREADS>(z, src, n, tw); }
+      else if constexpr (LTOP >= LMIN + 2) { acf_fast_transform<LMIN + 2, THREADS>(z, src, n, tw); }
+    }
+    // wrap term of the lags 0 .. ACF_WRAP_LAGS - 1 and the scale of the reference: r_ref = F/2 sum, circular = H/2 sum
+    const bool wrap = size_ok && (n + ACF_WRAP_LAGS > H);      // (then n >= H - 264 >= 1784: both runs lie inside the block)
+    if (wrap) {
+      for (uint32_t t = threadIdx.x; t < 2 * ACF_WRAP_LAGS + 8; t += THREADS) {
+        if (t < ACF_WRAP_LAGS) { s_head[t] = (double)src[t] * scale; }
+        else if (t < 2 * ACF_WRAP_LAGS) { s_tail[t - ACF_WRAP_LAGS] = (double)src[n - 2 * ACF_WRAP_LAGS + t] * scale; }
+        else { s_tail[t - ACF_WRAP_LAGS] = 0.0; }                                // (the window below reads zeros beyond the block's end)
+      }
+    }
+    const double ratio = (double)(1u << ((uint32_t)LTOP + 1u - l));             // F / H
+    for (uint32_t t = threadIdx.x; t < ACF_FAST_LAGS + 4; t += THREADS) { s_r[t] = (t < ACF_FAST_LAGS) ? ratio * acf_at(z, t) : 0.0; }
+    __syncthreads();
+    if (wrap) {
+      // wrap[k] = sum_{m < k - d} tail[264 - (k - d) + m] head[m], d = H - n, tail[i] = x[n - 264 + i] (zero from 264 on),
+      // head[m] = x[m].  Thread (g, c), g = tid / 8, c = tid % 8: the four lags k0 .. k0 + 3, k0 = 4 + 4 g (4 .. 259), over the
+      // terms m = 33 c .. 33 c + 32.  Lag k0 + q reads tail[base + m - q], base = 264 - k0 + d: a window of four values that
+      // slides by one per term -- one tail and one head value loaded per four FMAs; a term beyond its lag's count reads zeros.
+      const double fhalf = (double)(2u << (uint32_t)LTOP);                      // F / 2
+      const uint32_t d = H - n;
+      for (uint32_t it = threadIdx.x; it < 512u; it += THREADS) {
+        const uint32_t g = it >> 3, c = it & 7u, k0 = 4u + 4u * g, m0 = 33u * c;
+        const uint32_t base = ACF_WRAP_LAGS - k0 + d + m0;                      // >= 5
+        double w0 = s_tail[min(base, ACF_WRAP_LAGS)], w1 = s_tail[min(base - 1u, ACF_WRAP_LAGS)];
+        double w2 = s_tail[min(base - 2u, ACF_WRAP_LAGS)], w3 = s_tail[min(base - 3u, ACF_WRAP_LAGS)];
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+        for (uint32_t i = 0; i < 33u; i++) {
+          const double hm = s_head[min(m0 + i, ACF_WRAP_LAGS - 1u)];
+          a0 = fma(hm, w0, a0); a1 = fma(hm, w1, a1); a2 = fma(hm, w2, a2); a3 = fma(hm, w3, a3);
+          w3 = w2; w2 = w1; w1 = w0; w0 = s_tail[min(base + i + 1u, ACF_WRAP_LAGS)];
+        }
+#pragma unroll
+        for (int off = 1; off < 8; off <<= 1) {
+          a0 += __shfl_xor(a0, off); a1 += __shfl_xor(a1, off); a2 += __shfl_xor(a2, off); a3 += __shfl_xor(a3, off);
+        }
+        if (c < 4u) {
+          const double acc = (c == 0u) ? a0 : (c == 1u) ? a1 : (c == 2u) ? a2 : a3;
+          s_r[k0 + c] = fma(-fhalf, acc, s_r[k0 + c]);
+        }
+      }
+      if (threadIdx.x >= 1u && threadIdx.x < 4u) {                              // lags 1 .. 3: at most three terms
+        const uint32_t k = threadIdx.x, cnt = (k > d) ? (k - d) : 0u;
+        double acc = 0.0;
+        for (uint32_t m = 0; m < cnt; m++) { acc = fma(s_tail[ACF_WRAP_LAGS - cnt + m], s_head[m], acc); }
+        if (cnt != 0u) { s_r[k] = fma(-fhalf, acc, s_r[k]); }
+      }
+      __syncthreads();
+    }
+    acf_emit_cert<THREADS>(s_r, job, out, eps_out, eps_rel, size_ok, s_mask);
     __syncthreads();
   }
   span_end(span);
@@ -657,8 +941,10 @@ __device__ __forceinline__ double ext_to_double(ext80 x)
 // C5 launch for 45 000 tiny solves).  The pivot row and the permuted right-hand side are picked by compare-and-select
 // over the (at most five) candidates; the arithmetic and its order are the host's (sla_ltm.c), operation for operation.
 template <int D>
-__device__ __forceinline__ int ltm_lu_factor_s(double (&A)[D][D], uint32_t (&perm)[D], double (&scale)[D])
+__device__ __forceinline__ int ltm_lu_factor_s(double (&A)[D][D], uint32_t (&perm)[D], double (&scale)[D], double* clear = nullptr)
 {
+  // clear != nullptr (k_ltm_solve_cert): *clear = the smallest (best - runner-up) / best over the pivot searches, i.e. by how
+  // much every choice of a pivot row was decided
 #pragma unroll
   for (int row = 0; row < D; row++) {
     double big = 0.0;
@@ -677,7 +963,7 @@ __device__ __forceinline__ int ltm_lu_factor_s(double (&A)[D][D], uint32_t (&per
       for (int k = 0; k < row; k++) { sum -= A[row][k] * A[k][col]; }
       A[row][col] = sum;
     }
-    double big = 0.0;
+    double big = 0.0, second = 0.0;
     uint32_t imax = (uint32_t)col;
 #pragma unroll
     for (int row = col; row < D; row++) {
@@ -686,8 +972,9 @@ __device__ __forceinline__ int ltm_lu_factor_s(double (&A)[D][D], uint32_t (&per
       for (int k = 0; k < col; k++) { sum -= A[row][k] * A[k][col]; }
       A[row][col] = sum;
       const double t = scale[row] * fabs(sum);
-      if (t >= big) { big = t; imax = (uint32_t)row; }
+      if (t >= big) { second = big; big = t; imax = (uint32_t)row; } else if (t > second) { second = t; }
     }
+    if (clear != nullptr && col != D - 1) { *clear = fmin(*clear, (big > 0.0) ? (big - second) / big : 0.0); }
 #pragma unroll
     for (int r = col + 1; r < D; r++) {
       if (imax == (uint32_t)r) {
@@ -738,13 +1025,8 @@ __device__ __forceinline__ void ltm_lu_substitute_s(const double (&A)[D][D], dou
 }
 
 template <int D>
-__global__ __launch_bounds__(64)
-void k_ltm_solve(const double* __restrict__ acf, const sla_hip_lpc_group* __restrict__ groups, uint32_t num_jobs,
-                 sla_hip_tail_job* __restrict__ jobs)
+__device__ __forceinline__ sla_hip_tail_job ltm_solve_one(const double* __restrict__ rec, const sla_hip_lpc_group g)
 {
-  const uint32_t j = blockIdx.x * 64 + threadIdx.x;
-  if (j >= num_jobs) { return; }
-  const double* rec = acf + (uint64_t)j * SLA_HIP_ACF_RECORD;
   double low[5], mid[5];
 #pragma unroll
   for (int i = 0; i < 5; i++) { low[i] = rec[2 + i]; mid[i] = rec[7 + i]; }
@@ -797,7 +1079,6 @@ void k_ltm_solve(const double* __restrict__ acf, const sla_hip_lpc_group* __rest
     }
   }
   if (ret != 0 || pitch >= 256u) { pitch = 0; }            // src/SLAEncoder.c:629-632
-  const sla_hip_lpc_group g = groups[j];
   sla_hip_tail_job out;
   out.blk_off = g.pcm_off; out.blk_len = g.num_samples; out.channel = g.channel; out.pitch = pitch;
 #pragma unroll
@@ -809,5 +1090,170 @@ void k_ltm_solve(const double* __restrict__ acf, const sla_hip_lpc_group* __rest
     out.ltm_coef[t] = (int32_t)((uint32_t)q << 16);
   }
   out.pad_[0] = out.pad_[1] = 0;
+  return out;
+}
+
+template <int D>
+__global__ __launch_bounds__(64)
+void k_ltm_solve(const double* __restrict__ acf, const sla_hip_lpc_group* __restrict__ groups, uint32_t num_jobs,
+                 sla_hip_tail_job* __restrict__ jobs)
+{
+  const uint32_t j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= num_jobs) { return; }
+  jobs[j] = ltm_solve_one<D>(acf + (uint64_t)j * SLA_HIP_ACF_RECORD, groups[j]);
+}
+
+// the exact solve over the list k_ltm_solve_cert left (records rewritten by k_ltm_acf2_list): a fixed grid strides over it.
+// counters: [0] list entries, [1] uncertified jobs, [2] audited jobs whose certified pitch and taps equal the exact ones, [3] unequal
+template <int D>
+__global__ __launch_bounds__(64)
+void k_ltm_solve_list(const double* __restrict__ acf, const sla_hip_lpc_group* __restrict__ groups,
+                      const uint32_t* __restrict__ list, uint32_t* __restrict__ counters, sla_hip_tail_job* __restrict__ jobs)
+{
+  const uint32_t n_list = counters[0];
+  for (uint32_t i = blockIdx.x * 64 + threadIdx.x; i < n_list; i += gridDim.x * 64) {
+    const uint32_t entry = list[i], j = entry & ~LTM_LIST_AUDIT;
+    const sla_hip_tail_job out = ltm_solve_one<D>(acf + (uint64_t)j * SLA_HIP_ACF_RECORD, groups[j]);
+    if (entry & LTM_LIST_AUDIT) {
+      const sla_hip_tail_job was = jobs[j];
+      bool same = (was.pitch == out.pitch);
+#pragma unroll
+      for (int t = 0; t < LTM_NT; t++) { same = same && (was.ltm_coef[t] == out.ltm_coef[t]); }
+      atomicAdd(&counters[same ? 2 : 3], 1u);
+    }
+    jobs[j] = out;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_ltm_solve_cert: pitch and taps from k_ltm_acf_fast's record when they provably equal what k_ltm_solve makes of the
+// reference's record; otherwise the job goes onto the fallback list.  With |r' - r_ref| <= eps in every entry
+// (dR: Toeplitz of entries <= eps, ||dR||_inf <= D eps; db: entries <= eps) the first-order perturbation of R x = b is
+//     ||dx||_inf <= ||R^-1||_inf (eps + eps sum|x|)
+// doubled here for the second-order terms (||R^-1|| D eps < 1e-3 is required) and widened by 128 u cond (1 + sum|x|) for
+// the rounding of both solvers (LU with partial pivoting, refinement: a few u cond each).  ||R^-1||_inf comes from D unit
+// solves with the factorisation at hand.  Certified means: the factorisation's failure tests (row maximum and pivots
+// against FLT_EPSILON) are decided with margin, cond_inf <= 64, sum|x| is off 1 by more than D dx, and every tap * 2^15 is
+// further from a rounding boundary of the quantiser than dx * 2^15 plus a few ulp of the value.
+// ---------------------------------------------------------------------------------------------
+template <int D>
+__global__ __launch_bounds__(64)
+void k_ltm_solve_cert(const double* __restrict__ acf, const double* __restrict__ eps_in, const sla_hip_lpc_group* __restrict__ groups,
+                      uint32_t num_jobs, sla_hip_tail_job* __restrict__ jobs, uint32_t* __restrict__ list,
+                      uint32_t* __restrict__ counters, uint32_t audit_every)
+{
+  const uint32_t j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= num_jobs) { return; }
+  const double* rec = acf + (uint64_t)j * SLA_HIP_ACF_RECORD;
+  const double u = 1.1102230246251565e-16;
+  const double eps = eps_in[j];
+  double low[5], mid[5];
+#pragma unroll
+  for (int i = 0; i < 5; i++) { low[i] = rec[2 + i]; mid[i] = rec[7 + i]; }
+  const uint32_t chosen = (uint32_t)rec[1];
+  bool ok = (eps >= 0.0) && (eps < 1.0e300);             // the pick is certified (acf_emit_cert), nothing non-finite
+  double vec[LTM_NT] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  double delta = 0.0;
+  uint32_t pitch = 0;
+  int ret = 0;
+  if (!ok || rec[0] == 0.0) {
+    ret = 0;
+  } else if (rec[0] != 1.0 || chosen < (uint32_t)(D / 2 + 1)) {
+    ret = 4;
+  } else {
+    double R[D][D], A[D][D], x[D], err[D], scale[D], b[D];
+    uint32_t perm[D];
+    double rowmax = 0.0, normR = 0.0, clear = 1.0;
+#pragma unroll
+    for (int r = 0; r < D; r++) {
+      double rs = 0.0;
+#pragma unroll
+      for (int c = 0; c < D; c++) { R[r][c] = low[(r >= c) ? (r - c) : (c - r)]; A[r][c] = R[r][c]; rs += fabs(R[r][c]); }
+      normR = fmax(normR, rs);
+    }
+#pragma unroll
+    for (int c = 0; c < D; c++) { rowmax = fmax(rowmax, fabs(low[c])); ok = ok && (fabs(low[c]) < 1.0e300) && (fabs(mid[c]) < 1.0e300); }
+#pragma unroll
+    for (int r = 0; r < D; r++) { b[r] = mid[2 + r - D / 2]; x[r] = b[r]; }
+    if (rowmax + eps <= (double)FLT_EPSILON * (1.0 - 1.0e-9)) {
+      ret = 4;                                             // row 0 (it holds r[0 .. D-1]) fails the reference's row test for certain
+    } else if (!(low[0] - eps > (double)FLT_EPSILON * (1.0 + 1.0e-9))) {
+      ok = false;                                          // (r[0] sits in every row: above the threshold, every row passes)
+    } else if (ltm_lu_factor_s<D>(A, perm, scale, &clear) != 0) {
+      ok = false;                                          // a pivot at FLT_EPSILON here: not decided for the reference
+    } else {
+      double pivmin = fabs(A[0][0]);
+#pragma unroll
+      for (int r = 1; r < D; r++) { pivmin = fmin(pivmin, fabs(A[r][r])); }
+      ltm_lu_substitute_s<D>(A, x, perm);
+#pragma unroll
+      for (int r = 0; r < D; r++) {
+        double acc = -b[r];
+#pragma unroll
+        for (int c = 0; c < D; c++) { acc = fma(R[r][c], x[c], acc); }
+        err[r] = acc;
+      }
+      ltm_lu_substitute_s<D>(A, err, perm);
+#pragma unroll
+      for (int r = 0; r < D; r++) { x[r] -= err[r]; }
+      double rows[D];
+#pragma unroll
+      for (int r = 0; r < D; r++) { rows[r] = 0.0; }
+#pragma unroll
+      for (int c = 0; c < D; c++) {
+        double col[D];
+#pragma unroll
+        for (int r = 0; r < D; r++) { col[r] = (r == c) ? 1.0 : 0.0; }
+        ltm_lu_substitute_s<D>(A, col, perm);
+#pragma unroll
+        for (int r = 0; r < D; r++) { rows[r] += fabs(col[r]); }
+      }
+      double ninv = 0.0, mag = 0.0;
+#pragma unroll
+      for (int r = 0; r < D; r++) { ninv = fmax(ninv, rows[r]); mag += fabs(x[r]); }
+      const double kappa = ninv * normR;
+      delta = 2.0 * ninv * eps * (1.0 + mag) + 128.0 * u * kappa * (1.0 + mag);
+      // pivot = ratio of two leading minors of the row-permuted matrix; d det / det <= D ||R^-1|| D eps each: |d pivot| <=
+      // 2 D^2 cond eps, doubled.  That compares like with like only if the reference exchanges the same rows: every pivot
+      // search (scaled column entries, perturbed by at most ~2 D^2 cond^2 eps / r[0] ~ 1.5e-7 of the winner at cond = 64)
+      // must have been decided by 1e-5 of the winner, or the job is not certified
+      ok = ok && (clear > 1.0e-5) && (kappa <= 64.0) && (ninv * (double)D * eps < 1.0e-3)
+              && (pivmin * (1.0 - 1.0e-9) - 4.0 * (double)(D * D) * kappa * eps > (double)FLT_EPSILON);
+      if (mag - (double)D * delta - 1.0e-14 >= 1.0) {
+#pragma unroll
+        for (int r = 0; r < D; r++) { x[r] = 0.0; }
+        x[D / 2] = mid[2] / low[0];
+        delta = 2.0 * eps * (1.0 + fabs(x[D / 2])) / low[0] + 8.0 * u;       // the single tap r[p] / r[0]; the zero taps are exact
+      } else if (!(mag + (double)D * delta + 1.0e-14 < 1.0)) {
+        ok = false;
+      }
+      pitch = chosen;
+#pragma unroll
+      for (int r = 0; r < D; r++) { vec[r] = x[r]; }
+    }
+  }
+  if (ret != 0 || pitch >= 256u) { pitch = 0; }
+  const sla_hip_lpc_group g = groups[j];
+  sla_hip_tail_job out;
+  out.blk_off = g.pcm_off; out.blk_len = g.num_samples; out.channel = g.channel; out.pitch = pitch;
+#pragma unroll
+  for (int t = 0; t < LTM_NT; t++) {
+    const double v = ((t < D) ? vec[t] : 0.0) * 32768.0;
+    const double av = fabs(v);
+    // floor(|v| + 0.5) steps where |v| + 0.5 is an integer, and the sum itself rounds: stay dx 2^15 and a few ulp away
+    const double fr = (av + 0.5) - floor(av + 0.5);
+    const double dist = fmin(fr, 1.0 - fr);
+    if (t < D && !(dist > delta * 32768.0 + 16.0 * u * (av + 1.0) && av < 2.0e9)) { ok = false; }      // (a zero tap: dist = 0.5)
+    const double rv = (v >= 0.0) ? floor(v + 0.5) : -floor(-v + 0.5);
+    const int32_t q = (!(rv > -2147483649.0 && rv < 2147483648.0)) ? INT32_MIN : (int32_t)rv;
+    out.ltm_coef[t] = (int32_t)((uint32_t)q << 16);
+  }
+  out.pad_[0] = out.pad_[1] = 0;
   jobs[j] = out;
+  if (!ok) {
+    list[atomicAdd(&counters[0], 1u)] = j;
+    atomicAdd(&counters[1], 1u);
+  } else if (audit_every != 0 && (j % audit_every) == 0) {
+    list[atomicAdd(&counters[0], 1u)] = j | LTM_LIST_AUDIT;
+  }
 }

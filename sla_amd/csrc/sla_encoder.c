@@ -78,6 +78,10 @@ struct SLAEncoder {
                                      * the exact chain kernel for the rest; 0: every block through the exact kernel */
   double   block_cert_safety;       /* safety factor on the first-order bound of that certificate (16) */
   volatile int cert_broken;         /* a block flagged by the certificate was not redone (internal error), or an audited block differed */
+  int      ltm_cert;                /* 1: long-term stage by the certified FMA route (k_ltm_acf_fast), exact kernels on what does not certify (default) */
+  double   ltm_cert_safety;         /* safety factor on that certificate's first-order bound (16) */
+  int      ltm_cert_now;            /* this run's long-term stage takes the certified route */
+  uint32_t ltm_stat[5];             /* last analysis: jobs, certified, fallback, audit ok, audit bad */
   volatile uint32_t audit_ok, audit_bad;   /* option cert_audit: certified pairs the exact kernels found equal / different (last analysis) */
   int      cert_now;                /* this run's block stage takes the certified route */
   int      prelaunch;               /* 1 (default): short files queue the certified block kernels with the searches, sized for the most groups
@@ -113,7 +117,7 @@ struct SLAEncoder {
   devbuf_t d_pcm, d_res1, d_res2, d_or, d_nz, d_groups, d_cands, d_lpc_out, d_code, d_kint, d_rshift,
            d_winpool, d_chunks, d_jobs, d_fold, d_acf_jobs, d_acf, d_acf_scratch, d_twiddle, d_bgroups, d_bcands, d_blk_out, d_kk, d_pk_jobs, d_pk_blocks, d_pk_hdr, d_image,
            d_xgroups, d_tile_sums, d_fgroups, d_parts, d_nparts, d_pstatus, d_spans, d_cert_flag, d_fb_list, d_fb_count,
-           d_sframes, d_winmap, d_run, d_expref;
+           d_sframes, d_winmap, d_run, d_expref, d_fast_twiddle, d_ltm_eps, d_ltm_list;
   int twiddle_ready;
   /* pinned host staging */
   pinbuf_t h_nz, h_groups, h_cands, h_lpc_out, h_code, h_kint, h_rshift, h_chunks, h_jobs, h_fold, h_res, h_pcm, h_acf_jobs, h_acf,
@@ -378,6 +382,7 @@ struct SLAEncoder* SLAEncoder_Create(const struct SLAEncoderConfig* config)
   e->device_ltm = 1;
   e->search_exact = 1; e->exact_bits = 53; e->device_plan = 1; e->cert_safety = 64.0;
   e->block_cert = 1; e->block_cert_safety = 16.0;
+  e->ltm_cert = 1; e->ltm_cert_safety = SLA_HIP_LTM_CERT_SAFETY_MIN;
   e->table_cache = 1;
   e->prelaunch = 1;
   e->device_expand = 1; e->expand_silence = 1;
@@ -422,7 +427,7 @@ fail:
 
 void SLAEncoder_Destroy(struct SLAEncoder* e)
 {
-  devbuf_t* d[41];
+  devbuf_t* d[44];
   pinbuf_t* h[29];
   int i;
   if (e == NULL) { return; }
@@ -443,7 +448,8 @@ void SLAEncoder_Destroy(struct SLAEncoder* e)
   d[30] = &e->d_parts; d[31] = &e->d_nparts; d[32] = &e->d_pstatus; d[33] = &e->d_spans;
   d[34] = &e->d_cert_flag; d[35] = &e->d_fb_list; d[36] = &e->d_fb_count;
   d[37] = &e->d_sframes; d[38] = &e->d_winmap; d[39] = &e->d_run; d[40] = &e->d_expref;
-  for (i = 0; i < 41; i++) { if (d[i]->ptr != NULL) { (void)hipFree(d[i]->ptr); } }
+  d[41] = &e->d_fast_twiddle; d[42] = &e->d_ltm_eps; d[43] = &e->d_ltm_list;
+  for (i = 0; i < 44; i++) { if (d[i]->ptr != NULL) { (void)hipFree(d[i]->ptr); } }
   h[0] = &e->h_nz; h[1] = &e->h_groups; h[2] = &e->h_cands; h[3] = &e->h_lpc_out; h[4] = &e->h_code; h[5] = &e->h_kint;
   h[6] = &e->h_rshift; h[7] = &e->h_chunks; h[8] = &e->h_jobs; h[9] = &e->h_fold; h[10] = &e->h_res; h[11] = &e->h_pcm;
   h[12] = &e->h_acf_jobs; h[13] = &e->h_acf; h[14] = &e->h_bgroups; h[15] = &e->h_bcands; h[16] = &e->h_blk_out;
@@ -565,6 +571,11 @@ static int blocks_push(struct SLAEncoder* e, uint32_t start, uint32_t nsmpl, uin
  * All buffers are sized for the whole file before the first launch: nothing is reallocated in flight. */
 
 #define MAX_CHUNKS 8
+/* d_spans: MAX_CHUNKS x 4 span slots of two 64-bit words, then MAX_CHUNKS x 4 32-bit counters of the certified long-term
+ * stage (list entries, uncertified, audit ok, audit bad) -- cleared and brought home together */
+#define SPAN_ULLS (MAX_CHUNKS * 4 * 2)
+#define SPAN_AREA_ULLS (SPAN_ULLS + MAX_CHUNKS * 2)
+#define LTM_CNT_SLOT(e, c) ((uint32_t*)((unsigned long long*)(e)->d_spans.ptr + SPAN_ULLS) + 4 * (size_t)(c))
 #define SPECULATE_MAX_GROUPS 16384u      /* (super-frame, channel) pairs up to which the searches are launched on a guess */
 enum { EV_SEARCH_S, EV_SEARCH_E, EV_SEARCH_DONE, EV_LPCB_S, EV_LPCB_E, EV_LAT_E, EV_ACF_S, EV_ACF_E, EV_BLOCK_DONE,
        EV_TAIL_S, EV_TAIL_E, EV_TAIL_DONE, EV_UPLOADED, EV_PLANNED, EV_UPLOADED2, EV_LPC_DOWN, EV_SOLVED, EV_EXPANDED, EV_PER_CHUNK };
@@ -1240,6 +1251,8 @@ static int pipeline_reserve(struct SLAEncoder* e, const actx_t* a)
   RCCHK(dev_reserve(&e->d_cert_flag, sizeof(uint32_t) * nslots));
   RCCHK(dev_reserve(&e->d_fb_list, sizeof(uint32_t) * nslots));
   RCCHK(dev_reserve(&e->d_fb_count, sizeof(uint32_t) * MAX_CHUNKS));
+  RCCHK(dev_reserve(&e->d_ltm_eps, sizeof(double) * nslots));
+  RCCHK(dev_reserve(&e->d_ltm_list, sizeof(uint32_t) * nslots));
   RCCHK(pin_reserve(&e->h_cert_flag, sizeof(uint32_t) * (nslots + MAX_CHUNKS)));
   RCCHK(dev_reserve(&e->d_acf, sizeof(double) * nslots * SLAI_LTM_ACF_HEAD));
   RCCHK(dev_reserve(&e->d_fold, sizeof(uint64_t) * nslots));
@@ -1281,6 +1294,15 @@ static int pipeline_reserve(struct SLAEncoder* e, const actx_t* a)
     RCCHK(dev_reserve(&e->d_twiddle, sizeof(double) * SLA_HIP_TWIDDLE_DOUBLES(fft_size)));
     HIPCHK(hipMemcpy(e->d_twiddle.ptr, tw, sizeof(double) * SLA_HIP_TWIDDLE_DOUBLES(fft_size), hipMemcpyHostToDevice));
     free(tw);
+    if (sla_hip_ltm_cert_supported(fft_size)) {
+      /* the certified route's own tables (one per transform size it can pick) */
+      tw = (double*)malloc(sizeof(double) * SLA_HIP_FAST_TWIDDLE_DOUBLES(fft_size));
+      if (tw == NULL) { return SLA_APIRESULT_NG; }
+      if (sla_hip_ltm_fast_twiddles(fft_size, tw) != 0) { free(tw); return SLA_APIRESULT_NG; }
+      RCCHK(dev_reserve(&e->d_fast_twiddle, sizeof(double) * SLA_HIP_FAST_TWIDDLE_DOUBLES(fft_size)));
+      HIPCHK(hipMemcpy(e->d_fast_twiddle.ptr, tw, sizeof(double) * SLA_HIP_FAST_TWIDDLE_DOUBLES(fft_size), hipMemcpyHostToDevice));
+      free(tw);
+    }
     e->twiddle_ready = 1;
   }
   return 0;
@@ -1641,14 +1663,28 @@ static int blocks_launch(struct SLAEncoder* e, actx_t* a, uint32_t c, int mode)
     if (sizeof(double) * (size_t)fft_size > SLA_HIP_LDS_BUDGET) { slots = (ng < 512) ? ng : 512; }
     HIPCHK(hipEventRecord(ev[EV_ACF_S], bs));
     xb.d_span = SPAN_SLOT(e, c, 2);
-    RCCHK(sla_hip_launch_ltm_acf_x(RES1(e), e->stride, da, ng, fft_size, (const double*)e->d_twiddle.ptr,
-                                   (double*)e->d_acf_scratch.ptr, slots,
-                                   (double*)e->d_acf.ptr + (size_t)k->bg_lo * SLAI_LTM_ACF_HEAD, SLAI_LTM_ACF_HEAD, bs, &xb));
-    HIPCHK(hipEventRecord(ev[EV_ACF_E], bs));
+    if (e->ltm_cert_now) {
+      /* any-order FMA autocorrelation + certified solve; what does not certify goes through the exact kernels behind them,
+       * inside the stage's events: pitch + taps are in the job table when EV_ACF_E fires */
+      RCCHK(sla_hip_launch_ltm_cert_x(RES1(e), e->stride, da, dg, ng, fft_size, (const double*)e->d_twiddle.ptr,
+                                      (const double*)e->d_fast_twiddle.ptr, (double*)e->d_acf_scratch.ptr, slots,
+                                      (double*)e->d_acf.ptr + (size_t)k->bg_lo * SLAI_LTM_ACF_HEAD, (double*)e->d_ltm_eps.ptr + k->bg_lo,
+                                      e->encode_param.longterm_order, e->ltm_cert_safety, (sla_hip_tail_job*)e->d_jobs.ptr + k->bg_lo,
+                                      (uint32_t*)e->d_ltm_list.ptr + k->bg_lo, LTM_CNT_SLOT(e, c), bs, &xb));
+      HIPCHK(hipEventRecord(ev[EV_ACF_E], bs));
+    } else {
+      RCCHK(sla_hip_launch_ltm_acf_x(RES1(e), e->stride, da, ng, fft_size, (const double*)e->d_twiddle.ptr,
+                                     (double*)e->d_acf_scratch.ptr, slots,
+                                     (double*)e->d_acf.ptr + (size_t)k->bg_lo * SLAI_LTM_ACF_HEAD, SLAI_LTM_ACF_HEAD, bs, &xb));
+      HIPCHK(hipEventRecord(ev[EV_ACF_E], bs));
+      if (e->device_ltm) {
+        /* pitch + taps into the job table k_tail reads */
+        RCCHK(sla_hip_launch_ltm_solve((const double*)e->d_acf.ptr + (size_t)k->bg_lo * SLAI_LTM_ACF_HEAD, dg, ng,
+                                       e->encode_param.longterm_order, (sla_hip_tail_job*)e->d_jobs.ptr + k->bg_lo, bs));
+      }
+    }
     if (e->device_ltm) {
-      /* pitch + taps into the job table k_tail reads; the tail follows on the same stream, no host in between */
-      RCCHK(sla_hip_launch_ltm_solve((const double*)e->d_acf.ptr + (size_t)k->bg_lo * SLAI_LTM_ACF_HEAD, dg, ng,
-                                     e->encode_param.longterm_order, (sla_hip_tail_job*)e->d_jobs.ptr + k->bg_lo, bs));
+      /* the tail follows on the same stream, no host in between */
       if (!e->single_tail) { RCCHK(tail_enqueue(e, a, c, k->bg_lo, k->bg_hi)); }
       else { HIPCHK(hipEventRecord(ev[EV_SOLVED], bs)); }
     } else {
@@ -1859,8 +1895,8 @@ static int launch_searches(struct SLAEncoder* e, actx_t* a, int preset_blocks, i
   /* (with the tile-sum search those words, the rerun counter and k_expand's running numbers are cleared by the first search
    * kernel itself -- sla_hip_launch_extra.clear_ptr -- instead of by three fill kernels in front of it) */
   a->clear_in_kernel = (!preset_blocks && a->exact);
-  if (dev_reserve(&e->d_spans, sizeof(unsigned long long) * MAX_CHUNKS * 4 * 2) != 0
-      || (!a->clear_in_kernel && hipMemsetAsync(e->d_spans.ptr, 0, sizeof(unsigned long long) * MAX_CHUNKS * 4 * 2, e->stream) != hipSuccess)
+  if (dev_reserve(&e->d_spans, sizeof(unsigned long long) * SPAN_AREA_ULLS) != 0
+      || (!a->clear_in_kernel && hipMemsetAsync(e->d_spans.ptr, 0, sizeof(unsigned long long) * SPAN_AREA_ULLS, e->stream) != hipSuccess)
       || (preset_blocks && hipStreamSynchronize(e->stream) != hipSuccess)) { return SLA_APIRESULT_NG; }
   TRACE("reserved", 0);
 
@@ -1924,7 +1960,7 @@ static int launch_searches(struct SLAEncoder* e, actx_t* a, int preset_blocks, i
   if (!preset_blocks) {
     if (a->clear_in_kernel) {
       /* (the first search launch of this analysis takes them along: search_launch, chunk 0) */
-      a->clear_ptr[0] = (uint32_t*)e->d_spans.ptr; a->clear_words[0] = MAX_CHUNKS * 4 * 2 * 2;
+      a->clear_ptr[0] = (uint32_t*)e->d_spans.ptr; a->clear_words[0] = SPAN_AREA_ULLS * 2;
       a->clear_ptr[1] = (uint32_t*)e->d_or.ptr + 2; a->clear_words[1] = 1;
       a->clear_ptr[2] = a->expand ? (uint32_t*)e->d_run.ptr : NULL; a->clear_words[2] = 4;
     } else if (hipMemsetAsync((uint32_t*)e->d_or.ptr + 2, 0, sizeof(uint32_t), e->stream) != hipSuccess) { rc = SLA_APIRESULT_NG; }      /* groups rerun as serial chains */
@@ -1953,6 +1989,8 @@ static int run_pipeline(struct SLAEncoder* e, int preset_blocks)
 
   e->fallback_groups = 0; e->host_planned = 0; e->blocks_exact = 0; e->cert_broken = 0; e->audit_ok = 0; e->audit_bad = 0;
   e->expanded_chunks = 0;
+  memset(e->ltm_stat, 0, sizeof(e->ltm_stat));
+  e->ltm_cert_now = (e->ltm_cert && e->device_ltm && sla_hip_ltm_cert_supported(slai_fft_plan_size(e->fft)));
   e->cert_now = (e->block_cert && !(e->fuse_lattice && e->encode_param.parcor_order <= 64) && !e->tune.lpc_blocks_chains
                  && sla_hip_search_exact_lags(e->encode_param.parcor_order) != 0);
   a.trace = trace; a.t_begin = t_begin;
@@ -2071,7 +2109,7 @@ static int run_pipeline(struct SLAEncoder* e, int preset_blocks)
     int copied = 0;
     if (rc == 0) {
       hipStream_t last = (a.tail_stream != NULL) ? a.tail_stream : ((e->device_ltm && e->single_tail) ? e->stream2 : e->stream3);      /* the stream the last k_tail runs on */
-      copied = (hipMemcpyAsync(sp_host, e->d_spans.ptr, sizeof(unsigned long long) * MAX_CHUNKS * 4 * 2, hipMemcpyDeviceToHost, last) == hipSuccess);
+      copied = (hipMemcpyAsync(sp_host, e->d_spans.ptr, sizeof(unsigned long long) * SPAN_AREA_ULLS, hipMemcpyDeviceToHost, last) == hipSuccess);
       if (!preset_blocks && hipMemcpyAsync(e->h_or + 2, (uint32_t*)e->d_or.ptr + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, last) != hipSuccess) { rc = SLA_APIRESULT_NG; }
     }
   if (hipStreamSynchronize(e->stream) != hipSuccess || hipStreamSynchronize(e->stream2) != hipSuccess
@@ -2094,6 +2132,16 @@ static int run_pipeline(struct SLAEncoder* e, int preset_blocks)
       (void)hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, e->device);
       if (rate_khz <= 0) { rate_khz = 100000; }
       e->wall_clock_khz = rate_khz;
+    }
+    if (copied && e->ltm_cert_now) {
+      const uint32_t* lc = (const uint32_t*)(sp + SPAN_ULLS);
+      for (c = 0; c < a.nchunks; c++) {
+        e->ltm_stat[0] += a.ck[c].bg_hi - a.ck[c].bg_lo; e->ltm_stat[2] += lc[4 * c + 1];
+        e->ltm_stat[3] += lc[4 * c + 2]; e->ltm_stat[4] += lc[4 * c + 3];
+      }
+      e->ltm_stat[1] = e->ltm_stat[0] - e->ltm_stat[2];
+      e->audit_ok += e->ltm_stat[3]; e->audit_bad += e->ltm_stat[4];
+      if (e->ltm_stat[4] != 0) { e->cert_broken = 1; rc = SLA_APIRESULT_NG; }      /* an audited job differed: the certificate is wrong */
     }
     if (copied) {
       for (c = 0; c < a.nchunks; c++) {
@@ -2160,6 +2208,8 @@ int sla_hip_encoder_set_option(struct SLAEncoder* e, const char* name, double va
   else if (strcmp(name, "cert_safety") == 0)       { if ((value != 0.0 && value < 64.0) || value > 1e30) { return SLA_APIRESULT_INVALID_ARGUMENT; } e->cert_safety = value; }
   else if (strcmp(name, "upload24") == 0)          { OPT_RANGE(0, 1); e->upload24 = (int)iv; }
   else if (strcmp(name, "block_cert") == 0)        { OPT_RANGE(0, 1); e->block_cert = (int)iv; }
+  else if (strcmp(name, "ltm_cert") == 0)          { OPT_RANGE(0, 1); e->ltm_cert = (int)iv; }
+  else if (strcmp(name, "ltm_cert_safety") == 0)   { if (!(value >= SLA_HIP_LTM_CERT_SAFETY_MIN) || value > 1e6) { return SLA_APIRESULT_INVALID_ARGUMENT; } e->ltm_cert_safety = value; }
   else if (strcmp(name, "block_cert_safety") == 0) { if (!(value >= 16.0) || value > 1e30) { return SLA_APIRESULT_INVALID_ARGUMENT; } e->block_cert_safety = value; }
   else if (strcmp(name, "device_plan") == 0)       { OPT_RANGE(0, 1); e->device_plan = (int)iv; }
   else if (strcmp(name, "single_tail") == 0)       { OPT_RANGE(0, 1); e->single_tail = (int)iv; }
@@ -2386,6 +2436,13 @@ int sla_hip_last_block_cert(const struct SLAEncoder* e, uint32_t* counters)
 {
   if (e == NULL || counters == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   counters[0] = (uint32_t)e->cert_now; counters[1] = e->blocks_exact;
+  return 0;
+}
+
+int sla_hip_last_ltm_cert(const struct SLAEncoder* e, uint32_t* counters)
+{
+  if (e == NULL || counters == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  memcpy(counters, e->ltm_stat, sizeof(e->ltm_stat));
   return 0;
 }
 
@@ -3174,7 +3231,7 @@ static struct SLAEncoder* stream_lane(struct SLAEncoder* e, uint32_t t)
   l->chunks = e->chunks; l->chunks_forced = e->chunks_forced; l->first_chunk = e->first_chunk; l->split_count = 0;
   l->fuse_lattice = e->fuse_lattice; l->device_plan = e->device_plan; l->search_exact = e->search_exact; l->exact_bits = e->exact_bits;
   l->cert_safety = e->cert_safety; l->single_tail = e->single_tail; l->device_ltm = e->device_ltm; l->tune = e->tune;
-  l->block_cert = e->block_cert; l->block_cert_safety = e->block_cert_safety; l->alt_streams = e->alt_streams; l->device_expand = e->device_expand; l->expand_silence = e->expand_silence;
+  l->block_cert = e->block_cert; l->block_cert_safety = e->block_cert_safety; l->ltm_cert = e->ltm_cert; l->ltm_cert_safety = e->ltm_cert_safety; l->alt_streams = e->alt_streams; l->device_expand = e->device_expand; l->expand_silence = e->expand_silence;
   l->table_cache = e->table_cache; l->prelaunch = e->prelaunch; l->one_stream = e->one_stream;
   l->trace = 0;
   return l;
@@ -3626,6 +3683,15 @@ static void* batch_lane_main(void* varg)
     rc = sla_hip_encode_batch(l, bc->items + bc->lo[g], bc->lo[g + 1] - bc->lo[g]);
     l->upload_gate = NULL; l->upload_pool = NULL;
     { int q; for (q = 0; q < 4; q++) { bc->stamp[g][q + 1] = l->batch_stamp[q] - bc->t0; } bc->lane_of[g] = (uint8_t)ba->lane; }
+    if (rc == 0) {
+      /* the lanes' certificate counters add up in the parent: it is the handle the caller reads them from */
+      struct SLAEncoder* par = bc->parent;
+      int q;
+      pthread_mutex_lock(&bc->mu);
+      par->audit_ok += l->audit_ok; par->audit_bad += l->audit_bad;
+      for (q = 0; q < 5; q++) { par->ltm_stat[q] += l->ltm_stat[q]; }
+      pthread_mutex_unlock(&bc->mu);
+    }
     if (rc != 0) {
       pthread_mutex_lock(&bc->mu);
       if (bc->failed == 0) { bc->failed = rc; }
@@ -3658,6 +3724,7 @@ static int encode_batch_on_lanes(struct SLAEncoder* e, sla_hip_batch_item* items
   bc = (batch_ctx_t*)calloc(1, sizeof(*bc));
   if (bc == NULL) { return SLA_APIRESULT_NG; }
   bc->parent = e; bc->items = items;
+  e->audit_ok = 0; e->audit_bad = 0; memset(e->ltm_stat, 0, sizeof(e->ltm_stat));      /* summed over the lanes' groups (batch_lane_main) */
   /* groups of consecutive files, about equal in samples */
   target = (total + G - 1) / G;
   bc->lo[0] = 0; g = 0;

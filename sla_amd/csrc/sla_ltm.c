@@ -121,6 +121,62 @@ void slai_fft_plan_export(const slai_fft_plan* p, double* out)
   }
 }
 
+/* ---- certified route (k_ltm_acf_fast) -------------------------------------------------------------------------
+ * Twiddles of the any-order transform: for every transform size 2^(l+1) real points the kernel can pick, l = lmin ..
+ * log2(fft_size) - 2, one table in the layout of slai_fft_plan_export for that size, the smaller sizes first; the values
+ * are cos / sin of the exact angles evaluated in double (the reference's recurrence is not needed: nothing here is
+ * compared bit for bit). */
+static void fast_table(uint32_t F, double* out)
+{
+  const uint32_t half = F / 2, quarter = F / 4;
+  const double pi = 3.14159265358979323846;
+  double* pair = out + 3 * (size_t)F;
+  uint32_t d, hs, k, i;
+  memset(out, 0, sizeof(double) * 6 * (size_t)F);
+  for (d = 0; d < 2; d++) {
+    const double sign = (d == 0) ? 1.0 : -1.0;
+    double* re = out + (size_t)d * F;
+    double* im = re + half;
+    double* rre = out + 2 * (size_t)F + 2 * (size_t)d * quarter;
+    double* rim = rre + quarter;
+    for (hs = 1; hs < half; hs <<= 1) {             /* stage with half-span hs complex points: w_k = exp(sign i pi k / hs) */
+      for (k = 0; k < hs; k++) {
+        const double ang = pi * (double)k / (double)hs;
+        re[hs - 1 + k] = (2 * k == hs) ? 0.0 : cos(ang);
+        im[hs - 1 + k] = sign * sin(ang);
+      }
+    }
+    for (i = 2; i <= quarter; i++) {                /* recombination: exp(sign i 2 pi (i - 1) / F) at index i - 2 */
+      const double ang = 2.0 * pi * (double)(i - 1) / (double)F;
+      rre[i - 2] = (4 * (i - 1) == F) ? 0.0 : cos(ang);
+      rim[i - 2] = sign * sin(ang);
+    }
+    for (i = 0; i + 1 < half; i++) { pair[2 * ((size_t)d * half + i)] = re[i]; pair[2 * ((size_t)d * half + i) + 1] = im[i]; }
+    for (i = 0; i + 1 < quarter; i++) { pair[2 * ((size_t)F + (size_t)d * quarter + i)] = rre[i]; pair[2 * ((size_t)F + (size_t)d * quarter + i) + 1] = rim[i]; }
+  }
+}
+
+int sla_hip_ltm_fast_twiddles(uint32_t fft_size, double* out)
+{
+  uint32_t log2F = 0, l, lmin;
+  if (out == NULL || !sla_hip_ltm_cert_supported(fft_size)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  while ((1u << log2F) < fft_size) { log2F++; }
+  lmin = (log2F == 15) ? 11u : 10u;                   /* (the largest capacity runs 1024 threads: its smallest transform is 4096 points) */
+  for (l = lmin; l + 2 <= log2F; l++) {
+    fast_table(2u << l, out);
+    out += 6 * (size_t)(2u << l);
+  }
+  return 0;
+}
+
+/* eps / r'[0] of the certificate: safety * c * u * log2(F), F the reference's transform size */
+double sla_hip_ltm_cert_eps_rel(uint32_t fft_size, double safety)
+{
+  uint32_t log2F = 0;
+  while ((1u << log2F) < fft_size) { log2F++; }
+  return safety * SLA_HIP_LTM_CERT_C * 1.1102230246251565e-16 * (double)log2F;
+}
+
 /* ---- tiny dense solve (reference src/SLAUtility.c:487-674) ---------------- */
 #define NT SLAI_MAX_TAPS
 static int lu_factor(double A[NT][NT], uint32_t dim, uint32_t* perm, double* scale)
