@@ -89,7 +89,7 @@ typedef struct sla_hip_acf_job {
 /* One (block, channel) of the serial tail (long-term filter + LMS + Rice sum). */
 typedef struct sla_hip_tail_job {
   uint64_t blk_off;
-  uint32_t blk_len;
+  uint32_t blk_len;        /* 0 is allowed: nothing is read or written for the job but fold_sum[j] = 0 */
   uint32_t channel;
   uint32_t pitch;          /* 0 = long-term stage bypassed */
   int32_t  ltm_coef[5];    /* Q31 taps (<<16 form), longterm_order of them used */

@@ -273,3 +273,41 @@ def test_synthesis_entry_points_on_extreme_operands(oracle, L):
     assert L.SLAEmphasisFilter_DeEmphasisInt32(C.c_void_p(h), p(got, i32p), n, 5) == 0
     assert np.array_equal(got, oracle.deemph_i32(x))
     L.SLAEmphasisFilter_Destroy(C.c_void_p(h))
+
+
+def test_prediction_entry_points_on_extreme_operands(oracle, L):
+    """the encoder-side twin of the test above: SLALMSFilter_PredictInt32 and SLALongTermSynthesizer_PredictInt32 take any
+    caller-supplied int32 samples, taps and length -- full-range input and a constant INT32_MIN (every LMS error is INT32_MIN,
+    the coefficients climb by 16 per sample), long-term taps at the ends of int32, every LMS order, and one block beyond 2^18
+    samples (the tail kernel's 24-bit products are off there); pinned to the reference for these operands in
+    tests/test_oracle_vs_ref.py::test_unit_prediction_on_extreme_operands"""
+    import tailmodel as M
+    rng = np.random.default_rng(31)
+    n = 3000
+    x = rng.integers(-2 ** 31, 2 ** 31, n, dtype=np.int64).astype(np.int32)
+    x[:6] = [-2 ** 31, 2 ** 31 - 1, -1, 0, 1, -2 ** 31]
+    inputs = [("full", x), ("allmin", M.family("allmin", n))]
+    h = L.SLALMSFilter_Create(32)
+    for name, v in inputs:
+        for order in (4, 8, 16, 32):
+            out = np.zeros(n, np.int32)
+            assert L.SLALMSFilter_Reset(C.c_void_p(h)) == 0
+            assert L.SLALMSFilter_PredictInt32(C.c_void_p(h), order, p(v, i32p), n, p(out, i32p)) == 0
+            assert np.array_equal(out, oracle.lms_predict(v, order)), (name, order)
+    big = 2 ** 18 + 33
+    for name, order in (("allmin", 8), ("ramp", 32)):
+        v = M.family(name, big)
+        out = np.zeros(big, np.int32)
+        assert L.SLALMSFilter_Reset(C.c_void_p(h)) == 0
+        assert L.SLALMSFilter_PredictInt32(C.c_void_p(h), order, p(v, i32p), big, p(out, i32p)) == 0
+        assert np.array_equal(out, oracle.lms_predict(v, order)), (name, order, big)
+    L.SLALMSFilter_Destroy(C.c_void_p(h))
+    h = L.SLALongTermSynthesizer_Create(5, 256)
+    for name, v in inputs:
+        for pitch, tapset in [(3, "min1"), (255, "ends3"), (100, "ends3b"), (7, "ends5"), (3, "ends5"), (17, "plain3"), (4, "plain5")]:
+            coef = M.taps(tapset)
+            out = np.zeros(n, np.int32)
+            assert L.SLALongTermSynthesizer_Reset(C.c_void_p(h)) == 0
+            assert L.SLALongTermSynthesizer_PredictInt32(C.c_void_p(h), p(v, i32p), n, pitch, p(coef, i32p), len(coef), p(out, i32p)) == 0
+            assert np.array_equal(out, oracle.ltm_predict(v, pitch, coef)), (name, pitch, tapset)
+    L.SLALongTermSynthesizer_Destroy(C.c_void_p(h))

@@ -123,6 +123,36 @@ def test_unit_synthesis_on_extreme_operands(oracle, ref):
     assert np.array_equal(oracle.deemph_i32(x), ref.deemph_i32(x))
 
 
+def test_unit_prediction_on_extreme_operands(oracle, ref):
+    """the encoder-side twins, which take any caller-supplied int32 samples, taps and length: the LMS cascade and the
+    long-term filter on the operand families of tests/tailmodel.py (full range, +-INT32 ends, constants at the ends, a
+    steep ramp, tiny and 24-bit values), at lengths around the order and at one block beyond 2^18 samples per LMS order
+    (the operands of tests/test_gpu_tail.py and
+    tests/test_gpu_predictor_api.py::test_prediction_entry_points_on_extreme_operands)"""
+    import tailmodel as M
+    for name in M.FAMILIES:
+        for order in (4, 8, 16, 32):
+            for n in (1, order - 1, order, order + 1, 1500):
+                x = M.family(name, n)
+                assert np.array_equal(oracle.lms_predict(x, order), ref.lms_predict(x, order)), (name, order, n)
+        x = M.family(name, 1500)
+        for tapset in M.LTM_TAPS:
+            coef = M.taps(tapset)
+            for pitch in (3, 7, 100, 255):
+                assert np.array_equal(oracle.ltm_predict(x, pitch, coef), ref.ltm_predict(x, pitch, coef)), (name, tapset, pitch)
+    for order in (4, 8, 16, 32):
+        for name in ("allmin", "ramp", "full"):
+            x = M.family(name, 2 ** 18 + 33)
+            assert np.array_equal(oracle.lms_predict(x, order), ref.lms_predict(x, order)), (name, order)
+    rng = np.random.default_rng(31)
+    x = rng.integers(-2 ** 31, 2 ** 31, 3000, dtype=np.int64).astype(np.int32)       # the vector of the synthesis test above
+    x[:6] = [-2 ** 31, 2 ** 31 - 1, -1, 0, 1, -2 ** 31]
+    for order in (4, 8, 16, 32):
+        assert np.array_equal(oracle.lms_predict(x, order), ref.lms_predict(x, order)), order
+    for pitch, tapset in ((3, "min1"), (255, "ends3"), (100, "ends3b"), (7, "ends5")):
+        assert np.array_equal(oracle.ltm_predict(x, pitch, M.taps(tapset)), ref.ltm_predict(x, pitch, M.taps(tapset))), (pitch, tapset)
+
+
 @pytest.mark.parametrize("name", W.NAMES)
 def test_emphasis(oracle, ref, name):
     pcm = W.gen(name, 1, 4096, 24, seed=5)[0] >> 8
