@@ -13,6 +13,12 @@
 //                the <= 3 non-zero pieces of the codeword OR-ed into the zero-initialised image
 //                (MSB-first, 32-bit atomics on byte-swapped words).  Unary zero runs cost nothing.
 //   k_block_crc  one wave per block: slice-parallel CRC16-IBM over the block, size + CRC patched into the header.
+//
+// tests/test_gpu_pack.py drives these kernels alone through sla_hip_launch_rice_len / _rice_write against an independent
+// writer (tests/slastream.py): initial parameters up to 2^32 - 1, residuals at the ends of int32, gamma escapes of 32 digits,
+// tiles of more than 64 bits per sample, waves of jobs of 1 .. 1001 samples in both modes, every alignment of the planes and
+// of the image, RAW fields of 4 .. 33 bits (the 33-bit side field of 32-bit mid/side input: its top bit is always clear, and
+// the reference's own writer is undefined there -- the yardstick is the format).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t fold_u32(int32_t s) { const uint32_t u = (uint32_t)s << 1; return (s < 0) ? ~u : u; }
 __device__ __forceinline__ uint32_t ceil_log2_u32(uint32_t x) { return (x > 1) ? (32u - (uint32_t)__builtin_clz(x - 1u)) : 0u; }
@@ -124,8 +130,8 @@ void k_rice_k(const int32_t* __restrict__ res, uint64_t stride, const sla_hip_ri
 //       both leave the parameter AS IT STOOD before each sample in LDS
 //   P2  all lanes: k0 = rice_k(p0), the condition v >= 2^k0 and the second recurrence's code terms of v - 2^k0 -> LDS
 //   P3  all lanes, batch t - 1: k1 = rice_k(p1), k0 | k1 << 8 -> global memory
-// Eight jobs per wave (sixteen lanes in S).  Same values as k_rice_k, sample for sample (test_rice_walk_kernels_agree and
-// every byte comparison of the suite: the pack stage chooses by the number of jobs).
+// Eight jobs per wave (sixteen lanes in S).  Same values as k_rice_k, sample for sample (tests/test_gpu_pack.py on mixed
+// waves, test_rice_walk_kernels_agree and every byte comparison of the suite: the pack stage chooses by the number of jobs).
 // ---------------------------------------------------------------------------------------------
 #define RK2_JOBS 8
 // (Rows of 65 entries: in S sixteen lanes walk sixteen different rows in lock-step.  With rows of 64 every lane's operand sat on
@@ -257,7 +263,7 @@ void k_rice_bits(const int32_t* __restrict__ res, uint64_t stride, const sla_hip
   if (lane == 0) { chan_bits[j] = bits; }
 }
 
-// OR `len` (1..32) bits of `val` into the image, the first bit landing at absolute bit `pos` (MSB-first)
+// OR `len` (1..33; 33 = the side field of a 32-bit mid/side RAW block, its top bit clear) bits of `val` into the image, the first bit landing at absolute bit `pos` (MSB-first)
 __device__ __forceinline__ void put_piece(uint32_t* __restrict__ img, uint64_t pos, uint32_t val, uint32_t len)
 {
   const uint64_t w = pos >> 5;

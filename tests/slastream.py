@@ -9,7 +9,8 @@ Nothing in it calls the oracle, so a stream it writes is a second opinion on the
 
 Besides the bytes it returns what each stream reaches in a decoder (`Stats`): the coder branch of every compressed
 block, the Golomb moduli, the gamma escapes, the largest quotient, and the bits every 64-sample tile of every channel
-costs, so that tests can assert the coverage they claim.
+costs, so that tests can assert the coverage they claim, and the body bits of every channel of every compressed block
+(what the encoder's code-length pass must count).
 """
 from dataclasses import dataclass, field
 from typing import List, Optional
@@ -120,6 +121,7 @@ class Stats:
     max_tile_bits_per_sample: float = 0.0    # over every 64-sample tile of every block: its bits / (samples x channels)
     raw_widths: set = field(default_factory=set)
     max_init: int = 0
+    chan_bits: List[List[int]] = field(default_factory=list)    # per compressed block: the body bits of every channel
 
     def merge(self, o):
         self.coder += o.coder
@@ -130,6 +132,7 @@ class Stats:
         self.max_tile_bits_per_sample = max(self.max_tile_bits_per_sample, o.max_tile_bits_per_sample)
         self.raw_widths |= o.raw_widths
         self.max_init = max(self.max_init, o.max_init)
+        self.chan_bits += o.chan_bits
 
 
 def _unary(w, q):
@@ -203,6 +206,8 @@ def put_residuals(w, codes, inits, st=None):
     prm = [[f, f] for f in firsts]
     cols = [[int(x) for x in c] for c in codes]
     tile_bits = [0] * C
+    total_bits = [0] * C
+    st.chan_bits.append(total_bits)
     for s in range(n):
         for ch in range(C):
             before = w.nbits
@@ -211,6 +216,7 @@ def put_residuals(w, codes, inits, st=None):
             else:
                 _golomb(w, _rp_get(firsts[ch]), cols[ch][s])
             tile_bits[ch] += w.nbits - before
+            total_bits[ch] += w.nbits - before
         if (s + 1) % TILE == 0 or s == n - 1:
             cnt = (s % TILE) + 1
             st.max_tile_bits_per_sample = max(st.max_tile_bits_per_sample, sum(tile_bits) / (cnt * C))
@@ -284,14 +290,20 @@ def raw_widths(fmt):
     return [fmt.bits - fmt.lshift + (1 if (ch == 1 and fmt.ms == 1) else 0) for ch in range(fmt.num_channels)]
 
 
+def block_codes(fmt, blk):
+    """a compressed block's folded residuals [C][n] and the initial parameter of every channel as the stream holds it"""
+    codes = [np.asarray(c.res, np.uint64) if c.folded else fold_array(c.res) for c in blk.chans]
+    inits = [(natural_init(k) if c.init is None else int(c.init)) & ((1 << fmt.bits) - 1)
+             for c, k in zip(blk.chans, codes)]
+    return codes, inits
+
+
 def block_bytes(fmt, blk, st=None):
     """one block: sync, size, CRC16, samples, type, parameters, body, each part byte-aligned as the format has it"""
     st = st if st is not None else Stats()
     codes, inits = [], []
     if blk.type == COMPRESS:
-        codes = [np.asarray(c.res, np.uint64) if c.folded else fold_array(c.res) for c in blk.chans]
-        inits = [(natural_init(k) if c.init is None else int(c.init)) & ((1 << fmt.bits) - 1)
-                 for c, k in zip(blk.chans, codes)]
+        codes, inits = block_codes(fmt, blk)
     w = BitWriter()
     w.put(SYNC, 16)
     w.put(0, 32)

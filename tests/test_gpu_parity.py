@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import packmodel as PM
 import slalibs as S
 import waveforms as W
 from test_oracle_golden import CASES as GOLDEN_CASES, check_trace_against_golden, load_case
@@ -1020,6 +1021,37 @@ def test_host_and_device_pack_agree(oracle, hip, kind, nch, bits, ms):
     torch.cuda.synchronize()
     enc.analyze_device(d.data_ptr(), stride, n)
     cap = 8 * nch * n + 65536
+    host_bytes = enc.pack(cap, on_device=False)
+    dev_bytes = enc.pack(cap, on_device=True)
+    enc.close()
+    assert host_bytes == want
+    assert dev_bytes == want
+
+
+@pytest.mark.parametrize("bits,ms", [(32, 0), (32, 1), (24, 1)])
+def test_full_scale_raw_blocks(oracle, hip, bits, ms):
+    """noise over the whole sample range (the corner pairs of L / R first, sums and differences that wrap at 32 bits): every
+    block is RAW, at 32-bit mid/side with a 33-bit side field, which the library writes as the format defines it
+    (tests/test_oracle_vs_ref.py::test_32bit_mid_side_raw_blocks_follow_the_format; tests/test_gpu_pack.py has the kernels
+    alone).  EncodeWhole and the same analysis packed by the host threads and by the device kernels equal the oracle"""
+    import torch
+    n = 9000
+    pcm = PM.full_scale_noise(2, n, bits, seed=7)
+    p = S.make_params(2, bits, 48000, 16, 1, 8, ms, 1, 4096)
+    ret, want, to = oracle.encode_trace(p, pcm)
+    assert ret == 0 and (to.blk_type[:to.num_blocks] == 2).any()
+    got, tr = hip_encode(hip, p, pcm, want_residuals=False)
+    assert got == want
+    assert np.array_equal(tr.blk_type[:tr.num_blocks], to.blk_type[:to.num_blocks]) and (tr.blk_type[:tr.num_blocks] == 2).any()
+    enc = hip.Encoder()
+    enc.set_wave_format(2, bits, 48000)
+    enc.set_encode_parameter(16, 1, 8, ms, 1, 4096)
+    stride = (n + 63) // 64 * 64
+    d = torch.zeros((2, stride), dtype=torch.int32, device="cuda")
+    d[:, :n] = torch.from_numpy(pcm).cuda()
+    torch.cuda.synchronize()
+    enc.analyze_device(d.data_ptr(), stride, n)
+    cap = 8 * 2 * n + 65536
     host_bytes = enc.pack(cap, on_device=False)
     dev_bytes = enc.pack(cap, on_device=True)
     enc.close()

@@ -9,8 +9,11 @@ import re
 import numpy as np
 import pytest
 
+import crafted_catalogue as CC
+import packmodel as PM
 import sla_amd
 import slalibs as S
+import slastream as SS
 import waveforms as W
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -323,6 +326,77 @@ def test_block_packer_reproduces_oracle_bytes(L, oracle, kind, nch, bits, order,
             assert L.slai_pack_block(C.byref(bp), ptr(out, u8p), size - 1) == 0   # too small -> 0
         off += size
     assert off == len(data)
+
+
+def pack_crafted_block(L, fmt, e):
+    """slai_pack_block on the fields of a block of the independent writer (an Expected of tests/packmodel.py)"""
+    blk, nch, O1 = e.blk, fmt.num_channels, fmt.order + 1
+    code = np.zeros((nch, O1), np.int32)
+    rshift, pitch, rice = np.zeros(nch, np.uint32), np.zeros(nch, np.uint32), np.zeros(nch, np.uint32)
+    ltm_q = np.zeros((nch, 5), np.int32)
+    planes = [np.zeros(0, np.int32)] * nch
+    if blk.type == SS.COMPRESS:
+        for ch, c in enumerate(blk.chans):
+            code[ch, 1:] = c.codes
+            rshift[ch], rice[ch] = c.rshift, e.inits[ch]
+            if c.ltm is not None:
+                pitch[ch] = c.ltm[0]
+                ltm_q[ch, :fmt.ntaps] = ((np.array(c.ltm[1], np.int64) << 16) & SS.M32).astype(np.uint32).view(np.int32)
+        planes = [np.ascontiguousarray(r) for r in e.res]
+    elif blk.type == SS.RAW:
+        planes = [PM.unfold(r) for r in blk.raw]
+    bp = BlockParams(blk.n, blk.type, nch, fmt.order, fmt.ntaps, fmt.bits, fmt.lshift, fmt.ms,
+                     ptr(code, i32p), ptr(rshift, u32p), ptr(pitch, u32p), ptr(ltm_q, i32p), ptr(rice, u32p),
+                     (i32p * 8)(*([ptr(a, i32p) for a in planes] + [None] * (8 - nch))))
+    out = np.zeros(len(e.data) + 64, np.uint8)
+    L.slai_pack_block.restype = C.c_uint32
+    size = L.slai_pack_block(C.byref(bp), ptr(out, u8p), len(out))
+    return out[:size].tobytes()
+
+
+def test_block_packer_reproduces_the_crafted_catalogue(L):
+    """sla_pack.c against the independent writer on the crafted catalogue -- initial parameters on both sides of the
+    Golomb threshold and up to 2^24 - 1, Golomb moduli that are no power of two, quotients around the gamma escape,
+    residuals at the ends of int32, tiles of more than 64 bits per sample, 1 / 2 / 3 / 8 channels, RAW fields of 4 to 33
+    bits: every block an encoder can express gives the writer's bytes.  A block is left out only for one of the three
+    reasons of packmodel.inexpressible, and those must leave at least three quarters of the catalogue in"""
+    expected = PM.catalogue_expected()
+    packed, left_out = 0, {"init": 0, "ltm": 0, "raw": 0}
+    for case in CC.catalogue():
+        for b, e in enumerate(expected[case.name]):
+            why = PM.inexpressible(case.fmt, e.blk)
+            if why is not None:
+                left_out[why] += 1
+                continue
+            got = pack_crafted_block(L, case.fmt, e)
+            assert len(got) == len(e.data), (case.name, b, e.blk.type, len(got), len(e.data))
+            assert got == e.data, (case.name, b, e.blk.type, "first difference at byte",
+                                   next(i for i in range(len(got)) if got[i] != e.data[i]))
+            packed += 1
+    total = packed + sum(left_out.values())
+    print("catalogue blocks packed: %d of %d, left out: %s" % (packed, total, left_out))
+    assert total == sum(len(c.blocks) for c in CC.catalogue())
+    assert all(left_out.values())                                        # every rule is there for a block that needs it
+    assert 4 * sum(left_out.values()) <= total
+
+
+def test_coding_mode_on_the_crafted_inits(L):
+    """slai_coding_mode (the Golomb moduli the device pack is handed) against the model's `_rp_set` / `_rp_get` and the
+    threshold 8, on the initial parameters of every compressed block of the catalogue as the stream holds them --
+    0, 1, 8, 9, channel averages of exactly 8 and 9, 2^24 - 1, 2^24 (wraps to 0), 2^32 - 1"""
+    L.slai_coding_mode.restype = None
+    modes = set()
+    for case in CC.catalogue():
+        for b, e in enumerate(PM.catalogue_expected()[case.name]):
+            if e.blk.type != SS.COMPRESS:
+                continue
+            inits = np.array(e.inits, np.uint32)
+            got = np.full(8, 0xDEAD, np.uint32)
+            L.slai_coding_mode(ptr(inits, u32p), len(inits), ptr(got, u32p))
+            assert list(got[:len(inits)]) == e.golomb_m, (case.name, b, e.inits)
+            assert np.all(got[len(inits):] == 0xDEAD)
+            modes.add(bool(e.golomb_m[0]))
+    assert modes == {False, True}
 
 
 def test_crc16_known_answers(L):

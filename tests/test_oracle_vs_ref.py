@@ -11,7 +11,9 @@ import os
 import numpy as np
 import pytest
 
+import packmodel as PM
 import slalibs as S
+import slastream as SS
 import waveforms as W
 
 # the reference's own test fixtures (test/a.wav, test/PriChanIcon.png), stored verbatim
@@ -436,6 +438,55 @@ def test_raw_fallback(oracle, ref):
     assert (ta.blk_type[:ta.num_blocks] == 2).any()
     rd, dec, _ = oracle.decode_whole(p, da, 9000)
     assert rd == 0 and np.array_equal(dec, pcm)
+
+
+@pytest.mark.parametrize("bits,ms", [(32, 0), (24, 1)])
+def test_full_scale_raw_blocks_equal_the_reference(oracle, ref, bits, ms):
+    """noise over the whole sample range (the corner pairs of L / R first): every block is RAW, and the oracle's
+    bytes are the reference's at 32 bits L/R and at 24 bits mid/side (a 25-bit side field)"""
+    pcm = PM.full_scale_noise(2, 9000, bits, seed=7)
+    p = S.make_params(2, bits, 48000, 16, 1, 8, ms, 1, 4096)
+    ra, da, ta = oracle.encode_trace(p, pcm)
+    rb, db = ref.encode_whole(p, pcm)
+    assert ra == rb == 0 and da == db
+    assert (ta.blk_type[:ta.num_blocks] == 2).all()
+
+
+def test_32bit_mid_side_raw_blocks_follow_the_format(oracle, ref):
+    """A RAW block of 32-bit mid/side input carries its side channel in a 33-bit field, and there the reference's
+    writer is undefined: SLABitWriter_PutBits (src/include/private/SLABitStream.h:186-190) shifts a 32-bit value by
+    the number of bits that do not fit the current byte, which is 32 for a 33-bit field that starts at bit 7 of a byte
+    (the same hole the reader has, see tests/test_crafted_streams.py).  On x86 the shift by 32 is a shift by 0, and the
+    field's first bit -- always 0, an encoder's side code is below 2^32 -- comes out as the code's LOWEST bit.
+    The oracle (and so the library) writes the field as the format defines it: its bytes are those of the independent
+    writer on the wrap model of tests/packmodel.py: raw_codes, and they differ from the reference's in exactly the
+    bytes that hold the first bit of such a field whose code is odd, plus the CRC16 of every block"""
+    bits, ms = 32, 1
+    pcm = PM.full_scale_noise(2, 9000, bits, seed=7)
+    p = S.make_params(2, bits, 48000, 16, 1, 8, ms, 1, 4096)
+    ra, da, ta = oracle.encode_trace(p, pcm)
+    rb, db = ref.encode_whole(p, pcm)
+    assert ra == rb == 0 and len(da) == len(db)
+    nb = ta.num_blocks
+    assert (ta.blk_type[:nb] == 2).all()
+    fmt = SS.Format(2, bits, 48000, ta.offset_lshift, 16, 1, 8, ms, 1, 4096)
+    blocks = []
+    for b in range(nb):
+        s, n = int(ta.blk_start[b]), int(ta.blk_nsmpl[b])
+        blocks.append(SS.Block(SS.RAW, n, raw=PM.raw_codes(pcm[:, s:s + n], 32 - bits + ta.offset_lshift, ms)))
+    mine, _, offs = SS.write_file(fmt, blocks)
+    assert mine == da
+    differ = set(np.nonzero(np.frombuffer(da, np.uint8) != np.frombuffer(db, np.uint8))[0].tolist())
+    crc_fields, holes = set(), set()
+    for blk, off in zip(blocks, offs):
+        crc_fields |= {off + 6, off + 7}
+        assert differ & {off + 6, off + 7}, off
+        start = np.arange(blk.n) * 65 + 32                              # bit offset of the side field in the body
+        at_bit7 = start % 8 == 7
+        odd = (blk.raw[1][at_bit7] & np.uint64(1)) == 1
+        holes |= set((off + PM.header_len(fmt, blk) + start[at_bit7][odd] // 8).tolist())
+    assert len(holes) > 100
+    assert differ - crc_fields == holes
 
 
 @pytest.mark.parametrize("n", [1, 15, 16, 17, 100, 2047, 2048, 2049, 4096 + 15, 4096 + 17, 8192 + 1023])
