@@ -610,6 +610,33 @@ typedef struct sla_hip_dec_emit {
 int sla_hip_launch_dec_emit_batch(const int32_t* d_planes, uint64_t plane_stride, const sla_hip_dec_emit* d_files,
                                   uint32_t num_files, uint32_t max_samples, uint32_t sample_format, sla_hip_stream_t stream);
 
+/* Decode-and-compare of blocks (option "verify" of the encoder; kernel k_verify_blocks): for every block of the table and
+ * every channel, the decoded plane samples [smp_off, smp_off + num_samples) -- what dec_bits / dec_lms / dec_ltm /
+ * dec_lattice left, right-justified, mid/side still folded -- are finished as sla_hip_launch_dec_finish_batch finishes them
+ * (mid/side undone where mid_side = 1, left shift by `shift`) and compared with the words of d_source (planar int32,
+ * left-justified, [C][source_stride]) at the same positions.  Equality is on all 32 bits: stray low bits of the source
+ * count.  Nothing outside the blocks' sample ranges is read; blocks flagged SLA_HIP_DEC_HEADER_ONLY are skipped altogether.
+ * A block is BAD when d_info[b].type != d_expect[b].type, d_info[b].used_bytes != d_expect[b].bytes, d_info[b].overrun is
+ * set, or -- with a non-NULL d_image, the image dec_bits read, of image_bytes bytes -- the CRC16 dec_bits computed
+ * (want_crc) differs from the big-endian 16-bit field at byte 6 of the block (or the block's first 8 bytes do not lie
+ * inside the image).
+ * d_report: three 64-bit words per segment (d_seg_of_block[b] = the segment of block b; NULL: everything is segment 0),
+ * initialised by the caller to {0, ~0, 0}; afterwards {differing sample-channels, smallest (plane position << 3 | channel)
+ * of a differing one, bad blocks}.  Waves reduce first and touch the words (64-bit vector atomics) only when they have
+ * something to report: a clean table leaves them as they were.  16-byte loads wherever a row of the planes / the source is
+ * 16-byte aligned and the group of four lies inside the block, guarded 4-byte loads at block heads and tails and otherwise.
+ * INVALID_ARGUMENT before any launch for a NULL table, num_channels 0 or > 8, mid_side with num_channels != 2, shift > 31. */
+typedef struct sla_hip_verify_expect {
+  uint32_t type;            /* the block type the packer wrote */
+  uint32_t bytes;           /* the block's size in the image */
+} sla_hip_verify_expect;
+int sla_hip_launch_verify_blocks(const int32_t* d_planes, uint64_t plane_stride, const int32_t* d_source,
+                                 uint64_t source_stride, const sla_hip_dec_block* d_blocks,
+                                 const sla_hip_dec_info* d_info, const sla_hip_verify_expect* d_expect,
+                                 const uint32_t* d_seg_of_block, uint32_t num_blocks, uint32_t num_channels,
+                                 uint32_t mid_side, uint32_t shift, const uint32_t* d_image, uint64_t image_bytes,
+                                 uint64_t* d_report, sla_hip_stream_t stream);
+
 /* ---- (2) whole-file driver ---------------------------------------------- */
 
 /* Per-block results of the last analyze call, copied into caller arrays
@@ -642,7 +669,8 @@ int sla_hip_analyze_device(struct SLAEncoder* encoder, const int32_t* d_pcm, uin
 
 /* Bit-serial pack of the analysed file into `data` (host): D2H of the final
  * residual, block headers, Rice body, CRC16 (reference src/SLAEncoder.c:682-798,
- * src/SLACoder.c:429-467).  Needs a preceding sla_hip_analyze_device. */
+ * src/SLACoder.c:429-467).  Needs a preceding sla_hip_analyze_device.  These bytes are made on the host and
+ * never exist on the device: option "verify" does not cover them (SLAEncoder_EncodeBlock packs this way too). */
 int sla_hip_pack(struct SLAEncoder* encoder, uint8_t* data, uint32_t data_size, uint32_t* output_size);
 
 /* Same bytes as sla_hip_pack, but the Rice coding, block assembly and CRC16 run on the device and one
@@ -816,6 +844,10 @@ int sla_hip_get_trace(struct SLAEncoder* encoder, sla_hip_trace* trace);
  * reading the number from the device), "one_stream" (1: a one-chunk file keeps search, block stage and tail on one stream;
  * measured slower, default 0), "upload24" (1 = default: pageable input of 17..24 significant bits crosses the bus as three
  * bytes per sample; DESIGN section 7 has the A/B).
+ * "verify" (0 = default, 1): every call that packs on the device (sla_hip_pack_device, SLAEncoder_EncodeWhole plain and
+ * streamed, sla_hip_encode_batch, sla_hip_encode_batch_device) decodes the finished block bytes on the device with the
+ * decoder's kernels, while they cross the bus, and compares the result with the source planes; a file whose bytes do not
+ * decode back to its samples gets SLA_APIRESULT_NG (output_size 0 in a batch).  See sla_hip_last_verify; DESIGN section 2d.
  * SLAEncoder_EncodeWhole of long files: "stream" (0: never streamed), "stream_piece" (samples per piece, all channels
  * together; default 32 Mi; a file of fewer than two pieces is not streamed), "stream_lanes" (worker lanes, 1..6, default 6; pieces are handed to whichever lane is free),
  * "batch_lanes" (sla_hip_encode_batch: a batch of at least 8 files and 16 Mi samples is dealt out in groups of consecutive files to
@@ -849,6 +881,24 @@ int sla_hip_last_cert_audit(const struct SLAEncoder* encoder, uint32_t* counters
  * pieces of a streamed file (option stream) run on lanes whose counters are not collected: the counters then describe the
  * handle's own last analysis only. */
 int sla_hip_last_ltm_cert(const struct SLAEncoder* encoder, uint32_t* counters);
+
+/* Option "verify": 5 counters of the last call that packed on the device -- sample-channels compared (channels x block
+ * samples of the delivered files), sample-channels that differed, the first differing position ((sample << 3) | channel,
+ * the sample counted in the planes of the pass that saw it; ~0 when none differed), blocks decoded, bad blocks (type,
+ * size, overrun or CRC16 not what the packer laid out).  All zero when that call did not verify.  A batch's passes and
+ * worker lanes, and the pieces of a streamed file, are summed (the first position: the smallest).
+ * The check proves that the delivered block bytes decode, with this library's decoder kernels, to the source planes.  It
+ * does not prove identity with the reference encoder's bytes (option "cert_audit" and the tests cover that) and does not
+ * look at the 43-byte file header, which the host writes after the download. */
+int sla_hip_last_verify(const struct SLAEncoder* encoder, uint64_t counters[5]);
+/* The same pass on demand, against caller-given planes (planar int32, left-justified, [C][plane_stride], sample 0 = the
+ * file's sample 0): the image that the handle's last sla_hip_pack_device -- or SLAEncoder_EncodeWhole that was not
+ * streamed -- left on the device is decoded and compared with d_pcm; counters as above.  Works with option "verify" on or
+ * off and leaves sla_hip_last_verify alone.  Returns 0 when the pass ran, whatever it found (the verdict is in the
+ * counters); SLA_APIRESULT_PARAMETER_NOT_SET when the handle holds no such image (before any pack, after a batch, a
+ * streamed call, a new analysis or new parameters); SLA_APIRESULT_INVALID_ARGUMENT for NULL arguments or planes that are
+ * not device memory of the handle's device covering [C][num_samples]. */
+int sla_hip_verify_last_image(struct SLAEncoder* encoder, const int32_t* d_pcm, uint64_t plane_stride, uint64_t counters[5]);
 
 /* 4 counters: pipeline chunks of the last analysis whose block stage was launched from device-written tables
  * (sla_hip_launch_expand; option "device_expand"), its pipeline chunks in all; since the handle was created: the analyses

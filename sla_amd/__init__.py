@@ -164,6 +164,12 @@ def lib():
             L.sla_hip_ltm_cert_eps_rel.argtypes = [C.c_uint32, C.c_double]
             L.sla_hip_ltm_cert_supported.argtypes = [C.c_uint32]
         L.sla_hip_last_expand.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        if hasattr(L, "sla_hip_last_verify"):                # (SLA_HIP_LIB may name an older build in an A/B run)
+            L.sla_hip_last_verify.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+            L.sla_hip_verify_last_image.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+            L.sla_hip_launch_verify_blocks.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                       C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.sla_hip_search_exact_lags.restype = C.c_uint32
         L.sla_hip_encoder_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
         L.sla_hip_shard_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, u32p, C.POINTER(C.c_uint64)]
@@ -259,6 +265,8 @@ EXPORTED_SYMBOLS = [
     "sla_hip_decode_batch_device", "sla_hip_launch_dec_emit_batch",
     # batch encode from device memory (include/sla_hip.h)
     "sla_hip_encode_batch_device", "sla_hip_launch_enc_ingest_batch",
+    # verification of the encoded stream on the device (include/sla_hip.h)
+    "sla_hip_launch_verify_blocks", "sla_hip_last_verify", "sla_hip_verify_last_image",
 ]
 
 
@@ -575,6 +583,23 @@ class Encoder:
         c = (C.c_uint32 * 5)()
         self._check(self._lib.sla_hip_last_ltm_cert(self._h, c), "sla_hip_last_ltm_cert")
         return tuple(c)
+
+    def last_verify(self):
+        """option "verify": (sample-channels compared, sample-channels that differed, first differing position
+        (sample << 3 | channel, or 2^64 - 1 when none), blocks decoded, bad blocks) of the last call that packed on the
+        device; all zero when it did not verify (include/sla_hip.h)"""
+        c = (C.c_uint64 * 5)()
+        self._check(self._lib.sla_hip_last_verify(self._h, c), "sla_hip_last_verify")
+        return tuple(int(v) for v in c)
+
+    def verify_last_image(self, device_ptr, plane_stride):
+        """sla_hip_verify_last_image: decode the image the last pack(on_device=True) / non-streamed encode_whole left on the
+        device and compare it with the planes at device_ptr (planar left-justified int32 [C][plane_stride]); returns the
+        five counters of last_verify.  Raises SlaError PARAMETER_NOT_SET when the handle holds no such image."""
+        c = (C.c_uint64 * 5)()
+        self._check(self._lib.sla_hip_verify_last_image(self._h, C.c_void_p(device_ptr), plane_stride, c),
+                    "sla_hip_verify_last_image")
+        return tuple(int(v) for v in c)
 
     def bind_residual_planes(self, lattice_ptr, final_ptr, plane_stride):
         self._check(self._lib.sla_hip_bind_residual_planes(self._h, C.c_void_p(lattice_ptr), C.c_void_p(final_ptr),

@@ -18,6 +18,7 @@
 //   k_dec_finish         src/SLAUtility.c:415-433 (mid/side -> left/right), src/SLADecoder.c:540-547 (left-justify)
 //   k_dec_finish_batch   the same for every file of a batch pass, packed [file][ch][n] for one copy home
 //   k_dec_emit_batch     the same, converted and stored to every file's own device destination
+//   k_verify_blocks      (kernels/verify.inc) k_dec_finish fused with a compare against source planes, per block table
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -795,6 +796,8 @@ void k_dec_deemphasis(int32_t* __restrict__ data, uint32_t n, int32_t previous, 
   }
 }
 
+#include "kernels/verify.inc"
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -974,5 +977,26 @@ extern "C" int sla_hip_launch_dec_deemphasis(int32_t* d_data, uint32_t num_sampl
   if (d_data == nullptr || coef_shift < 1 || coef_shift > 30) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if (num_samples == 0) { return 0; }
   hipLaunchKernelGGL(k_dec_deemphasis, dim3(1), dim3(64), 0, (hipStream_t)stream, d_data, num_samples, previous, coef_shift);
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_verify_blocks(const int32_t* d_planes, uint64_t plane_stride, const int32_t* d_source,
+                                            uint64_t source_stride, const sla_hip_dec_block* d_blocks,
+                                            const sla_hip_dec_info* d_info, const sla_hip_verify_expect* d_expect,
+                                            const uint32_t* d_seg_of_block, uint32_t num_blocks, uint32_t num_channels,
+                                            uint32_t mid_side, uint32_t shift, const uint32_t* d_image, uint64_t image_bytes,
+                                            uint64_t* d_report, sla_hip_stream_t stream)
+{
+  if (d_planes == nullptr || d_source == nullptr || d_blocks == nullptr || d_info == nullptr || d_expect == nullptr
+      || d_report == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_channels == 0 || num_channels > 8 || shift > 31 || (mid_side && num_channels != 2)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_blocks == 0) { return 0; }
+  verify_args a;
+  a.planes = d_planes; a.stride = plane_stride; a.source = d_source; a.sstride = source_stride;
+  a.blocks = d_blocks; a.info = d_info; a.expect = d_expect; a.seg_of_block = d_seg_of_block;
+  a.image = (const uint8_t*)d_image; a.image_bytes = image_bytes;
+  a.report = (unsigned long long*)d_report;
+  a.num_channels = num_channels; a.mid_side = mid_side; a.shift = shift;
+  hipLaunchKernelGGL(k_verify_blocks, dim3(num_blocks), dim3(256), 0, (hipStream_t)stream, a);
   return hip_rc(hipGetLastError());
 }

@@ -170,6 +170,14 @@ struct SLAEncoder {
   struct slai_pool* upload_pool;    /* a lane's staging copies of its upload run on the parent's (otherwise idle, larger) pool: uploads take turns */
   int      streamed;                /* the last EncodeWhole ran on the lanes: this handle holds no analysis tables */
 
+  /* option "verify": the finished image is decoded on the device and compared with the source planes (verify_enqueue) */
+  int      verify;
+  devbuf_t d_ver_tab, d_ver_planes, d_ver_info, d_ver_chan, d_ver_kint;   /* tables + report words; scratch planes [C][stride]; the parser's outputs */
+  pinbuf_t h_ver;                   /* the tables as uploaded | the report words as they come home */
+  uint64_t ver[5]; int ver_ran;     /* sla_hip_last_verify: summed over the passes of the last call */
+  int      image_valid;             /* d_image holds the one file of the last sla_hip_pack_device, h_pk_blocks its table */
+  uint32_t img_nb, img_samples; uint64_t img_bytes;
+
   /* last analysis */
   const int32_t* pcm_dev;           /* borrowed or &d_pcm */
   uint64_t stride;
@@ -465,6 +473,12 @@ void SLAEncoder_Destroy(struct SLAEncoder* e)
   if (e->d_ingest.ptr != NULL) { (void)hipFree(e->d_ingest.ptr); }
   if (e->h_ingest.ptr != NULL) { (void)hipHostFree(e->h_ingest.ptr); }
   if (e->ev_order != NULL) { (void)hipEventDestroy(e->ev_order); }
+  if (e->d_ver_tab.ptr != NULL) { (void)hipFree(e->d_ver_tab.ptr); }
+  if (e->d_ver_planes.ptr != NULL) { (void)hipFree(e->d_ver_planes.ptr); }
+  if (e->d_ver_info.ptr != NULL) { (void)hipFree(e->d_ver_info.ptr); }
+  if (e->d_ver_chan.ptr != NULL) { (void)hipFree(e->d_ver_chan.ptr); }
+  if (e->d_ver_kint.ptr != NULL) { (void)hipFree(e->d_ver_kint.ptr); }
+  if (e->h_ver.ptr != NULL) { (void)hipHostFree(e->h_ver.ptr); }
   free(e->tab_segs);
   for (i = 0; i < 2; i++) {
     if (e->h_stage[i].ptr != NULL) { (void)hipHostFree(e->h_stage[i].ptr); }
@@ -495,7 +509,7 @@ SLAApiResult SLAEncoder_SetWaveFormat(struct SLAEncoder* e, const struct SLAWave
   if (wf->num_channels > e->cfg.max_num_channels || wf->bit_per_sample > 32) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
   e->wave_format = *wf;
   e->status_flag |= STATUS_WAVE_FORMAT;
-  e->analysed = 0;
+  e->analysed = 0; e->image_valid = 0;
   return SLA_APIRESULT_OK;
 }
 
@@ -510,7 +524,7 @@ SLAApiResult SLAEncoder_SetEncodeParameter(struct SLAEncoder* e, const struct SL
   if (ep->max_num_block_samples > MAX_ANALYSIS_WINDOW || ep->parcor_order < 1) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
   e->encode_param = *ep;
   e->status_flag |= STATUS_ENCODE_PARAM;
-  e->analysed = 0;
+  e->analysed = 0; e->image_valid = 0;
   return SLA_APIRESULT_OK;
 }
 
@@ -1989,6 +2003,7 @@ static int run_pipeline(struct SLAEncoder* e, int preset_blocks)
 
   e->fallback_groups = 0; e->host_planned = 0; e->blocks_exact = 0; e->cert_broken = 0; e->audit_ok = 0; e->audit_bad = 0;
   e->expanded_chunks = 0;
+  e->image_valid = 0;                /* a new analysis: whatever image a pack left belongs to other tables */
   memset(e->ltm_stat, 0, sizeof(e->ltm_stat));
   e->ltm_cert_now = (e->ltm_cert && e->device_ltm && sla_hip_ltm_cert_supported(slai_fft_plan_size(e->fft)));
   e->cert_now = (e->block_cert && !(e->fuse_lattice && e->encode_param.parcor_order <= 64) && !e->tune.lpc_blocks_chains
@@ -2226,6 +2241,11 @@ int sla_hip_encoder_set_option(struct SLAEncoder* e, const char* name, double va
   else if (strcmp(name, "table_cache") == 0)       { OPT_RANGE(0, 1); e->table_cache = (int)iv; e->tab_valid = 0; e->spec_valid = 0; }
   else if (strcmp(name, "device_ltm") == 0)        { OPT_RANGE(0, 1); e->device_ltm = (int)iv; }
   else if (strcmp(name, "fuse_lattice") == 0)      { OPT_RANGE(0, 1); e->fuse_lattice = (int)iv && !e->tune.lpc_blocks_chains; }
+  else if (strcmp(name, "verify") == 0) {
+    /* (checks what a pack delivers, changes nothing an analysis holds: the handle stays analysed) */
+    OPT_RANGE(0, 1); e->verify = (int)iv; memset(e->ver, 0, sizeof(e->ver)); e->ver_ran = 0;
+    return 0;
+  }
   else if (strcmp(name, "threads") == 0) {
     OPT_RANGE(1, 64);
     if ((uint32_t)iv != e->threads) {
@@ -2655,6 +2675,124 @@ static void pack_hdr_one(void* vctx, uint32_t b)
   }
 }
 
+/* ------------------------------------------------------------------ verification pass (option "verify")
+ * The finished image is still in device memory when the last block has been written, and so are the source planes: the
+ * decoder's kernels decode the blocks of the delivered files into scratch planes of the handle and k_verify_blocks compares
+ * them with the source, all queued on the handle's stream while the image's bytes leave on the download stream.  What it
+ * proves and what it does not: DESIGN section 2d.  The 43-byte file headers are written on the host after the download and
+ * are not part of the check. */
+typedef struct {
+  uint32_t nvb, nsegs;               /* blocks in the tables, files of the pass */
+  uint64_t compared;                 /* channels x samples of those blocks */
+  size_t   rep_off;                  /* the report words as they come home: byte offset in h_ver */
+} verify_run_t;
+
+static void verify_clear(struct SLAEncoder* e) { memset(e->ver, 0, sizeof(e->ver)); e->ver_ran = 0; }
+
+/* v: compared, differing, first, blocks, bad of one pass (or of a lane) into the handle's sum */
+static void verify_add(struct SLAEncoder* e, const uint64_t v[5])
+{
+  if (!e->ver_ran) { memset(e->ver, 0, sizeof(e->ver)); e->ver[2] = ~(uint64_t)0; e->ver_ran = 1; }
+  e->ver[0] += v[0]; e->ver[1] += v[1]; e->ver[3] += v[3]; e->ver[4] += v[4];
+  if (v[2] < e->ver[2]) { e->ver[2] = v[2]; }
+}
+
+/* Queue the pass on the handle's stream: tables (one upload), dec_bits .. dec_lattice over the scratch planes, the compare
+ * against d_src, the report words home.  pb / nb: the pack table of the image; segs: its files.  Nothing is waited for. */
+static int verify_enqueue(struct SLAEncoder* e, const sla_hip_pack_block* pb, uint32_t nb, const slai_verify_seg* segs, uint32_t nsegs,
+                          uint64_t image_bytes, uint64_t plane_stride, const int32_t* d_src, uint64_t src_stride, verify_run_t* run)
+{
+  const uint32_t C = e->wave_format.num_channels, bps = e->wave_format.bit_per_sample, order = e->encode_param.parcor_order;
+  const uint32_t ntaps = e->encode_param.longterm_order;
+  const uint32_t ms = (e->encode_param.ch_process_method == SLA_CHPROCESSMETHOD_STEREO_MS) ? 1u : 0u;
+  /* one buffer, every table on a 16-byte boundary: blocks | ends | expectations | segment indices | report words */
+  const size_t o_blk = 0, o_end = o_blk + (((size_t)nb * sizeof(sla_hip_dec_block) + 15) & ~(size_t)15);
+  const size_t o_exp = o_end + (((size_t)nb * sizeof(uint64_t) + 15) & ~(size_t)15);
+  const size_t o_seg = o_exp + (((size_t)nb * sizeof(sla_hip_verify_expect) + 15) & ~(size_t)15);
+  const size_t o_rep = o_seg + (((size_t)nb * sizeof(uint32_t) + 15) & ~(size_t)15);
+  const size_t rep_bytes = (size_t)nsegs * 3 * sizeof(uint64_t), up_bytes = o_rep + rep_bytes;
+  uint8_t* h; uint8_t* d;
+  uint64_t* rep;
+  uint32_t nvb, longest = 0, sg;
+  memset(run, 0, sizeof(*run));
+  run->nsegs = nsegs; run->rep_off = (up_bytes + 15) & ~(size_t)15;
+  RCCHK(pin_reserve(&e->h_ver, run->rep_off + rep_bytes));
+  h = (uint8_t*)e->h_ver.ptr;
+  nvb = slai_verify_tables(pb, nb, segs, nsegs, C, (sla_hip_dec_block*)(h + o_blk), (uint64_t*)(h + o_end),
+                           (sla_hip_verify_expect*)(h + o_exp), (uint32_t*)(h + o_seg), &run->compared, &longest);
+  run->nvb = nvb;
+  rep = (uint64_t*)(h + o_rep);
+  for (sg = 0; sg < nsegs; sg++) { rep[3 * sg] = 0; rep[3 * sg + 1] = ~(uint64_t)0; rep[3 * sg + 2] = 0; }
+  memcpy(h + run->rep_off, rep, rep_bytes);          /* (what comes home when there is nothing to launch) */
+  if (nvb == 0) { return 0; }
+  RCCHK(dev_reserve(&e->d_ver_tab, up_bytes));
+  RCCHK(dev_reserve(&e->d_ver_planes, sizeof(int32_t) * (size_t)C * plane_stride));
+  RCCHK(dev_reserve(&e->d_ver_info, sizeof(sla_hip_dec_info) * (size_t)nvb));
+  RCCHK(dev_reserve(&e->d_ver_chan, sizeof(sla_hip_dec_chan) * (size_t)nvb * C));
+  RCCHK(dev_reserve(&e->d_ver_kint, sizeof(int32_t) * (size_t)nvb * C * (order + 1)));
+  d = (uint8_t*)e->d_ver_tab.ptr;
+  HIPCHK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemsetAsync(e->d_ver_info.ptr, 0, sizeof(sla_hip_dec_info) * (size_t)nvb, e->stream));
+  {
+    const sla_hip_dec_block* db = (const sla_hip_dec_block*)(d + o_blk);
+    const sla_hip_dec_info* di = (const sla_hip_dec_info*)e->d_ver_info.ptr;
+    int32_t* planes = (int32_t*)e->d_ver_planes.ptr;
+    RCCHK(sla_hip_launch_dec_bits_x((const uint32_t*)e->d_image.ptr, image_bytes, db, nvb, C, bps, e->lshift, ms, order, ntaps, 1,
+                                    planes, plane_stride, (sla_hip_dec_info*)e->d_ver_info.ptr, (sla_hip_dec_chan*)e->d_ver_chan.ptr,
+                                    (int32_t*)e->d_ver_kint.ptr, e->stream, (const uint64_t*)(d + o_end)));
+    RCCHK(sla_hip_launch_dec_lms(planes, plane_stride, db, di, nvb, C, e->encode_param.lms_order_per_filter, e->stream));
+    RCCHK(sla_hip_launch_dec_ltm(planes, plane_stride, db, di, (const sla_hip_dec_chan*)e->d_ver_chan.ptr, nvb, C, ntaps, longest, e->stream));
+    RCCHK(sla_hip_launch_dec_lattice(planes, plane_stride, db, di, nvb, C, (const int32_t*)e->d_ver_kint.ptr, order, 1, e->stream));
+    RCCHK(sla_hip_launch_verify_blocks(planes, plane_stride, d_src, src_stride, db, di, (const sla_hip_verify_expect*)(d + o_exp),
+                                       (const uint32_t*)(d + o_seg), nvb, C, ms, 32u - bps + e->lshift,
+                                       (const uint32_t*)e->d_image.ptr, image_bytes, (uint64_t*)(d + o_rep), e->stream));
+  }
+  HIPCHK(hipMemcpyAsync(h + run->rep_off, d + o_rep, rep_bytes, hipMemcpyDeviceToHost, e->stream));
+  return 0;
+}
+
+/* Wait for the pass; the report words of file sg are at (*report)[3 sg ..]; v: the pass's five counters */
+static int verify_collect(struct SLAEncoder* e, const verify_run_t* run, const uint64_t** report, uint64_t v[5])
+{
+  const uint64_t* rep = (const uint64_t*)((const uint8_t*)e->h_ver.ptr + run->rep_off);
+  uint32_t sg;
+  HIPCHK(hipStreamSynchronize(e->stream));
+  v[0] = run->compared; v[1] = 0; v[2] = ~(uint64_t)0; v[3] = run->nvb; v[4] = 0;
+  for (sg = 0; sg < run->nsegs; sg++) {
+    v[1] += rep[3 * sg]; v[4] += rep[3 * sg + 2];
+    if (rep[3 * sg + 1] < v[2]) { v[2] = rep[3 * sg + 1]; }
+  }
+  *report = rep;
+  return 0;
+}
+
+int sla_hip_last_verify(const struct SLAEncoder* e, uint64_t counters[5])
+{
+  if (e == NULL || counters == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (e->ver_ran) { memcpy(counters, e->ver, sizeof(e->ver)); } else { memset(counters, 0, sizeof(e->ver)); }
+  return 0;
+}
+
+int sla_hip_verify_last_image(struct SLAEncoder* e, const int32_t* d_pcm, uint64_t plane_stride, uint64_t counters[5])
+{
+  slai_verify_seg seg;
+  verify_run_t run;
+  const uint64_t* rep;
+  int rc;
+  if (e == NULL || d_pcm == NULL || counters == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (!e->image_valid) { return SLA_APIRESULT_PARAMETER_NOT_SET; }
+  if (plane_stride < e->img_samples) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  RCCHK(enter(e));
+  if (!slai_device_region_ok(d_pcm, e->wave_format.num_channels, e->img_samples, plane_stride, 1, sizeof(int32_t), e->device)) {
+    return SLA_APIRESULT_INVALID_ARGUMENT;
+  }
+  seg.img_off = 0; seg.img_bytes = e->img_bytes; seg.deliver = 1;
+  rc = verify_enqueue(e, (const sla_hip_pack_block*)e->h_pk_blocks.ptr, e->img_nb, &seg, 1, e->img_bytes,
+                      (e->img_samples > 0) ? e->img_samples : 1u, d_pcm, plane_stride, &run);
+  if (rc != 0) { (void)hipStreamSynchronize(e->stream); return rc; }      /* (nothing of the pass stays in flight over its tables) */
+  return verify_collect(e, &run, &rep, counters);
+}
+
 /* Rice code lengths, block assembly and CRC16 on the device for every file of the analysed planes (segs sorted by
  * position, blocks are), one image holding the files back to back; each file is then copied to its buffer and gets
  * its 43-byte header.  A file that does not fit its buffer is reported in its `result`, the others are delivered. */
@@ -2665,8 +2803,10 @@ static int pack_device_core(struct SLAEncoder* e, pack_seg_t* segs, uint32_t nse
   size_t hdr_used = 0, hdr_cap;
   uint64_t cur = 0;
   struct SLAHeaderInfo hinfo;
-  int rc = 0;
+  verify_run_t vrun;
+  int rc = 0, verifying = 0;
   C = e->wave_format.num_channels; O1 = e->encode_param.parcor_order + 1; nb = e->num_blocks;
+  e->image_valid = 0;
   hdr_cap = (size_t)nb * (16 + C * (8 + 2 * O1 + 16)) + 64;
   RCCHK(pin_reserve(&e->h_pk_jobs, sizeof(sla_hip_rice_job) * ((size_t)nb * C + 1)));
   RCCHK(pin_reserve(&e->h_pk_blocks, sizeof(sla_hip_pack_block) * ((size_t)nb + 1)));
@@ -2810,8 +2950,37 @@ static int pack_device_core(struct SLAEncoder* e, pack_seg_t* segs, uint32_t nse
         if (nruns > 1) { HIPCHK(hipEventRecord(e->ev_pack[r], e->stream)); }
       }
     }
+    /* one whole file: sla_hip_verify_last_image can check this image against any planes until the next analysis */
+    if (nsegs == 1 && !segs[0].bare && !e->is_lane) {
+      e->image_valid = 1; e->img_nb = nb; e->img_samples = segs[0].hi - segs[0].lo; e->img_bytes = cur;
+    }
+    /* option "verify": the decode-and-compare of every file that is going to be delivered follows the last block on the
+     * handle's stream, the downloads move to the download stream behind the blocks, so the device decodes while the
+     * bytes cross the bus */
+    if (e->verify) {
+      slai_verify_seg one, *vs = &one;
+      uint32_t deliver = 0;
+      if (nsegs > 1 && (vs = (slai_verify_seg*)malloc(sizeof(slai_verify_seg) * nsegs)) == NULL) { return SLA_APIRESULT_NG; }
+      for (sg = 0; sg < nsegs; sg++) {
+        vs[sg].img_off = segs[sg].img_off; vs[sg].img_bytes = segs[sg].out_size; vs[sg].deliver = (segs[sg].result == 0);
+        deliver += (segs[sg].result == 0);
+      }
+      if (deliver > 0) {
+        if (nruns == 1) { rc = hiprc(hipEventRecord(e->ev_pack[0], e->stream)); }
+        if (rc == 0) { rc = verify_enqueue(e, pb, nb, vs, nsegs, cur, e->stride, e->pcm_dev, e->stride, &vrun); }
+        verifying = (rc == 0);
+      }
+      if (vs != &one) { free(vs); }
+      if (rc != 0) { (void)hipStreamSynchronize(e->stream); return rc; }
+    }
     tp3 = now_ms();
-    if (nruns > 1 && segs[0].result == 0) {
+    if (verifying && nruns == 1) {
+      for (sg = 0; sg < nsegs; sg++) {
+        if (segs[sg].result != 0) { continue; }
+        rc = download_bytes_after(e, segs[sg].data, (const uint8_t*)e->d_image.ptr + segs[sg].img_off, (size_t)segs[sg].out_size, e->ev_pack[0]);
+        if (rc != 0) { (void)hipStreamSynchronize(e->stream); return rc; }
+      }
+    } else if (nruns > 1 && segs[0].result == 0) {
       for (r = 0; r < nruns; r++) {
         const uint64_t from = (r == 0) ? segs[0].img_off : pb[run_lo[r]].out_off;
         const uint64_t upto = (r + 1 == nruns || run_lo[r + 1] >= nb) ? cur : pb[run_lo[r + 1]].out_off;
@@ -2822,6 +2991,16 @@ static int pack_device_core(struct SLAEncoder* e, pack_seg_t* segs, uint32_t nse
       for (sg = 0; sg < nsegs; sg++) {
         if (segs[sg].result != 0) { continue; }
         RCCHK(download_bytes(e, segs[sg].data, (const uint8_t*)e->d_image.ptr + segs[sg].img_off, (size_t)segs[sg].out_size));
+      }
+    }
+    if (verifying) {
+      /* the verdict: a file whose bytes do not decode back to its samples is not delivered */
+      const uint64_t* rep;
+      uint64_t v[5];
+      RCCHK(verify_collect(e, &vrun, &rep, v));
+      verify_add(e, v);
+      for (sg = 0; sg < nsegs; sg++) {
+        if (segs[sg].result == 0 && (rep[3 * sg] != 0 || rep[3 * sg + 2] != 0)) { segs[sg].result = SLA_APIRESULT_NG; }
       }
     }
     tp4 = now_ms();
@@ -2850,6 +3029,7 @@ int sla_hip_pack_device(struct SLAEncoder* e, uint8_t* data, uint32_t data_size,
   if (data == NULL || output_size == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if (data_size < SLA_HEADER_SIZE) { return SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE; }
   RCCHK(enter(e));
+  verify_clear(e);
   memset(&seg, 0, sizeof(seg));
   seg.lo = 0; seg.hi = e->num_samples; seg.data = data; seg.data_size = data_size;
   rc = pack_device_core(e, &seg, 1);
@@ -3233,6 +3413,7 @@ static struct SLAEncoder* stream_lane(struct SLAEncoder* e, uint32_t t)
   l->cert_safety = e->cert_safety; l->single_tail = e->single_tail; l->device_ltm = e->device_ltm; l->tune = e->tune;
   l->block_cert = e->block_cert; l->block_cert_safety = e->block_cert_safety; l->ltm_cert = e->ltm_cert; l->ltm_cert_safety = e->ltm_cert_safety; l->alt_streams = e->alt_streams; l->device_expand = e->device_expand; l->expand_silence = e->expand_silence;
   l->table_cache = e->table_cache; l->prelaunch = e->prelaunch; l->one_stream = e->one_stream;
+  l->verify = e->verify; verify_clear(l);
   l->trace = 0;
   return l;
 }
@@ -3274,6 +3455,7 @@ static int encode_whole_streamed(struct SLAEncoder* e, const int32_t* const* inp
   }
   for (t = 0; t < started; t++) { pthread_join(th[t], NULL); }
   (void)enter(e);                                         /* the lanes named their own knobs on their threads; this thread is ours */
+  for (t = 0; t < L; t++) { if (e->lane[t]->ver_ran) { verify_add(e, e->lane[t]->ver); } }      /* the pieces' verification counters add up here */
   rc = sc->failed;
   if (e->trace) {
     for (r = 0; r < K; r++) {
@@ -3287,7 +3469,7 @@ static int encode_whole_streamed(struct SLAEncoder* e, const int32_t* const* inp
     hinfo.encode_param = e->encode_param; hinfo.num_samples = n; hinfo.num_blocks = sc->num_blocks;
     hinfo.max_block_size = sc->max_block; hinfo.max_bit_per_second = sc->max_bps;
     rc = slai_write_header(&hinfo, data, data_size);
-    if (rc == 0) { *output_size = (uint32_t)sc->off[K]; e->streamed = 1; e->analysed = 0; e->lshift = sc->lshift; e->num_samples = n; }
+    if (rc == 0) { *output_size = (uint32_t)sc->off[K]; e->streamed = 1; e->analysed = 0; e->image_valid = 0; e->lshift = sc->lshift; e->num_samples = n; }
   }
   pthread_mutex_destroy(&sc->mu); pthread_cond_destroy(&sc->cv);
   free(sc);
@@ -3306,6 +3488,7 @@ SLAApiResult SLAEncoder_EncodeWhole(struct SLAEncoder* e, const int32_t* const* 
     const double t0 = now_ms();
     double t1, t2;
     e->streamed = 0;
+    verify_clear(e);
     rc = encode_whole_streamed(e, input, num_samples, data, data_size, output_size);
     if (rc >= 0) {
       if (e->trace) { fprintf(stderr, "[sla_hip] EncodeWhole: streamed, %.3f ms\n", now_ms() - t0); }
@@ -3590,6 +3773,7 @@ done:
   e->batch_stamp[3] = now_ms();
   e->nsegs = 0; e->seg_start = NULL; e->seg_len = NULL;
   e->analysed = 0;                                        /* the planes hold a batch, not a file: no trace / pack afterwards */
+  e->image_valid = 0;
   free(start); free(segs);
   return rc;
 #undef BATCH_CHK
@@ -3690,6 +3874,7 @@ static void* batch_lane_main(void* varg)
       pthread_mutex_lock(&bc->mu);
       par->audit_ok += l->audit_ok; par->audit_bad += l->audit_bad;
       for (q = 0; q < 5; q++) { par->ltm_stat[q] += l->ltm_stat[q]; }
+      if (l->ver_ran) { verify_add(par, l->ver); }
       pthread_mutex_unlock(&bc->mu);
     }
     if (rc != 0) {
@@ -3754,7 +3939,7 @@ static int encode_batch_on_lanes(struct SLAEncoder* e, sla_hip_batch_item* items
   }
   pthread_mutex_destroy(&bc->mu); pthread_mutex_destroy(&bc->gate);
   free(bc);
-  e->analysed = 0;
+  e->analysed = 0; e->image_valid = 0;
   return (rc > 0) ? rc : (rc < 0 ? SLA_APIRESULT_NG : 0);
 }
 
@@ -3765,6 +3950,7 @@ int sla_hip_encode_batch(struct SLAEncoder* e, sla_hip_batch_item* items, uint32
   if (e == NULL || (items == NULL && num_items != 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if ((rc = check_ready(e)) != 0) { return rc; }
   RCCHK(enter(e));
+  verify_clear(e);
   for (i = 0; i < num_items; i++) {
     if (items[i].input == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
     for (ch = 0; ch < e->wave_format.num_channels; ch++) { if (items[i].input[ch] == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; } }
@@ -3806,6 +3992,7 @@ int sla_hip_encode_batch_device(struct SLAEncoder* e, sla_hip_encode_device_item
   }
   if (num_items == 0) { return 0; }
   RCCHK(enter(e));
+  verify_clear(e);
   C = e->wave_format.num_channels;
   esize = (sample_format == SLA_HIP_PCM_S16) ? 2u : 4u;
   bi = (sla_hip_batch_item*)calloc(num_items, sizeof(*bi));

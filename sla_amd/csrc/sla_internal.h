@@ -78,6 +78,22 @@ void     slai_coding_mode(const uint32_t* rice_init, uint32_t num_channels, uint
 uint32_t slai_crc16(const uint8_t* data, size_t n);
 int      slai_write_header(const struct SLAHeaderInfo* h, uint8_t* data, uint32_t data_size);
 
+/* ---- sla_verify.c: tables of the encoder's verification pass (no device calls) --------- */
+typedef struct slai_verify_seg {
+  uint64_t img_off;      /* where the file (43-byte header + blocks, or bare blocks) starts in the device image */
+  uint64_t img_bytes;    /* its size there */
+  int      deliver;      /* 0: the file is not delivered (e.g. its buffer is too small): its blocks are left out */
+} slai_verify_seg;
+/* From the pack table (blocks ascending in the image) and the files of the pass (ascending, back to back; files without
+ * blocks allowed anywhere): the decoder's block table, every block's end of stream (the end of its file), what the parser
+ * must find, and the block's file index -- for the blocks of delivered files only, in order.  Returns the number of blocks
+ * written (<= num_blocks: the arrays' capacity); *compared = channels x samples of those blocks, *max_block_samples their
+ * longest. */
+uint32_t slai_verify_tables(const sla_hip_pack_block* pb, uint32_t num_blocks, const slai_verify_seg* segs, uint32_t num_segs,
+                            uint32_t num_channels, sla_hip_dec_block* blocks, uint64_t* block_end,
+                            sla_hip_verify_expect* expect, uint32_t* seg_of_block, uint64_t* compared,
+                            uint32_t* max_block_samples);
+
 /* ---- sla_decoder.c: caller-owned device memory of the batch calls --------- */
 /* 1 when [0, C) x [0, n) of esize-byte elements at p (element (c, i) at c * channel_stride + i * sample_stride) is aligned,
  * its byte extent does not overflow, the runtime reports p as device memory (of `device` when >= 0) and the region lies
