@@ -195,6 +195,36 @@ int sla_hip_launch_batch_scan(const uint64_t* d_nz_mask, const uint32_t* d_tile_
                               const uint32_t* d_file_len, uint32_t num_files, uint32_t max_block_samples,
                               uint32_t* d_info, sla_hip_stream_t stream);
 
+/* The run list of a silence mask: what the host's super-frame hop and its "is this block all zero" test need to know
+ * instead of the mask itself (option "silence_runs").
+ * d_nz_mask: the prepass mask, 16-byte aligned, ceil(span / 64) words, bits at or above span zero.  Segments (the files of a
+ * batch): device arrays d_seg_start / d_seg_len of num_segs entries, ascending, not overlapping, starts multiples of
+ * SLA_HIP_PREPASS_TILE, every bit outside them zero; d_seg_start == NULL: one segment [0, span) (d_seg_len, num_segs ignored).
+ * The list holds every maximal run of zero bits inside a segment that is at least min_run samples long or ends at the
+ * segment's end (any length; an empty segment has none).  A run never crosses a segment boundary: the zero gap between two
+ * files neither joins their runs nor makes one.  Whoever treats every sample outside the listed runs as non-zero gets, for
+ * min_run = SLA_HIP_ZERO_RUN_MIN, the hop tables and the block types of the true mask: a super-frame or block can only be
+ * SILENT when it is at least SLA's minimum block long or ends at its file's end (reference src/SLAEncoder.c:392-408,
+ * src/SLAPredictor.c:1623-1630).
+ * d_count[0] = number of such runs, exact also beyond `capacity`; nothing is written at or behind d_runs[capacity]; when the
+ * count exceeds the capacity the list's content is unspecified.  The order of the entries is unspecified: sort on the host.
+ * min_run >= 64 (a run inside one mask word then never qualifies); span <= SLA_HIP_ZERO_RUN_MAX_SPAN.
+ * d_scratch: SLA_HIP_ZERO_RUN_SCRATCH_BYTES(span) bytes, 4-byte aligned; the launcher initialises what it needs of it and of
+ * d_count (two kernels on `stream`, no memset, no synchronisation).
+ * Returns SLA_APIRESULT_INVALID_ARGUMENT before any launch for a NULL mask, runs, count or scratch pointer, a mask that is
+ * not 16-byte aligned, capacity == 0, min_run < 64, a span over the limit, or a table (d_seg_start != NULL) without
+ * d_seg_len or with num_segs == 0. */
+typedef struct sla_hip_zero_run { uint32_t start; uint32_t length; } sla_hip_zero_run;   /* 8 bytes */
+#define SLA_HIP_ZERO_RUN_MIN 2048u      /* what the encoder passes: SLA's minimum block */
+#define SLA_HIP_ZERO_RUN_TILE 1024u     /* mask words one workgroup scans (65536 samples) */
+#define SLA_HIP_ZERO_RUN_MAX_SPAN 0xFFFF0000u
+#define SLA_HIP_ZERO_RUN_SCRATCH_BYTES(span) \
+  (4u * (size_t)(SLA_HIP_ZERO_RUN_TILE / 128u + 1u) * (size_t)((((uint64_t)(span) + 63u) / 64u + SLA_HIP_ZERO_RUN_TILE - 1u) / SLA_HIP_ZERO_RUN_TILE + 1u))
+int sla_hip_launch_zero_runs(const uint64_t* d_nz_mask, uint32_t span,
+                             const uint32_t* d_seg_start, const uint32_t* d_seg_len, uint32_t num_segs,
+                             uint32_t min_run, sla_hip_zero_run* d_runs, uint32_t capacity,
+                             uint32_t* d_count, uint32_t* d_scratch, sla_hip_stream_t stream);
+
 /* Autocorrelation + Levinson-Durbin for every candidate of every group.
  * d_out: per slot (order+2) doubles = { r[0], parcor[0..order] }.
  * When d_code/d_kint/d_rshift are non-NULL (chosen blocks: one candidate per
@@ -848,6 +878,13 @@ int sla_hip_get_trace(struct SLAEncoder* encoder, sla_hip_trace* trace);
  * streamed, sla_hip_encode_batch, sla_hip_encode_batch_device) decodes the finished block bytes on the device with the
  * decoder's kernels, while they cross the bus, and compares the result with the source planes; a file whose bytes do not
  * decode back to its samples gets SLA_APIRESULT_NG (output_size 0 in a batch).  See sla_hip_last_verify; DESIGN section 2d.
+ * "silence_runs" (0 = default: off; 1..65536: capacity of the list): input with silence no longer brings the prepass mask
+ * (num_samples / 8 bytes, and a second wait) to the host: sla_hip_launch_zero_runs lists the zero runs that can matter
+ * behind the prepass, count and list (8 + 8 x capacity bytes) come home in the prepass's own wait, and the super-frame hop and
+ * the block types are decided from the list.  More runs than the capacity: the mask route, as with 0.  Same bytes either way.
+ * Covers sla_hip_analyze_device / SLAEncoder_EncodeWhole (not streamed), sla_hip_encode_batch (lanes included),
+ * sla_hip_encode_batch_device and sla_hip_analyze_batch_device; the pieces of a streamed file, the sla_hip_shard_* calls and
+ * SLAEncoder_EncodeBlock keep the mask.  See sla_hip_last_silence; DESIGN section 2e.
  * SLAEncoder_EncodeWhole of long files: "stream" (0: never streamed), "stream_piece" (samples per piece, all channels
  * together; default 32 Mi; a file of fewer than two pieces is not streamed), "stream_lanes" (worker lanes, 1..6, default 6; pieces are handed to whichever lane is free),
  * "batch_lanes" (sla_hip_encode_batch: a batch of at least 8 files and 16 Mi samples is dealt out in groups of consecutive files to
@@ -899,6 +936,13 @@ int sla_hip_last_verify(const struct SLAEncoder* encoder, uint64_t counters[5]);
  * streamed call, a new analysis or new parameters); SLA_APIRESULT_INVALID_ARGUMENT for NULL arguments or planes that are
  * not device memory of the handle's device covering [C][num_samples]. */
 int sla_hip_verify_last_image(struct SLAEncoder* encoder, const int32_t* d_pcm, uint64_t plane_stride, uint64_t counters[5]);
+
+/* Option "silence_runs": 4 counters of the last analysis (or batch call) -- the route: 0 = nothing silent was found and no mask
+ * was needed, 1 = the tables came from the device's run list, 2 = the mask was downloaded (option off, or the list
+ * overflowed); zero runs the device found (0 with the option off); the capacity of the list; mask bytes downloaded beyond
+ * the fixed tail words of a single file.  A batch's passes and worker lanes are summed: the route is the maximum, runs and
+ * bytes add up. */
+int sla_hip_last_silence(const struct SLAEncoder* encoder, uint32_t counters[4]);
 
 /* 4 counters: pipeline chunks of the last analysis whose block stage was launched from device-written tables
  * (sla_hip_launch_expand; option "device_expand"), its pipeline chunks in all; since the handle was created: the analyses

@@ -170,6 +170,10 @@ def lib():
             L.sla_hip_launch_verify_blocks.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                        C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        if hasattr(L, "sla_hip_last_silence"):               # (SLA_HIP_LIB may name an older build in an A/B run)
+            L.sla_hip_last_silence.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+            L.sla_hip_launch_zero_runs.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                   C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sla_hip_search_exact_lags.restype = C.c_uint32
         L.sla_hip_encoder_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
         L.sla_hip_shard_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, u32p, C.POINTER(C.c_uint64)]
@@ -267,6 +271,8 @@ EXPORTED_SYMBOLS = [
     "sla_hip_encode_batch_device", "sla_hip_launch_enc_ingest_batch",
     # verification of the encoded stream on the device (include/sla_hip.h)
     "sla_hip_launch_verify_blocks", "sla_hip_last_verify", "sla_hip_verify_last_image",
+    # silence from a device-written run list (include/sla_hip.h)
+    "sla_hip_launch_zero_runs", "sla_hip_last_silence",
 ]
 
 
@@ -582,6 +588,14 @@ class Encoder:
         """certified long-term stage (option ltm_cert) in the last analysis: (jobs, certified, fallback, audit_ok, audit_bad)"""
         c = (C.c_uint32 * 5)()
         self._check(self._lib.sla_hip_last_ltm_cert(self._h, c), "sla_hip_last_ltm_cert")
+        return tuple(c)
+
+    def last_silence(self):
+        """option "silence_runs": (route of the last analysis or batch call -- 0: nothing silent, no mask needed; 1: tables
+        from the device's run list; 2: the mask was downloaded --, zero runs the device found, capacity of the list, mask
+        bytes downloaded beyond the fixed tail words); a batch's passes and worker lanes are summed (the route: the maximum)"""
+        c = (C.c_uint32 * 4)()
+        self._check(self._lib.sla_hip_last_silence(self._h, c), "sla_hip_last_silence")
         return tuple(c)
 
     def last_verify(self):

@@ -94,6 +94,30 @@ extern "C" int sla_hip_launch_batch_scan(const uint64_t* d_nz_mask, const uint32
   return hip_rc(hipGetLastError());
 }
 
+extern "C" int sla_hip_launch_zero_runs(const uint64_t* d_nz_mask, uint32_t span,
+                                        const uint32_t* d_seg_start, const uint32_t* d_seg_len, uint32_t num_segs,
+                                        uint32_t min_run, sla_hip_zero_run* d_runs, uint32_t capacity,
+                                        uint32_t* d_count, uint32_t* d_scratch, sla_hip_stream_t stream)
+{
+  if (d_nz_mask == nullptr || d_runs == nullptr || d_count == nullptr || d_scratch == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (((uintptr_t)d_nz_mask & 15u) != 0 || ((uintptr_t)d_scratch & 3u) != 0 || ((uintptr_t)d_count & 3u) != 0 || ((uintptr_t)d_runs & 3u) != 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (capacity == 0 || min_run < 64u || span > SLA_HIP_ZERO_RUN_MAX_SPAN) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (d_seg_start != nullptr && (d_seg_len == nullptr || num_segs == 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  hipStream_t st = (hipStream_t)stream;
+  if (d_seg_start == nullptr) { d_seg_len = nullptr; num_segs = 1; }
+  // (a span of no samples still runs: the first kernel zeroes the count, one workgroup over a mask of no words)
+  const uint64_t nwords = ((uint64_t)span + 63) / 64;
+  uint32_t ntiles = (uint32_t)((nwords + SLA_HIP_ZERO_RUN_TILE - 1) / SLA_HIP_ZERO_RUN_TILE);
+  if (ntiles == 0) { ntiles = 1; }
+  const uint32_t seg_blocks = (num_segs + ZR_GROUPS - 1) / ZR_GROUPS;
+  hipLaunchKernelGGL(k_zero_run_tiles, dim3(ntiles), dim3(64 * ZR_GROUPS), 0, st, d_nz_mask, span, d_scratch, d_count);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { return hip_rc(e); }
+  hipLaunchKernelGGL(k_zero_run_list, dim3(ntiles + seg_blocks), dim3(64 * ZR_GROUPS), 0, st, d_nz_mask, span, d_seg_start, d_seg_len, num_segs,
+                     min_run, ntiles, (const uint32_t*)d_scratch, d_runs, capacity, d_count);
+  return hip_rc(hipGetLastError());
+}
+
 extern "C" int sla_hip_launch_prepass_tiles(const int32_t* d_pcm, uint64_t plane_stride, uint32_t num_channels,
                                             uint32_t num_samples, uint32_t bits_per_sample, uint32_t mid_side,
                                             uint32_t* d_or_mask, uint64_t* d_nz_mask, uint32_t* d_tile_or, sla_hip_stream_t stream)

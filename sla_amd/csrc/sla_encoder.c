@@ -92,6 +92,13 @@ struct SLAEncoder {
                                      * stage launched from two counts, the host's own tables following under the kernels; 0: host tables first */
   int      expand_silence;          /* 1 (default): files / batches WITH silence take device-written block tables too (k_expand reads the
                                      * prepass mask: all-zero blocks of searched super-frames get no group); 0: host tables for them (rounds 2-3) */
+  /* option "silence_runs" (0 = default: off; else the capacity of the list): the prepass mask stays on the device also when
+   * the input has silence; the device lists the zero runs the super-frame hop and the block test can see
+   * (sla_hip_launch_zero_runs) and the host answers from the list.  A list that overflows: the mask route. */
+  uint32_t silence_runs;
+  devbuf_t d_zruns, d_zscratch; pinbuf_t h_zruns;      /* count word (8 bytes with its padding) | the entries; the kernels' scratch */
+  slai_silence sil;                 /* where this analysis' questions about silence are answered from (mask_absent: nowhere, nothing is silent) */
+  uint32_t sil_stat[4];             /* sla_hip_last_silence */
   uint32_t expand_seq;              /* sequence number of the last k_expand launch (what the host polls for) */
   uint32_t expanded_chunks;         /* last analysis: pipeline chunks whose block stage was launched from device tables */
   /* Search tables (super-frames, candidate shapes, groups) of the last file WITHOUT silence, host and device copies, kept for
@@ -473,6 +480,9 @@ void SLAEncoder_Destroy(struct SLAEncoder* e)
   if (e->d_ingest.ptr != NULL) { (void)hipFree(e->d_ingest.ptr); }
   if (e->h_ingest.ptr != NULL) { (void)hipHostFree(e->h_ingest.ptr); }
   if (e->ev_order != NULL) { (void)hipEventDestroy(e->ev_order); }
+  if (e->d_zruns.ptr != NULL) { (void)hipFree(e->d_zruns.ptr); }
+  if (e->d_zscratch.ptr != NULL) { (void)hipFree(e->d_zscratch.ptr); }
+  if (e->h_zruns.ptr != NULL) { (void)hipHostFree(e->h_zruns.ptr); }
   if (e->d_ver_tab.ptr != NULL) { (void)hipFree(e->d_ver_tab.ptr); }
   if (e->d_ver_planes.ptr != NULL) { (void)hipFree(e->d_ver_planes.ptr); }
   if (e->d_ver_info.ptr != NULL) { (void)hipFree(e->d_ver_info.ptr); }
@@ -742,9 +752,9 @@ static void actx_free(actx_t* a)
 static double g_trace_t0;
 #define PTRACE(label) do { if (g_trace_on) { fprintf(stderr, "[sla_hip]   prepare +%7.3f ms  %s\n", now_ms() - g_trace_t0, (label)); } } while (0)
 
-/* whole-file tables: super-frames (hop over silence runs), candidate shapes, search groups.  nz == NULL: no
+/* whole-file tables: super-frames (hop over silence runs), candidate shapes, search groups.  sil == NULL: no
  * sample is silent (the speculative pass that runs while the prepass is still on the device) */
-static int build_tables(struct SLAEncoder* e, actx_t* a, const uint64_t* nz)
+static int build_tables(struct SLAEncoder* e, actx_t* a, const slai_silence* sil)
 {
   const uint32_t C = e->wave_format.num_channels, bps = e->wave_format.bit_per_sample;
   const uint32_t order = e->encode_param.parcor_order, O1 = order + 1;
@@ -765,7 +775,7 @@ static int build_tables(struct SLAEncoder* e, actx_t* a, const uint64_t* nz)
     const uint32_t remain = seg_hi - pos;
     const uint32_t window = (maxb < remain) ? maxb : remain;
     const uint32_t min_blk = (SLAI_MIN_BLOCK < remain) ? SLAI_MIN_BLOCK : remain;
-    const uint32_t run = slai_zero_run(nz, pos, window);
+    const uint32_t run = slai_silence_run(sil, pos, window);
     sframe_t* f;
     uint32_t s;
     if (a->nsf == sf_cap) {
@@ -1056,6 +1066,46 @@ static int lshift_of(uint32_t mask, uint32_t bps, uint32_t* lshift)
   return 0;
 }
 
+/* ---- option "silence_runs": the device's list of zero runs instead of the mask on the host ---- */
+#define ZRUNS_HEAD 8u        /* bytes in front of the entries: the count word and its padding */
+static int zruns_reserve(struct SLAEncoder* e, uint64_t span)
+{
+  const size_t bytes = ZRUNS_HEAD + sizeof(sla_hip_zero_run) * (size_t)e->silence_runs;
+  RCCHK(dev_reserve(&e->d_zruns, bytes));
+  RCCHK(pin_reserve(&e->h_zruns, bytes));
+  RCCHK(dev_reserve(&e->d_zscratch, SLA_HIP_ZERO_RUN_SCRATCH_BYTES(span)));
+  return 0;
+}
+
+/* behind the prepass on the handle's stream: the list kernels, then count and entries on their way home in one copy */
+static int zruns_enqueue(struct SLAEncoder* e, uint32_t span, const uint32_t* d_seg_start, const uint32_t* d_seg_len, uint32_t nsegs)
+{
+  RCCHK(sla_hip_launch_zero_runs((const uint64_t*)e->d_nz.ptr, span, d_seg_start, d_seg_len, nsegs, SLA_HIP_ZERO_RUN_MIN,
+                                 (sla_hip_zero_run*)((uint8_t*)e->d_zruns.ptr + ZRUNS_HEAD), e->silence_runs, (uint32_t*)e->d_zruns.ptr,
+                                 (uint32_t*)e->d_zscratch.ptr, e->stream));
+  HIPCHK(hipMemcpyAsync(e->h_zruns.ptr, e->d_zruns.ptr, ZRUNS_HEAD + sizeof(sla_hip_zero_run) * (size_t)e->silence_runs,
+                        hipMemcpyDeviceToHost, e->stream));
+  return 0;
+}
+
+/* after the wait: the number of runs the device found; when they fit the list, e->sil answers from it (sorted) */
+static uint32_t zruns_take(struct SLAEncoder* e, int* complete)
+{
+  const uint32_t count = ((const uint32_t*)e->h_zruns.ptr)[0];
+  *complete = (count <= e->silence_runs);
+  if (*complete) {
+    sla_hip_zero_run* runs = (sla_hip_zero_run*)((uint8_t*)e->h_zruns.ptr + ZRUNS_HEAD);
+    slai_sort_runs(runs, count);
+    e->sil.nz = NULL; e->sil.runs = runs; e->sil.num_runs = count; e->sil.by_runs = 1;
+  }
+  return count;
+}
+
+static void silence_from_mask(struct SLAEncoder* e)
+{
+  e->sil.nz = (const uint64_t*)e->h_nz.ptr; e->sil.runs = NULL; e->sil.num_runs = 0; e->sil.by_runs = 0;
+}
+
 /* routes that depend on what the prepass found (or is guessed to find): tile-sum search, device-written block tables */
 static void decide_routes(struct SLAEncoder* e, actx_t* a, uint32_t or_word, int silence)
 {
@@ -1081,7 +1131,8 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
   const uint32_t ms = (e->encode_param.ch_process_method == SLA_CHPROCESSMETHOD_STEREO_MS);
   const uint32_t n = e->num_samples, maxb = e->encode_param.max_num_block_samples;
   const uint64_t nwords = ((uint64_t)n + 63) / 64;
-  const uint64_t* nz;
+  /* (ranges of a longer file, sla_hip_shard_*, keep the mask route) */
+  const int want_runs = (e->silence_runs != 0 && e->nsegs == 0 && e->file_or_word == 0 && n <= SLA_HIP_ZERO_RUN_MAX_SPAN);
   int rebuild = 0;
 
   g_trace_t0 = now_ms();
@@ -1099,7 +1150,7 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
     }
     e->mask_absent = 0;
     e->tab_valid = 0;                                     /* the batch's tables take the place of the kept ones */
-    RCCHK(build_tables(e, a, (const uint64_t*)e->h_nz.ptr));
+    RCCHK(build_tables(e, a, &e->sil));                    /* (batch_prepass: the mask, or the run list) */
     RCCHK(pipeline_reserve(e, a));
     RCCHK(upload_search_tables(e, a));
     decide_routes(e, a, e->h_or[0], 1);
@@ -1109,6 +1160,8 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
   RCCHK(dev_reserve(&e->d_or, 64));
   RCCHK(dev_reserve(&e->d_nz, (size_t)(nwords + 2) * 8));
   RCCHK(pin_reserve(&e->h_nz, (size_t)(nwords + 2) * 8));
+  if (want_runs) { RCCHK(zruns_reserve(e, n)); }
+  e->sil_stat[0] = 0; e->sil_stat[1] = 0; e->sil_stat[2] = e->silence_runs; e->sil_stat[3] = 0;
   HIPCHK(hipEventRecord(e->ev[0], e->stream));
   /* (one exception keeps the prepass: a last super-frame of fewer than 127 samples can be all zero -- and then is a SILENT
    * block, its minimum length being what is left of the file, src/SLAEncoder.c:401-407 -- without containing an aligned
@@ -1121,11 +1174,14 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
     if (e->nz_ones_cap != e->h_nz.cap) { e->nz_ones_cap = e->h_nz.cap; e->nz_ones_words = 0; }
     if (e->nz_ones_words < nwords) { memset((uint64_t*)e->h_nz.ptr + e->nz_ones_words, 0xFF, (size_t)(nwords - e->nz_ones_words) * 8); }
     e->nz_ones_words = nwords;
+    silence_from_mask(e);
     RCCHK(tables_no_silence(e, a));
   } else {
   RCCHK(sla_hip_launch_prepass(e->pcm_dev, e->stride, C, n, bps, ms, (uint32_t*)e->d_or.ptr, (uint64_t*)e->d_nz.ptr, e->stream));
   HIPCHK(hipEventRecord(e->ev[1], e->stream));
   {
+    int by_runs = 0;
+    uint32_t zcount = 0;
     /* Without an all-zero mask word there is no silence to find, except at the very end of the file where the
      * minimum block length shrinks with what is left (src/SLAEncoder.c:846-869): only the last words of the mask
      * are fetched then, everything before them counts as "not silent" (a run of zeros shorter than the minimum
@@ -1134,6 +1190,7 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
     const uint64_t head_words = nwords - tail_words;
     HIPCHK(hipMemcpyAsync(e->h_or, e->d_or.ptr, 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync((uint64_t*)e->h_nz.ptr + head_words, (uint64_t*)e->d_nz.ptr + head_words, (size_t)tail_words * 8, hipMemcpyDeviceToHost, e->stream));
+    if (want_runs) { RCCHK(zruns_enqueue(e, n, NULL, NULL, 0)); }      /* (count and list come home in the same wait) */
     HIPCHK(hipEventRecord(e->ev_prep, e->stream));
     /* while the prepass runs: the tables of a file without silence (the usual case; checked below), every buffer of
      * the pipeline, and the tables on their way to the device behind the prepass -- so that the first search kernel
@@ -1152,21 +1209,32 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
       }
     }
     HIPCHK(hipEventSynchronize(e->ev_prep));
-    if (e->h_or[1] != 0) {
+    if (want_runs) { zcount = zruns_take(e, &by_runs); e->sil_stat[1] = zcount; }
+    if (by_runs && (zcount != 0 || e->h_or[1] != 0)) {
+      /* silence, and the device's list of it is complete: no mask comes home, no second wait.  The head of h_nz is not
+       * touched (what is known to be all ones there stays so; the tail copy has overwritten the words behind it) */
+      if (e->nz_ones_cap != e->h_nz.cap) { e->nz_ones_cap = e->h_nz.cap; e->nz_ones_words = 0; }
+      if (e->nz_ones_words > head_words) { e->nz_ones_words = head_words; }
+      e->sil_stat[0] = 1;
+      if (e->h_or[1] != 0) { rebuild = 1; }               /* (without an all-zero word: only the last super-frame, checked below) */
+    } else if (e->h_or[1] != 0) {
       HIPCHK(hipMemcpyAsync(e->h_nz.ptr, e->d_nz.ptr, (size_t)head_words * 8, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipStreamSynchronize(e->stream));
       e->nz_ones_words = 0;
       rebuild = 1;
+      by_runs = 0;
+      e->sil_stat[0] = 2; e->sil_stat[3] = (uint32_t)(head_words * 8);
     } else {
+      by_runs = 0;
       if (e->nz_ones_cap != e->h_nz.cap) { e->nz_ones_cap = e->h_nz.cap; e->nz_ones_words = 0; }   /* reallocated since (a new block may reuse the address) */
       if (e->nz_ones_words < head_words) {
         memset((uint64_t*)e->h_nz.ptr + e->nz_ones_words, 0xFF, (size_t)(head_words - e->nz_ones_words) * 8);
       }
       e->nz_ones_words = head_words;       /* the words behind it were just overwritten by the tail copy */
     }
+    if (!by_runs) { silence_from_mask(e); }
   }
   }
-  nz = (const uint64_t*)e->h_nz.ptr;
   ((uint64_t*)e->h_nz.ptr)[nwords] = 0; ((uint64_t*)e->h_nz.ptr)[nwords + 1] = 0;
   if (e->file_or_word != 0) {
     if ((e->h_or[0] & ~e->file_or_word) != 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }   /* not a range of that file */
@@ -1183,7 +1251,7 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
     const uint32_t remain = n - f->start;
     const uint32_t window = (maxb < remain) ? maxb : remain;
     const uint32_t min_blk = (SLAI_MIN_BLOCK < remain) ? SLAI_MIN_BLOCK : remain;
-    if (slai_zero_run(nz, f->start, window) >= min_blk) { rebuild = 1; }
+    if (slai_silence_run(&e->sil, f->start, window) >= min_blk) { rebuild = 1; }
   }
   if (rebuild) {
     if (!a->borrowed) { free(a->sf); free(a->shapes); }
@@ -1191,7 +1259,7 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
     a->sf = NULL; a->shapes = NULL;
     a->nsf = 0; a->nshapes = 0; a->ncands = 0; a->nsgroups = 0; a->nslots = 0; a->nxg = 0;
     a->blocks_bound = 0; a->lchunks_bound = 0;
-    RCCHK(build_tables(e, a, nz));
+    RCCHK(build_tables(e, a, &e->sil));
     RCCHK(pipeline_reserve(e, a));
     RCCHK(upload_search_tables(e, a));
   }
@@ -1442,7 +1510,7 @@ static int search_launch(struct SLAEncoder* e, actx_t* a, uint32_t c)
 static int plan_chunk(struct SLAEncoder* e, actx_t* a, uint32_t c)
 {
   chunk_t* k = &a->ck[c];
-  const uint64_t* nz = e->mask_absent ? NULL : (const uint64_t*)e->h_nz.ptr;      /* NULL: nothing is silent (slai_zero_run) */
+  const slai_silence* sil = e->mask_absent ? NULL : &e->sil;      /* NULL: nothing is silent (slai_silence_run) */
   plan_ctx_t ctx;
   uint32_t i;
   int certified_only = 0;
@@ -1489,7 +1557,7 @@ static int plan_chunk(struct SLAEncoder* e, actx_t* a, uint32_t c)
       if (a->status[i] != 0) { return a->status[i]; }
       for (p = 0; p < a->nparts[i]; p++) {
         const uint32_t len = a->parts[(size_t)i * SLAI_MAX_NODES + p];
-        RCCHK(blocks_push(e, at, len, slai_range_is_zero(nz, at, len) ? SLAI_BLK_SILENT : SLAI_BLK_COMPRESS));
+        RCCHK(blocks_push(e, at, len, slai_silence_is_zero(sil, at, len) ? SLAI_BLK_SILENT : SLAI_BLK_COMPRESS));
         at += len;
       }
     }
@@ -2236,6 +2304,7 @@ int sla_hip_encoder_set_option(struct SLAEncoder* e, const char* name, double va
   else if (strcmp(name, "alt_streams") == 0)       { OPT_RANGE(0, 2); e->alt_streams = (int)iv; }
   else if (strcmp(name, "device_expand") == 0)     { OPT_RANGE(0, 1); e->device_expand = (int)iv; }
   else if (strcmp(name, "expand_silence") == 0)    { OPT_RANGE(0, 1); e->expand_silence = (int)iv; }
+  else if (strcmp(name, "silence_runs") == 0)      { OPT_RANGE(0, 65536); e->silence_runs = (uint32_t)iv; }
   else if (strcmp(name, "one_stream") == 0)        { OPT_RANGE(0, 1); e->one_stream = (int)iv; }
   else if (strcmp(name, "prelaunch") == 0)         { OPT_RANGE(0, 1); e->prelaunch = (int)iv; }
   else if (strcmp(name, "table_cache") == 0)       { OPT_RANGE(0, 1); e->table_cache = (int)iv; e->tab_valid = 0; e->spec_valid = 0; }
@@ -2449,6 +2518,13 @@ int sla_hip_last_expand(const struct SLAEncoder* e, uint32_t* counters)
 {
   if (e == NULL || counters == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   counters[0] = e->expanded_chunks; counters[1] = (uint32_t)e->timing[9]; counters[2] = e->table_hits; counters[3] = e->spec_misses;
+  return 0;
+}
+
+int sla_hip_last_silence(const struct SLAEncoder* e, uint32_t counters[4])
+{
+  if (e == NULL || counters == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  memcpy(counters, e->sil_stat, sizeof(e->sil_stat));
   return 0;
 }
 
@@ -3411,7 +3487,7 @@ static struct SLAEncoder* stream_lane(struct SLAEncoder* e, uint32_t t)
   l->chunks = e->chunks; l->chunks_forced = e->chunks_forced; l->first_chunk = e->first_chunk; l->split_count = 0;
   l->fuse_lattice = e->fuse_lattice; l->device_plan = e->device_plan; l->search_exact = e->search_exact; l->exact_bits = e->exact_bits;
   l->cert_safety = e->cert_safety; l->single_tail = e->single_tail; l->device_ltm = e->device_ltm; l->tune = e->tune;
-  l->block_cert = e->block_cert; l->block_cert_safety = e->block_cert_safety; l->ltm_cert = e->ltm_cert; l->ltm_cert_safety = e->ltm_cert_safety; l->alt_streams = e->alt_streams; l->device_expand = e->device_expand; l->expand_silence = e->expand_silence;
+  l->block_cert = e->block_cert; l->block_cert_safety = e->block_cert_safety; l->ltm_cert = e->ltm_cert; l->ltm_cert_safety = e->ltm_cert_safety; l->alt_streams = e->alt_streams; l->device_expand = e->device_expand; l->expand_silence = e->expand_silence; l->silence_runs = e->silence_runs;
   l->table_cache = e->table_cache; l->prelaunch = e->prelaunch; l->one_stream = e->one_stream;
   l->verify = e->verify; verify_clear(l);
   l->trace = 0;
@@ -3599,19 +3675,21 @@ static int batch_prepass(struct SLAEncoder* e, uint64_t span, const uint32_t* st
   const uint64_t nwords = (span + 63) / 64;
   const uint32_t ntiles = (uint32_t)((span + 4 * SLA_HIP_PREPASS_TILE - 1) / (4 * SLA_HIP_PREPASS_TILE) * 4);
   const uint32_t words = (err != NULL) ? 6u : 5u;          /* per file in d_binfo */
+  const int want_runs = (e->silence_runs != 0 && span <= SLA_HIP_ZERO_RUN_MAX_SPAN);
   uint32_t i;
   RCCHK(dev_reserve(&e->d_or, 64));
   RCCHK(dev_reserve(&e->d_nz, (size_t)(nwords + 2) * 8));
   RCCHK(dev_reserve(&e->d_tile_or, sizeof(uint32_t) * ((size_t)ntiles + 4)));
   RCCHK(dev_reserve(&e->d_binfo, sizeof(uint32_t) * words * (size_t)count + 64));
   RCCHK(pin_reserve(&e->h_binfo, sizeof(uint32_t) * words * (size_t)count + 64));
+  if (want_runs) { RCCHK(zruns_reserve(e, span)); }
   {
     /* the files' positions go up behind nothing, the prepass and the per-file summary (k_batch_scan) follow, and what
      * comes home is 12 bytes per file: its OR word, its all-zero mask words, "its last super-frame is silent".  Only a
      * batch with silence in it brings the whole mask home (N/8 bytes: 7.5 MB and 0.3 ms for 125 ten-second clips) */
     uint32_t* hb = (uint32_t*)e->h_binfo.ptr;
     const uint32_t* info = hb + 2 * (size_t)count;
-    int silence = 0;
+    int silence = 0, by_runs = 0;
     memcpy(hb, start, sizeof(uint32_t) * count); memcpy(hb + count, len, sizeof(uint32_t) * count);
     HIPCHK(hipMemcpyAsync(e->d_binfo.ptr, hb, sizeof(uint32_t) * 2 * (size_t)count, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipEventRecord(e->ev[0], e->stream));
@@ -3623,16 +3701,28 @@ static int batch_prepass(struct SLAEncoder* e, uint64_t span, const uint32_t* st
                                     (uint32_t*)e->d_binfo.ptr + 2 * (size_t)count, e->stream));
     HIPCHK(hipMemcpyAsync(hb + 2 * (size_t)count, (uint32_t*)e->d_binfo.ptr + 2 * (size_t)count, sizeof(uint32_t) * (words - 2) * (size_t)count,
                           hipMemcpyDeviceToHost, e->stream));
+    /* option "silence_runs": the zero runs of every file, from the file table that is already on the device, home in the same wait */
+    if (want_runs) { RCCHK(zruns_enqueue(e, (uint32_t)span, (const uint32_t*)e->d_binfo.ptr, (const uint32_t*)e->d_binfo.ptr + count, count)); }
     HIPCHK(hipStreamSynchronize(e->stream));
     if (err != NULL) { memcpy(err, hb + 5 * (size_t)count, sizeof(uint32_t) * count); }
     for (i = 0; i < count; i++) { if (info[3 * i + 1] != 0 || info[3 * i + 2] != 0) { silence = 1; } }
     e->batch_silence = silence;
-    if (silence) {
+    e->sil_stat[2] = e->silence_runs;
+    if (want_runs) {
+      const uint32_t zcount = zruns_take(e, &by_runs);
+      e->sil_stat[1] += zcount;
+    }
+    if (silence && by_runs) {
+      if (e->sil_stat[0] < 1) { e->sil_stat[0] = 1; }      /* the mask stays on the device: the tables come from the list */
+    } else if (silence) {
+      if (e->sil_stat[0] < 2) { e->sil_stat[0] = 2; }
+      e->sil_stat[3] += (uint32_t)(nwords * 8);
       RCCHK(pin_reserve(&e->h_nz, (size_t)(nwords + 2) * 8));
       HIPCHK(hipMemcpyAsync(e->h_nz.ptr, e->d_nz.ptr, (size_t)nwords * 8, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipStreamSynchronize(e->stream));
       ((uint64_t*)e->h_nz.ptr)[nwords] = 0; ((uint64_t*)e->h_nz.ptr)[nwords + 1] = 0;
       e->nz_ones_words = 0;                               /* the single-file path may not assume anything about h_nz any more */
+      silence_from_mask(e);
     }
     for (i = 0; i < count; i++) {
       const uint32_t mask = info[3 * i];
@@ -3805,6 +3895,7 @@ int sla_hip_analyze_batch_device(struct SLAEncoder* e, const int32_t* d_pcm, uin
   orv = lsh + num_files; seg_start = orv + num_files; seg_len = seg_start + num_files;
   e->pcm_dev = d_pcm; e->stride = plane_stride; e->num_samples = span;
   memset(acc, 0, sizeof(acc));
+  memset(e->sil_stat, 0, sizeof(e->sil_stat));
   rc = batch_prepass(e, span, file_start, file_samples, num_files, lsh, orv, NULL);
   for (i = 0; rc == 0 && i < num_files; i++) {
     if (file_lshift != NULL) { file_lshift[i] = lsh[i]; }
@@ -3875,6 +3966,8 @@ static void* batch_lane_main(void* varg)
       par->audit_ok += l->audit_ok; par->audit_bad += l->audit_bad;
       for (q = 0; q < 5; q++) { par->ltm_stat[q] += l->ltm_stat[q]; }
       if (l->ver_ran) { verify_add(par, l->ver); }
+      if (l->sil_stat[0] > par->sil_stat[0]) { par->sil_stat[0] = l->sil_stat[0]; }
+      par->sil_stat[1] += l->sil_stat[1]; par->sil_stat[2] = l->sil_stat[2]; par->sil_stat[3] += l->sil_stat[3];
       pthread_mutex_unlock(&bc->mu);
     }
     if (rc != 0) {
@@ -3951,6 +4044,7 @@ int sla_hip_encode_batch(struct SLAEncoder* e, sla_hip_batch_item* items, uint32
   if ((rc = check_ready(e)) != 0) { return rc; }
   RCCHK(enter(e));
   verify_clear(e);
+  memset(e->sil_stat, 0, sizeof(e->sil_stat));
   for (i = 0; i < num_items; i++) {
     if (items[i].input == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
     for (ch = 0; ch < e->wave_format.num_channels; ch++) { if (items[i].input[ch] == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; } }
@@ -3993,6 +4087,7 @@ int sla_hip_encode_batch_device(struct SLAEncoder* e, sla_hip_encode_device_item
   if (num_items == 0) { return 0; }
   RCCHK(enter(e));
   verify_clear(e);
+  memset(e->sil_stat, 0, sizeof(e->sil_stat));
   C = e->wave_format.num_channels;
   esize = (sample_format == SLA_HIP_PCM_S16) ? 2u : 4u;
   bi = (sla_hip_batch_item*)calloc(num_items, sizeof(*bi));

@@ -48,6 +48,13 @@ int      slai_shortest_path(const double* adj, uint32_t nodes, uint32_t* path);
 int      slai_host_check(void);       /* 0: long double / double arithmetic of this host is the reference build's */
 uint32_t slai_zero_run(const uint64_t* nz_mask, uint64_t from, uint64_t limit);
 int      slai_range_is_zero(const uint64_t* nz_mask, uint64_t from, uint64_t count);
+/* where the host's questions about silence are answered from: the mask (by_runs == 0; nz == NULL: nothing is silent) or the
+ * device's run list, sorted by start (slai_sort_runs) */
+typedef struct slai_silence { const uint64_t* nz; const sla_hip_zero_run* runs; uint32_t num_runs; int by_runs; } slai_silence;
+void     slai_sort_runs(sla_hip_zero_run* runs, uint32_t num_runs);
+uint32_t slai_runs_zero_run(const sla_hip_zero_run* runs, uint32_t num_runs, uint64_t from, uint64_t limit);
+uint32_t slai_silence_run(const slai_silence* s, uint64_t from, uint64_t limit);      /* s == NULL: nothing is silent */
+int      slai_silence_is_zero(const slai_silence* s, uint64_t from, uint64_t count);
 
 /* ---- sla_ltm.c: long-term predictor analysis ------------------------------ */
 typedef struct slai_fft_plan slai_fft_plan;

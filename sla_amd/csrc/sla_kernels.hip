@@ -9,6 +9,7 @@
 //
 // Kernel (file under kernels/)           replaces (reference file:line)
 //   k_prepass, k_batch_scan (prepass)     src/SLAEncoder.c:425-455 (OR of all words), :392-408 / :520-528 (silence)
+//   k_zero_run_tiles / _list (zero_runs)  no counterpart: the zero runs the hop of src/SLAEncoder.c:392-408, 846-869 can see, as a list
 //   k_acf_tiles[_lds], k_search_finish,   src/SLAPredictor.c:1615-1649 (partition search) over :331-388 (autocorrelation): tile sums
 //   k_search_cert (search)                where the order of summation provably cannot matter, certified where it can; :253-328
 //   k_lpc (lpc_chains)                    src/SLAPredictor.c:331-388 in the reference's serial order + :253-328: the rerun of windows
@@ -91,6 +92,7 @@ __device__ __forceinline__ uint32_t umax_wave(uint32_t v)
 // One translation unit, cut by stage (the file had grown to 4 700 lines); the order matters: later
 // parts use device functions of earlier ones.
 #include "kernels/prepass.inc"
+#include "kernels/zero_runs.inc"
 #include "kernels/lpc_chains.inc"
 #include "kernels/lattice_wave.inc"
 #include "kernels/blocks.inc"

@@ -10,6 +10,7 @@
 
 #include <float.h>
 #include <math.h>
+#include <stdlib.h>
 
 #define SLAI_PI 3.1415926535897932384626433832795029
 
@@ -95,6 +96,53 @@ uint32_t slai_zero_run(const uint64_t* nz, uint64_t from, uint64_t limit)
 int slai_range_is_zero(const uint64_t* nz, uint64_t from, uint64_t count)
 {
   return slai_zero_run(nz, from, count) == count;
+}
+
+/* ---- silence from either source: the mask, or the device's run list (sla_hip_launch_zero_runs) -------------------------
+ * The run list holds the maximal zero runs of at least SLA's minimum block, or that end at their file's end; every sample
+ * outside them counts as non-zero.  The super-frame hop and the block test get the same answers from it as from the mask
+ * (include/sla_hip.h), at O(log runs) per question and without the mask on the host. */
+static int run_cmp(const void* a, const void* b)
+{
+  const uint32_t x = ((const sla_hip_zero_run*)a)->start, y = ((const sla_hip_zero_run*)b)->start;
+  return (x > y) - (x < y);
+}
+
+void slai_sort_runs(sla_hip_zero_run* runs, uint32_t num_runs)
+{
+  if (num_runs > 1) { qsort(runs, num_runs, sizeof(*runs), run_cmp); }
+}
+
+/* slai_zero_run's answer from a sorted run list: zero samples from `from` on, capped at `limit` (runs that touch -- the end
+ * of one file's tail and the next file's head -- continue one another, as their bits do in the mask) */
+uint32_t slai_runs_zero_run(const sla_hip_zero_run* runs, uint32_t num_runs, uint64_t from, uint64_t limit)
+{
+  uint32_t lo = 0, hi = num_runs;
+  uint64_t pos = from;
+  const uint64_t end = from + limit;
+  while (lo < hi) {                                       /* the last run that starts at or before `from` */
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (runs[mid].start <= from) { lo = mid + 1; } else { hi = mid; }
+  }
+  if (lo == 0) { return 0; }
+  for (lo--; lo < num_runs && pos < end; lo++) {
+    const uint64_t rs = runs[lo].start, re = rs + runs[lo].length;
+    if (rs > pos || re <= pos) { break; }
+    pos = re;
+  }
+  if (pos > end) { pos = end; }
+  return (uint32_t)(pos - from);
+}
+
+uint32_t slai_silence_run(const slai_silence* s, uint64_t from, uint64_t limit)
+{
+  if (s == NULL) { return 0; }                            /* nothing is silent */
+  return s->by_runs ? slai_runs_zero_run(s->runs, s->num_runs, from, limit) : slai_zero_run(s->nz, from, limit);
+}
+
+int slai_silence_is_zero(const slai_silence* s, uint64_t from, uint64_t count)
+{
+  return slai_silence_run(s, from, count) == count;
 }
 
 /* Bit-identical output leans on two host properties the reference's own x86-64 build has: the Toeplitz solve
