@@ -157,6 +157,9 @@ typedef struct sla_hip_launch_extra {
                                        has seen the count) */
   uint32_t* clear_ptr[3];           /* sla_hip_launch_search_exact_x: up to three regions of device words that the first workgroup of its first */
   uint32_t  clear_words[3];         /* kernel zeroes on the way (instead of one fill kernel each in front of it) */
+  uint32_t* d_rice_init;            /* sla_hip_launch_tail_x: num_jobs device words; the kernel stores every job's initial Rice parameter beside
+                                       fold_sum[j] -- the mean fold_sum[j] / blk_len, at least 1, as it survives the coder's 24.8 fixed-point word
+                                       (1 for a job with blk_len 0).  NULL: only fold_sum is written */
 } sla_hip_launch_extra;
 int sla_hip_launch_lpc_x(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
                          const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window, uint32_t max_cands_per_group,

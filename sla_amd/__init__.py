@@ -104,6 +104,12 @@ class EncodeDeviceItem(C.Structure):
                 ("num_samples", C.c_uint32), ("data_size", C.c_uint32), ("output_size", C.c_uint32), ("result", C.c_int32)]
 
 
+class LaunchExtra(C.Structure):
+    """sla_hip_launch_extra (include/sla_hip.h): optional extras of one launch of an `_x` launcher; all zero = none"""
+    _fields_ = [("d_span", C.c_void_p), ("d_group_count", C.c_void_p), ("clear_ptr", C.c_void_p * 3),
+                ("clear_words", C.c_uint32 * 3), ("d_rice_init", C.c_void_p)]
+
+
 # sample formats of sla_hip_decode_batch_device / sla_hip_encode_batch_device, flag of the former
 PCM_S32_LEFT, PCM_S32, PCM_S16, PCM_F32 = range(4)
 DEC_ZERO_FILL = 1

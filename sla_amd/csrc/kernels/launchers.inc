@@ -591,13 +591,14 @@ extern "C" int sla_hip_launch_emphasis_f64(const double* d_in, double* d_out, ui
 static int launch_tail_impl(const int32_t* d_res_in, int32_t* d_res_out, uint64_t plane_stride,
                             const sla_hip_tail_job* d_jobs, uint32_t num_jobs, uint32_t longterm_order,
                             uint32_t lms_order, uint64_t* d_fold_sum, sla_hip_stream_t stream, uint32_t stage_flags,
-                            unsigned long long* span = nullptr);
+                            unsigned long long* span = nullptr, uint32_t* d_rice_init = nullptr);
 
 extern "C" int sla_hip_launch_tail_x(const int32_t* d_res_in, int32_t* d_res_out, uint64_t plane_stride,
                                      const sla_hip_tail_job* d_jobs, uint32_t num_jobs, uint32_t longterm_order,
                                      uint32_t lms_order, uint64_t* d_fold_sum, sla_hip_stream_t stream, const sla_hip_launch_extra* extra)
 {
-  return launch_tail_impl(d_res_in, d_res_out, plane_stride, d_jobs, num_jobs, longterm_order, lms_order, d_fold_sum, stream, 0u, span_of(extra));
+  return launch_tail_impl(d_res_in, d_res_out, plane_stride, d_jobs, num_jobs, longterm_order, lms_order, d_fold_sum, stream, 0u, span_of(extra),
+                          (extra != nullptr) ? extra->d_rice_init : nullptr);
 }
 
 extern "C" int sla_hip_launch_tail(const int32_t* d_res_in, int32_t* d_res_out, uint64_t plane_stride,
@@ -620,7 +621,7 @@ extern "C" int sla_hip_launch_tail_stages(const int32_t* d_res_in, int32_t* d_re
 static int launch_tail_impl(const int32_t* d_res_in, int32_t* d_res_out, uint64_t plane_stride,
                             const sla_hip_tail_job* d_jobs, uint32_t num_jobs, uint32_t longterm_order,
                             uint32_t lms_order, uint64_t* d_fold_sum, sla_hip_stream_t stream, uint32_t stage_flags,
-                            unsigned long long* span)
+                            unsigned long long* span, uint32_t* d_rice_init)
 {
   if (d_res_in == nullptr || d_res_out == nullptr || d_jobs == nullptr || d_fold_sum == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if (longterm_order > 5 || !(longterm_order & 1)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
@@ -654,7 +655,7 @@ static int launch_tail_impl(const int32_t* d_res_in, int32_t* d_res_out, uint64_
     const uint32_t jpw = 64 / (lms_order / k);
     const uint32_t jpb = twk * jpw;
     dim3 gridk((num_jobs + jpb - 1) / jpb), blockk(64 * twk);
-#define LAUNCH_TAILK(O, KK) hipLaunchKernelGGL((k_tailk<O, KK>), gridk, blockk, 0, st, d_res_in, d_res_out, plane_stride, d_jobs, num_jobs, longterm_order, d_fold_sum, span, stage_flags)
+#define LAUNCH_TAILK(O, KK) hipLaunchKernelGGL((k_tailk<O, KK>), gridk, blockk, 0, st, d_res_in, d_res_out, plane_stride, d_jobs, num_jobs, longterm_order, d_fold_sum, span, stage_flags, d_rice_init)
     switch (lms_order * 16 + k) {
       case 4 * 16 + 1:  LAUNCH_TAILK(4, 1); break;
       case 8 * 16 + 1:  LAUNCH_TAILK(8, 1); break;

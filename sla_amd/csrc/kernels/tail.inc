@@ -1,4 +1,4 @@
-// kernels/tail.inc -- part of sla_kernels.hip (one translation unit; included there, in this order): k_tailk: long-term filter, sign-log LMS cascade, folded sum
+// kernels/tail.inc -- part of sla_kernels.hip (one translation unit; included there, in this order): k_tailk: long-term filter, sign-log LMS cascade, folded sum, Rice initial parameter
 // ---------------------------------------------------------------------------------------------
 // Tail stage: long-term filter -> sign-log LMS -> folded sum (src/SLAPredictor.c:1031-1119, 1202-1331; src/SLACoder.c:361-385).
 // The LMS is serial in time (every sample updates all 2 * ORDER coefficients from the error it just produced), so the
@@ -174,11 +174,23 @@ __device__ __forceinline__ void tailk_block(const int32_t (&vm)[TAILK_BLK * K / 
   }
 }
 
+// The coder's initial Rice parameter of a job from its folded sum (src/SLACoder.c:371-384): the mean of the folded residual, at
+// least 1, as the value that survives the coder's 32-bit 24.8 fixed-point word (src/SLACoder.c:14,19) -- init << 8 wraps at 2^24,
+// and a word that comes back as 0 is sent as 1.  A job without samples divides nothing and gets 1.
+__device__ __forceinline__ uint32_t rice_init_of(uint64_t fsum, uint32_t blk_len)
+{
+  if (blk_len == 0) { return 1u; }
+  const uint64_t mean = fsum / blk_len;
+  const uint32_t init = (uint32_t)(mean > 1 ? mean : 1);
+  const uint32_t kept = (uint32_t)((((uint64_t)(uint32_t)(init << 8)) + 128u) >> 8);
+  return kept ? kept : 1u;
+}
+
 template <int ORDER, int K>
 __global__ __launch_bounds__(256)
 void k_tailk(const int32_t* __restrict__ res_in, int32_t* __restrict__ res_out, uint64_t stride,
              const sla_hip_tail_job* __restrict__ jobs, uint32_t num_jobs, uint32_t ntaps,
-             uint64_t* __restrict__ fold_sum, unsigned long long* span, uint32_t stage_flags)
+             uint64_t* __restrict__ fold_sum, unsigned long long* span, uint32_t stage_flags, uint32_t* __restrict__ rice_init)
 {
   span_begin(span);
   constexpr int LPJ = ORDER / K;               // lanes per job: 2 .. 16
@@ -273,6 +285,9 @@ void k_tailk(const int32_t* __restrict__ res_in, int32_t* __restrict__ res_out, 
     const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(fsum >> 32), off);
     fsum += ((uint64_t)hi << 32) | lo;
   }
-  if (have && L == 0) { fold_sum[j] = fsum; }
+  if (have && L == 0) {
+    fold_sum[j] = fsum;
+    if (rice_init != nullptr) { rice_init[j] = rice_init_of(fsum, n); }      // one 64-bit divide per job, on one lane
+  }
   span_end(span);
 }

@@ -35,6 +35,7 @@
 
 typedef struct { void* ptr; size_t cap; } devbuf_t;
 typedef struct { void* ptr; size_t cap; } pinbuf_t;
+typedef struct { void* ptr; size_t cap; } hostbuf_t;      /* pageable host memory */
 
 typedef struct {
   uint32_t start, nsmpl, type, bytes;
@@ -130,6 +131,9 @@ struct SLAEncoder {
   pinbuf_t h_nz, h_groups, h_cands, h_lpc_out, h_code, h_kint, h_rshift, h_chunks, h_jobs, h_fold, h_res, h_pcm, h_acf_jobs, h_acf,
            h_bgroups, h_bcands, h_blk_out, h_pk_jobs, h_pk_blocks, h_pk_hdr, h_xgroups, h_fgroups, h_parts, h_nparts, h_pstatus, h_cert_flag,
            h_sframes, h_winmap, h_counts;
+  devbuf_t d_rice; pinbuf_t h_rice;  /* initial Rice parameter per tail job, written by k_tailk (device long-term route, one tail) */
+  /* host workspace of one analysis (actx_t borrows it): grows with the longest file seen, freed with the handle */
+  hostbuf_t w_job_blk, w_job_ch, w_job_grp, w_grp_of_slot, w_parts, w_nparts, w_status;
   uint32_t* h_or;
   size_t nz_ones_cap; uint64_t nz_ones_words;    /* h_nz words [0, nz_ones_words) are known to be all ones (h_nz.cap == nz_ones_cap) */
   pinbuf_t h_stage[2]; devbuf_t d_stage[2]; hipEvent_t ev_stage[2];
@@ -236,6 +240,18 @@ static int pin_reserve(pinbuf_t* b, size_t bytes)
   if (b->ptr != NULL) { (void)hipHostFree(b->ptr); b->ptr = NULL; b->cap = 0; }
   bytes += bytes / 8 + 256;
   HIPCHK(hipHostMalloc(&b->ptr, bytes, hipHostMallocDefault));
+  b->cap = bytes;
+  return 0;
+}
+
+static int host_reserve(hostbuf_t* b, size_t bytes)
+{
+  if (bytes == 0) { bytes = 16; }
+  if (b->cap >= bytes) { return 0; }
+  free(b->ptr); b->ptr = NULL; b->cap = 0;
+  bytes += bytes / 8 + 256;
+  b->ptr = malloc(bytes);
+  if (b->ptr == NULL) { return SLA_APIRESULT_NG; }
   b->cap = bytes;
   return 0;
 }
@@ -381,8 +397,24 @@ struct SLAEncoder* SLAEncoder_Create(const struct SLAEncoderConfig* config)
   if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess
       || hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking) != hipSuccess
       || hipStreamCreateWithFlags(&e->stream3, hipStreamNonBlocking) != hipSuccess
-      || hipStreamCreateWithFlags(&e->stream_up, hipStreamNonBlocking) != hipSuccess
-      || hipStreamCreateWithFlags(&e->stream_down, hipStreamNonBlocking) != hipSuccess) { goto fail; }
+      || hipStreamCreateWithFlags(&e->stream_up, hipStreamNonBlocking) != hipSuccess) { goto fail; }
+  /* The download stream exists to run beside the kernel streams: the block stage's results (45 MB per hour of stereo) go
+   * home under the lattice and the long-term stage, and the host decides RAW blocks meanwhile.  The runtime deals the
+   * streams of one priority out over a fixed number of hardware queues (four unless GPU_MAX_HW_QUEUES says otherwise), and
+   * with five streams per handle the download stream came to share a queue with the block stage's: a queue is served in
+   * order, so the copies sat between the long-term stage and k_tailk -- 0.9 ms of every C3 step with nothing else running,
+   * and the host's RAW decision (1.7 ms) only began behind them and ended after the tail (profiles/r6_c3_timeline_parent.txt,
+   * r6_c3_kernel_trace_parent.txt).  Queues are pooled per priority, so a download stream of another priority gets a queue
+   * none of the kernel streams can be dealt: the highest, its copies being short and the host waiting for them. */
+  {
+    int prio_least = 0, prio_greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess || prio_greatest == prio_least
+        || hipStreamCreateWithPriority(&e->stream_down, hipStreamNonBlocking, prio_greatest) != hipSuccess) {
+      (void)hipGetLastError();
+      e->stream_down = NULL;
+      if (hipStreamCreateWithFlags(&e->stream_down, hipStreamNonBlocking) != hipSuccess) { goto fail; }
+    }
+  }
   e->own_copy_streams = 1;
   for (i = 0; i < (int)(sizeof(e->ev) / sizeof(e->ev[0])); i++) { if (hipEventCreate(&e->ev[i]) != hipSuccess) { goto fail; } }
   if (hipEventCreate(&e->ev_stage[0]) != hipSuccess || hipEventCreate(&e->ev_stage[1]) != hipSuccess
@@ -489,6 +521,10 @@ void SLAEncoder_Destroy(struct SLAEncoder* e)
   if (e->d_ver_chan.ptr != NULL) { (void)hipFree(e->d_ver_chan.ptr); }
   if (e->d_ver_kint.ptr != NULL) { (void)hipFree(e->d_ver_kint.ptr); }
   if (e->h_ver.ptr != NULL) { (void)hipHostFree(e->h_ver.ptr); }
+  if (e->d_rice.ptr != NULL) { (void)hipFree(e->d_rice.ptr); }
+  if (e->h_rice.ptr != NULL) { (void)hipHostFree(e->h_rice.ptr); }
+  free(e->w_job_blk.ptr); free(e->w_job_ch.ptr); free(e->w_job_grp.ptr); free(e->w_grp_of_slot.ptr);
+  free(e->w_parts.ptr); free(e->w_nparts.ptr); free(e->w_status.ptr);
   free(e->tab_segs);
   for (i = 0; i < 2; i++) {
     if (e->h_stage[i].ptr != NULL) { (void)hipHostFree(e->h_stage[i].ptr); }
@@ -602,7 +638,7 @@ static int blocks_push(struct SLAEncoder* e, uint32_t start, uint32_t nsmpl, uin
 #define LTM_CNT_SLOT(e, c) ((uint32_t*)((unsigned long long*)(e)->d_spans.ptr + SPAN_ULLS) + 4 * (size_t)(c))
 #define SPECULATE_MAX_GROUPS 16384u      /* (super-frame, channel) pairs up to which the searches are launched on a guess */
 enum { EV_SEARCH_S, EV_SEARCH_E, EV_SEARCH_DONE, EV_LPCB_S, EV_LPCB_E, EV_LAT_E, EV_ACF_S, EV_ACF_E, EV_BLOCK_DONE,
-       EV_TAIL_S, EV_TAIL_E, EV_TAIL_DONE, EV_UPLOADED, EV_PLANNED, EV_UPLOADED2, EV_LPC_DOWN, EV_SOLVED, EV_EXPANDED, EV_PER_CHUNK };
+       EV_TAIL_S, EV_TAIL_E, EV_TAIL_DONE, EV_UPLOADED, EV_PLANNED, EV_UPLOADED2, EV_LPC_DOWN, EV_SOLVED, EV_EXPANDED, EV_JOBS_DOWN, EV_PER_CHUNK };
 typedef char ev_array_holds_every_chunk[(2 + MAX_CHUNKS * EV_PER_CHUNK <= 2 + 8 * 20) ? 1 : -1];
 
 typedef struct { uint32_t start, window, min_blk, shape, slot_base, grp_lo, grp_hi, xg; } sframe_t;
@@ -626,8 +662,10 @@ typedef struct {
   int exact;                                      /* this run searches with tile sums            */
   uint32_t blocks_bound, lchunks_bound;
   uint32_t nbg, nlc, njobs, ltm_done;                      /* running counters of the block stage */
-  uint32_t *job_blk, *job_ch, *job_grp, *grp_of_slot;
+  uint32_t *job_blk, *job_ch, *job_grp, *grp_of_slot;      /* (these seven live in the handle: SLAEncoder.w_*) */
   uint32_t *parts, *nparts; int* status;          /* per super-frame plan results        */
+  int fast_rice;                                  /* device long-term route with one tail: k_tailk stores the Rice parameters, the job
+                                                   * table comes home under it (tail_enqueue, jobs_home) */
   chunk_t ck[MAX_CHUNKS]; uint32_t nchunks;
   hipEvent_t* ev;                                 /* [nchunks][EV_PER_CHUNK]             */
   /* device-written block tables (k_expand) */
@@ -744,8 +782,6 @@ static void ltm_one(void* vctx, uint32_t rel)
 static void actx_free(actx_t* a)
 {
   if (!a->borrowed) { free(a->sf); free(a->shapes); }
-  free(a->job_blk); free(a->job_ch); free(a->job_grp); free(a->grp_of_slot);
-  free(a->parts); free(a->nparts); free(a->status);
 }
 
 /* prepass + whole-file tables: offset_lshift, super-frames, candidate shapes, search groups */
@@ -1338,6 +1374,8 @@ static int pipeline_reserve(struct SLAEncoder* e, const actx_t* a)
   RCCHK(pin_reserve(&e->h_cert_flag, sizeof(uint32_t) * (nslots + MAX_CHUNKS)));
   RCCHK(dev_reserve(&e->d_acf, sizeof(double) * nslots * SLAI_LTM_ACF_HEAD));
   RCCHK(dev_reserve(&e->d_fold, sizeof(uint64_t) * nslots));
+  RCCHK(dev_reserve(&e->d_rice, sizeof(uint32_t) * nslots));
+  RCCHK(pin_reserve(&e->h_rice, sizeof(uint32_t) * nslots));
   if (sizeof(double) * (size_t)fft_size > SLA_HIP_LDS_BUDGET) {
     RCCHK(dev_reserve(&e->d_acf_scratch, sizeof(double) * (size_t)fft_size * 512));
   }
@@ -1569,7 +1607,10 @@ static int plan_chunk(struct SLAEncoder* e, actx_t* a, uint32_t c)
 
 
 /* device long-term mode: k_tail over the jobs [lo, hi) (job == block group) right behind k_ltm_solve on the kernel
- * stream; folded sums and the solved pitch/taps go home on the download stream */
+ * stream; folded sums and the solved pitch/taps go home on the download stream.
+ * One tail for the file (a->fast_rice): the job table is final once the last solve has run -- k_tailk only reads it -- so it
+ * goes home UNDER the tail, and the kernel stores the Rice parameters itself: behind it 4 bytes per job travel on its own
+ * stream (no cross-queue wait), followed there by run_pipeline's span and counter words. */
 static int tail_enqueue(struct SLAEncoder* e, actx_t* a, uint32_t c, uint32_t lo, uint32_t hi)
 {
   const uint32_t ntaps = e->encode_param.longterm_order, lms = e->encode_param.lms_order_per_filter;
@@ -1587,15 +1628,33 @@ static int tail_enqueue(struct SLAEncoder* e, actx_t* a, uint32_t c, uint32_t lo
       if (a->ck[cc].bg_hi > a->ck[cc].bg_lo) { HIPCHK(hipStreamWaitEvent(ts, a->ev[(size_t)cc * EV_PER_CHUNK + EV_SOLVED], 0)); }
     }
   }
+  if (a->fast_rice) {
+    uint32_t cc;
+    for (cc = 0; cc < a->nchunks && hi > lo; cc++) {
+      if (a->ck[cc].bg_hi > a->ck[cc].bg_lo) { HIPCHK(hipStreamWaitEvent(e->stream_down, a->ev[(size_t)cc * EV_PER_CHUNK + EV_SOLVED], 0)); }
+    }
+    if (hi > lo) {
+      HIPCHK(hipMemcpyAsync((sla_hip_tail_job*)e->h_jobs.ptr + lo, (sla_hip_tail_job*)e->d_jobs.ptr + lo, sizeof(sla_hip_tail_job) * (hi - lo),
+                            hipMemcpyDeviceToHost, e->stream_down));
+    }
+    HIPCHK(hipEventRecord(ev[EV_JOBS_DOWN], e->stream_down));      /* the last thing on the download stream */
+  }
   HIPCHK(hipEventRecord(ev[EV_TAIL_S], ts));
   if (hi > lo) {
     sla_hip_tail_job* dj = (sla_hip_tail_job*)e->d_jobs.ptr + lo;
     sla_hip_launch_extra xt;
     memset(&xt, 0, sizeof(xt));
     xt.d_span = SPAN_SLOT(e, c, 3);
+    if (a->fast_rice) { xt.d_rice_init = (uint32_t*)e->d_rice.ptr + lo; }
     RCCHK(sla_hip_launch_tail_x(RES1(e), RES2(e), e->stride, dj, hi - lo, ntaps, lms, (uint64_t*)e->d_fold.ptr + lo, ts, &xt));
   }
   HIPCHK(hipEventRecord(ev[EV_TAIL_E], ts));
+  if (a->fast_rice) {
+    if (hi > lo) {
+      HIPCHK(hipMemcpyAsync((uint32_t*)e->h_rice.ptr + lo, (uint32_t*)e->d_rice.ptr + lo, sizeof(uint32_t) * (hi - lo), hipMemcpyDeviceToHost, ts));
+    }
+    return 0;
+  }
   if (hi > lo) {
     HIPCHK(hipStreamWaitEvent(e->stream_down, ev[EV_TAIL_E], 0));
     HIPCHK(hipMemcpyAsync((uint64_t*)e->h_fold.ptr + lo, (uint64_t*)e->d_fold.ptr + lo, sizeof(uint64_t) * (hi - lo), hipMemcpyDeviceToHost, e->stream_down));
@@ -1915,7 +1974,8 @@ static int tail_launch(struct SLAEncoder* e, actx_t* a, uint32_t c)
   return 0;
 }
 
-/* Rice initial parameters from the folded sums, once every tail kernel has landed */
+/* Rice initial parameters from the folded sums, once every tail kernel has landed: the routes with a tail per chunk, the
+ * host long-term solve and EncodeBlock's preset blocks (one tail on the device long-term route: rice_home_one) */
 static void finish_rice(struct SLAEncoder* e, const actx_t* a)
 {
   const uint32_t C = e->wave_format.num_channels;
@@ -1941,6 +2001,33 @@ static void finish_rice(struct SLAEncoder* e, const actx_t* a)
     e->bc[(size_t)a->job_blk[j] * C + a->job_ch[j]].rice_init = kept ? kept : 1u;
     }
   }
+}
+
+/* one tail for the file on the device long-term route (a->fast_rice): the two halves of finish_rice, each on the pool.
+ * jobs_home_one: pitch and taps of job j from the job table, which came home under the tail -- for blocks that stayed
+ * COMPRESS, so the RAW decision of every chunk has run.  rice_home_one: the parameter k_tailk stored for job j. */
+typedef struct { struct SLAEncoder* e; const actx_t* a; } home_ctx_t;
+
+static void jobs_home_one(void* vctx, uint32_t j)
+{
+  const home_ctx_t* c = (const home_ctx_t*)vctx;
+  struct SLAEncoder* e = c->e;
+  const uint32_t b = c->a->job_blk[j];
+  const sla_hip_tail_job* jb = (const sla_hip_tail_job*)e->h_jobs.ptr + j;
+  blkch_t* bc = &e->bc[(size_t)b * e->wave_format.num_channels + c->a->job_ch[j]];
+  uint32_t t;
+  if (e->blk[b].type != SLAI_BLK_COMPRESS) { return; }
+  bc->pitch = jb->pitch;
+  for (t = 0; t < SLAI_MAX_TAPS; t++) { bc->ltm_q[t] = jb->ltm_coef[t]; }
+}
+
+static void rice_home_one(void* vctx, uint32_t j)
+{
+  const home_ctx_t* c = (const home_ctx_t*)vctx;
+  struct SLAEncoder* e = c->e;
+  const uint32_t b = c->a->job_blk[j];
+  if (e->blk[b].type != SLAI_BLK_COMPRESS) { return; }
+  e->bc[(size_t)b * e->wave_format.num_channels + c->a->job_ch[j]].rice_init = ((const uint32_t*)e->h_rice.ptr)[j];
 }
 
 /* wait for k_expand's counts of one chunk: the kernel writes them into page-locked memory, the sequence word last, so the
@@ -2077,6 +2164,7 @@ static int run_pipeline(struct SLAEncoder* e, int preset_blocks)
   e->cert_now = (e->block_cert && !(e->fuse_lattice && e->encode_param.parcor_order <= 64) && !e->tune.lpc_blocks_chains
                  && sla_hip_search_exact_lags(e->encode_param.parcor_order) != 0);
   a.trace = trace; a.t_begin = t_begin;
+  a.fast_rice = (!preset_blocks && e->device_ltm && e->single_tail);
   if (!preset_blocks) {
     e->num_blocks = 0;
     if ((rc = pipeline_prepare(e, &a)) != 0) { actx_free(&a); return rc; }
@@ -2093,14 +2181,20 @@ static int run_pipeline(struct SLAEncoder* e, int preset_blocks)
   }
   {
     const size_t nslots = (size_t)a.blocks_bound * C + 1;
-    a.job_blk = (uint32_t*)malloc(sizeof(uint32_t) * nslots);
-    a.job_ch = (uint32_t*)malloc(sizeof(uint32_t) * nslots);
-    a.job_grp = (uint32_t*)malloc(sizeof(uint32_t) * nslots);
-    a.grp_of_slot = (uint32_t*)malloc(sizeof(uint32_t) * nslots);
-    a.parts = (uint32_t*)malloc(sizeof(uint32_t) * ((size_t)a.nsf + 1) * SLAI_MAX_NODES);
-    a.nparts = (uint32_t*)calloc((size_t)a.nsf + 1, sizeof(uint32_t));
-    a.status = (int*)calloc((size_t)a.nsf + 1, sizeof(int));
-    if (!a.job_blk || !a.job_ch || !a.job_grp || !a.grp_of_slot || !a.parts || !a.nparts || !a.status) { actx_free(&a); return SLA_APIRESULT_NG; }
+    const size_t nsf1 = (size_t)a.nsf + 1;
+    /* kept in the handle: a steady stream of files of one length allocates nothing here (4.3 MB per hour of stereo, above
+     * malloc's mmap threshold: mapped, faulted in and unmapped again per call) */
+    if (host_reserve(&e->w_job_blk, sizeof(uint32_t) * nslots) != 0 || host_reserve(&e->w_job_ch, sizeof(uint32_t) * nslots) != 0
+        || host_reserve(&e->w_job_grp, sizeof(uint32_t) * nslots) != 0 || host_reserve(&e->w_grp_of_slot, sizeof(uint32_t) * nslots) != 0
+        || host_reserve(&e->w_parts, sizeof(uint32_t) * nsf1 * SLAI_MAX_NODES) != 0
+        || host_reserve(&e->w_nparts, sizeof(uint32_t) * nsf1) != 0 || host_reserve(&e->w_status, sizeof(int) * nsf1) != 0) {
+      actx_free(&a); return SLA_APIRESULT_NG;
+    }
+    a.job_blk = (uint32_t*)e->w_job_blk.ptr; a.job_ch = (uint32_t*)e->w_job_ch.ptr; a.job_grp = (uint32_t*)e->w_job_grp.ptr;
+    a.grp_of_slot = (uint32_t*)e->w_grp_of_slot.ptr; a.parts = (uint32_t*)e->w_parts.ptr;
+    a.nparts = (uint32_t*)e->w_nparts.ptr; a.status = (int*)e->w_status.ptr;
+    memset(a.nparts, 0, sizeof(uint32_t) * nsf1);
+    memset(a.status, 0, sizeof(int) * nsf1);
   }
   TRACE("prepared (prepass + tables)", a.nsf);
   if (preset_blocks && (rc = pipeline_reserve(e, &a)) != 0) { actx_free(&a); return rc; }      /* (otherwise done while the prepass ran) */
@@ -2170,6 +2264,14 @@ static int run_pipeline(struct SLAEncoder* e, int preset_blocks)
     if (rc == 0 && hipEventSynchronize(pv[EV_LPC_DOWN]) != hipSuccess) { rc = SLA_APIRESULT_NG; }
     if (rc == 0) { rc = raw_phase(e, &a, a.nchunks - 1); }
     TRACE("RAW decided", a.nchunks - 1);
+    if (rc == 0 && a.fast_rice) {
+      /* every block is COMPRESS or RAW by now and the job table has come home (or does so under the tail): pitch + taps of
+       * the blocks that stayed COMPRESS, on the pool, while the device still works */
+      home_ctx_t hc;
+      hc.e = e; hc.a = &a;
+      if (hipEventSynchronize(pv[EV_JOBS_DOWN]) != hipSuccess) { rc = SLA_APIRESULT_NG; }
+      else { TRACE("job table home", a.njobs); parallel_for(e->pool, a.njobs, jobs_home_one, &hc); TRACE("pitch + taps stored", a.njobs); }
+    }
   } else if (rc == 0) {
     hipEvent_t* pv = a.ev + (size_t)(a.nchunks - 1) * EV_PER_CHUNK;
     if (hipEventSynchronize(pv[EV_LPC_DOWN]) != hipSuccess || (rc = raw_phase(e, &a, a.nchunks - 1)) != 0
@@ -2186,18 +2288,32 @@ static int run_pipeline(struct SLAEncoder* e, int preset_blocks)
     }
   }
   /* the rerun counter and the kernels' execution spans ride home behind the last k_tail (every other stream has been
-   * waited for by then): two synchronous copies here cost 70-90 us per step */
+   * waited for by then): two synchronous copies here cost 70-90 us per step.
+   * One tail on the device long-term route (a.fast_rice): they follow the Rice parameters on the tail's stream and ONE event
+   * behind them ends the call.  Nothing else is in flight then: the search stream ends in EV_SEARCH_DONE / EV_EXPANDED, the
+   * upload stream in EV_UPLOADED / EV_UPLOADED2 and the block streams in EV_SOLVED, all of which the tail's stream or the host
+   * has waited for, and the download stream's last entry is EV_JOBS_DOWN, which the host saw above.  Every other route, and
+   * every error, synchronises all five streams. */
   {
     unsigned long long* sp_host = (unsigned long long*)((uint8_t*)e->h_or + 64);
     int copied = 0;
+    if (trace && rc == 0) {
+      (void)hipEventSynchronize(a.ev[(size_t)(a.nchunks - 1) * EV_PER_CHUNK + EV_TAIL_E]);
+      TRACE("last tail kernel done", a.nchunks - 1);
+    }
     if (rc == 0) {
       hipStream_t last = (a.tail_stream != NULL) ? a.tail_stream : ((e->device_ltm && e->single_tail) ? e->stream2 : e->stream3);      /* the stream the last k_tail runs on */
       copied = (hipMemcpyAsync(sp_host, e->d_spans.ptr, sizeof(unsigned long long) * SPAN_AREA_ULLS, hipMemcpyDeviceToHost, last) == hipSuccess);
       if (!preset_blocks && hipMemcpyAsync(e->h_or + 2, (uint32_t*)e->d_or.ptr + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, last) != hipSuccess) { rc = SLA_APIRESULT_NG; }
+      if (rc == 0 && a.fast_rice) {
+        hipEvent_t done = a.ev[(size_t)(a.nchunks - 1) * EV_PER_CHUNK + EV_TAIL_DONE];
+        if (!copied || hipEventRecord(done, last) != hipSuccess || hipEventSynchronize(done) != hipSuccess) { rc = SLA_APIRESULT_NG; }
+      }
     }
-  if (hipStreamSynchronize(e->stream) != hipSuccess || hipStreamSynchronize(e->stream2) != hipSuccess
-      || hipStreamSynchronize(e->stream_up) != hipSuccess || hipStreamSynchronize(e->stream_down) != hipSuccess
-      || hipStreamSynchronize(e->stream3) != hipSuccess) { if (rc == 0) { rc = SLA_APIRESULT_NG; } }
+  if (!(rc == 0 && a.fast_rice)
+      && (hipStreamSynchronize(e->stream) != hipSuccess || hipStreamSynchronize(e->stream2) != hipSuccess
+          || hipStreamSynchronize(e->stream_up) != hipSuccess || hipStreamSynchronize(e->stream_down) != hipSuccess
+          || hipStreamSynchronize(e->stream3) != hipSuccess)) { if (rc == 0) { rc = SLA_APIRESULT_NG; } }
   if (rc == 0 && !preset_blocks) { e->fallback_groups = e->h_or[2]; }
   if (rc == 0 && e->cert_now) {
     const uint32_t* cnt = (const uint32_t*)e->h_cert_flag.ptr + (size_t)a.blocks_bound * C + 1;
@@ -2238,7 +2354,13 @@ static int run_pipeline(struct SLAEncoder* e, int preset_blocks)
   }
   TRACE("all streams idle", 0);
   if (rc == 0) {
-    finish_rice(e, &a);
+    if (a.fast_rice) {
+      home_ctx_t hc;
+      hc.e = e; hc.a = &a;
+      parallel_for(e->pool, a.njobs, rice_home_one, &hc);
+    } else {
+      finish_rice(e, &a);
+    }
     e->timing[0] = preset_blocks ? 0.f : ev_ms(e->ev[0], e->ev[1]);
     e->timing[5] = (float)t_host;
     for (c = 0; c < a.nchunks; c++) {
@@ -2254,7 +2376,9 @@ static int run_pipeline(struct SLAEncoder* e, int preset_blocks)
     e->timing[10] = (float)e->fallback_groups;
     e->timing[11] = (float)a.exact;
   }
+  TRACE("Rice parameters stored", 0);
   actx_free(&a);
+  TRACE("returning", 0);
   return rc;
 }
 
