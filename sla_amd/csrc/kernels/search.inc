@@ -777,7 +777,9 @@ __device__ __forceinline__ double plan_code_length(double sumsq, uint32_t n, uin
     // of eight factors >= 2^-53 cannot underflow
     double prod = 1.0;
     for (uint32_t ord = 1; ord <= order; ord++) {
-      prod *= 1.0 - parcor[ord] * parcor[ord];
+      const double f = 1.0 - parcor[ord] * parcor[ord];
+      if (f < 0.0) { sure = false; }     // |k| > 1: the host's single logarithm is NaN; two such factors would cancel in the product
+      prod *= f;
       if ((ord & 7u) == 0 || ord == order) { gain += log(prod) * l2e; prod = 1.0; }
     }
   }
@@ -808,7 +810,7 @@ void k_plan(const sla_hip_lpc_group* __restrict__ groups, uint32_t num_sf, uint3
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   for (uint32_t k = lane; k < g.cand_count; k += 64) {
     const sla_hip_lpc_cand cd = cands[g.cand_first + k];
-    const uint32_t i = cd.start / SLA_HIP_XTILE, j = (cd.start + cd.len + SLA_HIP_XTILE - 1) / SLA_HIP_XTILE;
+    const uint32_t i = cd.start / SLA_HIP_XTILE, j = (uint32_t)(((uint64_t)cd.start + cd.len + SLA_HIP_XTILE - 1) / SLA_HIP_XTILE);
     double wedge = 0.0, est = 0.0;
     for (uint32_t ch = 0; ch < nch; ch++) {
       const double* o = lpc_out + ((uint64_t)g.slot_first + (uint64_t)ch * g.cand_count + k) * O2;
@@ -822,7 +824,10 @@ void k_plan(const sla_hip_lpc_group* __restrict__ groups, uint32_t num_sf, uint3
     est += 50.0;                                   // SLAOPTIMALENCODEESTIMATOR_ESTIMATE_BLOCK_SIZE
     est += 300.0;                                  // ..._LONGPATH_PENALTY
     if (!(fabs(est) < PLAN_BIG / 2)) { sure = false; }          // NaN (also the "rerun as serial chains" flag), inf, absurd
-    if (i < nodes && j < nodes && j > i) { adj[i * nodes + j] = est; } else { sure = false; }
+    // an edge of the lattice starts on the tile grid and ends on it or at the window's end; anything else is not the reference's edge
+    const uint64_t end = (uint64_t)cd.start + cd.len;
+    const bool on_grid = (cd.start % SLA_HIP_XTILE == 0) && end <= window && (end % SLA_HIP_XTILE == 0 || end == window);
+    if (on_grid && i < nodes && j < nodes && j > i) { adj[i * nodes + j] = est; } else { sure = false; }
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
