@@ -281,7 +281,8 @@ int sla_hip_launch_lpc_rerun(const int32_t* d_pcm, uint64_t plane_stride, uint32
  * candidates are prefix differences of tile sums minus the pairs that straddle the candidate's end, and
  * the result is bit-identical to the serial order.  Groups: one per (super-frame, channel) listing ALL its
  * candidates; candidates must start on a tile boundary and end on one or at the end of the window.
- * d_tile_sums: num_groups * SLA_HIP_XTILES * 2 * sla_hip_search_exact_lags(order) doubles of scratch.
+ * d_tile_sums: num_groups * SLA_HIP_XTILES * 2 * sla_hip_search_exact_lags(order) doubles of scratch
+ * (per tile P[lags] | X[lags]; only the entries of the lags <= order are defined afterwards).
  * A group whose energy reaches the limit: with cert_safety <= 0 it gets NaN in r[0] of every candidate and the
  * caller reruns it through sla_hip_launch_lpc_rerun.  With cert_safety > 0 (the encoder passes 64) its candidates
  * keep their tile-sum results -- close to, but no longer bit-identical with, the reference's serially rounded sums --

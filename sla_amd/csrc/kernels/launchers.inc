@@ -197,14 +197,16 @@ extern "C" int sla_hip_launch_lpc_blocks_cert_x(const int32_t* d_pcm, uint64_t p
   unsigned long long* span = span_of(extra);
   const uint32_t* dyn = (extra != nullptr) ? extra->d_group_count : nullptr;      // num_groups is then an upper bound, the kernels read the number
   const dim3 grid((num_groups + 3) / 4), block(256);
-#define SLA_ACFB(NBB) do { \
-    if (mid_side) { hipLaunchKernelGGL((k_acf_blocks<NBB, true>), grid, block, 0, st, d_pcm, plane_stride, order, d_groups, num_groups, d_window_pool, d_out, d_rshift, span, d_fallback_count, dyn); } \
-    else { hipLaunchKernelGGL((k_acf_blocks<NBB, false>), grid, block, 0, st, d_pcm, plane_stride, order, d_groups, num_groups, d_window_pool, d_out, d_rshift, span, d_fallback_count, dyn); } } while (0)
+  // the lags that have a reader: order + 1.  The BASELINE orders 16 / 32 / 48 leave three lags of the last block of four without
+  // one and get kernels that do not compute them; every other order keeps the full blocks.
+#define SLA_ACFB(NBB, TOPP) do { \
+    if (mid_side) { hipLaunchKernelGGL((k_acf_blocks<NBB, TOPP, true>), grid, block, 0, st, d_pcm, plane_stride, order, d_groups, num_groups, d_window_pool, d_out, d_rshift, span, d_fallback_count, dyn); } \
+    else { hipLaunchKernelGGL((k_acf_blocks<NBB, TOPP, false>), grid, block, 0, st, d_pcm, plane_stride, order, d_groups, num_groups, d_window_pool, d_out, d_rshift, span, d_fallback_count, dyn); } } while (0)
   switch (lags) {
-    case 12: SLA_ACFB(3); break;
-    case 20: SLA_ACFB(5); break;
-    case 36: SLA_ACFB(9); break;
-    default: SLA_ACFB(13); break;
+    case 12: SLA_ACFB(3, 12); break;
+    case 20: if (order == 16) { SLA_ACFB(5, 17); } else { SLA_ACFB(5, 20); } break;
+    case 36: if (order == 32) { SLA_ACFB(9, 33); } else { SLA_ACFB(9, 36); } break;
+    default: if (order == 48) { SLA_ACFB(13, 49); } else { SLA_ACFB(13, 52); } break;
   }
 #undef SLA_ACFB
   e = hipGetLastError();
@@ -384,9 +386,12 @@ extern "C" int sla_hip_launch_search_exact_x(const int32_t* d_pcm, uint64_t plan
   const dim3 grid((waves + 3) / 4), block(256);
   switch (lags) {
     case 12: hipLaunchKernelGGL(k_acf_tiles<3>, grid, block, 0, st, d_pcm, plane_stride, mid_side, d_groups, num_groups, tiles, d_tile_sums, cl); break;
-    case 20: hipLaunchKernelGGL(k_acf_tiles_lds<5>, grid, block, 0, st, d_pcm, plane_stride, mid_side, d_groups, num_groups, tiles, d_tile_sums, cl); break;
-    case 36: hipLaunchKernelGGL(k_acf_tiles_lds<9>, grid, block, 0, st, d_pcm, plane_stride, mid_side, d_groups, num_groups, tiles, d_tile_sums, cl); break;
-    default: hipLaunchKernelGGL(k_acf_tiles_lds<13>, grid, block, 0, st, d_pcm, plane_stride, mid_side, d_groups, num_groups, tiles, d_tile_sums, cl); break;
+    // (lag slots that no order <= `order` reads stay unwritten: orders 16 / 32 / 48 skip the top three of 20 / 36 / 52)
+#define SLA_ACFT(NBB, TOPP) hipLaunchKernelGGL((k_acf_tiles_lds<NBB, TOPP>), grid, block, 0, st, d_pcm, plane_stride, mid_side, d_groups, num_groups, tiles, d_tile_sums, cl)
+    case 20: if (order == 16) { SLA_ACFT(5, 17); } else { SLA_ACFT(5, 20); } break;
+    case 36: if (order == 32) { SLA_ACFT(9, 33); } else { SLA_ACFT(9, 36); } break;
+    default: if (order == 48) { SLA_ACFT(13, 49); } else { SLA_ACFT(13, 52); } break;
+#undef SLA_ACFT
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { return hip_rc(e); }

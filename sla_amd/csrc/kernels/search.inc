@@ -95,8 +95,9 @@ __device__ __forceinline__ double wave_transpose_sum(double (&v)[M], uint32_t la
   transpose_step<M, 3>(v, lane); transpose_step<M, 4>(v, lane); transpose_step<M, 5>(v, lane);
   const uint32_t b0 = lane & 1u, b1 = (lane >> 1) & 1u, b2 = (lane >> 2) & 1u, b3 = (lane >> 3) & 1u, b4 = (lane >> 4) & 1u, b5 = (lane >> 5) & 1u;
   // step k keeps the half selected by its bit: the bits spell the index from the top (M/2, M/4, ..)
-  static_assert(M == 64 || M == 32 || M == 16 || M == 4, "wave_transpose_sum: 4, 16, 32 or 64 values per lane");
-  if (M == 64) { index = b0 * 32 + b1 * 16 + b3 * 8 + b2 * 4 + b4 * 2 + b5; writer = true; }
+  static_assert(M == 64 || M == 32 || M == 16 || M == 4 || M == 1, "wave_transpose_sum: 1, 4, 16, 32 or 64 values per lane");
+  if (M == 1) { index = 0; writer = (lane == 0u); }       // nothing to hand over: six plain exchange-and-adds, lane 0's total is the one a piece of 4 gives its value 0
+  else if (M == 64) { index = b0 * 32 + b1 * 16 + b3 * 8 + b2 * 4 + b4 * 2 + b5; writer = true; }
   else if (M == 32) { index = b0 * 16 + b1 * 8 + b3 * 4 + b2 * 2 + b4; writer = (b5 == 0); }
   else if (M == 16) { index = b0 * 8 + b1 * 4 + b3 * 2 + b2; writer = (b4 == 0 && b5 == 0); }
   else { index = b0 * 2 + b1; writer = (lane < 4u); }
@@ -118,11 +119,15 @@ __device__ __forceinline__ void acf_reduce_piece(const double (&acc)[LAGS], uint
   const double total = wave_transpose_sum<M>(tv, lane, index, writer);
   if (writer && FIRST + index < (uint32_t)LAGS && FIRST + index < limit) { dst[FIRST + index] = total; }
 }
-template <int LAGS>
-__device__ __forceinline__ void acf_reduce_store(const double (&acc)[LAGS], uint32_t lane, double* __restrict__ dst, uint32_t limit)
+// TOP <= LAGS accumulators are live (see acf_tile_fma): TOP = LAGS - 3 leaves one value behind the first piece, which is summed on
+// its own -- the same additions in the same order as its place in a piece of 4, so the total is the same double.
+template <int LAGS, int TOP>
+__device__ __forceinline__ void acf_reduce_store(const double (&acc)[TOP], uint32_t lane, double* __restrict__ dst, uint32_t limit)
 {
-  if constexpr (LAGS == 36) { acf_reduce_piece<32, 0>(acc, lane, dst, limit); acf_reduce_piece<4, 32>(acc, lane, dst, limit); }
-  else if constexpr (LAGS == 20) { acf_reduce_piece<16, 0>(acc, lane, dst, limit); acf_reduce_piece<4, 16>(acc, lane, dst, limit); }
+  if constexpr (LAGS == 36 && TOP == 36) { acf_reduce_piece<32, 0>(acc, lane, dst, limit); acf_reduce_piece<4, 32>(acc, lane, dst, limit); }
+  else if constexpr (LAGS == 36 && TOP == 33) { acf_reduce_piece<32, 0>(acc, lane, dst, limit); acf_reduce_piece<1, 32>(acc, lane, dst, limit); }
+  else if constexpr (LAGS == 20 && TOP == 20) { acf_reduce_piece<16, 0>(acc, lane, dst, limit); acf_reduce_piece<4, 16>(acc, lane, dst, limit); }
+  else if constexpr (LAGS == 20 && TOP == 17) { acf_reduce_piece<16, 0>(acc, lane, dst, limit); acf_reduce_piece<1, 16>(acc, lane, dst, limit); }
   else { acf_reduce_piece<(LAGS <= 16) ? 16 : (LAGS <= 32) ? 32 : 64, 0>(acc, lane, dst, limit); }
 }
 
@@ -150,25 +155,35 @@ __device__ __forceinline__ void load4_raw(const int32_t* __restrict__ plane, uin
 // ds_read_b128 per 16 FMAs.  (The first form of these kernels moved the partners from lane to lane by DPP: 16 moves per
 // 16 FMAs, the last NB lanes of a pass only supplied partners, and nothing was in flight while a pass computed.)
 // ---------------------------------------------------------------------------------------------
-template <int NB>
+// TOP: the number of lags that have a reader (lag < TOP <= 4 NB; the BASELINE orders 16 / 32 / 48 need 17 / 33 / 49 of the 20 / 36 / 52).
+// A lag at or above TOP is not computed, and a pair that only such lags touch is not read: with TOP = 4 NB - 3 the last block
+// is 4 FMAs on pairs the block before it has already loaded.  The live lags' chains are the ones of the full form.
+template <int NB, int TOP>
 __device__ __forceinline__ void acf_tile_fma(const double (&own)[4], const double2* __restrict__ E, const double2* __restrict__ O,
-                                             uint32_t lane, double (&acc)[NB * 4])
+                                             uint32_t lane, double (&acc)[TOP])
 {
+  static_assert(TOP > 4 * (NB - 1) && TOP <= 4 * NB, "acf_tile_fma: the last lag block holds the top lag");
   constexpr uint32_t HL = NB + 1;
   const double2* e = E + HL + lane;
   const double2* o = O + HL + lane;
-  // block k works on P[i] = x[4(t-k) - 3 + i], i = 0 .. 6: (E[-k-1].y, O[-k-1].x, O[-k-1].y, E[-k].x, E[-k].y, O[-k].x, O[-k].y)
+  // block k works on P[i] = x[4(t-k) - 3 + i], i = 0 .. 6: (E[-k-1].y, O[-k-1].x, O[-k-1].y, E[-k].x, E[-k].y, O[-k].x, O[-k].y);
+  // lag 4k + j reads P[3 - j ..]: the pair O[-k-1] from j = 1 on, E[-k-1] for j = 3 only
   double2 e0 = make_double2(own[0], own[1]), o0 = make_double2(own[2], own[3]);
-  double2 e1 = e[-1], o1 = o[-1];
+  double2 e1 = e0, o1 = o0;
+  if (TOP >= 4) { e1 = e[-1]; }
+  if (TOP >= 2) { o1 = o[-1]; }
 #pragma unroll
   for (int k = 0; k < NB; k++) {
     double2 e2 = e1, o2 = o1;
-    if (k + 1 < NB) { e2 = e[-k - 2]; o2 = o[-k - 2]; }                    // the next block's new pairs travel under this block's FMAs
+    if (4 * (k + 1) + 3 < TOP) { e2 = e[-k - 2]; }                          // the next block's new pairs travel under this block's FMAs
+    if (4 * (k + 1) + 1 < TOP) { o2 = o[-k - 2]; }
     const double P[7] = {e1.y, o1.x, o1.y, e0.x, e0.y, o0.x, o0.y};
 #pragma unroll
     for (int j = 0; j < 4; j++) {
+      if (4 * k + j < TOP) {
 #pragma unroll
-      for (int q = 0; q < 4; q++) { acc[4 * k + j] = __builtin_fma(own[q], P[q - j + 3], acc[4 * k + j]); }
+        for (int q = 0; q < 4; q++) { acc[4 * k + j] = __builtin_fma(own[q], P[q - j + 3], acc[4 * k + j]); }
+      }
     }
     e0 = e1; o0 = o1; e1 = e2; o1 = o2;
   }
@@ -286,6 +301,14 @@ void k_acf_tiles(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ms,
   }
 }
 
+typedef double f64x2_u __attribute__((ext_vector_type(2), aligned(8)));
+
+// A sample in the analysis' unit: raw * 2^-31; mid/side: l = a * 2^-31, r = b * 2^-31, mid = (l + r) / 2, side = l - r
+// (src/SLAUtility.c:370-412).  Every step of that is exact in a double -- 32-bit integers, their 33-bit sum or difference, powers
+// of two -- so the scale is applied once, to the sum: the same doubles from four operations instead of six.
+__device__ __forceinline__ double mid_f64(int32_t a, int32_t b) { return ((double)a + (double)b) * 2.3283064365386962890625e-10; }       // 2^-32
+__device__ __forceinline__ double side_f64(int32_t a, int32_t b) { return ((double)a - (double)b) * 4.656612873077392578125e-10; }      // 2^-31
+
 // ---------------------------------------------------------------------------------------------
 // k_acf_tiles_lds: the tile sums of k_acf_tiles with the partners from LDS (acf_tile_fma) instead of DPP moves -- for 52
 // lags, where the moves are most of the instructions (C5: 489 -> see DESIGN us per launch; at 36 lags and below the DPP
@@ -294,10 +317,10 @@ void k_acf_tiles(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ms,
 // coordinates u = (t1 + 4 HL - 1) - m the partner m + lag is u - lag, the first 4 HL reversed samples -- the ones just
 // above the tile's end -- are the front nobody owns, and the tile's own samples follow as up to four sub-tiles of 256.
 // Samples below t0 count as zero (they are another tile's), samples from the window's end on are zero anyway.  X_t as
-// in k_acf_tiles, from an edge buffer.  (The first LDS port of round 3 kept the forward walk and re-defined P and X by
+// in k_acf_tiles, from an edge buffer (filled from the values the wave stages anyway).  TOP: see acf_tile_fma.  (The first LDS port of round 3 kept the forward walk and re-defined P and X by
 // the position of a pair's LATER sample; it was three times slower and was dropped.)
 // ---------------------------------------------------------------------------------------------
-template <int NB>
+template <int NB, int TOP>
 __global__ __launch_bounds__(256, (NB >= 13) ? 3 : 1)
 void k_acf_tiles_lds(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ms,
                      const sla_hip_lpc_group* __restrict__ groups, uint32_t num_groups, uint32_t tiles_per_group,
@@ -307,7 +330,8 @@ void k_acf_tiles_lds(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t 
   __shared__ double2 s_e[4][2][64 + HL], s_o[4][2][64 + HL];
   __shared__ double s_edge[4][2 * LAGS];       // x[t1-LAGS .. t1+LAGS) of each wave's tile end t1 (zero below t0)
   clear_words(cl);
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // the same in the wave's 64 lanes: the group, the tile and their bounds live in scalar registers
   const uint32_t w = blockIdx.x * 4 + wv;
   const uint32_t gi = w / tiles_per_group, tile = w - gi * tiles_per_group;
   if (gi >= num_groups) { return; }
@@ -319,11 +343,25 @@ void k_acf_tiles_lds(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t 
   const int32_t* p0 = pcm + (ms ? 0 : (uint64_t)g.channel * stride) + g.pcm_off;
   const int32_t* p1 = pcm + stride + g.pcm_off;
   auto value = [&](int32_t a, int32_t b) -> double {
-    if (ms) { const double l = (double)a * scale, r = (double)b * scale; return (g.channel == 0) ? ((l + r) / 2) : (l - r); }
+    if (ms) { return (g.channel == 0) ? mid_f64(a, b) : side_f64(a, b); }
     return (double)a * scale;
   };
-  // four consecutive samples m0 .. m0+3 (m0 may be negative), zero outside [lo, N)
   struct raw4 { int32_t a[4]; int32_t b[4]; };
+  // a lane's four samples, reversed (the highest first).  Which of the three forms applies is the same for the whole wave:
+  // one scalar branch per sub-tile, not both forms and a select per sample.
+  auto values4 = [&](const raw4& c, double (&v)[4]) {
+    if (!ms) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) { v[q] = (double)c.a[3 - q] * scale; }
+    } else if (g.channel == 0) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) { v[q] = mid_f64(c.a[3 - q], c.b[3 - q]); }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; q++) { v[q] = side_f64(c.a[3 - q], c.b[3 - q]); }
+    }
+  };
+  // four consecutive samples m0 .. m0+3 (m0 may be negative), zero outside [lo, N)
   auto fetch = [&](int64_t m0, uint32_t lo, raw4& r) {
 #pragma unroll
     for (int q = 0; q < 4; q++) { r.a[q] = 0; r.b[q] = 0; }
@@ -339,56 +377,92 @@ void k_acf_tiles_lds(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t 
       }
     }
   };
-  // edge buffer for X
-  for (uint32_t i = lane; i < 2 * LAGS; i += 64) {
-    const int64_t m = (int64_t)t1 - (int64_t)LAGS + (int64_t)i;
-    double v = 0.0;
-    if (m >= (int64_t)t0 && m < (int64_t)N) { v = value(p0[m], ms ? p1[m] : 0); }
-    s_edge[wv][i] = v;
-  }
-  // front: the 4 HL samples from t1 on, reversed; lane i < HL holds reversed positions 4 i .. 4 i + 3 = x[t1 + 4 HL - 1 - 4 i] downwards
+  // the same for a sub-tile that lies wholly inside [t0, t1): no guards (any alignment: i32x4_u is aligned(4))
+  auto fetch_inside = [&](int64_t m0, raw4& r) {
+    const i32x4_u t = *(const i32x4_u*)(p0 + m0);
+    r.a[0] = t.x; r.a[1] = t.y; r.a[2] = t.z; r.a[3] = t.w;
+#pragma unroll
+    for (int q = 0; q < 4; q++) { r.b[q] = 0; }
+    if (ms) { const i32x4_u u = *(const i32x4_u*)(p1 + m0); r.b[0] = u.x; r.b[1] = u.y; r.b[2] = u.z; r.b[3] = u.w; }
+  };
+  // sub-tile `sub` is [t1 - 256 (sub + 1), t1 - 256 sub): inside the tile when the tile has that many samples -- all four of a
+  // whole tile, all but the lowest of a window's last one.  One scalar compare per sub-tile instead of 64-bit compares per lane.
+  const uint32_t span = t1 - t0;
+  auto fetch_sub = [&](uint32_t sub, raw4& r) {
+    const int64_t m0 = (int64_t)t1 - (int64_t)ACF_TILE * (sub + 1) + 4 * (int64_t)(63 - lane);
+    if ((sub + 1) * ACF_TILE <= span) { fetch_inside(m0, r); } else { fetch(m0, t0, r); }
+  };
+  // front: the 4 HL samples from t1 on, reversed; lane i < HL holds reversed positions 4 i .. 4 i + 3 = x[t1 + 4 HL - 1 - 4 i] downwards.
+  // The edge buffer for X takes its upper half x[t1 .. t1 + LAGS) from them (lane 0's four lie beyond it) and its lower half from
+  // the first sub-tile's own values below: nothing is loaded or converted a second time.
   if (lane < HL) {
     raw4 f;
     fetch((int64_t)t1 + 4 * (int64_t)HL - 4 - 4 * (int64_t)lane, t0, f);
-    s_e[wv][0][lane] = make_double2(value(f.a[3], f.b[3]), value(f.a[2], f.b[2]));
-    s_o[wv][0][lane] = make_double2(value(f.a[1], f.b[1]), value(f.a[0], f.b[0]));
+    const double f0 = value(f.a[0], f.b[0]), f1 = value(f.a[1], f.b[1]), f2 = value(f.a[2], f.b[2]), f3 = value(f.a[3], f.b[3]);
+    s_e[wv][0][lane] = make_double2(f3, f2);
+    s_o[wv][0][lane] = make_double2(f1, f0);
+    if (lane >= 1) {
+      double* up = s_edge[wv] + LAGS + 4 * (HL - 1 - lane);
+      up[0] = f0; up[1] = f1; up[2] = f2; up[3] = f3;
+    }
   }
-  double acc[LAGS];
+  double acc[TOP];
 #pragma unroll
-  for (int i = 0; i < (int)LAGS; i++) { acc[i] = 0.0; }
-  const uint32_t nsub = (t1 - t0 + ACF_TILE - 1) / ACF_TILE;
+  for (int i = 0; i < TOP; i++) { acc[i] = 0.0; }
+  const uint32_t nsub = (span + ACF_TILE - 1) / ACF_TILE;
   raw4 nxt;
-  fetch((int64_t)t1 - (int64_t)ACF_TILE + 4 * (int64_t)(63 - lane), t0, nxt);
-  uint32_t buf = 0;
-  for (uint32_t sub = 0; sub < nsub; sub++, buf ^= 1u) {
+  fetch_sub(0, nxt);
+  double2* E = s_e[wv][0], * O = s_o[wv][0], * En = s_e[wv][1], * On = s_o[wv][1];      // this sub-tile's buffers and the next one's
+  for (uint32_t sub = 0; sub < nsub; sub++) {
     const raw4 cur = nxt;
-    if (sub + 1 < nsub) { fetch((int64_t)t1 - (int64_t)ACF_TILE * (sub + 2) + 4 * (int64_t)(63 - lane), t0, nxt); }
+    if (sub + 1 < nsub) { fetch_sub(sub + 1, nxt); }
     double own[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) { own[q] = value(cur.a[3 - q], cur.b[3 - q]); }      // reversed: the lane's highest sample first
-    double2* E = s_e[wv][buf];
-    double2* O = s_o[wv][buf];
+    values4(cur, own);
+    if (sub == 0 && lane < (uint32_t)NB) {     // x[t1 - LAGS .. t1): the top of the tile (zero below t0, as fetched)
+      double* low = s_edge[wv] + LAGS - 4 - 4 * lane;
+      low[0] = own[3]; low[1] = own[2]; low[2] = own[1]; low[3] = own[0];
+    }
     E[HL + lane] = make_double2(own[0], own[1]);
     O[HL + lane] = make_double2(own[2], own[3]);
     if (lane >= 64 - HL) {                     // this sub-tile's last HL pairs are what the next one finds in front of it
-      s_e[wv][buf ^ 1u][lane - (64 - HL)] = make_double2(own[0], own[1]);
-      s_o[wv][buf ^ 1u][lane - (64 - HL)] = make_double2(own[2], own[3]);
+      En[lane - (64 - HL)] = make_double2(own[0], own[1]);
+      On[lane - (64 - HL)] = make_double2(own[2], own[3]);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    acf_tile_fma<NB>(own, E, O, lane, acc);
+    acf_tile_fma<NB, TOP>(own, E, O, lane, acc);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    { double2* t = E; E = En; En = t; t = O; O = On; On = t; }
   }
+  // lag slots >= TOP of P and X are not written: k_search_finish and k_search_cert use lag <= order < TOP
   double* dst = tile_sums + ((uint64_t)gi * SLA_HIP_XTILES + tile) * (2 * LAGS);
-  acf_reduce_store<(int)LAGS>(acc, lane, dst, LAGS);
-  // pairs that straddle t1: lane = lag.  Every lane runs all LAGS - 1 terms and keeps the first `lane` of them (the same
-  // sums in the same order as a loop to `lane`, whose trips -- two dependent LDS reads and a multiply-add each, ~130 cycles
-  // of latency, 35 of them -- held a wave's slot for as long as the tile's multiply-adds took to issue)
-  if (lane < LAGS) {
+  acf_reduce_store<(int)LAGS, TOP>(acc, lane, dst, TOP);
+  // pairs that straddle t1: X[lag] = sum over j < lag of x[t1 - lag + j] x[t1 + j], a chain of dependent multiply-adds.
+  if constexpr (TOP == 17 || TOP == 33) {
+    // W = TOP - 1 lags (lag 0 has no such pair) times NP = 64 / W parts of the terms: all 64 lanes work, the chain is W / NP
+    // long instead of W, and the parts meet in log2(NP) cross-lane additions.  Exact windows stay exact in any order; for
+    // the others a sum takes at most W / NP + 2 roundings instead of W, inside the certificates' 48.
+    constexpr uint32_t W = TOP - 1, NP = 64 / W, CH = W / NP;
+    const uint32_t lag = (lane & (W - 1)) + 1, part = lane / W;
+    const double* e = s_edge[wv] + LAGS + part * CH;
+    double x = 0.0;
+#pragma unroll
+    for (uint32_t j = 0; j < CH; j++) {
+      const double t = __builtin_fma(e[(int)j - (int)lag], e[j], x);      // (terms from `lag` on read on inside the buffer; not kept)
+      x = (part * CH + j < lag) ? t : x;
+    }
+    if (NP == 4) { x += swz_f64_xor16(x); }
+    x += shfl_f64_xor32(x);
+    if (lane < W) { dst[LAGS + lag] = x; }
+    if (lane == W) { dst[LAGS] = 0.0; }
+  } else if (lane < (uint32_t)TOP) {
+    // lane = lag.  Every lane runs all TOP - 1 terms and keeps the first `lane` of them (the same sums in the same order as a
+    // loop to `lane`, whose trips -- two dependent LDS reads and a multiply-add each, ~130 cycles of latency, 35 of them --
+    // held a wave's slot for as long as the tile's multiply-adds took to issue)
     double x = 0.0;
     const double* e = s_edge[wv];
     if constexpr (LAGS <= 36) {
 #pragma unroll
-      for (uint32_t j = 0; j + 1 < LAGS; j++) {
+      for (uint32_t j = 0; j + 1 < (uint32_t)TOP; j++) {
         const double t = __builtin_fma(e[LAGS - lane + j], e[LAGS + j], x);      // (j >= lane reads on inside the buffer; not kept)
         x = (j < lane) ? t : x;
       }
@@ -417,7 +491,7 @@ __device__ __forceinline__ double shr1_f64(double v, double first)       // lane
   return __hiloint2double(hi, lo);
 }
 
-template <int NB, bool MS>
+template <int NB, int TOP, bool MS>
 __global__ __launch_bounds__(256, (NB >= 13) ? 3 : 1)      // 52 lags: 104 accumulator registers -- keep three waves per SIMD
 void k_acf_blocks(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t order,
                   const sla_hip_lpc_group* __restrict__ groups, uint32_t num_groups,
@@ -429,7 +503,11 @@ void k_acf_blocks(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ord
   if (dyn != nullptr) { num_groups = (dyn[2] != 0u) ? 0u : (dyn[1] - dyn[3]); }      // (see k_blocks_finish)
   span_begin(exec_span);
   if (blockIdx.x == 0 && threadIdx.x == 0 && zero_word != nullptr) { *zero_word = 0u; }      // the fallback count k_blocks_finish appends to
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t lane = threadIdx.x & 63;
+  // the wave's number is the same in its 64 lanes: told so, the compiler keeps the group and its bounds in scalar registers and
+  // branches on them.  Not at 52 lags, where every register move counts: C5-240 s block stage 0.70 ms without, 0.79 with
+  // (0.78 before either; profiles/r7_acf_lags_ab.txt)
+  const uint32_t wv = (NB < 13) ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (threadIdx.x >> 6);
   const uint32_t gi = blockIdx.x * 4 + wv;
   if (gi >= num_groups) { span_end(exec_span); return; }
   const sla_hip_lpc_group g = groups[gi];
@@ -446,60 +524,77 @@ void k_acf_blocks(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ord
 #pragma unroll
     for (int q = 0; q < 4; q++) { r.w[q] = (idx + q < N) ? win[idx + q] : 0.0; }
   };
+  // the same for a tile that lies wholly inside the block: no guards, the window as two 16-byte loads (any alignment:
+  // i32x4_u is aligned(4), f64x2_u aligned(8))
+  auto fetch_inside = [&](uint32_t idx, raw4& r) {
+    const i32x4_u t = *(const i32x4_u*)(p0 + g.pcm_off + idx);
+    r.a[0] = t.x; r.a[1] = t.y; r.a[2] = t.z; r.a[3] = t.w;
+    if (MS) { const i32x4_u u = *(const i32x4_u*)(p1 + g.pcm_off + idx); r.b[0] = u.x; r.b[1] = u.y; r.b[2] = u.z; r.b[3] = u.w; }
+    const f64x2_u w0 = *(const f64x2_u*)(win + idx), w1 = *(const f64x2_u*)(win + idx + 2);
+    r.w[0] = w0.x; r.w[1] = w0.y; r.w[2] = w1.x; r.w[3] = w1.y;
+  };
 
-  double acc[LAGS];
+  double acc[TOP];
 #pragma unroll
-  for (int i = 0; i < (int)LAGS; i++) { acc[i] = 0.0; }
+  for (int i = 0; i < TOP; i++) { acc[i] = 0.0; }
   uint32_t maxabs = 0;
   double carry = 0.0;                          // windowed sample right before the tile (0 before the block: src/SLAPredictor.c:1729-1738)
   if (lane < HL) { s_e[wv][0][lane] = make_double2(0.0, 0.0); s_o[wv][0][lane] = make_double2(0.0, 0.0); }      // nothing in front of the block
   raw4 nxt;
-  fetch(4 * lane, nxt);
-  uint32_t buf = 0;
-  for (uint32_t s0 = 0; s0 < N; s0 += ACF_TILE, buf ^= 1u) {
+  if (ACF_TILE <= N) { fetch_inside(4 * lane, nxt); } else { fetch(4 * lane, nxt); }      // (one scalar compare per tile: N is the wave's)
+  double2* E = s_e[wv][0], * O = s_o[wv][0], * En = s_e[wv][1], * On = s_o[wv][1];      // this tile's buffers and the next one's
+  for (uint32_t s0 = 0; s0 < N; s0 += ACF_TILE) {
     const uint32_t idx = s0 + 4 * lane;
     const raw4 cur = nxt;
-    if (s0 + ACF_TILE < N) { fetch(idx + ACF_TILE, nxt); }      // the next tile's samples travel while this one is multiplied
+    if (s0 + 2 * ACF_TILE <= N) { fetch_inside(idx + ACF_TILE, nxt); }      // the next tile's samples travel while this one is multiplied
+    else if (s0 + ACF_TILE < N) { fetch(idx + ACF_TILE, nxt); }
     double y[4], own[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      double v;
-      int32_t iv;
-      if (MS) {
-        const double l = (double)cur.a[q] * scale, r = (double)cur.b[q] * scale;
-        v = (g.channel == 0) ? ((l + r) / 2) : (l - r);
-        const int32_t li = cur.a[q] >> g.int_shift, ri = cur.b[q] >> g.int_shift;
-        iv = (g.channel == 0) ? ((int32_t)((uint32_t)li + (uint32_t)ri) >> 1) : (int32_t)((uint32_t)li - (uint32_t)ri);
-      } else {
-        v = (double)cur.a[q] * scale;
-        iv = cur.a[q] >> g.int_shift;
-      }
+    // (mid, side or plain: the same for the whole wave -- one scalar branch per tile, not both forms and a select per sample)
+    auto staged = [&](int q, double v, int32_t iv) {
       y[q] = v * cur.w[q];
       const uint32_t a = (iv > 0) ? (uint32_t)iv : (0u - (uint32_t)iv);
       maxabs = (a > maxabs) ? a : maxabs;        // (samples past the block are zero)
+    };
+    if (!MS) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) { staged(q, (double)cur.a[q] * scale, cur.a[q] >> g.int_shift); }
+    } else if (g.channel == 0) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int32_t li = cur.a[q] >> g.int_shift, ri = cur.b[q] >> g.int_shift;
+        staged(q, mid_f64(cur.a[q], cur.b[q]), (int32_t)((uint32_t)li + (uint32_t)ri) >> 1);
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int32_t li = cur.a[q] >> g.int_shift, ri = cur.b[q] >> g.int_shift;
+        staged(q, side_f64(cur.a[q], cur.b[q]), (int32_t)((uint32_t)li - (uint32_t)ri));
+      }
     }
     const double below = shr1_f64(y[3], carry);
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       const double pv = (q == 0) ? below : y[q - 1];
-      const double x = y[q] - pv * 0.96875;
-      own[q] = (idx + q < N) ? x : 0.0;
+      own[q] = y[q] - pv * 0.96875;
+    }
+    if (s0 + ACF_TILE > N) {                   // the block's last tile: nothing past its end
+#pragma unroll
+      for (int q = 0; q < 4; q++) { own[q] = (idx + q < N) ? own[q] : 0.0; }
     }
     carry = readlane_f64(y[3], 63);
-    double2* E = s_e[wv][buf];
-    double2* O = s_o[wv][buf];
     E[HL + lane] = make_double2(own[0], own[1]);
     O[HL + lane] = make_double2(own[2], own[3]);
     if (lane >= 64 - HL) {                     // this tile's last HL pairs are what the next tile finds in front of it
-      s_e[wv][buf ^ 1u][lane - (64 - HL)] = make_double2(own[0], own[1]);
-      s_o[wv][buf ^ 1u][lane - (64 - HL)] = make_double2(own[2], own[3]);
+      En[lane - (64 - HL)] = make_double2(own[0], own[1]);
+      On[lane - (64 - HL)] = make_double2(own[2], own[3]);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    acf_tile_fma<NB>(own, E, O, lane, acc);
+    acf_tile_fma<NB, TOP>(own, E, O, lane, acc);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    { double2* t = E; E = En; En = t; t = O; O = On; On = t; }
   }
   double* o = out + (uint64_t)g.slot_first * (order + 2);
-  acf_reduce_store<(int)LAGS>(acc, lane, o + 1, order + 1);
+  acf_reduce_store<(int)LAGS, TOP>(acc, lane, o + 1, order + 1);      // (order + 1 <= TOP: the launcher's choice)
   maxabs = umax_wave(maxabs);
   if (lane == 0) {
     const uint32_t l2c = (maxabs > 1) ? (32u - (uint32_t)__builtin_clz(maxabs - 1u)) : 0u;    // src/SLAUtility.c:677-696
