@@ -142,6 +142,9 @@ typedef struct sla_hip_tuning {
   uint32_t cert_audit;          /* N > 0: every N-th (block, channel) pair that sla_hip_launch_lpc_blocks_cert CERTIFIES is analysed by the
                                    exact kernels as well, which compare codes, lattice coefficients and the RAW side with what the certified
                                    run stored: d_cert_flag 4 = audited and equal, 5 = the certificate was wrong (the encoder fails the call) */
+  uint32_t ltm_int;             /* 1: sla_hip_launch_ltm_cert_x takes its autocorrelation from exact integer sums on the int8 matrix pipe
+                                   (k_ltm_acf_int) instead of the FMA transform (k_ltm_acf_fast); the encoder's default.  (The field fills
+                                   what was the struct's tail padding: its size is unchanged.) */
 } sla_hip_tuning;
 void sla_hip_use_tuning(const sla_hip_tuning* tuning);
 
@@ -455,6 +458,14 @@ int sla_hip_launch_ltm_cert_x(const int32_t* d_residual, uint64_t plane_stride, 
                               double* d_acf_records, double* d_eps, uint32_t longterm_order, double safety,
                               sla_hip_tail_job* d_jobs, uint32_t* d_list, uint32_t* d_counters,
                               sla_hip_stream_t stream, const sla_hip_launch_extra* extra);
+/* With tuning ltm_int = 1 the autocorrelation of the certified route comes from k_ltm_acf_int instead: every sample split
+ * into balanced base-256 digits, the lags 0 .. 263 as int8 matrix products (v_mfma_i32_16x16x64_i8) summed exactly in
+ * integers and rounded to double once -- its own error is at most half an ulp, eps is unchanged (it still covers the
+ * reference's error).  sla_hip_launch_ltm_acf_int runs that kernel without the pick and stores the sums themselves:
+ * d_out[job * 264 + k] = 2^-62 * fft_size / 2 * sum_m x[m] x[m + k], k = 0 .. 263 (exact where |sum| < 2^53). */
+#define SLA_HIP_ACF_INT_LAGS 264u
+int sla_hip_launch_ltm_acf_int(const int32_t* d_residual, uint64_t plane_stride, const sla_hip_acf_job* d_acf_jobs,
+                               uint32_t num_jobs, uint32_t fft_size, double* d_out, sla_hip_stream_t stream);
 
 /* Long-term filter + sign-log LMS + folded-residual sum, one lane per job.
  * d_res_in/d_res_out are channel planes with the same stride as the PCM. */
@@ -878,6 +889,9 @@ int sla_hip_get_trace(struct SLAEncoder* encoder, sla_hip_trace* trace);
  * reading the number from the device), "one_stream" (1: a one-chunk file keeps search, block stage and tail on one stream;
  * measured slower, default 0), "upload24" (1 = default: pageable input of 17..24 significant bits crosses the bus as three
  * bytes per sample; DESIGN section 7 has the A/B).
+ * "ltm_int" (1 = default: the certified long-term stage takes its autocorrelation from exact integer sums on the int8
+ * matrix pipe, k_ltm_acf_int; 0: from the FMA transform k_ltm_acf_fast.  Same bytes either way; every route that reaches
+ * sla_hip_launch_ltm_cert_x honours it, worker lanes included).
  * "verify" (0 = default, 1): every call that packs on the device (sla_hip_pack_device, SLAEncoder_EncodeWhole plain and
  * streamed, sla_hip_encode_batch, sla_hip_encode_batch_device) decodes the finished block bytes on the device with the
  * decoder's kernels, while they cross the bus, and compares the result with the source planes; a file whose bytes do not

@@ -741,13 +741,29 @@ extern "C" int sla_hip_launch_ltm_solve(const double* d_acf_records, const sla_h
   return hip_rc(hipGetLastError());
 }
 
-// The certified long-term stage (k_ltm_acf_fast -> k_ltm_solve_cert -> exact kernels over the fallback list), all on one
+// The certified long-term stage (k_ltm_acf_int or k_ltm_acf_fast -> k_ltm_solve_cert -> exact kernels over the fallback list), all on one
 // stream.  The list kernels run on a fixed small grid and read the list's length on the device: an empty list costs two
 // near-empty launches.  d_counters (4 words, zero before the call): list entries, uncertified jobs, audit ok, audit bad.
 #define LIST_LTM_GRID 64u
 extern "C" int sla_hip_ltm_cert_supported(uint32_t fft_size)
 {
   return (fft_size == 4096 || fft_size == 8192 || fft_size == 16384 || fft_size == 32768) ? 1 : 0;
+}
+
+extern "C" int sla_hip_launch_ltm_acf_int(const int32_t* d_residual, uint64_t plane_stride, const sla_hip_acf_job* d_acf_jobs,
+                                          uint32_t num_jobs, uint32_t fft_size, double* d_out, sla_hip_stream_t stream)
+{
+  if (d_residual == nullptr || d_acf_jobs == nullptr || d_out == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (!sla_hip_ltm_cert_supported(fft_size)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_jobs == 0) { return 0; }
+  uint32_t log2F = 0;
+  while ((1u << log2F) < fft_size) { log2F++; }
+  const size_t lds = ACF_INT_LDS(fft_size / 2u);
+  const hipError_t e = ensure_dynamic_lds((const void*)k_ltm_acf_int<true>, lds);
+  if (e != hipSuccess) { return hip_rc(e); }
+  hipLaunchKernelGGL((k_ltm_acf_int<true>), dim3(num_jobs), dim3(ACF_INT_THREADS), lds, (hipStream_t)stream, d_residual, plane_stride, d_acf_jobs,
+                     num_jobs, log2F, d_out, (double*)nullptr, 0.0, (unsigned long long*)nullptr);
+  return hip_rc(hipGetLastError());
 }
 
 extern "C" int sla_hip_launch_ltm_cert_x(const int32_t* d_residual, uint64_t plane_stride, const sla_hip_acf_job* d_acf_jobs,
@@ -776,7 +792,14 @@ extern "C" int sla_hip_launch_ltm_cert_x(const int32_t* d_residual, uint64_t pla
     e = ensure_dynamic_lds((const void*)k_ltm_acf_fast<LTOP, TT>, lds); \
     if (e != hipSuccess) { return hip_rc(e); } \
     hipLaunchKernelGGL((k_ltm_acf_fast<LTOP, TT>), dim3(num_jobs), dim3(TT), lds, st, d_residual, plane_stride, d_acf_jobs, num_jobs, d_fast_twiddles, d_acf_records, d_eps, eps_rel, span); } while (0)
-  if (log2F == 12) { SLA_ACFF(10, 128); }
+  if (tuning().ltm_int) {
+    // the same record from exact integer sums on the int8 matrix pipe (k_ltm_acf_int): digit planes of a whole block in LDS
+    const size_t lds = ACF_INT_LDS(fft_size / 2u);
+    e = ensure_dynamic_lds((const void*)k_ltm_acf_int<false>, lds);
+    if (e != hipSuccess) { return hip_rc(e); }
+    hipLaunchKernelGGL((k_ltm_acf_int<false>), dim3(num_jobs), dim3(ACF_INT_THREADS), lds, st, d_residual, plane_stride, d_acf_jobs, num_jobs, log2F, d_acf_records, d_eps, eps_rel, span);
+  }
+  else if (log2F == 12) { SLA_ACFF(10, 128); }
   else if (log2F == 13) { SLA_ACFF(11, 256); }
   else if (log2F == 14) { SLA_ACFF(12, 512); }
   else { SLA_ACFF(13, 1024); }

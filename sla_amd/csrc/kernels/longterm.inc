@@ -863,6 +863,257 @@ void k_ltm_acf_fast(const int32_t* __restrict__ res, uint64_t stride, const sla_
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_ltm_acf_int: the same stage without a transform.  The record reads the lags 0 .. 263 of an int32 block only, and with
+// every sample split into balanced base-256 digits, x = sum_a d_a 2^(8a), d_a in [-128, 127], the direct sum becomes a
+// handful of int8 matrix products (v_mfma_i32_16x16x64_i8), exact in i32:
+//   sample m = 16 kappa + i;  A_a[i][kappa] = d_a(x[16 kappa + i]);  B_b,s[kappa][c] = d_b(x[16 (kappa + s) + c]), s = 0 .. 17
+//   C[i][c] = sum_kappa A_a B_b,s adds 2^(8(a+b)) C[i][c] to the lag k = 16 s + c - i        (s = 0: c >= i only)
+// Every (m, k) with 0 <= k <= 263 occurs once.  All digit pairs of one weight w = a + b share an accumulator.
+//   * digit count D = 1 .. 5 (workgroup-uniform): the first D after which no sample leaves a remainder; digits beyond D are zero
+//   * LDS: plane a, row i, byte kappa (row stride RS = 64 NT + 48 bytes, RS / 16 odd; zeros behind the block).  Lane
+//     (r, h) = (lane & 15, lane >> 4) holds bytes kappa = 64 T + 16 h .. + 15 of row r as its A fragment and the same bytes
+//     from kappa + s on as its B fragment of shift s: A and B pair the same kappa in the same (h, byte), so which k the
+//     instruction gives a byte does not matter.  The B fragments of a wave's shifts come out of one window of dwords by
+//     v_alignbyte_b32.
+//   * the four waves deal the 18 shifts out 5 / 5 / 4 / 4 (rotated by the job, so that no SIMD always gets five)
+//   * headroom: |cell| <= pairs (<= 5) * 1024 kappa * 2^14 < 2^27; a lag's sum of one weight <= 5 * 16384 * 2^14 < 2^31:
+//     the diagonals are added up in i32 (LDS atomics after a DPP sum over the four rows a lane holds)
+//   * sum_w 2^(8w) S_w[k] in 128 bits, rounded to double ONCE (exact below 2^53), times 2^-62 F/2: the scale of
+//     k_ltm_acf_fast's samples (2^-31 each) and of the reference's unnormalised inverse
+// RAW: no pick, the scaled sums of the lags 0 .. 263 go to `out` (sla_hip_launch_ltm_acf_int, tests).
+// ---------------------------------------------------------------------------------------------
+#define ACF_INT_LAGS 264u
+#define ACF_INT_SHIFTS 18
+#define ACF_INT_THREADS 256
+#define ACF_INT_ROW(nt) (64u * (nt) + 48u)                         // bytes of a digit row for nt tiles of 64 kappa
+#define ACF_INT_LDS(cap) (5u * 16u * ACF_INT_ROW(((cap) + 1023u) / 1024u))
+
+typedef int acf_i32x4 __attribute__((ext_vector_type(4)));
+
+template <int R>
+__device__ __forceinline__ int acf_int_row_from(int v)            // lane c of a row of 16 receives lane (c + R) % 16
+{
+  if constexpr (R == 0) { return v; }
+  else { return __builtin_amdgcn_update_dpp(0, v, 0x120 + (16 - R), 0xF, 0xF, false); }      // row_ror:(16 - R)
+}
+
+template <int D, int S0, int S>
+__device__ __forceinline__ void acf_int_shifts(const unsigned char* planes, uint32_t rs, uint32_t nt, uint32_t lane, int (*s_sum)[ACF_INT_LAGS + 8])
+{
+  constexpr int W = 2 * D - 1;
+  constexpr int WOFF = S0 & ~3, SH0 = S0 & 3;
+  constexpr int NW = ((SH0 + S - 1) >> 2) + 5;                      // dwords of the B window
+  const uint32_t r = lane & 15u, h = lane >> 4;
+  const uint32_t ps = 16u * rs;
+  acf_i32x4 acc[S][W];
+#pragma unroll
+  for (int s = 0; s < S; s++) {
+#pragma unroll
+    for (int w = 0; w < W; w++) { acc[s][w] = acf_i32x4{0, 0, 0, 0}; }
+  }
+  const unsigned char* row = planes + r * rs + 16u * h;
+  for (uint32_t t = 0; t < nt; t++, row += 64) {
+    acf_i32x4 a[D];
+    uint32_t win[D][NW];
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+      a[d] = *(const acf_i32x4*)(row + d * ps);
+      const uint32_t* wp = (const uint32_t*)(row + d * ps + WOFF);
+#pragma unroll
+      for (int q = 0; q < NW; q++) { win[d][q] = wp[q]; }
+    }
+#pragma unroll
+    for (int s = 0; s < S; s++) {
+      const int off = SH0 + s, dw = off >> 2, sh = off & 3;
+#pragma unroll
+      for (int b = 0; b < D; b++) {
+        acf_i32x4 f;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          f[j] = (sh == 0) ? (int)win[b][dw + j] : (int)__builtin_amdgcn_alignbyte(win[b][dw + j + 1], win[b][dw + j], (uint32_t)sh);
+        }
+#pragma unroll
+        for (int d = 0; d < D; d++) { acc[s][d + b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[d], f, acc[s][d + b], 0, 0, 0); }
+      }
+    }
+  }
+  // C[i][c]: c = lane & 15, i = 4 (lane >> 4) + reg, lag 16 s + c - i.  Lane c takes reg R of lane (c + R) % 16: all four on
+  // the diagonal c - 4 h, or, where c + R wrapped, on c - 16 - 4 h -- which is the diagonal c - 4 h of the shift before,
+  // so inside a wave's run of shifts the wrapped part joins the next lower shift's sum in the lane's own register.
+  const int kbase = 16 * S0 + (int)r - 4 * (int)h;
+#pragma unroll
+  for (int w = 0; w < W; w++) {
+    int carry = 0;
+#pragma unroll
+    for (int s = S - 1; s >= 0; s--) {
+      const int v1 = acf_int_row_from<1>(acc[s][w][1]), v2 = acf_int_row_from<2>(acc[s][w][2]), v3 = acf_int_row_from<3>(acc[s][w][3]);
+      const int yw = ((r >= 15u) ? v1 : 0) + ((r >= 14u) ? v2 : 0) + ((r >= 13u) ? v3 : 0);
+      const int ym = acc[s][w][0] + v1 + v2 + v3 - yw + carry;
+      carry = yw;
+      if ((uint32_t)(kbase + 16 * s) < ACF_INT_LAGS && ym != 0) { atomicAdd(&s_sum[w][kbase + 16 * s], ym); }
+    }
+    if ((uint32_t)(kbase - 16) < ACF_INT_LAGS && carry != 0) { atomicAdd(&s_sum[w][kbase - 16], carry); }
+  }
+}
+
+template <int D, int S0, int S>
+__device__ __forceinline__ void acf_int_range(const unsigned char* planes, uint32_t rs, uint32_t nt, uint32_t lane, int (*s_sum)[ACF_INT_LAGS + 8])
+{
+  // (D >= 4: 7 or 9 weights per shift -- two shifts' accumulators at a time, the planes are read more than once)
+  if constexpr (D >= 4 && S > 2) {
+    acf_int_shifts<D, S0, 2>(planes, rs, nt, lane, s_sum);
+    acf_int_range<D, S0 + 2, S - 2>(planes, rs, nt, lane, s_sum);
+  } else {
+    acf_int_shifts<D, S0, S>(planes, rs, nt, lane, s_sum);
+  }
+}
+
+template <int D>
+__device__ __forceinline__ void acf_int_products(const unsigned char* planes, uint32_t rs, uint32_t nt, uint32_t role, uint32_t lane, int (*s_sum)[ACF_INT_LAGS + 8])
+{
+  if (role == 0u) { acf_int_range<D, 0, 5>(planes, rs, nt, lane, s_sum); }
+  else if (role == 1u) { acf_int_range<D, 5, 5>(planes, rs, nt, lane, s_sum); }
+  else if (role == 2u) { acf_int_range<D, 10, 4>(planes, rs, nt, lane, s_sum); }
+  else { acf_int_range<D, 14, 4>(planes, rs, nt, lane, s_sum); }
+}
+
+// sum_w 2^(8w) s_w, rounded to double once (round to nearest even; exact below 2^53)
+__device__ __forceinline__ double acf_int_combine(const int (*s_sum)[ACF_INT_LAGS + 8], uint32_t k, uint32_t nw)
+{
+  // weights 0 .. 3 and 4 .. 8 in int64 each (|s_w| < 2^31; s_4 .. s_8 2^(8(w-4)) add up to less than 2^45)
+  long long slo = 0, shi = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < 4; w++) { if (w < nw) { slo += (long long)s_sum[w][k] * (1ll << (8u * w)); } }
+#pragma unroll
+  for (uint32_t w = 4; w < 9; w++) { if (w < nw) { shi += (long long)s_sum[w][k] * (1ll << (8u * (w - 4u))); } }
+  if (shi > -(1ll << 29) && shi < (1ll << 29)) { return (double)(slo + shi * (1ll << 32)); }       // fits int64: one conversion
+  const __int128 t = (__int128)shi * ((__int128)1 << 32) + (__int128)slo;
+  const bool neg = t < 0;
+  const unsigned __int128 mag = neg ? (unsigned __int128)(-t) : (unsigned __int128)t;
+  const unsigned long long hi = (unsigned long long)(mag >> 64), lo = (unsigned long long)mag;
+  double d;
+  if (hi == 0ull) { d = (double)lo; }
+  else {
+    const uint32_t sh = 64u - (uint32_t)__clzll((long long)hi);                        // 1 .. 64 (here at most 32)
+    unsigned long long top = (unsigned long long)(mag >> sh);
+    if ((lo << (64u - sh)) != 0ull) { top |= 1ull; }                                     // sticky bit: 64 kept bits > 53 + 1
+    d = ldexp((double)top, (int)sh);
+  }
+  return neg ? -d : d;
+}
+
+template <bool RAW>
+__global__ __launch_bounds__(ACF_INT_THREADS, 3)
+void k_ltm_acf_int(const int32_t* __restrict__ res, uint64_t stride, const sla_hip_acf_job* __restrict__ jobs,
+                   uint32_t njobs, uint32_t log2F, double* __restrict__ out, double* __restrict__ eps_out,
+                   double eps_rel, unsigned long long* span)
+{
+  extern __shared__ double2 lds2[];
+  span_begin(span);
+  __shared__ double s_r[ACF_FAST_LAGS + 4];
+  __shared__ int s_sum[9][ACF_INT_LAGS + 8];
+  __shared__ unsigned long long s_mask[4][ACF_PICK_LAGS / 64];
+  __shared__ uint32_t s_nd;
+  unsigned char* planes = (unsigned char*)lds2;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t cap = 1u << (log2F - 1u);
+  const double scl = ldexp(1.0, (int)log2F - 1 - 62);                    // 2^-62 F/2
+  for (uint32_t job = blockIdx.x; job < njobs; job += gridDim.x) {
+    const sla_hip_acf_job jb = jobs[job];
+    const int32_t* src = res + (uint64_t)jb.channel * stride + jb.blk_off;
+    const bool size_ok = (jb.blk_len <= cap);                             // (a block beyond the capacity the LDS was sized for: never certified)
+    const uint32_t n = size_ok ? jb.blk_len : 0u;
+    const uint32_t nt = (n + 1023u) >> 10;
+    const uint32_t rs = ACF_INT_ROW(nt);
+    for (uint32_t t = tid; t < 9u * (ACF_INT_LAGS + 8u); t += ACF_INT_THREADS) { (&s_sum[0][0])[t] = 0; }
+    if (tid == 0) { s_nd = 1u; }
+    __syncthreads();
+    // digit planes: thread (i, q) packs kappa = 4q .. 4q + 3 of row i into one dword per plane; zeros from n on.  Sixteen
+    // quads of samples are fetched before the first is split (the loads of a job are one round trip, not one per quad).
+    // The digits come four at a time: x1 = (x + 128) >> 8 is the remainder behind digit 0, and so on, hence
+    // digit a = byte a of y = x + 0x80808080, less 128 -- the byte XOR 0x80 read as int8 -- and digit 4 = the carry out of
+    // that sum, 1 from x = 2139062144 on.  D digits suffice when every higher one is zero: the table of DESIGN section 2c.
+    const uint32_t nq = 16u * (rs >> 2), nlive = 16u * ((n + 63u) >> 6);
+    uint32_t zor = 0;                                                     // OR of the samples' four low digits
+    int top = 0;
+    for (uint32_t base = tid; base < nlive; base += 4u * ACF_INT_THREADS) {
+      int v[4][4];
+#pragma unroll
+      for (uint32_t it = 0; it < 4; it++) {
+        const uint32_t idx = base + it * ACF_INT_THREADS, i = idx & 15u, q = idx >> 4;
+        const int32_t* p = src + (64u * q + i);
+        if (64u * q + 64u <= n) {
+#pragma unroll
+          for (uint32_t j = 0; j < 4; j++) { v[it][j] = p[16u * j]; }
+        } else {
+#pragma unroll
+          for (uint32_t j = 0; j < 4; j++) { v[it][j] = (64u * q + 16u * j + i < n) ? p[16u * j] : 0; }
+        }
+      }
+#pragma unroll
+      for (uint32_t it = 0; it < 4; it++) {
+        const uint32_t idx = base + it * ACF_INT_THREADS, i = idx & 15u, q = idx >> 4;
+        if (idx < nlive) {
+          uint32_t z[4];
+#pragma unroll
+          for (uint32_t j = 0; j < 4; j++) { z[j] = ((uint32_t)v[it][j] + 0x80808080u) ^ 0x80808080u; }
+          zor |= z[0] | z[1] | z[2] | z[3];
+          const int mx = max(max(v[it][0], v[it][1]), max(v[it][2], v[it][3]));
+          top = max(top, mx);
+          // 4 x 4 byte transpose: byte j of plane d's dword = digit d of sample j
+          const uint32_t lo01 = (z[0] & 0x00FF00FFu) | ((z[1] & 0x00FF00FFu) << 8), hi01 = ((z[0] >> 8) & 0x00FF00FFu) | (z[1] & 0xFF00FF00u);
+          const uint32_t lo23 = (z[2] & 0x00FF00FFu) | ((z[3] & 0x00FF00FFu) << 8), hi23 = ((z[2] >> 8) & 0x00FF00FFu) | (z[3] & 0xFF00FF00u);
+          uint32_t pk[5];
+          pk[0] = (lo01 & 0xFFFFu) | (lo23 << 16); pk[2] = (lo01 >> 16) | (lo23 & 0xFFFF0000u);
+          pk[1] = (hi01 & 0xFFFFu) | (hi23 << 16); pk[3] = (hi01 >> 16) | (hi23 & 0xFFFF0000u);
+          pk[4] = 0u;
+          if (__ballot(mx >= 2139062144) != 0ull) {                       // (wave-uniform, rare: a fifth digit)
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) { pk[4] |= (v[it][j] >= 2139062144 ? 1u : 0u) << (8u * j); }
+          }
+          uint32_t* dst = (uint32_t*)(planes + i * rs) + q;
+#pragma unroll
+          for (uint32_t d = 0; d < 5; d++) { dst[d * 4u * rs] = pk[d]; }                    // (16 rs bytes per plane)
+        }
+      }
+    }
+    for (uint32_t idx = nlive + tid; idx < nq; idx += ACF_INT_THREADS) {                  // zeros behind the block
+      uint32_t* dst = (uint32_t*)(planes + (idx & 15u) * rs) + (idx >> 4);
+#pragma unroll
+      for (uint32_t d = 0; d < 5; d++) { dst[d * 4u * rs] = 0u; }
+    }
+    {
+      const uint32_t need = (__ballot(top >= 2139062144) != 0ull) ? 5u : (__ballot((zor >> 24) != 0u) != 0ull) ? 4u
+                          : (__ballot((zor >> 16) != 0u) != 0ull) ? 3u : (__ballot((zor >> 8) != 0u) != 0ull) ? 2u : 1u;
+      if (lane == 0 && need > 1u) { atomicMax(&s_nd, need); }
+    }
+    __syncthreads();
+    const uint32_t nd = s_nd;
+    const uint32_t role = (wave + job) & 3u;
+    if (nt != 0u) {
+      if (nd == 1u) { acf_int_products<1>(planes, rs, nt, role, lane, s_sum); }
+      else if (nd == 2u) { acf_int_products<2>(planes, rs, nt, role, lane, s_sum); }
+      else if (nd == 3u) { acf_int_products<3>(planes, rs, nt, role, lane, s_sum); }
+      else if (nd == 4u) { acf_int_products<4>(planes, rs, nt, role, lane, s_sum); }
+      else { acf_int_products<5>(planes, rs, nt, role, lane, s_sum); }
+    }
+    __syncthreads();
+    for (uint32_t t = tid; t < ACF_FAST_LAGS + 4; t += ACF_INT_THREADS) {
+      s_r[t] = (t < ACF_INT_LAGS) ? scl * acf_int_combine(s_sum, t, 2u * nd - 1u) : 0.0;
+    }
+    __syncthreads();
+    if constexpr (RAW) {
+      for (uint32_t t = tid; t < ACF_INT_LAGS; t += ACF_INT_THREADS) { out[(uint64_t)job * ACF_INT_LAGS + t] = s_r[t]; }
+    } else {
+      acf_emit_cert<ACF_INT_THREADS>(s_r, job, out, eps_out, eps_rel, size_ok, s_mask);
+      if (!size_ok && tid == 0) { eps_out[job] = -1.0; }                 // (its sums were not formed: not the silent case)
+    }
+    __syncthreads();
+  }
+  span_end(span);
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_ltm_solve: pitch and taps of every (block, channel) from k_ltm_acf's compact record, written straight into the
 // job table k_tail reads -- the long-term stage never leaves the device (src/SLAPredictor.c:855-863, 913-979;
 // the 5x5 LU solve with two refinement passes is src/SLAUtility.c:487-674; the tap quantiser src/SLAEncoder.c:629-640).

@@ -430,6 +430,7 @@ struct SLAEncoder* SLAEncoder_Create(const struct SLAEncoderConfig* config)
   e->search_exact = 1; e->exact_bits = 53; e->device_plan = 1; e->cert_safety = 64.0;
   e->block_cert = 1; e->block_cert_safety = 16.0;
   e->ltm_cert = 1; e->ltm_cert_safety = SLA_HIP_LTM_CERT_SAFETY_MIN;
+  e->tune.ltm_int = 1;  /* that stage's autocorrelation from k_ltm_acf_int (int8 matrix products) instead of k_ltm_acf_fast; lanes copy e->tune */
   e->table_cache = 1;
   e->prelaunch = 1;
   e->device_expand = 1; e->expand_silence = 1;
@@ -2416,7 +2417,8 @@ int sla_hip_encoder_set_option(struct SLAEncoder* e, const char* name, double va
   else if (strcmp(name, "upload24") == 0)          { OPT_RANGE(0, 1); e->upload24 = (int)iv; }
   else if (strcmp(name, "block_cert") == 0)        { OPT_RANGE(0, 1); e->block_cert = (int)iv; }
   else if (strcmp(name, "ltm_cert") == 0)          { OPT_RANGE(0, 1); e->ltm_cert = (int)iv; }
-  else if (strcmp(name, "ltm_cert_safety") == 0)   { if (!(value >= SLA_HIP_LTM_CERT_SAFETY_MIN) || value > 1e6) { return SLA_APIRESULT_INVALID_ARGUMENT; } e->ltm_cert_safety = value; }
+  else if (strcmp(name, "ltm_int") == 0)           { OPT_RANGE(0, 1); e->tune.ltm_int = (uint32_t)iv; }
+  else if (strcmp(name, "ltm_cert_safety") == 0)  { if (!(value >= SLA_HIP_LTM_CERT_SAFETY_MIN) || value > 1e6) { return SLA_APIRESULT_INVALID_ARGUMENT; } e->ltm_cert_safety = value; }
   else if (strcmp(name, "block_cert_safety") == 0) { if (!(value >= 16.0) || value > 1e30) { return SLA_APIRESULT_INVALID_ARGUMENT; } e->block_cert_safety = value; }
   else if (strcmp(name, "device_plan") == 0)       { OPT_RANGE(0, 1); e->device_plan = (int)iv; }
   else if (strcmp(name, "single_tail") == 0)       { OPT_RANGE(0, 1); e->single_tail = (int)iv; }
