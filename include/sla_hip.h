@@ -655,6 +655,91 @@ typedef struct sla_hip_dec_emit {
 int sla_hip_launch_dec_emit_batch(const int32_t* d_planes, uint64_t plane_stride, const sla_hip_dec_emit* d_files,
                                   uint32_t num_files, uint32_t max_samples, uint32_t sample_format, sla_hip_stream_t stream);
 
+/* Many .sla files whose BYTES ARE IN DEVICE MEMORY decoded into caller-owned device memory: sla_hip_decode_batch_device
+ * without a host copy of the streams, without staging and without an upload.  The item struct is that call's and `data`
+ * is a device pointer (any byte alignment: slices of one big uint8 buffer are fine); sources are only read.
+ * Every item gets exactly what sla_hip_decode_batch_device on this handle gives for the same bytes in host memory: result,
+ * output_num_samples, the contents of dst in every format, the zero fill, nothing written outside [0, C) x [0, capacity),
+ * the handle's wave format and encode parameter afterwards, the call-level refusals.
+ * Per item, on the host and before anything of the item is read or written, INVALID_ARGUMENT (nothing written) also
+ * for: NULL data, a data the runtime does not report as device memory, a [data, data + data_size) that does not lie
+ * inside its allocation.  The destination checks need the header's channel count: they run once the headers are home
+ * and before anything is written to dst.
+ * How it runs: (a) a gather kernel (sla_hip_launch_dec_gather) collects the first min(data_size, 43) bytes of every
+ * admissible item, one copy brings them home and the header pass of sla_hip_decode_batch runs on that copy; (b) a walk
+ * kernel (sla_hip_launch_dec_walk, count mode) follows every file's block chain on the device and returns its block
+ * count, stop reason and extent, from which the host cuts the passes as ever; (c) per pass the gather copies the files
+ * into the handle's pass image at their 4-byte offsets, the walk in write mode fills the block table, every block's end
+ * of stream and stored CRC field, and the decode kernels run unchanged; (d) table, CRC fields and block infos come home
+ * in the pass's one wait and are examined with the host call's code; a file that needs a resync is copied to the host
+ * and decoded again on its own.  A single long file walks its blocks serially on one lane, about 0.7 us per block and
+ * walk on an MI355X (two walks: 10 ms of the 16 ms a ten-minute file takes; 125 ten-second clips: 0.4 ms of 9.3 ms;
+ * DESIGN section 4b).  That is accepted; there is no second walker for long files.
+ * The handle's stream waits on an event recorded on `stream` before the first read of any source and before the first
+ * write; the call returns when every write has completed and no kernel reads a source any more.
+ * sla_hip_decoder_last_timing: [0] = the gathers, [1] = the walks (kernels and their copies), the rest as for
+ * sla_hip_decode_batch_device. */
+int sla_hip_decode_batch_resident(struct SLADecoder* decoder, sla_hip_decode_device_item* items, uint32_t num_items,
+                                  uint32_t sample_format, uint32_t flags, sla_hip_stream_t stream);
+
+/* The headers of `num` resident streams (d_data[i]: device pointer, data_size[i] bytes), for a caller that shapes its
+ * destinations from them: results[i] is SLADecoder_DecodeHeader's code on item i's first bytes and headers[i] what it
+ * delivered (zero when nothing), INVALID_ARGUMENT for a source sla_hip_decode_batch_resident would refuse.  One gather,
+ * one copy home, ordered behind `stream` as above.  The handle's wave format and encode parameter are left alone.
+ * INVALID_ARGUMENT for a NULL decoder, or NULL arrays with num > 0. */
+int sla_hip_resident_headers(struct SLADecoder* decoder, const uint8_t* const* d_data, const uint32_t* data_size,
+                             uint32_t num, struct SLAHeaderInfo* headers, int32_t* results, sla_hip_stream_t stream);
+
+/* The block-chain walk on the device: the host's walk of whole files (from byte 43, sample 0) restated one file per
+ * lane -- same checks, same order, same 32-bit arithmetic, the wrap of `size field + 6` included.  A block whose sample
+ * count exceeds capacity - pos or max_block_samples ends the walk; with crc_check 1 it is kept, flagged
+ * SLA_HIP_DEC_HEADER_ONLY, with crc_check 0 it is not.  d_results[f].stop is the SLAApiResult that says why the walk
+ * stopped short of `total` samples (OK when it did not), extent the highest smp_off + num_samples over the blocks that
+ * are not header-only (positions in the file).
+ * Count mode (d_blocks NULL): only d_results is written.  Write mode (d_blocks, d_block_end and d_crc_field all given):
+ * file f's rows go to [first, first + max_rows) of the three tables -- sla_hip_dec_block with byte_off + img_off and
+ * smp_off + plane_off, img_off + data_size, and the big-endian 16-bit field at byte 6 of the block -- and never at or
+ * behind first + max_rows, which the caller sets to the count of a count-mode walk.  Should a file yield fewer rows
+ * than max_rows (its bytes changed in between) the rest become empty header-only rows at the file's start, so that no
+ * row of the range is left as it was; d_results tells.
+ * The walk reads bytes, at any alignment, and none outside [src, src + data_size).  One dependent load per block: a
+ * file of tens of thousands of blocks walks them serially.
+ * INVALID_ARGUMENT before any launch for a NULL file table or result table, or for write mode with a table missing. */
+typedef struct sla_hip_dec_walk_file {
+  const uint8_t* src;             /* device: the whole .sla stream */
+  uint64_t img_off;               /* write mode: the file's offset in the pass image */
+  uint32_t data_size;
+  uint32_t total;                 /* the header's num_samples */
+  uint32_t capacity;              /* samples per channel of the destination */
+  uint32_t first;                 /* write mode: the file's first row */
+  uint32_t max_rows;              /* write mode: its rows */
+  uint32_t plane_off;             /* write mode: the file's first sample in the pass planes */
+} sla_hip_dec_walk_file;          /* 40 bytes */
+typedef struct sla_hip_dec_walk_result {
+  uint32_t num_blocks;            /* rows the walk kept */
+  uint32_t stop;                  /* SLAApiResult */
+  uint32_t extent;                /* samples per channel the kept blocks write */
+  uint32_t reserved;
+} sla_hip_dec_walk_result;        /* 16 bytes */
+int sla_hip_launch_dec_walk(const sla_hip_dec_walk_file* d_files, uint32_t num_files, uint32_t max_block_samples,
+                            uint32_t crc_check, sla_hip_dec_walk_result* d_results, sla_hip_dec_block* d_blocks,
+                            uint64_t* d_block_end, uint32_t* d_crc_field, sla_hip_stream_t stream);
+
+/* The byte-granular gather into an image: entry k copies `bytes` bytes from src (device, any alignment) to
+ * d_image + dst_off (dst_off a multiple of 4) and writes zeros from there to the next 4-byte boundary.  Nothing outside
+ * each entry's padded range is written; an entry whose dst_off is no multiple of 4 or whose padded range does not lie
+ * inside [0, image_bytes) is skipped.  max_bytes: the largest `bytes` of the table (sizes the grid).
+ * Loads touch only the aligned 16-byte words that overlap [src, src + bytes).
+ * INVALID_ARGUMENT before any launch for a NULL table or image. */
+typedef struct sla_hip_dec_gather {
+  const uint8_t* src;             /* device */
+  uint64_t dst_off;               /* bytes from d_image, a multiple of 4 */
+  uint32_t bytes;
+  uint32_t reserved;
+} sla_hip_dec_gather;             /* 24 bytes */
+int sla_hip_launch_dec_gather(const sla_hip_dec_gather* d_table, uint32_t num_entries, uint32_t max_bytes,
+                              uint8_t* d_image, uint64_t image_bytes, sla_hip_stream_t stream);
+
 /* Decode-and-compare of blocks (option "verify" of the encoder; kernel k_verify_blocks): for every block of the table and
  * every channel, the decoded plane samples [smp_off, smp_off + num_samples) -- what dec_bits / dec_lms / dec_ltm /
  * dec_lattice left, right-justified, mid/side still folded -- are finished as sla_hip_launch_dec_finish_batch finishes them

@@ -98,6 +98,22 @@ class DecodeDeviceItem(C.Structure):
                 ("result", C.c_int32)]
 
 
+class DecWalkFile(C.Structure):
+    """sla_hip_dec_walk_file (include/sla_hip.h): one file of sla_hip_launch_dec_walk"""
+    _fields_ = [("src", C.c_void_p), ("img_off", C.c_uint64), ("data_size", C.c_uint32), ("total", C.c_uint32),
+                ("capacity", C.c_uint32), ("first", C.c_uint32), ("max_rows", C.c_uint32), ("plane_off", C.c_uint32)]
+
+
+class DecWalkResult(C.Structure):
+    """sla_hip_dec_walk_result (include/sla_hip.h): what the walk returns per file"""
+    _fields_ = [("num_blocks", C.c_uint32), ("stop", C.c_uint32), ("extent", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DecGather(C.Structure):
+    """sla_hip_dec_gather (include/sla_hip.h): one entry of sla_hip_launch_dec_gather"""
+    _fields_ = [("src", C.c_void_p), ("dst_off", C.c_uint64), ("bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class EncodeDeviceItem(C.Structure):
     """sla_hip_encode_device_item (include/sla_hip.h): one file of sla_hip_encode_batch_device"""
     _fields_ = [("src", C.c_void_p), ("channel_stride", C.c_uint64), ("sample_stride", C.c_uint64), ("data", u8p),
@@ -229,6 +245,14 @@ def lib():
                                                 C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sla_hip_launch_dec_finish_batch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
                                                       C.c_void_p, C.c_void_p]
+        if hasattr(L, "sla_hip_decode_batch_resident"):      # (SLA_HIP_LIB may name an older build in an A/B run)
+            L.sla_hip_decode_batch_resident.argtypes = [C.c_void_p, C.POINTER(DecodeDeviceItem), C.c_uint32, C.c_uint32,
+                                                        C.c_uint32, C.c_void_p]
+            L.sla_hip_resident_headers.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), u32p, C.c_uint32,
+                                                   C.POINTER(SLAHeaderInfo), i32p, C.c_void_p]
+            L.sla_hip_launch_dec_walk.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sla_hip_launch_dec_gather.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
         _lib = L
     return _lib
 
@@ -277,6 +301,8 @@ EXPORTED_SYMBOLS = [
     "sla_hip_decode_batch", "sla_hip_launch_dec_bits_x", "sla_hip_launch_dec_finish_batch",
     # batch decode into device memory (include/sla_hip.h)
     "sla_hip_decode_batch_device", "sla_hip_launch_dec_emit_batch",
+    # batch decode of streams that are in device memory (include/sla_hip.h)
+    "sla_hip_decode_batch_resident", "sla_hip_resident_headers", "sla_hip_launch_dec_walk", "sla_hip_launch_dec_gather",
     # batch encode from device memory (include/sla_hip.h)
     "sla_hip_encode_batch_device", "sla_hip_launch_enc_ingest_batch",
     # verification of the encoded stream on the device (include/sla_hip.h)
@@ -845,6 +871,120 @@ class Decoder:
                     out[b, :, nchs[b]:].zero_()
         return out, [n for _, n in got], [rc for rc, _ in got]
 
+    @staticmethod
+    def _resident_sources(srcs):
+        """[(device pointer, bytes)] of 1-D contiguous uint8 CUDA tensors or (ptr, size) pairs"""
+        out = []
+        for i, s in enumerate(srcs):
+            if isinstance(s, (tuple, list)):
+                ptr, size = int(s[0] or 0), int(s[1])
+            else:
+                if s.dim() != 1 or str(s.dtype) != "torch.uint8" or not s.is_contiguous() or s.device.type != "cuda":
+                    raise ValueError("source %d: need a 1-D contiguous uint8 CUDA tensor or a (ptr, size) pair" % i)
+                ptr, size = s.data_ptr(), s.numel()
+            if size < 0 or size > 0xFFFFFFFF:
+                raise ValueError("source %d: %d bytes" % (i, size))
+            out.append((ptr, size))
+        return out
+
+    def resident_headers(self, srcs, stream=None):
+        """[(DecodeHeader's code, SLAHeaderInfo)] of streams that are in device memory (sla_hip_resident_headers); the
+        code is INVALID_ARGUMENT for a source the resident decode refuses"""
+        import torch
+        ps = self._resident_sources(srcs)
+        n = len(ps)
+        ptrs = (C.c_void_p * max(n, 1))(*[p or None for p, _ in ps])
+        sizes = (C.c_uint32 * max(n, 1))(*[s for _, s in ps])
+        hdrs = (SLAHeaderInfo * max(n, 1))()
+        codes = (C.c_int32 * max(n, 1))()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        self._check(self._lib.sla_hip_resident_headers(self._h, ptrs, sizes, n, hdrs, codes, C.c_void_p(st.cuda_stream)),
+                    "sla_hip_resident_headers")
+        return [(int(codes[i]), hdrs[i]) for i in range(n)]
+
+    def decode_resident_into(self, srcs, outs, sample_format, zero_fill=True, stream=None, _headers=None):
+        """decode_batch_into for .sla streams whose bytes are in device memory (sla_hip_decode_batch_resident): no host
+        copy of the streams, no staging, no upload.  srcs[i] is a 1-D contiguous uint8 CUDA tensor (a slice of a bigger
+        one at any offset is fine) or a (device pointer, bytes) pair; outs, sample_format, zero_fill and stream as for
+        decode_batch_into.  Returns [(result code, samples)], each what decode_batch_into gives the same bytes."""
+        import torch
+        if sample_format not in self._FORMAT_DTYPE:
+            raise ValueError("unknown sample format %r" % (sample_format,))
+        if len(outs) != len(srcs):
+            raise ValueError("%d outputs for %d files" % (len(outs), len(srcs)))
+        want = getattr(torch, self._FORMAT_DTYPE[sample_format])
+        ps = self._resident_sources(srcs)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        heads = _headers if _headers is not None else self.resident_headers(ps, stream=st)
+        items = (DecodeDeviceItem * len(ps))()
+        for i, ((ptr, size), out) in enumerate(zip(ps, outs)):
+            if not isinstance(out, torch.Tensor) or out.dim() != 2:
+                raise ValueError("output %d: need a 2-D torch tensor [channel][sample]" % i)
+            if out.dtype != want:
+                raise ValueError("output %d: dtype %s, the format wants %s" % (i, out.dtype, want))
+            if out.device.type != "cuda" or out.device.index != self.device_index:
+                raise ValueError("output %d: on %s, the decoder's device is cuda:%d" % (i, out.device, self.device_index))
+            rc, h = heads[i]
+            nch = h.wave_format.num_channels if rc in (0, 11) else 0
+            if out.shape[0] < nch:
+                raise ValueError("output %d: %d rows for a file of %d channels" % (i, out.shape[0], nch))
+            if out.shape[1] > 0xFFFFFFFF or min(out.stride()) < 0 or (out.shape[1] > 1 and out.stride(1) == 0) \
+                    or (nch > 1 and out.stride(0) == 0):
+                raise ValueError("output %d: unsupported shape %s / strides %s" % (i, tuple(out.shape), out.stride()))
+            items[i].data = C.cast(C.c_void_p(ptr or None), u8p)
+            items[i].data_size = size
+            items[i].dst = out.data_ptr() or None
+            items[i].channel_stride = out.stride(0)
+            items[i].sample_stride = max(out.stride(1), 1)
+            items[i].capacity = out.shape[1]
+        rc = self._lib.sla_hip_decode_batch_resident(self._h, items, len(ps), sample_format,
+                                                     DEC_ZERO_FILL if zero_fill else 0, C.c_void_p(st.cuda_stream))
+        self._check(rc, "sla_hip_decode_batch_resident")
+        return [(int(items[i].result), int(items[i].output_num_samples)) for i in range(len(ps))]
+
+    def decode_resident_tensor(self, srcs, dtype=None, layout="planar", length=None, right_justify=False):
+        """decode_batch_tensor for .sla streams whose bytes are in device memory: the same padded tensor, lengths and
+        results; the shapes come from the headers sla_hip_resident_headers brings home"""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype == torch.float32:
+            fmt = PCM_F32
+        elif dtype == torch.int16:
+            fmt = PCM_S16
+        elif dtype == torch.int32:
+            fmt = PCM_S32 if right_justify else PCM_S32_LEFT
+        else:
+            raise ValueError("dtype must be float32, int16 or int32, not %s" % (dtype,))
+        if layout not in ("planar", "interleaved"):
+            raise ValueError("layout must be 'planar' or 'interleaved', not %r" % (layout,))
+        ps = self._resident_sources(srcs)
+        heads = self.resident_headers(ps) if ps else []
+        given = [rc in (0, 11) for rc, _ in heads]         # OK, or a header CRC failure: the fields are delivered
+        nchs = [h.wave_format.num_channels if g else 0 for g, (_, h) in zip(given, heads)]
+        nsmp = [h.num_samples if g else 0 for g, (_, h) in zip(given, heads)]
+        B, Cn = len(ps), max(nchs, default=0)
+        L = int(length) if length is not None else max(nsmp, default=0)
+        if L < 0 or L > 0xFFFFFFFF:
+            raise ValueError("length %d out of range" % L)
+        dev = torch.device("cuda", self.device_index)
+        shape = (B, Cn, L) if layout == "planar" else (B, L, Cn)
+        out = torch.empty(shape, dtype=dtype, device=dev)
+        if out.numel() == 0:
+            # nothing can be written: a one-element stand-in keeps the per-item pointers valid, the results are real
+            scratch = torch.empty(1, dtype=dtype, device=dev)
+            outs = [scratch.as_strided((Cn, L), (1, 1)) for _ in range(B)]
+        else:
+            outs = [out[b] if layout == "planar" else out[b].t() for b in range(B)]
+        got = self.decode_resident_into(ps, outs, fmt, zero_fill=True, _headers=heads)
+        # the zero fill covers [n, L) of the rows a header gave; what no header covers is zeroed here
+        for b in range(B):
+            if nchs[b] < Cn:
+                if layout == "planar":
+                    out[b, nchs[b]:].zero_()
+                else:
+                    out[b, :, nchs[b]:].zero_()
+        return out, [n for _, n in got], [rc for rc, _ in got]
+
     def decode_device(self, data, image_ptr, planes_ptr, plane_stride):
         """decode an image that already lives in device memory into device planes; returns (rc, samples)"""
         buf = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data
@@ -855,7 +995,8 @@ class Decoder:
 
     def last_timing(self):
         """[ms] upload, block walk, kernels (stream events), download, total; number of kernel batches
-        (after decode_batch: of passes; after decode_batch_into: [3] is the emit and zero-fill stage)"""
+        (after decode_batch: of passes; after decode_batch_into: [3] is the emit and zero-fill stage; after
+        decode_resident_into: [0] the gathers, [1] the device walks and their copies)"""
         t = (C.c_float * 6)()
         self._lib.sla_hip_decoder_last_timing(self._h, t)
         return list(t)

@@ -18,6 +18,8 @@
 //   k_dec_finish         src/SLAUtility.c:415-433 (mid/side -> left/right), src/SLADecoder.c:540-547 (left-justify)
 //   k_dec_finish_batch   the same for every file of a batch pass, packed [file][ch][n] for one copy home
 //   k_dec_emit_batch     the same, converted and stored to every file's own device destination
+//   k_dec_walk           src/SLADecoder.c:696-722 (the block chain of whole files whose bytes are in device memory)
+//   k_dec_gather         the staging copies of a batch pass, for files that are in device memory already
 //   k_verify_blocks      (kernels/verify.inc) k_dec_finish fused with a compare against source planes, per block table
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -796,6 +798,151 @@ void k_dec_deemphasis(int32_t* __restrict__ data, uint32_t n, int32_t previous, 
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_dec_walk: the host's walk_chain (sla_decoder.c; src/SLADecoder.c:696-722) for whole files whose bytes are in
+// device memory, one file per lane: the chain is one dependent load per block, so blocks cannot go on lanes, but files
+// are independent.  The checks, their order and the 32-bit arithmetic (`size field + 6` wraps) are the host's.  Ten
+// byte loads per block, all inside [src + off, src + off + 11) with off + 11 <= data_size checked first: no byte
+// outside the stream is read, whatever the alignment of src.  Count mode writes the per-file result only; write mode
+// also the rows [first, first + max_rows) of the block table, of the block ends and of the stored CRC fields.
+// A workgroup is one wave: a batch of a few hundred files spreads over as many CUs as it has waves, and a long file
+// holds up only the 63 lanes next to it.
+// ---------------------------------------------------------------------------------------------
+#define DEC_WALK_SYNC       0xFFFFu     // SLAI_SYNC_CODE
+#define DEC_WALK_MIN_HEADER 11u         // SLA_MINIMUM_BLOCK_HEADER_SIZE
+#define DEC_WALK_CRC_START  8u          // SLAI_BLK_CRC_START
+
+__global__ __launch_bounds__(64)
+void k_dec_walk(const sla_hip_dec_walk_file* __restrict__ files, uint32_t num_files, uint32_t cap_n, uint32_t crc_check,
+                sla_hip_dec_walk_result* __restrict__ results, sla_hip_dec_block* __restrict__ blocks,
+                uint64_t* __restrict__ block_end, uint32_t* __restrict__ crc_field)
+{
+  const uint32_t f = blockIdx.x * 64u + threadIdx.x;
+  if (f >= num_files) { return; }
+  const sla_hip_dec_walk_file fi = files[f];
+  const uint8_t* data = fi.src;
+  const uint32_t data_size = fi.data_size, total = fi.total, rows = (blocks != nullptr) ? fi.max_rows : 0u;
+  const uint64_t end = fi.img_off + data_size;
+  uint32_t off = SLA_HEADER_SIZE, pos = 0, nb = 0, extent = 0, stop = SLA_APIRESULT_OK;
+  while (pos < total) {
+    if (off > data_size) { stop = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE; break; }
+    const uint32_t left = data_size - off;
+    if (left < DEC_WALK_MIN_HEADER) { stop = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE; break; }
+    const uint8_t* p = data + off;
+    uint32_t h[10];
+#pragma unroll
+    for (int k = 0; k < 10; k++) { h[k] = p[k]; }
+    if (((h[0] << 8) | h[1]) != DEC_WALK_SYNC) { stop = SLA_APIRESULT_FAILED_TO_FIND_SYNC_CODE; break; }
+    const uint32_t bsize = ((h[2] << 24) | (h[3] << 16) | (h[4] << 8) | h[5]) + 6u;
+    const uint32_t n = (h[8] << 8) | h[9];
+    if (bsize > left || bsize < DEC_WALK_CRC_START) { stop = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE; break; }
+    uint32_t flags = 0;
+    if (n > fi.capacity - pos || n > cap_n) {
+      stop = SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE;
+      if (crc_check != 1u) { break; }
+      flags = SLA_HIP_DEC_HEADER_ONLY;
+    }
+    if (nb < rows) {
+      sla_hip_dec_block b;
+      b.byte_off = fi.img_off + off; b.byte_len = bsize; b.smp_off = fi.plane_off + pos; b.num_samples = n; b.flags = flags;
+      blocks[fi.first + nb] = b;
+      block_end[fi.first + nb] = end;
+      crc_field[fi.first + nb] = (h[6] << 8) | h[7];
+    }
+    nb++;
+    if (flags != 0) { break; }
+    if (pos + n > extent) { extent = pos + n; }
+    off += bsize; pos += n;
+  }
+  // rows the walk did not reach (the bytes changed since they were counted): empty, header-only, at the file's start
+  for (uint32_t r = nb; r < rows; r++) {
+    sla_hip_dec_block b;
+    b.byte_off = fi.img_off; b.byte_len = DEC_WALK_CRC_START; b.smp_off = fi.plane_off; b.num_samples = 0; b.flags = SLA_HIP_DEC_HEADER_ONLY;
+    blocks[fi.first + r] = b;
+    block_end[fi.first + r] = end;
+    crc_field[fi.first + r] = 0;
+  }
+  sla_hip_dec_walk_result res;
+  res.num_blocks = nb; res.stop = stop; res.extent = extent; res.reserved = 0;
+  results[f] = res;
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_dec_gather: files at any byte address into the pass image at 4-byte-aligned offsets, zeros from each file's end to
+// its 4-byte boundary.  blockIdx.y walks the table, the x dimension the aligned 16-byte chunks of the file's
+// destination; a lane makes the four words of its chunk.  A chunk that lies wholly inside the padded destination range
+// takes its 16 source bytes from the one or two ALIGNED 16-byte source words that hold them (two 16-byte loads, a word
+// select by the source's word misalignment, v_alignbyte_b32 by its byte misalignment) and goes out in one 16-byte store;
+// the chunks at a file's head and tail make their words one by one from aligned 4-byte loads, funnel-shifted the same
+// way, and store those inside the range.  Bytes at or past `bytes` are masked to zero, which is the pad.
+// Loads touch only aligned words that hold at least one byte of [src, src + bytes): such a word may reach up to 15 bytes
+// before src or past the end, and is still inside the source's mapping, because device allocations start at least
+// 16-byte aligned and are mapped in whole pages.
+// ---------------------------------------------------------------------------------------------
+typedef uint32_t gather_u4 __attribute__((ext_vector_type(4)));
+
+// the word at byte offset o (a multiple of 4, o < bytes) of a source of `bytes` bytes, bytes past the end zero
+__device__ __forceinline__ uint32_t gather_word(const uint8_t* src, uint32_t bytes, uint32_t o)
+{
+  const uintptr_t s = (uintptr_t)src + o;
+  const uint32_t sh = (uint32_t)(s & 3u), valid = bytes - o;
+  const uint32_t* a = (const uint32_t*)(s & ~(uintptr_t)3);
+  const uint32_t lo = a[0];                                     // holds byte o
+  const uint32_t hi = (sh != 0 && 4u - sh < valid) ? a[1] : 0u;  // holds byte o + 4 - sh
+  const uint32_t w = __builtin_amdgcn_alignbyte(hi, lo, sh);
+  return (valid >= 4u) ? w : (w & ((1u << (8u * valid)) - 1u));
+}
+
+__global__ __launch_bounds__(256)
+void k_dec_gather(const sla_hip_dec_gather* __restrict__ table, uint32_t num_entries, uint8_t* __restrict__ image,
+                  uint64_t image_bytes)
+{
+  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (uint64_t)gridDim.x * blockDim.x;
+  for (uint32_t e = blockIdx.y; e < num_entries; e += gridDim.y) {
+    const sla_hip_dec_gather g = table[e];
+    const uint32_t bytes = g.bytes;
+    const uint64_t padded = ((uint64_t)bytes + 3u) & ~(uint64_t)3;
+    if ((g.dst_off & 3u) != 0 || g.dst_off > image_bytes || padded > image_bytes - g.dst_off) { continue; }
+    uint8_t* dst = image + g.dst_off;
+    const uint32_t head = (uint32_t)((uintptr_t)dst & 15u);     // bytes of the first chunk before the destination
+    const uint64_t chunks = (head + padded + 15u) >> 4;
+    for (uint64_t c = tid; c < chunks; c += nt) {
+      const int64_t o0 = (int64_t)(c << 4) - head;               // the chunk's first byte, relative to the destination
+      if (o0 >= 0 && (uint64_t)o0 + 16u <= padded) {
+        const uint32_t o = (uint32_t)o0;
+        const uintptr_t s = (uintptr_t)g.src + o;
+        const uint32_t r = (uint32_t)(s & 15u);
+        const gather_u4* a = (const gather_u4*)(s & ~(uintptr_t)15);
+        const gather_u4 q0 = a[0];                               // holds byte o (o < bytes)
+        gather_u4 q1 = {0u, 0u, 0u, 0u};
+        if (r != 0 && 16u - r < bytes - o) { q1 = a[1]; }        // holds byte o + 16 - r
+        uint32_t w[5];
+        switch (r >> 2) {
+          case 0:  w[0] = q0.x; w[1] = q0.y; w[2] = q0.z; w[3] = q0.w; w[4] = q1.x; break;
+          case 1:  w[0] = q0.y; w[1] = q0.z; w[2] = q0.w; w[3] = q1.x; w[4] = q1.y; break;
+          case 2:  w[0] = q0.z; w[1] = q0.w; w[2] = q1.x; w[3] = q1.y; w[4] = q1.z; break;
+          default: w[0] = q0.w; w[1] = q1.x; w[2] = q1.y; w[3] = q1.z; w[4] = q1.w; break;
+        }
+        uint32_t v[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+          const uint32_t valid = (bytes - o > 4u * k) ? (bytes - o - 4u * k) : 0u;
+          const uint32_t x = __builtin_amdgcn_alignbyte(w[k + 1], w[k], r & 3u);
+          v[k] = (valid >= 4u) ? x : (x & ((1u << (8u * valid)) - 1u));
+        }
+        gather_u4 q; q.x = v[0]; q.y = v[1]; q.z = v[2]; q.w = v[3];
+        *(gather_u4*)(dst + o) = q;
+      } else {
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+          const int64_t ok = o0 + 4 * (int64_t)k;
+          if (ok >= 0 && (uint64_t)ok < padded) { *(uint32_t*)(dst + ok) = gather_word(g.src, bytes, (uint32_t)ok); }
+        }
+      }
+    }
+  }
+}
+
 #include "kernels/verify.inc"
 
 }  // namespace
@@ -968,6 +1115,32 @@ extern "C" int sla_hip_launch_dec_emit_batch(const int32_t* d_planes, uint64_t p
     case SLA_HIP_PCM_S16:      hipLaunchKernelGGL(k_dec_emit_batch<SLA_HIP_PCM_S16>, grid, block, 0, st, d_planes, plane_stride, d_files, num_files); break;
     default:                   hipLaunchKernelGGL(k_dec_emit_batch<SLA_HIP_PCM_F32>, grid, block, 0, st, d_planes, plane_stride, d_files, num_files); break;
   }
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_dec_walk(const sla_hip_dec_walk_file* d_files, uint32_t num_files, uint32_t max_block_samples,
+                                       uint32_t crc_check, sla_hip_dec_walk_result* d_results, sla_hip_dec_block* d_blocks,
+                                       uint64_t* d_block_end, uint32_t* d_crc_field, sla_hip_stream_t stream)
+{
+  if (d_files == nullptr || d_results == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if ((d_blocks != nullptr || d_block_end != nullptr || d_crc_field != nullptr)
+      && (d_blocks == nullptr || d_block_end == nullptr || d_crc_field == nullptr)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_files == 0) { return 0; }
+  hipLaunchKernelGGL(k_dec_walk, dim3((num_files + 63) / 64), dim3(64), 0, (hipStream_t)stream, d_files, num_files,
+                     max_block_samples, crc_check, d_results, d_blocks, d_block_end, d_crc_field);
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_dec_gather(const sla_hip_dec_gather* d_table, uint32_t num_entries, uint32_t max_bytes,
+                                         uint8_t* d_image, uint64_t image_bytes, sla_hip_stream_t stream)
+{
+  if (d_table == nullptr || d_image == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_entries == 0 || max_bytes == 0) { return 0; }
+  // a workgroup row covers 4096 bytes of a file (256 lanes x 16); longer files grid-stride
+  uint64_t gx = ((uint64_t)max_bytes + 15 + 4095) / 4096;
+  if (gx > 1024) { gx = 1024; }
+  const dim3 grid((uint32_t)gx, (num_entries < 65535u) ? num_entries : 65535u), block(256);
+  hipLaunchKernelGGL(k_dec_gather, grid, block, 0, (hipStream_t)stream, d_table, num_entries, d_image, image_bytes);
   return hip_rc(hipGetLastError());
 }
 

@@ -36,8 +36,12 @@ struct SLADecoder {
   dbuf_t                    d_image, d_planes, d_blocks, d_info, d_chan, d_kint;
   dbuf_t                    d_ftab, d_out;              /* sla_hip_decode_batch: file table, packed samples */
   hbuf_t                    h_img, h_ptab, h_out;       /* sla_hip_decode_batch: page-locked staging */
+  dbuf_t                    d_src, d_wres, d_crcf;      /* sla_hip_decode_batch_resident: gather / walk tables, walk results, CRC fields */
+  hbuf_t                    h_src, h_hdr;               /* the same: tables and results, the headers brought home */
+  hipEvent_t                ev_src[3];                  /* the same: around a pass's gather and walk */
   sla_hip_dec_block*        h_blocks;
   sla_hip_dec_info*         h_info;
+  uint32_t*                 h_crcf;                     /* every block's stored CRC field, next to h_blocks */
   uint32_t                  h_cap;
   float                     timing[6];
 };
@@ -131,8 +135,12 @@ void SLADecoder_Destroy(struct SLADecoder* d)
   dbuf_free(&d->d_info); dbuf_free(&d->d_chan); dbuf_free(&d->d_kint);
   dbuf_free(&d->d_ftab); dbuf_free(&d->d_out);
   hbuf_free(&d->h_img); hbuf_free(&d->h_ptab); hbuf_free(&d->h_out);
+  dbuf_free(&d->d_src); dbuf_free(&d->d_wres); dbuf_free(&d->d_crcf);
+  hbuf_free(&d->h_src); hbuf_free(&d->h_hdr);
+  { int k; for (k = 0; k < 3; k++) { if (d->ev_src[k] != NULL) { (void)hipEventDestroy(d->ev_src[k]); } } }
   if (d->h_blocks != NULL) { (void)hipHostFree(d->h_blocks); }
   if (d->h_info != NULL) { (void)hipHostFree(d->h_info); }
+  if (d->h_crcf != NULL) { (void)hipHostFree(d->h_crcf); }
   (void)hipEventDestroy(d->ev[0]); (void)hipEventDestroy(d->ev[1]);
   if (d->ev_order != NULL) { (void)hipEventDestroy(d->ev_order); }
   (void)hipStreamDestroy(d->stream);
@@ -164,14 +172,17 @@ static int host_tables_reserve(struct SLADecoder* d, uint32_t blocks)
 {
   sla_hip_dec_block* nb = NULL;
   sla_hip_dec_info* ni = NULL;
+  uint32_t* nc = NULL;
   uint32_t cap;
   if (blocks <= d->h_cap) { return 0; }
   cap = blocks + blocks / 2 + 64;
   if (hipHostMalloc((void**)&nb, sizeof(*nb) * cap, hipHostMallocDefault) != hipSuccess) { return -1; }
   if (hipHostMalloc((void**)&ni, sizeof(*ni) * cap, hipHostMallocDefault) != hipSuccess) { (void)hipHostFree(nb); return -1; }
+  if (hipHostMalloc((void**)&nc, sizeof(*nc) * cap, hipHostMallocDefault) != hipSuccess) { (void)hipHostFree(nb); (void)hipHostFree(ni); return -1; }
   if (d->h_blocks != NULL) { memcpy(nb, d->h_blocks, sizeof(*nb) * d->h_cap); (void)hipHostFree(d->h_blocks); }
   if (d->h_info != NULL) { (void)hipHostFree(d->h_info); }
-  d->h_blocks = nb; d->h_info = ni; d->h_cap = cap;
+  if (d->h_crcf != NULL) { memcpy(nc, d->h_crcf, sizeof(*nc) * d->h_cap); (void)hipHostFree(d->h_crcf); }
+  d->h_blocks = nb; d->h_info = ni; d->h_crcf = nc; d->h_cap = cap;
   return 0;
 }
 
@@ -179,7 +190,7 @@ static int host_tables_reserve(struct SLADecoder* d, uint32_t blocks)
 #define RCCHK(call)  do { const int rc_ = (call); if (rc_ != 0) { return (rc_ > 0) ? (SLAApiResult)rc_ : SLA_APIRESULT_NG; } } while (0)
 
 /* Walk a file's block chain from byte `off`, sample `pos` (positions in the file) and append the blocks to
- * d->h_blocks[*nb ...]; *walk_err says why the walk stopped short of `total` samples.    src/SLADecoder.c:696-722
+ * d->h_blocks[*nb ...], their stored CRC fields to d->h_crcf[*nb ...]; *walk_err says why the walk stopped short of `total` samples.    src/SLADecoder.c:696-722
  * Returns -1 when the host table could not grow. */
 static int walk_chain(struct SLADecoder* d, const uint8_t* data, uint32_t data_size, uint32_t off, uint32_t pos,
                       uint32_t total, uint32_t buffer_num_samples, uint32_t* nb, SLAApiResult* walk_err)
@@ -206,6 +217,7 @@ static int walk_chain(struct SLADecoder* d, const uint8_t* data, uint32_t data_s
     if (host_tables_reserve(d, *nb + 1) != 0) { return -1; }
     d->h_blocks[*nb].byte_off = off; d->h_blocks[*nb].byte_len = bsize; d->h_blocks[*nb].smp_off = pos;
     d->h_blocks[*nb].num_samples = n; d->h_blocks[*nb].flags = flags;
+    d->h_crcf[*nb] = rd_be16(p + 6);
     (*nb)++;
     if (flags != 0) { break; }
     off += bsize; pos += n;
@@ -214,10 +226,11 @@ static int walk_chain(struct SLADecoder* d, const uint8_t* data, uint32_t data_s
 }
 
 /* Examine the decoded blocks of one file in file order: the first failure decides (*result), *done_samples counts the
- * samples of the blocks before it.  Table positions are the file's own (byte offsets into `data`).  Returns 1 when a
+ * samples of the blocks before it.  Table positions are the file's own; crc_field[i] is block i's stored CRC field (the
+ * walk's, host or device).  Returns 1 when a
  * block's body did not end where its size field says: the reference continues from where its reader stopped (:715),
  * so the walk resumes at (*off, *pos). */
-static int examine_blocks(const struct SLADecoder* d, const uint8_t* data, const sla_hip_dec_block* blocks,
+static int examine_blocks(const struct SLADecoder* d, const uint32_t* crc_field, const sla_hip_dec_block* blocks,
                           const sla_hip_dec_info* info, uint32_t nb, int lms_ok, SLAApiResult walk_err,
                           uint32_t* one_block_size, uint32_t* done_samples, uint32_t* off, uint32_t* pos, SLAApiResult* result)
 {
@@ -226,7 +239,7 @@ static int examine_blocks(const struct SLADecoder* d, const uint8_t* data, const
   for (i = 0; i < nb; i++) {
     const sla_hip_dec_block* b = &blocks[i];
     const sla_hip_dec_info* in = &info[i];
-    if (d->cfg.enable_crc_check == 1 && in->crc != rd_be16(data + b->byte_off + 6)) { *result = SLA_APIRESULT_DETECT_DATA_CORRUPTION; return 0; }
+    if (d->cfg.enable_crc_check == 1 && in->crc != crc_field[i]) { *result = SLA_APIRESULT_DETECT_DATA_CORRUPTION; return 0; }
     if (b->flags & SLA_HIP_DEC_HEADER_ONLY) { *result = walk_err; return 0; }
     if (in->type > 2) { *result = SLA_APIRESULT_INVALID_HEADER_FORMAT; return 0; }
     if (in->type == 0 && !lms_ok) { *result = SLA_APIRESULT_FAILED_TO_SYNTHESIZE; return 0; }
@@ -370,7 +383,7 @@ static SLAApiResult decode_run(struct SLADecoder* d, const uint8_t* data, uint32
     }
 
     /* ---- examine the blocks in file order: the first failure decides */
-    if (!examine_blocks(d, data, d->h_blocks, d->h_info, nb, lms_ok, walk_err, one_block_size, &done_samples, &off, &pos, &result)) { break; }
+    if (!examine_blocks(d, d->h_crcf, d->h_blocks, d->h_info, nb, lms_ok, walk_err, one_block_size, &done_samples, &off, &pos, &result)) { break; }
   }
 
   /* ---- mid/side, left-justification, copy-out of everything before the failing block */
@@ -418,6 +431,10 @@ SLAApiResult sla_hip_decode_device(struct SLADecoder* decoder, const uint8_t* ho
  * sla_hip_launch_dec_bits_x) and its block table once, runs each kernel once over one set of planes in which every
  * file has a region of its own, and brings the finished samples of all its files home in one copy
  * (sla_hip_launch_dec_finish_batch).  The results are then examined file by file with decode_run's code.
+ * With resident sources (sla_hip_decode_batch_resident) the streams are in device memory and the host never reads them:
+ * the headers come home through a gather, the walk runs on the device (count mode before the passes are cut, write mode
+ * in each pass), the gather fills the pass image in place of staging and upload, and the examination reads the table
+ * and the stored CRC fields the pass brought home.
  * ------------------------------------------------------------------------------------------------------------ */
 #define DEC_BATCH_PASS_BYTES (1ull << 30)    /* stream bytes of one pass (staging and device image) */
 #define DEC_BATCH_ALIGN      64u             /* samples: every file's plane region starts on a 256-byte boundary */
@@ -507,7 +524,150 @@ typedef struct {
   uint32_t  format, zero_fill;
   uint8_t*  state;          /* DEV_* per item */
   uint32_t* chans;          /* per item: the channel count its header gave, 0 when none */
+  int       resident;       /* sla_hip_decode_batch_resident: items[].data are device pointers; the internal items' data
+                             * is the host copy of each header, nothing behind byte 43 of it exists */
 } dev_out_t;
+
+/* ---- resident sources: the device walk and the gather stand in for walk_chain and the staging copies ---- */
+#define RES_HDR_SLOT 48u     /* bytes of one header in the gathered header image (43, padded, a multiple of 4) */
+
+static int res_events(struct SLADecoder* d)
+{
+  int k;
+  for (k = 0; k < 3; k++) {
+    if (d->ev_src[k] == NULL && hipEventCreate(&d->ev_src[k]) != hipSuccess) { d->ev_src[k] = NULL; return -1; }
+  }
+  return 0;
+}
+
+/* 1 when [p, p + size) may be read by a kernel: the source check of the resident calls, before anything is read */
+static int src_region_ok(const uint8_t* p, uint32_t size)
+{
+  return p != NULL && slai_device_region_ok(p, 1, size, 0, 1, 1, -1);
+}
+
+/* The first min(size, 43) bytes of every source with ok[i] set, gathered into one device buffer and brought home in one
+ * copy: header i is at d->h_hdr + i * RES_HDR_SLOT.  On the handle's stream, waited for. */
+static int res_fetch_headers(struct SLADecoder* d, const uint8_t* const* src, const uint32_t* size, const uint8_t* ok, uint32_t n)
+{
+  sla_hip_dec_gather* gt;
+  uint32_t i, ng = 0;
+  const size_t img = (size_t)n * RES_HDR_SLOT;
+  if (hbuf_reserve(&d->h_hdr, img) != 0 || hbuf_reserve(&d->h_src, sizeof(*gt) * (size_t)n) != 0
+      || dbuf_reserve(&d->d_src, sizeof(*gt) * (size_t)n) != 0 || dbuf_reserve(&d->d_image, img + 16) != 0) { return -1; }
+  gt = (sla_hip_dec_gather*)d->h_src.ptr;
+  for (i = 0; i < n; i++) {
+    if (!ok[i]) { continue; }
+    gt[ng].src = src[i]; gt[ng].dst_off = (uint64_t)i * RES_HDR_SLOT;
+    gt[ng].bytes = (size[i] < SLA_HEADER_SIZE) ? size[i] : SLA_HEADER_SIZE; gt[ng].reserved = 0;
+    ng++;
+  }
+  if (ng == 0) { return 0; }
+  BCHK(hipMemcpyAsync(d->d_src.ptr, gt, sizeof(*gt) * ng, hipMemcpyHostToDevice, d->stream));
+  BRC(sla_hip_launch_dec_gather((const sla_hip_dec_gather*)d->d_src.ptr, ng, SLA_HEADER_SIZE, (uint8_t*)d->d_image.ptr, img, d->stream));
+  BCHK(hipMemcpyAsync(d->h_hdr.ptr, d->d_image.ptr, img, hipMemcpyDeviceToHost, d->stream));
+  BCHK(hipStreamSynchronize(d->stream));
+  return 0;
+}
+
+/* The count-mode walk of files[0, nf): one launch, one small copy home; sets every file's first / nb / walk_err / extent
+ * and *nblocks, and makes room for that many rows in the host tables. */
+static int res_count_walk(struct SLADecoder* d, const sla_hip_decode_item* items, const dev_out_t* dev, bfile_t* files, uint32_t nf,
+                          uint32_t* nblocks)
+{
+  sla_hip_dec_walk_file* wt;
+  sla_hip_dec_walk_result* wr;
+  uint64_t total = 0;
+  uint32_t i;
+  if (nf == 0) { return 0; }
+  if (hbuf_reserve(&d->h_src, (sizeof(*wt) + sizeof(*wr)) * (size_t)nf) != 0 || dbuf_reserve(&d->d_src, sizeof(*wt) * (size_t)nf) != 0
+      || dbuf_reserve(&d->d_wres, sizeof(*wr) * (size_t)nf) != 0) { return -1; }
+  wt = (sla_hip_dec_walk_file*)d->h_src.ptr;
+  wr = (sla_hip_dec_walk_result*)(wt + nf);
+  for (i = 0; i < nf; i++) {
+    const sla_hip_decode_item* it = &items[files[i].item];
+    memset(&wt[i], 0, sizeof(wt[i]));
+    wt[i].src = dev->items[files[i].item].data; wt[i].data_size = it->data_size;
+    wt[i].total = files[i].f.total; wt[i].capacity = it->buffer_num_samples;
+  }
+  BCHK(hipMemcpyAsync(d->d_src.ptr, wt, sizeof(*wt) * nf, hipMemcpyHostToDevice, d->stream));
+  BRC(sla_hip_launch_dec_walk((const sla_hip_dec_walk_file*)d->d_src.ptr, nf, d->cfg.max_num_block_samples, d->cfg.enable_crc_check,
+                              (sla_hip_dec_walk_result*)d->d_wres.ptr, NULL, NULL, NULL, d->stream));
+  BCHK(hipMemcpyAsync(wr, d->d_wres.ptr, sizeof(*wr) * nf, hipMemcpyDeviceToHost, d->stream));
+  BCHK(hipStreamSynchronize(d->stream));
+  for (i = 0; i < nf; i++) {
+    files[i].first = (uint32_t)total; files[i].nb = wr[i].num_blocks;
+    files[i].walk_err = (SLAApiResult)wr[i].stop; files[i].extent = wr[i].extent;
+    total += wr[i].num_blocks;
+  }
+  if (total > 0xFFFFFFFFull || host_tables_reserve(d, (uint32_t)total) != 0) { return -1; }
+  *nblocks = (uint32_t)total;
+  return 0;
+}
+
+/* A pass's stage for resident sources, queued and not waited for: the gather fills the pass image, the walk in write mode
+ * the block table (d->d_blocks: nb rows, then nb ends) and d->d_crcf; rows, CRC fields and the walk's results are on their
+ * way home (d->h_blocks / d->h_crcf from the pass's first row, the results behind the tables in d->h_src) and d->d_info is
+ * cleared.  Nothing when the pass has no block. */
+static int res_stage_pass(struct SLADecoder* d, const sla_hip_decode_item* items, const dev_out_t* dev, const bfile_t* files,
+                          uint32_t nf, uint32_t nb, uint64_t img_bytes)
+{
+  sla_hip_dec_gather* gt;
+  sla_hip_dec_walk_file* wt;
+  sla_hip_dec_walk_result* wr;
+  sla_hip_dec_block* db;
+  const uint32_t first = files[0].first;
+  uint32_t i, max_bytes = 0;
+  if (nb == 0) { return 0; }
+  if (hbuf_reserve(&d->h_src, (sizeof(*gt) + sizeof(*wt) + sizeof(*wr)) * (size_t)nf) != 0
+      || dbuf_reserve(&d->d_src, (sizeof(*gt) + sizeof(*wt)) * (size_t)nf) != 0 || dbuf_reserve(&d->d_wres, sizeof(*wr) * (size_t)nf) != 0
+      || dbuf_reserve(&d->d_crcf, sizeof(uint32_t) * (size_t)nb) != 0 || res_events(d) != 0) { return -1; }
+  gt = (sla_hip_dec_gather*)d->h_src.ptr;
+  wt = (sla_hip_dec_walk_file*)(gt + nf);
+  wr = (sla_hip_dec_walk_result*)(wt + nf);
+  for (i = 0; i < nf; i++) {
+    const sla_hip_decode_item* it = &items[files[i].item];
+    gt[i].src = dev->items[files[i].item].data; gt[i].dst_off = files[i].img_off; gt[i].bytes = it->data_size; gt[i].reserved = 0;
+    wt[i].src = gt[i].src; wt[i].img_off = files[i].img_off; wt[i].data_size = it->data_size; wt[i].total = files[i].f.total;
+    wt[i].capacity = it->buffer_num_samples; wt[i].first = files[i].first - first; wt[i].max_rows = files[i].nb;
+    wt[i].plane_off = (uint32_t)files[i].plane_off;
+    if (it->data_size > max_bytes) { max_bytes = it->data_size; }
+  }
+  db = (sla_hip_dec_block*)d->d_blocks.ptr;
+  BCHK(hipMemcpyAsync(d->d_src.ptr, gt, (sizeof(*gt) + sizeof(*wt)) * (size_t)nf, hipMemcpyHostToDevice, d->stream));
+  BCHK(hipEventRecord(d->ev_src[0], d->stream));
+  BRC(sla_hip_launch_dec_gather((const sla_hip_dec_gather*)d->d_src.ptr, nf, max_bytes, (uint8_t*)d->d_image.ptr, img_bytes, d->stream));
+  BCHK(hipEventRecord(d->ev_src[1], d->stream));
+  BRC(sla_hip_launch_dec_walk((const sla_hip_dec_walk_file*)((const sla_hip_dec_gather*)d->d_src.ptr + nf), nf, d->cfg.max_num_block_samples,
+                              d->cfg.enable_crc_check, (sla_hip_dec_walk_result*)d->d_wres.ptr, db, (uint64_t*)(db + nb),
+                              (uint32_t*)d->d_crcf.ptr, d->stream));
+  BCHK(hipMemcpyAsync(wr, d->d_wres.ptr, sizeof(*wr) * nf, hipMemcpyDeviceToHost, d->stream));
+  BCHK(hipMemcpyAsync(d->h_blocks + first, db, sizeof(*db) * (size_t)nb, hipMemcpyDeviceToHost, d->stream));
+  BCHK(hipMemcpyAsync(d->h_crcf + first, d->d_crcf.ptr, sizeof(uint32_t) * (size_t)nb, hipMemcpyDeviceToHost, d->stream));
+  BCHK(hipEventRecord(d->ev_src[2], d->stream));
+  BCHK(hipMemsetAsync(d->d_info.ptr, 0, sizeof(sla_hip_dec_info) * nb, d->stream));
+  return 0;
+}
+
+/* After the pass's wait: the stage's times, the rows brought back to positions in their own files (what examine_blocks
+ * reads), and the write-mode walk checked against the count: a file whose chain changed in between fails the call. */
+static int res_finish_pass(struct SLADecoder* d, const bfile_t* files, uint32_t nf, double* t_gather, double* t_walk)
+{
+  const sla_hip_dec_walk_result* wr = (const sla_hip_dec_walk_result*)((const uint8_t*)d->h_src.ptr
+                                      + (sizeof(sla_hip_dec_gather) + sizeof(sla_hip_dec_walk_file)) * (size_t)nf);
+  float ms = 0.0f;
+  uint32_t i, b;
+  if (hipEventElapsedTime(&ms, d->ev_src[0], d->ev_src[1]) == hipSuccess) { *t_gather += ms; }
+  if (hipEventElapsedTime(&ms, d->ev_src[1], d->ev_src[2]) == hipSuccess) { *t_walk += ms; }
+  for (i = 0; i < nf; i++) {
+    if (wr[i].num_blocks != files[i].nb || wr[i].stop != (uint32_t)files[i].walk_err || wr[i].extent != files[i].extent) { return -1; }
+    for (b = 0; b < files[i].nb; b++) {
+      d->h_blocks[files[i].first + b].byte_off -= files[i].img_off;
+      d->h_blocks[files[i].first + b].smp_off -= (uint32_t)files[i].plane_off;
+    }
+  }
+  return 0;
+}
 
 /* one emit table entry for item `it` (0 when there is nothing to write) */
 static uint32_t emit_entry(sla_hip_dec_emit* e, const sla_hip_decode_device_item* it, uint32_t zero_fill, uint64_t plane_off,
@@ -546,11 +706,11 @@ static int emit_run(struct SLADecoder* d, const int32_t* planes, uint64_t stride
  * dev != NULL: the samples go to the caller's device destinations through the emit kernel, nothing comes home.
  * Returns -1 on a device or allocation failure. */
 static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t* files, uint32_t nf, copy_list_t* cl,
-                      const dev_out_t* dev, double* t_up, double* t_down, float* kernel_ms)
+                      const dev_out_t* dev, double* t_up, double* t_walk, double* t_down, float* kernel_ms)
 {
   const dec_format_t* f = &files[0].f;
   const uint32_t C = f->C, first = files[0].first, cap_n = d->cfg.max_num_block_samples;
-  const int lms_ok = lms_order_ok(f->lms);
+  const int lms_ok = lms_order_ok(f->lms), res = (dev != NULL && dev->resident);
   uint64_t img_bytes = 0, span = 0, out_elems = 0;
   uint32_t nb = 0, i, k, nfin = 0, max_done = 0;
   uint32_t* done;
@@ -570,7 +730,7 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
   /* ---- images into staging (the bytes after each file up to its 4-byte boundary are zero) and over in one copy,
    *      the block table -- positions in the pass, then every block's end of stream -- likewise */
   t = now_ms();
-  if (hbuf_reserve(&d->h_img, img_bytes + 16) != 0 || dbuf_reserve(&d->d_image, img_bytes + 16) != 0
+  if ((!res && hbuf_reserve(&d->h_img, img_bytes + 16) != 0) || dbuf_reserve(&d->d_image, img_bytes + 16) != 0
       || hbuf_reserve(&d->h_ptab, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb + sizeof(sla_hip_dec_emit) * nf) != 0
       || dbuf_reserve(&d->d_blocks, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb) != 0
       || dbuf_reserve(&d->d_info, sizeof(sla_hip_dec_info) * nb) != 0
@@ -578,31 +738,36 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
       || dbuf_reserve(&d->d_kint, sizeof(int32_t) * (size_t)nb * C * (f->order + 1)) != 0
       || dbuf_reserve(&d->d_planes, sizeof(int32_t) * (size_t)span * C) != 0
       || dbuf_reserve(&d->d_ftab, sizeof(sla_hip_dec_file) * nf) != 0) { return -1; }
-  for (i = 0; i < nf; i++) {
-    const sla_hip_decode_item* it = &items[files[i].item];
-    uint8_t* dst = (uint8_t*)d->h_img.ptr + files[i].img_off;
-    const uint32_t pad = (uint32_t)(((uint64_t)it->data_size + 3) & ~(uint64_t)3) - it->data_size;
-    if (pad != 0) { memset(dst + it->data_size, 0, pad); }
-    if (copy_add(cl, dst, it->data, it->data_size) != 0) { return -1; }
-  }
-  copy_run(cl);
   tb = (sla_hip_dec_block*)d->h_ptab.ptr;
   tend = (uint64_t*)(tb + nb);
-  for (i = 0, k = 0; i < nf; i++) {
-    const uint64_t end = files[i].img_off + items[files[i].item].data_size;
-    uint32_t b;
-    for (b = 0; b < files[i].nb; b++, k++) {
-      tb[k] = d->h_blocks[files[i].first + b];
-      tb[k].byte_off += files[i].img_off;
-      tb[k].smp_off += (uint32_t)files[i].plane_off;
-      tend[k] = end;
+  if (res) {
+    /* resident sources: the gather and the walk in write mode do on the device what the rest of this stage does here */
+    if (res_stage_pass(d, items, dev, files, nf, nb, img_bytes) != 0) { return -1; }
+  } else {
+    for (i = 0; i < nf; i++) {
+      const sla_hip_decode_item* it = &items[files[i].item];
+      uint8_t* dst = (uint8_t*)d->h_img.ptr + files[i].img_off;
+      const uint32_t pad = (uint32_t)(((uint64_t)it->data_size + 3) & ~(uint64_t)3) - it->data_size;
+      if (pad != 0) { memset(dst + it->data_size, 0, pad); }
+      if (copy_add(cl, dst, it->data, it->data_size) != 0) { return -1; }
     }
+    copy_run(cl);
+    for (i = 0, k = 0; i < nf; i++) {
+      const uint64_t end = files[i].img_off + items[files[i].item].data_size;
+      uint32_t b;
+      for (b = 0; b < files[i].nb; b++, k++) {
+        tb[k] = d->h_blocks[files[i].first + b];
+        tb[k].byte_off += files[i].img_off;
+        tb[k].smp_off += (uint32_t)files[i].plane_off;
+        tend[k] = end;
+      }
+    }
+    BCHK(hipMemcpyAsync(d->d_image.ptr, d->h_img.ptr, img_bytes, hipMemcpyHostToDevice, d->stream));
+    BCHK(hipMemcpyAsync(d->d_blocks.ptr, tb, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb, hipMemcpyHostToDevice, d->stream));
+    BCHK(hipMemsetAsync(d->d_info.ptr, 0, sizeof(sla_hip_dec_info) * nb, d->stream));
+    BCHK(hipStreamSynchronize(d->stream));
+    *t_up += now_ms() - t;
   }
-  BCHK(hipMemcpyAsync(d->d_image.ptr, d->h_img.ptr, img_bytes, hipMemcpyHostToDevice, d->stream));
-  BCHK(hipMemcpyAsync(d->d_blocks.ptr, tb, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb, hipMemcpyHostToDevice, d->stream));
-  BCHK(hipMemsetAsync(d->d_info.ptr, 0, sizeof(sla_hip_dec_info) * nb, d->stream));
-  BCHK(hipStreamSynchronize(d->stream));
-  *t_up += now_ms() - t;
 
   /* ---- the kernels, once each over all blocks of the pass */
   if (nb > 0) {
@@ -623,6 +788,7 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
     BCHK(hipEventRecord(d->ev[1], d->stream));
     BCHK(hipStreamSynchronize(d->stream));
     if (hipEventElapsedTime(&ms_k, d->ev[0], d->ev[1]) == hipSuccess) { *kernel_ms += ms_k; }
+    if (res && res_finish_pass(d, files, nf, t_up, t_walk) != 0) { return -1; }
   }
 
   /* ---- every file examined on its own, in file order, with decode_run's code */
@@ -633,7 +799,7 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
     sla_hip_decode_item* it = &items[files[i].item];
     uint32_t off = SLA_HEADER_SIZE, pos = 0;
     SLAApiResult result;
-    if (examine_blocks(d, it->data, d->h_blocks + files[i].first, d->h_info + files[i].first, files[i].nb, lms_ok,
+    if (examine_blocks(d, d->h_crcf + files[i].first, d->h_blocks + files[i].first, d->h_info + files[i].first, files[i].nb, lms_ok,
                        files[i].walk_err, NULL, &done[i], &off, &pos, &result)) {
       /* a block body that does not end where its size field says: the walk would resume where the reader stopped.
        * Rare (damaged or hand-made streams) -- the file is decoded again on its own, which is exact by construction. */
@@ -699,6 +865,7 @@ static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t 
   struct SLAWaveFormat wf_after;
   struct SLAEncodeParameter ep_after;
   uint32_t flag_after, nf = 0, nblocks = 0, passes = 0, i, p0;
+  const int res = (dev != NULL && dev->resident);
   int rc = 0;
   float kernel_ms = 0.0f;
   double t0 = now_ms(), t_walk = 0.0, t_up = 0.0, t_down = 0.0, t;
@@ -731,7 +898,12 @@ static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t 
 
   /* ---- files that share the launch parameters next to each other, each one's block chain walked */
   qsort(files, nf, sizeof(*files), bfile_cmp);
-  for (i = 0; i < nf; i++) {
+  if (res) {
+    /* on the device, all files in one launch (none is `alone` yet: that is decided for NULL planes, which device
+     * destinations do not have) */
+    if (res_count_walk(d, items, dev, files, nf, &nblocks) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+  }
+  for (i = 0; i < nf && !res; i++) {
     const sla_hip_decode_item* it = &items[files[i].item];
     uint32_t b;
     if (files[i].alone) { continue; }
@@ -758,7 +930,7 @@ static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t 
       if (p1 > p0 && (smp + s1 > SLA_HIP_DEC_BATCH_PASS || bytes + b1 > DEC_BATCH_PASS_BYTES)) { break; }
       smp += s1; bytes += b1; p1++;
     }
-    if (batch_pass(d, items, files + p0, p1 - p0, &cl, dev, &t_up, &t_down, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+    if (batch_pass(d, items, files + p0, p1 - p0, &cl, dev, &t_up, &t_walk, &t_down, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; goto out; }
     passes++;
     p0 = p1;
   }
@@ -768,7 +940,14 @@ static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t 
   for (i = 0; i < nf; i++) {
     sla_hip_decode_item* it = &items[files[i].item];
     if (!files[i].alone) { continue; }
-    it->result = decode_run(d, it->data, it->data_size, NULL, NULL, 0, it->buffer, it->buffer_num_samples, &it->output_num_samples, NULL);
+    if (res) {
+      /* a resident file that needs a resync: its bytes come to host staging and decode_run reads them there */
+      if (hbuf_reserve(&d->h_img, (size_t)it->data_size + 16) != 0
+          || hipMemcpyAsync(d->h_img.ptr, dev->items[files[i].item].data, it->data_size, hipMemcpyDeviceToHost, d->stream) != hipSuccess
+          || hipStreamSynchronize(d->stream) != hipSuccess) { rc = SLA_APIRESULT_NG; goto out; }
+    }
+    it->result = decode_run(d, res ? (const uint8_t*)d->h_img.ptr : it->data, it->data_size, NULL, NULL, 0, it->buffer, it->buffer_num_samples,
+                            &it->output_num_samples, NULL);
     if (dev != NULL) {
       sla_hip_dec_emit e;
       uint32_t max_lim = 0, ne;
@@ -865,7 +1044,7 @@ int sla_hip_decode_batch_device(struct SLADecoder* d, sla_hip_decode_device_item
   }
   if (num_items == 0) { memset(d->timing, 0, sizeof(d->timing)); return 0; }
   bi = (sla_hip_decode_item*)calloc(num_items, sizeof(*bi));
-  dev.items = items; dev.format = sample_format; dev.zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u;
+  dev.items = items; dev.format = sample_format; dev.zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u; dev.resident = 0;
   dev.state = (uint8_t*)calloc(num_items, 1);
   dev.chans = (uint32_t*)calloc(num_items, sizeof(uint32_t));
   if (bi == NULL || dev.state == NULL || dev.chans == NULL) { rc = SLA_APIRESULT_NG; goto out; }
@@ -884,6 +1063,86 @@ int sla_hip_decode_batch_device(struct SLADecoder* d, sla_hip_decode_device_item
   for (i = 0; i < num_items; i++) { items[i].result = bi[i].result; items[i].output_num_samples = bi[i].output_num_samples; }
 out:
   free(bi); free(dev.state); free(dev.chans);
+  return rc;
+}
+
+/* the handle's stream behind what the caller's stream holds at this moment */
+static int order_behind(struct SLADecoder* d, sla_hip_stream_t stream)
+{
+  if (d->ev_order == NULL && hipEventCreateWithFlags(&d->ev_order, hipEventDisableTiming) != hipSuccess) { d->ev_order = NULL; return -1; }
+  if (hipEventRecord(d->ev_order, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(d->stream, d->ev_order, 0) != hipSuccess) { return -1; }
+  return 0;
+}
+
+int sla_hip_decode_batch_resident(struct SLADecoder* d, sla_hip_decode_device_item* items, uint32_t num_items,
+                                  uint32_t sample_format, uint32_t flags, sla_hip_stream_t stream)
+{
+  sla_hip_decode_item* bi;
+  const uint8_t** src;
+  uint32_t* size;
+  uint8_t* ok;
+  dev_out_t dev;
+  uint32_t i;
+  int rc = 0;
+  double t_hdr;
+  if (d == NULL || (items == NULL && num_items > 0) || sample_format > SLA_HIP_PCM_F32 || (flags & ~SLA_HIP_DEC_ZERO_FILL) != 0) {
+    return SLA_APIRESULT_INVALID_ARGUMENT;
+  }
+  if (num_items == 0) { memset(d->timing, 0, sizeof(d->timing)); return 0; }
+  bi = (sla_hip_decode_item*)calloc(num_items, sizeof(*bi));
+  src = (const uint8_t**)calloc(num_items, sizeof(*src));
+  size = (uint32_t*)calloc(num_items, sizeof(*size));
+  ok = (uint8_t*)calloc(num_items, 1);
+  dev.items = items; dev.format = sample_format; dev.zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u; dev.resident = 1;
+  dev.state = (uint8_t*)calloc(num_items, 1);
+  dev.chans = (uint32_t*)calloc(num_items, sizeof(uint32_t));
+  if (bi == NULL || src == NULL || size == NULL || ok == NULL || dev.state == NULL || dev.chans == NULL) { rc = SLA_APIRESULT_NG; goto out; }
+  /* the sources, on the host, before anything of an item is read */
+  for (i = 0; i < num_items; i++) {
+    src[i] = items[i].data; size[i] = items[i].data_size;
+    ok[i] = (uint8_t)src_region_ok(items[i].data, items[i].data_size);
+  }
+  /* nothing is read or written before the caller's stream has reached this call */
+  if (order_behind(d, stream) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+  t_hdr = now_ms();
+  if (res_fetch_headers(d, src, size, ok, num_items) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+  t_hdr = now_ms() - t_hdr;
+  /* the destinations, with each header's channel count, before anything is written */
+  for (i = 0; i < num_items; i++) {
+    const sla_hip_decode_device_item* it = &items[i];
+    bi[i].data = (const uint8_t*)d->h_hdr.ptr + (size_t)i * RES_HDR_SLOT; bi[i].data_size = it->data_size;
+    bi[i].buffer_num_samples = it->capacity; bi[i].buffer = NULL;
+    if (!ok[i]) { dev.state[i] = DEV_REFUSED; continue; }
+    dev.chans[i] = header_channels(bi[i].data, it->data_size);
+    if (!dst_region_ok(it, dev.chans[i], (sample_format == SLA_HIP_PCM_S16) ? 2u : 4u)) { dev.state[i] = DEV_REFUSED; }
+  }
+  rc = batch_run(d, bi, num_items, &dev);
+  d->timing[0] += (float)t_hdr;
+  for (i = 0; i < num_items; i++) { items[i].result = bi[i].result; items[i].output_num_samples = bi[i].output_num_samples; }
+out:
+  free(bi); free((void*)src); free(size); free(ok); free(dev.state); free(dev.chans);
+  return rc;
+}
+
+int sla_hip_resident_headers(struct SLADecoder* d, const uint8_t* const* d_data, const uint32_t* data_size, uint32_t num,
+                             struct SLAHeaderInfo* headers, int32_t* results, sla_hip_stream_t stream)
+{
+  uint8_t* ok;
+  uint32_t i;
+  int rc = 0;
+  if (d == NULL || (num > 0 && (d_data == NULL || data_size == NULL || headers == NULL || results == NULL))) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num == 0) { return 0; }
+  ok = (uint8_t*)calloc(num, 1);
+  if (ok == NULL) { return SLA_APIRESULT_NG; }
+  for (i = 0; i < num; i++) { ok[i] = (uint8_t)src_region_ok(d_data[i], data_size[i]); }
+  if (order_behind(d, stream) != 0 || res_fetch_headers(d, d_data, data_size, ok, num) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+  for (i = 0; i < num; i++) {
+    memset(&headers[i], 0, sizeof(headers[i]));
+    results[i] = ok[i] ? (int32_t)SLADecoder_DecodeHeader((const uint8_t*)d->h_hdr.ptr + (size_t)i * RES_HDR_SLOT, data_size[i], &headers[i])
+                       : (int32_t)SLA_APIRESULT_INVALID_ARGUMENT;
+  }
+out:
+  free(ok);
   return rc;
 }
 

@@ -2129,6 +2129,18 @@ static int launch_searches(struct SLAEncoder* e, actx_t* a, int preset_blocks, i
 
   if (!preset_blocks) {
     if (a->clear_in_kernel) {
+      /* The kernel that clears on its way is the first search launch that has groups.  A range of nothing but silence
+       * (a piece of a streamed file, a gap that fills a chunk) has none, or none with a live super-frame, and no search
+       * kernel is launched: then the words are cleared here, as without the tile-sum search -- a fresh handle's d_spans
+       * holds whatever the allocation held, and the long-term audit counter behind the spans is read in any case. */
+      for (c = 0; c < a->nchunks && a->ck[c].grp_hi == a->ck[c].grp_lo; c++) { }
+      if (c == a->nchunks || a->ck[c].xg_hi == a->ck[c].xg_lo) {
+        a->clear_in_kernel = 0;
+        if (hipMemsetAsync(e->d_spans.ptr, 0, sizeof(unsigned long long) * SPAN_AREA_ULLS, e->stream) != hipSuccess
+            || (a->expand && hipMemsetAsync(e->d_run.ptr, 0, 16, e->stream) != hipSuccess)) { rc = SLA_APIRESULT_NG; }
+      }
+    }
+    if (a->clear_in_kernel) {
       /* (the first search launch of this analysis takes them along: search_launch, chunk 0) */
       a->clear_ptr[0] = (uint32_t*)e->d_spans.ptr; a->clear_words[0] = SPAN_AREA_ULLS * 2;
       a->clear_ptr[1] = (uint32_t*)e->d_or.ptr + 2; a->clear_words[1] = 1;
