@@ -891,6 +891,67 @@ int sla_hip_launch_enc_ingest_batch(const sla_hip_enc_ingest* d_files, uint32_t 
                                     uint32_t num_channels, uint32_t sample_format, int32_t* d_planes, uint64_t plane_stride,
                                     uint32_t* d_error, sla_hip_stream_t stream);
 
+/* sla_hip_encode_batch_device with the .sla bytes delivered to DEVICE memory: nothing of a file ever crosses the bus, so
+ * Decoder-side sla_hip_decode_batch_resident (or a collective, or a GPUDirect write) can take the files where they are.
+ * The item struct, the source side and the formats, the per-item source refusals, the pass grouping, the ingest, the
+ * ordering behind `stream` and the run in one piece (no worker lanes) are sla_hip_encode_batch_device's.  Result code,
+ * output_size and every byte of every file equal what that call on this handle gives for the same sources with a host
+ * buffer of the same capacity.
+ * Per-buffer mode (d_arena NULL): items[i].data is a device pointer of any byte alignment (slices of one big uint8 buffer
+ * are fine) with capacity data_size.  Per item, on the host before any device work, INVALID_ARGUMENT also for: NULL data, a
+ * data the runtime does not report as memory of the handle's device, a [data, data + data_size) that does not lie inside
+ * its allocation.  INSUFFICIENT_BUFFER_SIZE exactly where the host call gives it (data_size < 43, or the file does not fit).
+ * A refused or failed item gets output_size 0 and nothing of its buffer is written; a delivered one has exactly
+ * [data, data + output_size) written.  Overlapping destinations are undefined.
+ * Arena mode (d_arena non-NULL): data and data_size of every item are ignored on input; the delivered files are placed back
+ * to back, no padding, in [d_arena, d_arena + arena_bytes), and on output data is the file's first byte and output_size its
+ * size.  Placement follows delivery order: passes in item order; inside a pass the groups of equal offset_lshift in the
+ * order of each group's first item, items ascending inside a group -- a batch whose files share one offset_lshift and one
+ * pass lies in item order.  A running cursor starts at 0; a file that does not fit the remaining bytes gets
+ * INSUFFICIENT_BUFFER_SIZE, data NULL and output_size 0, the cursor stays and later files are still tried.  Refused items
+ * take no space and get data NULL.  An arena that is not memory of the handle's device or does not lie in one allocation:
+ * the call returns INVALID_ARGUMENT and touches no item.
+ * How it runs: per pack of a pass (one per offset_lshift group) the host builds every delivered file's 43-byte header into
+ * a table of sla_hip_enc_emit, one upload brings the table to the device and one sla_hip_launch_enc_emit_batch copies the
+ * files out of the pack image, headers in front, before the next group's pack reuses the image.  No block byte is copied to
+ * the host.  With option "verify" the decode-and-compare runs on the image as ever and the emit is launched only after the
+ * verdict is home: a file that fails gets SLA_APIRESULT_NG, nothing written and (arena mode) no arena space; the files that
+ * did not fit the arena were settled before the verdict and are not tried again in the room a failing file leaves.
+ * sla_hip_last_verify reports as for the host route.
+ * The call returns when every write has completed and no kernel reads a source any more.  Call-level refusals as for
+ * sla_hip_encode_batch_device -- then no item is touched. */
+int sla_hip_encode_batch_resident(struct SLAEncoder* encoder, sla_hip_encode_device_item* items, uint32_t num_items,
+                                  uint32_t sample_format, uint8_t* d_arena, uint64_t arena_bytes, sla_hip_stream_t stream);
+
+/* sla_hip_pack_device of the analysed file into a DEVICE buffer (any byte alignment): same preconditions, result codes and
+ * bytes, plus INVALID_ARGUMENT for a d_data that is not memory of the handle's device or whose [d_data, d_data + data_size)
+ * does not lie inside its allocation.  The blocks are written in a single run (no overlapped download: there is none) and
+ * one sla_hip_launch_enc_emit_batch delivers the file; on a refusal nothing is written.  Afterwards the handle holds the
+ * image as after sla_hip_pack_device: sla_hip_verify_last_image works on it. */
+int sla_hip_pack_resident(struct SLAEncoder* encoder, uint8_t* d_data, uint32_t data_size, uint32_t* output_size);
+
+/* The emit kernel of sla_hip_encode_batch_resident (k_enc_emit), the mirror of sla_hip_launch_dec_gather: entry k writes
+ * exactly [dst, dst + bytes): byte i is header[i] for i < header_bytes and d_image[img_off + i] otherwise.  No byte outside
+ * that range is written, not even with the value it already holds -- entries may be packed back to back, sharing 4-byte
+ * words and 16-byte chunks that other lanes write in the same launch: the head (with the header) and the tail of every
+ * destination go out as guarded byte stores, the interior as 16-byte stores to 16-byte-aligned chunks, each made from two
+ * aligned 16-byte loads.  Loads touch only the 16-byte words, aligned by ADDRESS, that hold at least one byte of
+ * [img_off, img_off + bytes) of the image: such a word may reach up to 15 bytes before d_image + img_off or past the file's
+ * end, so the image's allocation must be readable from the 16-byte boundary at or before its first file to the one at or
+ * behind its last (a d_image aligned to 16 bytes in an allocation padded to a multiple of 16 is; the driver's is).
+ * An entry is skipped whole when img_off + bytes exceeds image_bytes, when header_bytes is neither 0 nor 43, or when
+ * header_bytes > bytes.  max_bytes: the largest `bytes` of the table (sizes the grid).  d_image and the destinations must
+ * not overlap.  INVALID_ARGUMENT before any launch for a NULL table or image. */
+typedef struct sla_hip_enc_emit {
+  uint64_t img_off;               /* first byte of the file in d_image (any alignment) */
+  uint8_t* dst;                   /* device, any alignment */
+  uint32_t bytes;                 /* size of the file, header included */
+  uint32_t header_bytes;          /* 0 (bare image: copy everything) or 43 */
+  uint8_t  header[48];            /* the first header_bytes bytes of the file; the rest of the array is ignored */
+} sla_hip_enc_emit;               /* 72 bytes */
+int sla_hip_launch_enc_emit_batch(const sla_hip_enc_emit* d_table, uint32_t num_entries, uint32_t max_bytes,
+                                  const uint8_t* d_image, uint64_t image_bytes, sla_hip_stream_t stream);
+
 /* ---- one file, several GPUs ------------------------------------------------------------------------------
  * Blocks are independent (every filter and the coder reset per block, src/SLAEncoder.c:594-659), so the super-frames
  * of ONE file shard over the GPUs of a node, one process and one encoder handle per GPU.  Three facts of the whole
@@ -978,8 +1039,9 @@ int sla_hip_get_trace(struct SLAEncoder* encoder, sla_hip_trace* trace);
  * matrix pipe, k_ltm_acf_int; 0: from the FMA transform k_ltm_acf_fast.  Same bytes either way; every route that reaches
  * sla_hip_launch_ltm_cert_x honours it, worker lanes included).
  * "verify" (0 = default, 1): every call that packs on the device (sla_hip_pack_device, SLAEncoder_EncodeWhole plain and
- * streamed, sla_hip_encode_batch, sla_hip_encode_batch_device) decodes the finished block bytes on the device with the
- * decoder's kernels, while they cross the bus, and compares the result with the source planes; a file whose bytes do not
+ * streamed, sla_hip_encode_batch, sla_hip_encode_batch_device, sla_hip_encode_batch_resident, sla_hip_pack_resident)
+ * decodes the finished block bytes on the device with the decoder's kernels, while they cross the bus (the resident calls:
+ * before they are emitted), and compares the result with the source planes; a file whose bytes do not
  * decode back to its samples gets SLA_APIRESULT_NG (output_size 0 in a batch).  See sla_hip_last_verify; DESIGN section 2d.
  * "silence_runs" (0 = default: off; 1..65536: capacity of the list): input with silence no longer brings the prepass mask
  * (num_samples / 8 bytes, and a second wait) to the host: sla_hip_launch_zero_runs lists the zero runs that can matter

@@ -120,6 +120,12 @@ class EncodeDeviceItem(C.Structure):
                 ("num_samples", C.c_uint32), ("data_size", C.c_uint32), ("output_size", C.c_uint32), ("result", C.c_int32)]
 
 
+class EncEmit(C.Structure):
+    """sla_hip_enc_emit (include/sla_hip.h): one entry of sla_hip_launch_enc_emit_batch"""
+    _fields_ = [("img_off", C.c_uint64), ("dst", C.c_void_p), ("bytes", C.c_uint32), ("header_bytes", C.c_uint32),
+                ("header", C.c_uint8 * 48)]
+
+
 class LaunchExtra(C.Structure):
     """sla_hip_launch_extra (include/sla_hip.h): optional extras of one launch of an `_x` launcher; all zero = none"""
     _fields_ = [("d_span", C.c_void_p), ("d_group_count", C.c_void_p), ("clear_ptr", C.c_void_p * 3),
@@ -253,6 +259,11 @@ def lib():
             L.sla_hip_launch_dec_walk.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]
             L.sla_hip_launch_dec_gather.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+        if hasattr(L, "sla_hip_encode_batch_resident"):      # (SLA_HIP_LIB may name an older build in an A/B run)
+            L.sla_hip_encode_batch_resident.argtypes = [C.c_void_p, C.POINTER(EncodeDeviceItem), C.c_uint32, C.c_uint32,
+                                                        C.c_void_p, C.c_uint64, C.c_void_p]
+            L.sla_hip_pack_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, u32p]
+            L.sla_hip_launch_enc_emit_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
         _lib = L
     return _lib
 
@@ -305,6 +316,8 @@ EXPORTED_SYMBOLS = [
     "sla_hip_decode_batch_resident", "sla_hip_resident_headers", "sla_hip_launch_dec_walk", "sla_hip_launch_dec_gather",
     # batch encode from device memory (include/sla_hip.h)
     "sla_hip_encode_batch_device", "sla_hip_launch_enc_ingest_batch",
+    # batch encode to .sla streams that stay in device memory (include/sla_hip.h)
+    "sla_hip_encode_batch_resident", "sla_hip_pack_resident", "sla_hip_launch_enc_emit_batch",
     # verification of the encoded stream on the device (include/sla_hip.h)
     "sla_hip_launch_verify_blocks", "sla_hip_last_verify", "sla_hip_verify_last_image",
     # silence from a device-written run list (include/sla_hip.h)
@@ -460,9 +473,32 @@ class Encoder:
             raise ValueError("unknown sample format %r" % (sample_format,))
         if outs is not None and len(outs) != len(srcs):
             raise ValueError("%d outputs for %d files" % (len(outs), len(srcs)))
+        items = self._device_items(srcs, sample_format)
+        bufs = []
+        for i, x in enumerate(srcs):
+            n = x.shape[1]
+            if outs is not None:
+                buf, cap = outs[i], min(len(outs[i]), 0xFFFFFFFF)
+            else:
+                cap = capacities[i] if capacities is not None else 8 * self.num_channels * n + 65536
+                buf = np.empty(cap, np.uint8)
+            bufs.append(buf)
+            items[i].data = buf.ctypes.data_as(u8p)
+            items[i].data_size = cap
+        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        self._check(self._lib.sla_hip_encode_batch_device(self._h, items, len(srcs), sample_format, C.c_void_p(st.cuda_stream)),
+                    "sla_hip_encode_batch_device")
+        if outs is not None:
+            return [(int(items[i].result), bufs[i][:items[i].output_size]) for i in range(len(srcs))]
+        return [(int(items[i].result), bufs[i][:items[i].output_size].tobytes()) for i in range(len(srcs))]
+
+    def _device_items(self, srcs, sample_format):
+        """the source side of an EncodeDeviceItem array for 2-D device tensors [channel][sample] (encode_batch_from)"""
+        import torch
+        if sample_format not in Decoder._FORMAT_DTYPE:
+            raise ValueError("unknown sample format %r" % (sample_format,))
         want = getattr(torch, Decoder._FORMAT_DTYPE[sample_format])
         items = (EncodeDeviceItem * len(srcs))()
-        bufs = []
         for i, x in enumerate(srcs):
             if not isinstance(x, torch.Tensor) or x.dim() != 2:
                 raise ValueError("source %d: need a 2-D torch tensor [channel][sample]" % i)
@@ -475,12 +511,6 @@ class Encoder:
             n = x.shape[1]
             if n > 0xFFFFFFFF or min(x.stride()) < 0:
                 raise ValueError("source %d: unsupported shape %s / strides %s" % (i, tuple(x.shape), x.stride()))
-            if outs is not None:
-                buf, cap = outs[i], min(len(outs[i]), 0xFFFFFFFF)
-            else:
-                cap = capacities[i] if capacities is not None else 8 * self.num_channels * n + 65536
-                buf = np.empty(cap, np.uint8)
-            bufs.append(buf)
             cs, ss = x.stride(0), x.stride(1)
             if n <= 1:                                  # strides that are never stepped along: any valid value
                 ss = max(ss, 1)
@@ -489,14 +519,45 @@ class Encoder:
             items[i].channel_stride = cs
             items[i].sample_stride = ss
             items[i].num_samples = n
-            items[i].data = buf.ctypes.data_as(u8p)
-            items[i].data_size = cap
-        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
-        self._check(self._lib.sla_hip_encode_batch_device(self._h, items, len(srcs), sample_format, C.c_void_p(st.cuda_stream)),
-                    "sla_hip_encode_batch_device")
+        return items
+
+    def encode_resident_from(self, srcs, sample_format, outs=None, arena=None, stream=None):
+        """encode_batch_from with the .sla bytes delivered to device memory (sla_hip_encode_batch_resident): no byte of a
+        file crosses the bus.  srcs, sample_format and stream as for encode_batch_from.  Exactly one of outs and arena:
+        outs is a list of 1-D contiguous uint8 CUDA tensors, one per file (slices of a bigger tensor at any offset are
+        fine), arena one such tensor in which the library places the delivered files back to back in delivery order
+        (include/sla_hip.h).  Returns [(result code, uint8 tensor view of the file's bytes)], each what encode_batch_from
+        gives with a host buffer of the same room; where nothing was delivered the view is empty."""
+        import torch
+        if (outs is None) == (arena is None):
+            raise ValueError("exactly one of outs and arena")
+        for i, t in enumerate(outs if outs is not None else [arena]):
+            if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.uint8 or not t.is_contiguous() \
+                    or t.device.type != "cuda" or t.device.index != self.device_index:
+                raise ValueError("%s: need a 1-D contiguous uint8 tensor on cuda:%d"
+                                 % ("arena" if outs is None else "output %d" % i, self.device_index))
+        if outs is not None and len(outs) != len(srcs):
+            raise ValueError("%d outputs for %d files" % (len(outs), len(srcs)))
+        items = self._device_items(srcs, sample_format)
         if outs is not None:
-            return [(int(items[i].result), bufs[i][:items[i].output_size]) for i in range(len(srcs))]
-        return [(int(items[i].result), bufs[i][:items[i].output_size].tobytes()) for i in range(len(srcs))]
+            for i, t in enumerate(outs):
+                items[i].data = C.cast(C.c_void_p(t.data_ptr() or None), u8p)
+                items[i].data_size = min(t.numel(), 0xFFFFFFFF)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        self._check(self._lib.sla_hip_encode_batch_resident(self._h, items, len(srcs), sample_format,
+                                                            C.c_void_p(arena.data_ptr() or None) if arena is not None else None,
+                                                            arena.numel() if arena is not None else 0, C.c_void_p(st.cuda_stream)),
+                    "sla_hip_encode_batch_resident")
+        got = []
+        for i in range(len(srcs)):
+            size = int(items[i].output_size)
+            if outs is not None:
+                view = outs[i][:size]
+            else:
+                off = (C.cast(items[i].data, C.c_void_p).value or arena.data_ptr()) - arena.data_ptr()
+                view = arena[off:off + size]
+            got.append((int(items[i].result), view))
+        return got
 
     def encode_batch_tensor(self, x, lengths=None, layout="planar", right_justify=False):
         """a padded batch in one device tensor -> .sla bytes, the mirror of Decoder.decode_batch_tensor: x is [B][C][L]
@@ -504,6 +565,12 @@ class Encoder:
         The dtype picks the format: float32 -> PCM_F32, int16 -> PCM_S16, int32 -> PCM_S32_LEFT, or PCM_S32 with
         right_justify.  Returns encode_batch_from's [(result code, bytes)];
         enc.encode_batch_tensor(*dec.decode_batch_tensor(datas)[:2]) gives the files back."""
+        srcs, fmt = self._tensor_sources(x, lengths, layout, right_justify)
+        return self.encode_batch_from(srcs, fmt)
+
+    @staticmethod
+    def _tensor_sources(x, lengths, layout, right_justify):
+        """(the per-file 2-D views, the sample format) of encode_batch_tensor's arguments"""
         import torch
         if not isinstance(x, torch.Tensor) or x.dim() != 3:
             raise ValueError("need a 3-D torch tensor [B][C][L] or [B][L][C]")
@@ -521,8 +588,25 @@ class Encoder:
         lengths = [L] * B if lengths is None else [int(n) for n in lengths]
         if len(lengths) != B or any(n < 0 or n > L for n in lengths):
             raise ValueError("need %d lengths in [0, %d]" % (B, L))
-        srcs = [(x[b] if layout == "planar" else x[b].t())[:, :lengths[b]] for b in range(B)]
-        return self.encode_batch_from(srcs, fmt)
+        return [(x[b] if layout == "planar" else x[b].t())[:, :lengths[b]] for b in range(B)], fmt
+
+    def encode_resident_tensor(self, x, lengths=None, layout="planar", right_justify=False, capacity=None):
+        """encode_batch_tensor with the files left in device memory, the mirror of Decoder.decode_resident_tensor: one uint8
+        arena of `capacity` bytes (default: the sum of 4 * C * n + 65536 over the files) is allocated on the handle's
+        device and the files are placed in it back to back.  Returns (arena[:used], offsets, sizes, results), offsets and
+        sizes Python lists (0 and 0 where nothing was delivered);
+        dec.decode_resident_tensor([a[o:o + s] for o, s in zip(offsets, sizes)]) gives x back."""
+        import torch
+        srcs, fmt = self._tensor_sources(x, lengths, layout, right_justify)
+        if capacity is None:
+            capacity = sum(4 * self.num_channels * s.shape[1] + 65536 for s in srcs)
+        arena = torch.empty(max(int(capacity), 1), dtype=torch.uint8, device=torch.device("cuda", self.device_index))
+        got = self.encode_resident_from(srcs, fmt, arena=arena[:int(capacity)])
+        base = arena.data_ptr()
+        sizes = [int(v.numel()) for _, v in got]
+        offsets = [(v.data_ptr() - base) if n > 0 else 0 for (_, v), n in zip(got, sizes)]
+        used = max([o + n for o, n in zip(offsets, sizes)], default=0)
+        return arena[:used], offsets, sizes, [rc for rc, _ in got]
 
     def encode_block(self, pcm, capacity=None):
         pcm, ptrs = self._planes(pcm)
@@ -662,6 +746,18 @@ class Encoder:
         fn = self._lib.sla_hip_pack_device if on_device else self._lib.sla_hip_pack
         self._check(fn(self._h, out.ctypes.data_as(u8p), capacity, C.byref(size)), "sla_hip_pack")
         return out[:size.value].tobytes()
+
+    def pack_resident(self, out):
+        """sla_hip_pack_resident: pack(on_device=True) of the analysed file into `out`, a 1-D contiguous uint8 CUDA tensor
+        on the handle's device (a slice at any offset is fine); returns the view of `out` that holds the file"""
+        import torch
+        if not isinstance(out, torch.Tensor) or out.dim() != 1 or out.dtype != torch.uint8 or not out.is_contiguous() \
+                or out.device.type != "cuda" or out.device.index != self.device_index:
+            raise ValueError("need a 1-D contiguous uint8 tensor on cuda:%d" % self.device_index)
+        size = C.c_uint32(0)
+        self._check(self._lib.sla_hip_pack_resident(self._h, C.c_void_p(out.data_ptr() or None), min(out.numel(), 0xFFFFFFFF),
+                                                    C.byref(size)), "sla_hip_pack_resident")
+        return out[:size.value]
 
     def trace(self, want_residuals=True, max_blocks=None):
         tr = Trace(self.num_channels, self.order, self.ltm_order, self.num_samples,

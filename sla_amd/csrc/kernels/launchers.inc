@@ -829,3 +829,16 @@ extern "C" int sla_hip_launch_ltm_cert_x(const int32_t* d_residual, uint64_t pla
 #undef SLA_SOLVEL
   return hip_rc(hipGetLastError());
 }
+
+extern "C" int sla_hip_launch_enc_emit_batch(const sla_hip_enc_emit* d_table, uint32_t num_entries, uint32_t max_bytes,
+                                             const uint8_t* d_image, uint64_t image_bytes, sla_hip_stream_t stream)
+{
+  if (d_table == nullptr || d_image == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_entries == 0 || max_bytes == 0) { return 0; }
+  // a workgroup row covers 4096 bytes of a file (256 lanes x 16); longer files grid-stride
+  uint64_t gx = ((uint64_t)max_bytes + 15 + 4095) / 4096;
+  if (gx > 1024) { gx = 1024; }
+  const dim3 grid((uint32_t)gx, (num_entries < 65535u) ? num_entries : 65535u), block(256);
+  hipLaunchKernelGGL(k_enc_emit, grid, block, 0, (hipStream_t)stream, d_table, num_entries, d_image, image_bytes);
+  return hip_rc(hipGetLastError());
+}

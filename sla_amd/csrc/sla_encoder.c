@@ -189,6 +189,13 @@ struct SLAEncoder {
   int      image_valid;             /* d_image holds the one file of the last sla_hip_pack_device, h_pk_blocks its table */
   uint32_t img_nb, img_samples; uint64_t img_bytes;
 
+  /* sla_hip_encode_batch_resident / sla_hip_pack_resident: pack_device_core delivers the files with k_enc_emit to device
+   * memory instead of downloading them.  0: host buffers; 1: every file's data is a device buffer of its own; 2: the files
+   * are placed back to back in [arena, arena + arena_bytes) from arena_used on */
+  int      resident;
+  uint8_t* arena; uint64_t arena_bytes, arena_used;
+  devbuf_t d_emit; pinbuf_t h_emit;  /* the emit table */
+
   /* last analysis */
   const int32_t* pcm_dev;           /* borrowed or &d_pcm */
   uint64_t stride;
@@ -513,6 +520,8 @@ void SLAEncoder_Destroy(struct SLAEncoder* e)
   if (e->d_ingest.ptr != NULL) { (void)hipFree(e->d_ingest.ptr); }
   if (e->h_ingest.ptr != NULL) { (void)hipHostFree(e->h_ingest.ptr); }
   if (e->ev_order != NULL) { (void)hipEventDestroy(e->ev_order); }
+  if (e->d_emit.ptr != NULL) { (void)hipFree(e->d_emit.ptr); }
+  if (e->h_emit.ptr != NULL) { (void)hipHostFree(e->h_emit.ptr); }
   if (e->d_zruns.ptr != NULL) { (void)hipFree(e->d_zruns.ptr); }
   if (e->d_zscratch.ptr != NULL) { (void)hipFree(e->d_zscratch.ptr); }
   if (e->h_zruns.ptr != NULL) { (void)hipHostFree(e->h_zruns.ptr); }
@@ -3007,6 +3016,51 @@ int sla_hip_verify_last_image(struct SLAEncoder* e, const int32_t* d_pcm, uint64
   return verify_collect(e, &run, &rep, counters);
 }
 
+/* [p, p + bytes) is memory of `device` inside one allocation (bytes of any 64-bit size: two "samples" one apart) */
+static int device_bytes_ok(const void* p, uint64_t bytes, int device)
+{
+  return (bytes <= 1) ? slai_device_region_ok(p, 1, (uint32_t)bytes, 0, 1, 1, device)
+                      : slai_device_region_ok(p, 1, 2, 0, bytes - 1, 1, device);
+}
+
+/* Device delivery of the files of a pack (e->resident): every file that is still to be delivered gets its place (arena
+ * mode: at the cursor -- pack_device_core has settled that it fits) and its 43-byte header, built into the emit table; one
+ * upload, one k_enc_emit launch over the image of image_bytes bytes, and the wait for it: the table is the handle's, and
+ * the next pack overwrites the image. */
+static int emit_files(struct SLAEncoder* e, pack_seg_t* segs, uint32_t nsegs, uint64_t image_bytes)
+{
+  struct SLAHeaderInfo hinfo;
+  sla_hip_enc_emit* t;
+  uint32_t sg, n = 0, max_bytes = 0;
+  int rc;
+  RCCHK(pin_reserve(&e->h_emit, sizeof(sla_hip_enc_emit) * (size_t)nsegs));
+  RCCHK(dev_reserve(&e->d_emit, sizeof(sla_hip_enc_emit) * (size_t)nsegs));
+  t = (sla_hip_enc_emit*)e->h_emit.ptr;
+  for (sg = 0; sg < nsegs; sg++) {
+    if (segs[sg].result != 0) { continue; }
+    memset(&t[n], 0, sizeof(t[n]));
+    if (!segs[sg].bare) {
+      hinfo.wave_format = e->wave_format; hinfo.wave_format.offset_lshift = (uint8_t)e->lshift;
+      hinfo.encode_param = e->encode_param; hinfo.num_samples = segs[sg].hi - segs[sg].lo; hinfo.num_blocks = segs[sg].num_blocks;
+      hinfo.max_block_size = segs[sg].max_block; hinfo.max_bit_per_second = segs[sg].max_bps;
+      rc = slai_write_header(&hinfo, t[n].header, (uint32_t)sizeof(t[n].header));
+      if (rc != 0) { segs[sg].result = rc; continue; }
+      t[n].header_bytes = SLA_HEADER_SIZE;
+    }
+    if (e->resident == 2) { segs[sg].data = e->arena + e->arena_used; e->arena_used += segs[sg].out_size; }
+    t[n].img_off = segs[sg].img_off; t[n].dst = segs[sg].data; t[n].bytes = segs[sg].out_size;
+    if (segs[sg].out_size > max_bytes) { max_bytes = segs[sg].out_size; }
+    n++;
+  }
+  if (n > 0) {
+    HIPCHK(hipMemcpyAsync(e->d_emit.ptr, t, sizeof(sla_hip_enc_emit) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+    RCCHK(sla_hip_launch_enc_emit_batch((const sla_hip_enc_emit*)e->d_emit.ptr, n, max_bytes, (const uint8_t*)e->d_image.ptr,
+                                        image_bytes, e->stream));
+  }
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
 /* Rice code lengths, block assembly and CRC16 on the device for every file of the analysed planes (segs sorted by
  * position, blocks are), one image holding the files back to back; each file is then copied to its buffer and gets
  * its 43-byte header.  A file that does not fit its buffer is reported in its `result`, the others are delivered. */
@@ -3128,11 +3182,24 @@ static int pack_device_core(struct SLAEncoder* e, pack_seg_t* segs, uint32_t nse
     if (rc != 0) { return rc; }
     if (segs[0].out_size > segs[0].data_size) { segs[0].result = SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE; }
   }
-  if (nsegs == 1 && segs[0].result != 0) { return segs[0].result; }     /* one file: nothing worth assembling */
+  if (e->resident == 2) {
+    /* arena: what fits is settled here, in delivery order and before the verification pass, so that the pass covers the
+     * files a host buffer of the same room would get; emit_files gives the places */
+    uint64_t used = e->arena_used;
+    for (sg = 0; sg < nsegs; sg++) {
+      if (segs[sg].result != 0) { continue; }
+      if (segs[sg].out_size > e->arena_bytes - used) { segs[sg].result = SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE; } else { used += segs[sg].out_size; }
+    }
+  }
+  if (nsegs == 1 && segs[0].result != 0) {                              /* one file: nothing worth assembling */
+    /* (the arena: a file without room is that file's result, as in a larger group -- the cursor stays, the call goes on) */
+    return (e->resident == 2) ? 0 : segs[0].result;
+  }
 
   /* assemble the image on the device, bring it back with one copy */
   {
-    const size_t img_bytes = ((size_t)cur + 8 + 3) & ~(size_t)3;
+    /* (whole 16-byte words and one more: k_enc_emit and the verification pass read the aligned words that hold the last bytes) */
+    const size_t img_bytes = (((size_t)cur + 15) & ~(size_t)15) + 16;
     RCCHK(dev_reserve(&e->d_image, img_bytes));
     RCCHK(dev_reserve(&e->d_pk_blocks, sizeof(sla_hip_pack_block) * (nb + 1)));
     RCCHK(dev_reserve(&e->d_pk_hdr, hdr_used + 16));
@@ -3141,7 +3208,7 @@ static int pack_device_core(struct SLAEncoder* e, pack_seg_t* segs, uint32_t nse
     /* one file of some size: the blocks are written in up to four runs of about equal bytes, and a run's bytes leave
      * on the download stream while the next run is written (blocks are byte-aligned and only ever OR into their own
      * bytes, so a finished run is final even where it shares a word with its neighbour) */
-    uint32_t nruns = (nsegs == 1 && nb >= 64 && cur >= (8u << 20)) ? 4u : 1u, run_lo[5], r;
+    uint32_t nruns = (nsegs == 1 && nb >= 64 && cur >= (8u << 20) && !e->resident) ? 4u : 1u, run_lo[5], r;
     run_lo[0] = 0;
     for (r = 1; r < nruns; r++) {
       uint32_t lo = run_lo[r - 1], hi = nb;
@@ -3188,7 +3255,22 @@ static int pack_device_core(struct SLAEncoder* e, pack_seg_t* segs, uint32_t nse
       if (rc != 0) { (void)hipStreamSynchronize(e->stream); return rc; }
     }
     tp3 = now_ms();
-    if (verifying && nruns == 1) {
+    if (e->resident) {
+      /* delivery on the device: the verdict first -- a file that fails is not written and takes no room --, then one
+       * table, one k_enc_emit launch */
+      if (verifying) {
+        const uint64_t* rep;
+        uint64_t v[5];
+        RCCHK(verify_collect(e, &vrun, &rep, v));
+        verify_add(e, v);
+        for (sg = 0; sg < nsegs; sg++) {
+          if (segs[sg].result == 0 && (rep[3 * sg] != 0 || rep[3 * sg + 2] != 0)) { segs[sg].result = SLA_APIRESULT_NG; }
+        }
+        verifying = 0;
+      }
+      rc = emit_files(e, segs, nsegs, cur);
+      if (rc != 0) { (void)hipStreamSynchronize(e->stream); return rc; }
+    } else if (verifying && nruns == 1) {
       for (sg = 0; sg < nsegs; sg++) {
         if (segs[sg].result != 0) { continue; }
         rc = download_bytes_after(e, segs[sg].data, (const uint8_t*)e->d_image.ptr + segs[sg].img_off, (size_t)segs[sg].out_size, e->ev_pack[0]);
@@ -3220,11 +3302,11 @@ static int pack_device_core(struct SLAEncoder* e, pack_seg_t* segs, uint32_t nse
     tp4 = now_ms();
   }
   if (e->trace) {
-    fprintf(stderr, "[sla_hip] pack: headers + jobs %.3f ms, k_rice_len + sizes home %.3f ms, offsets + launches %.3f ms, write/crc kernels + download %.3f ms\n",
-            tp1 - tp0, tp2 - tp1, tp3 - tp2, tp4 - tp3);
+    fprintf(stderr, "[sla_hip] pack: headers + jobs %.3f ms, k_rice_len + sizes home %.3f ms, offsets + launches %.3f ms, write/crc kernels + %s %.3f ms\n",
+            tp1 - tp0, tp2 - tp1, tp3 - tp2, e->resident ? "emit" : "download", tp4 - tp3);
   }
   for (sg = 0; sg < nsegs; sg++) {
-    if (segs[sg].result != 0 || segs[sg].bare) { continue; }
+    if (segs[sg].result != 0 || segs[sg].bare || e->resident) { continue; }      /* (resident: the emit wrote the headers) */
     hinfo.wave_format = e->wave_format; hinfo.wave_format.offset_lshift = (uint8_t)e->lshift;
     hinfo.encode_param = e->encode_param; hinfo.num_samples = segs[sg].hi - segs[sg].lo; hinfo.num_blocks = segs[sg].num_blocks;
     hinfo.max_block_size = segs[sg].max_block; hinfo.max_bit_per_second = segs[sg].max_bps;
@@ -3247,6 +3329,29 @@ int sla_hip_pack_device(struct SLAEncoder* e, uint8_t* data, uint32_t data_size,
   memset(&seg, 0, sizeof(seg));
   seg.lo = 0; seg.hi = e->num_samples; seg.data = data; seg.data_size = data_size;
   rc = pack_device_core(e, &seg, 1);
+  if (rc != 0) { return rc; }
+  if (seg.result != 0) { return seg.result; }
+  *output_size = seg.out_size;
+  return 0;
+}
+
+/* sla_hip_pack_device into device memory (include/sla_hip.h): the same pack, delivered by k_enc_emit */
+int sla_hip_pack_resident(struct SLAEncoder* e, uint8_t* d_data, uint32_t data_size, uint32_t* output_size)
+{
+  pack_seg_t seg;
+  int rc;
+  if (e == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (!e->analysed) { return SLA_APIRESULT_PARAMETER_NOT_SET; }
+  if (d_data == NULL || output_size == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (data_size < SLA_HEADER_SIZE) { return SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE; }
+  RCCHK(enter(e));
+  if (!device_bytes_ok(d_data, data_size, e->device)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  verify_clear(e);
+  memset(&seg, 0, sizeof(seg));
+  seg.lo = 0; seg.hi = e->num_samples; seg.data = d_data; seg.data_size = data_size;
+  e->resident = 1;
+  rc = pack_device_core(e, &seg, 1);
+  e->resident = 0;
   if (rc != 0) { return rc; }
   if (seg.result != 0) { return seg.result; }
   *output_size = seg.out_size;
@@ -3996,6 +4101,9 @@ static int encode_batch_pass(struct SLAEncoder* e, sla_hip_batch_item* items, ui
     rc = pack_device_core(e, segs, ns);
     if (rc != 0) { goto done; }
     for (s = 0; s < ns; s++) { items[seg_item[s]].result = segs[s].result; items[seg_item[s]].output_size = (segs[s].result == 0) ? segs[s].out_size : 0; }
+    if (e->resident == 2) {                                 /* the arena: where each delivered file was placed */
+      for (s = 0; s < ns; s++) { items[seg_item[s]].data = (segs[s].result == 0) ? segs[s].data : NULL; }
+    }
   }
 done:
   e->batch_stamp[3] = now_ms();
@@ -4208,9 +4316,12 @@ int sla_hip_encode_batch(struct SLAEncoder* e, sla_hip_batch_item* items, uint32
 /* Many files from caller-owned device memory (include/sla_hip.h).  The items become sla_hip_batch_item copies -- sizes and
  * buffers; a refused item gets no samples and no buffer, so the pass answers it INVALID_ARGUMENT without reading or writing
  * anything of it -- and go through encode_batch_pass with the ingest kernel as the upload leg, passes grouped exactly as in
- * sla_hip_encode_batch.  No worker lanes: they exist to overlap host uploads, and there are none here. */
-int sla_hip_encode_batch_device(struct SLAEncoder* e, sla_hip_encode_device_item* items, uint32_t num_items,
-                                uint32_t sample_format, sla_hip_stream_t stream)
+ * sla_hip_encode_batch.  No worker lanes: they exist to overlap host uploads, and there are none here.
+ * resident 0: the host delivery of sla_hip_encode_batch_device; 1 / 2: sla_hip_encode_batch_resident into the items' device
+ * buffers / into the arena -- pack_device_core then delivers with k_enc_emit and no block byte crosses the bus. */
+static int encode_batch_device_impl(struct SLAEncoder* e, sla_hip_encode_device_item* items, uint32_t num_items,
+                                    uint32_t sample_format, sla_hip_stream_t stream, int resident, uint8_t* d_arena,
+                                    uint64_t arena_bytes)
 {
   sla_hip_batch_item* bi;
   ingest_src_t dev;
@@ -4224,6 +4335,7 @@ int sla_hip_encode_batch_device(struct SLAEncoder* e, sla_hip_encode_device_item
   }
   if (num_items == 0) { return 0; }
   RCCHK(enter(e));
+  if (resident == 2 && !device_bytes_ok(d_arena, arena_bytes, e->device)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   verify_clear(e);
   memset(e->sil_stat, 0, sizeof(e->sil_stat));
   C = e->wave_format.num_channels;
@@ -4232,14 +4344,16 @@ int sla_hip_encode_batch_device(struct SLAEncoder* e, sla_hip_encode_device_item
   if (bi == NULL) { return SLA_APIRESULT_NG; }
   for (i = 0; i < num_items; i++) {
     const sla_hip_encode_device_item* it = &items[i];
-    int ok = (it->data != NULL && it->sample_stride != 0 && (C <= 1 || it->channel_stride != 0));
+    int ok = ((resident == 2 || it->data != NULL) && it->sample_stride != 0 && (C <= 1 || it->channel_stride != 0));
     if (ok) {
       ok = (it->src == NULL) ? (it->num_samples == 0)
                              : slai_device_region_ok(it->src, C, it->num_samples, it->channel_stride, it->sample_stride, esize, e->device);
     }
+    if (ok && resident == 1) { ok = device_bytes_ok(it->data, it->data_size, e->device); }
     bi[i].num_samples = ok ? it->num_samples : 0;
-    bi[i].data = ok ? it->data : NULL;
-    bi[i].data_size = it->data_size;
+    /* (the arena: a stand-in until the file is placed, and no capacity of its own -- pack_device_core sees to the room) */
+    bi[i].data = !ok ? NULL : (resident == 2) ? d_arena : it->data;
+    bi[i].data_size = (resident == 2) ? 0xFFFFFFFFu : it->data_size;
   }
   /* nothing is read before the caller's stream has reached this call */
   if (e->ev_order == NULL && hipEventCreateWithFlags(&e->ev_order, hipEventDisableTiming) != hipSuccess) { e->ev_order = NULL; free(bi); return SLA_APIRESULT_NG; }
@@ -4247,6 +4361,7 @@ int sla_hip_encode_batch_device(struct SLAEncoder* e, sla_hip_encode_device_item
     free(bi); return SLA_APIRESULT_NG;
   }
   dev.items = items; dev.format = sample_format;
+  e->resident = resident; e->arena = d_arena; e->arena_bytes = arena_bytes; e->arena_used = 0;
   while (first < num_items) {
     uint64_t span = 0;
     uint32_t count = 0;
@@ -4256,16 +4371,36 @@ int sla_hip_encode_batch_device(struct SLAEncoder* e, sla_hip_encode_device_item
       span += add; count++;
     }
     rc = encode_batch_pass(e, bi, first, count, &dev);
-    if (rc != 0) { free(bi); return (rc > 0) ? rc : SLA_APIRESULT_NG; }
+    if (rc != 0) { break; }
     if (e->trace) {
-      fprintf(stderr, "[sla_hip] encode_batch_device pass of %u files: ingest + prepass %.3f ms, analysis %.3f ms, pack + download %.3f ms\n", count,
-              e->batch_stamp[1] - e->batch_stamp[0], e->batch_stamp[2] - e->batch_stamp[1], e->batch_stamp[3] - e->batch_stamp[2]);
+      fprintf(stderr, "[sla_hip] %s pass of %u files: ingest + prepass %.3f ms, analysis %.3f ms, pack + %s %.3f ms\n",
+              resident ? "encode_batch_resident" : "encode_batch_device", count, e->batch_stamp[1] - e->batch_stamp[0],
+              e->batch_stamp[2] - e->batch_stamp[1], resident ? "emit" : "download", e->batch_stamp[3] - e->batch_stamp[2]);
     }
-    for (i = first; i < first + count; i++) { items[i].result = bi[i].result; items[i].output_size = bi[i].output_size; }
+    for (i = first; i < first + count; i++) {
+      items[i].result = bi[i].result; items[i].output_size = bi[i].output_size;
+      if (resident == 2) { items[i].data = (bi[i].result == 0) ? bi[i].data : NULL; }
+    }
     first += count;
   }
+  e->resident = 0; e->arena = NULL; e->arena_bytes = 0;
   free(bi);
+  if (rc != 0) { return (rc > 0) ? rc : SLA_APIRESULT_NG; }
   return 0;
+}
+
+int sla_hip_encode_batch_device(struct SLAEncoder* e, sla_hip_encode_device_item* items, uint32_t num_items,
+                                uint32_t sample_format, sla_hip_stream_t stream)
+{
+  return encode_batch_device_impl(e, items, num_items, sample_format, stream, 0, NULL, 0);
+}
+
+/* The same call with the files delivered to device memory (include/sla_hip.h): the items' own buffers, or back to back in
+ * the caller's arena. */
+int sla_hip_encode_batch_resident(struct SLAEncoder* e, sla_hip_encode_device_item* items, uint32_t num_items,
+                                  uint32_t sample_format, uint8_t* d_arena, uint64_t arena_bytes, sla_hip_stream_t stream)
+{
+  return encode_batch_device_impl(e, items, num_items, sample_format, stream, (d_arena != NULL) ? 2 : 1, d_arena, arena_bytes);
 }
 
 /* One block with the encoder's current offset_lshift; no partition search (src/SLAEncoder.c:458-801). */

@@ -29,6 +29,7 @@
 //   k_rice_k/_k2/_bits/_write,            src/SLACoder.c:45-83,120-139,165-271,388-467 (Golomb, gamma, recursive Rice, PutDataArray),
 //   k_block_crc, k_unpack16/24 (pack)     src/SLAEncoder.c:682-798 (block assembly), src/SLAUtility.c:321-339 (CRC16)
 //   k_enc_ingest_batch (ingest)           no counterpart: caller-owned device PCM into the planes of a batch pass
+//   k_enc_emit (emit)                     no counterpart: the files of a pack image into caller-owned device memory, headers in front
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <float.h>
@@ -101,6 +102,7 @@ __device__ __forceinline__ uint32_t umax_wave(uint32_t v)
 #include "kernels/lattice.inc"
 #include "kernels/tail.inc"
 #include "kernels/longterm.inc"
+#include "kernels/emit.inc"
 #include "kernels/launchers.inc"
 #include "kernels/pack.inc"
 #include "kernels/ingest.inc"
