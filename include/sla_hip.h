@@ -244,7 +244,10 @@ int sla_hip_launch_lpc(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid
 
 /* Chosen blocks in one launch: sla_hip_launch_lpc in its quantiser form (one candidate per group = the whole
  * block) followed, inside the same workgroups, by the PARCOR lattice of sla_hip_launch_lattice with the
- * coefficients just quantised -> d_lattice_residual (plane layout of d_pcm). */
+ * coefficients just quantised -> d_lattice_residual (plane layout of d_pcm).  Orders up to
+ * SLA_HIP_FUSED_LATTICE_MAX_ORDER (the recursion runs with one lane of a wave per coefficient, k[0] included);
+ * SLA_APIRESULT_INVALID_ARGUMENT above. */
+#define SLA_HIP_FUSED_LATTICE_MAX_ORDER 63u
 int sla_hip_launch_lpc_blocks(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
                               const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
                               const sla_hip_lpc_cand* d_cands, const double* d_window_pool,
@@ -260,7 +263,7 @@ int sla_hip_launch_lpc_blocks(const int32_t* d_pcm, uint64_t plane_stride, uint3
  * ends.  d_cert_flag[slot]: 0 = certified, 2 = exact (4 / 5: audited, see sla_hip_tuning.cert_audit).  safety >= 1 scales the
  * certificate's bound (the encoder: 16).  The bound is a FIRST-ORDER perturbation bound of the Levinson-Durbin recursion times
  * that factor, validated empirically -- not a proof; the audit is the standing check on it.
- * Orders above 52 are not covered (SLA_APIRESULT_EXCEED_HANDLE_CAPACITY): use sla_hip_launch_lpc. */
+ * Orders above 51 (more than 52 lags) are not covered (SLA_APIRESULT_EXCEED_HANDLE_CAPACITY): use sla_hip_launch_lpc. */
 int sla_hip_launch_lpc_blocks_cert(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
                                    const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
                                    const sla_hip_lpc_cand* d_cands, const double* d_window_pool,

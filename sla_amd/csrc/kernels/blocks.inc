@@ -236,7 +236,7 @@ void lpc_blocks_body(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t 
     if (wv < ng) {
       const sla_hip_lpc_group g = s_g[wv];
       double* o = out + (uint64_t)g.slot_first * O2;
-      if (lane <= order) { o[1 + lane] = r[wv * O1 + lane]; }
+      for (uint32_t i = lane; i <= order; i += 64) { o[1 + i] = r[wv * O1 + i]; }      // (order 64: r[64] has no lane of its own)
       if (lane == 0) {
         const uint32_t m = s_maxabs[wv];
         const uint32_t l2c = (m > 1) ? (32u - (uint32_t)__builtin_clz(m - 1u)) : 0u;    // src/SLAUtility.c:677-696

@@ -190,7 +190,7 @@ extern "C" int sla_hip_launch_lpc_blocks_cert_x(const int32_t* d_pcm, uint64_t p
   }
   if (order < 1 || max_window == 0 || bits_per_sample == 0 || bits_per_sample > 32 || !(safety >= 1.0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   const uint32_t lags = sla_hip_search_exact_lags(order);
-  if (lags == 0) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }      // orders above 52: the exact kernels only
+  if (lags == 0) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }      // orders above 51 (more than 52 lags): the exact kernels only
   if (num_groups == 0) { return 0; }
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipSuccess;
@@ -264,6 +264,8 @@ static int launch_lpc_impl(const int32_t* d_pcm, uint64_t plane_stride, uint32_t
   if (d_code != nullptr && order <= 64 && (!tune.lpc_blocks_chains || list != nullptr)) {
     // chosen blocks: term tiles + lane-parallel Levinson (k_lpc_blocks)
     if (d_window_pool == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+    // the recursion inside k_lpc_blocks (the fused lattice needs it there) keeps coefficient j in lane j: orders up to 63
+    if (d_lat_residual != nullptr && order > SLA_HIP_FUSED_LATTICE_MAX_ORDER) { return SLA_APIRESULT_INVALID_ARGUMENT; }
     uint32_t pmax = 64 / order;
     if (pmax > LPC_MAX_PACK) { pmax = LPC_MAX_PACK; }
     if (pmax > 2) { pmax = 2; }
@@ -295,7 +297,7 @@ static int launch_lpc_impl(const int32_t* d_pcm, uint64_t plane_stride, uint32_t
 #endif
       // Levinson-Durbin + quantiser: in registers, one lane per window (k_blocks_finish), unless the lattice is fused in
       // (it needs the coefficients inside the workgroup)
-      const uint32_t defer = (d_lat_residual == nullptr && order <= 64) ? 1u : 0u;
+      const uint32_t defer = (d_lat_residual == nullptr) ? 1u : 0u;
       if (spl == 12) {
         hipLaunchKernelGGL((k_lpc_blocks<12, 24>), grid, block, bytes, (hipStream_t)stream, d_pcm, plane_stride, mid_side, order,
                            d_groups, num_groups, p, d_window_pool, d_out, d_code, d_kint, d_rshift, (uint32_t)xr, nch, clk, span, d_lat_residual, defer, list, list_count);
@@ -407,7 +409,7 @@ extern "C" int sla_hip_launch_search_exact_x(const int32_t* d_pcm, uint64_t plan
   // |x| < 2 in the search's unit (mid/side: side = l - r), so a window's energy stays below 4 x its length: when even
   // that is under the limit (16-bit material) every group takes the exact path and one launch does
   const bool all_exact = (exact_limit >= 4.0 * (double)max_window);
-  const int pclass = (order <= 16) ? 16 : (order <= 32) ? 32 : (order <= 48) ? 48 : 64;      // (lags != 0: order <= 52)
+  const int pclass = (order <= 16) ? 16 : (order <= 32) ? 32 : (order <= 48) ? 48 : 64;      // (lags != 0: order <= 51)
 #define SLA_FINISH(PP) do { \
     if (all_exact) { \
       e = ensure_dynamic_lds((const void*)k_search_finish<PP, 0>, lds_r); \

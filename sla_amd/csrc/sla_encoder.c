@@ -794,6 +794,18 @@ static void actx_free(actx_t* a)
   if (!a->borrowed) { free(a->sf); free(a->shapes); }
 }
 
+/* Candidates one search group may carry so that k_lpc's LDS stays inside SLA_HIP_LDS_BUDGET (launch_lpc_impl): per candidate
+ * order + 1 doubles of r[] behind the window, and the 2 (order + 2) doubles of Levinson work vectors that overlay the window
+ * and widen it where they are the larger of the two (order 255: from 16 candidates on a 8192-sample window).  At least 1
+ * for every window and order SLAEncoder_SetEncodeParameter accepts (16384 samples, order 255: 15). */
+static uint32_t search_cands_per_group(uint32_t window, uint32_t order)
+{
+  const size_t budget = SLA_HIP_LDS_BUDGET / 8, O1 = (size_t)order + 1;
+  const size_t by_window = (budget > window) ? (budget - window) / O1 : 0;
+  const size_t by_overlay = budget / (2 * ((size_t)order + 2) + O1);
+  return (uint32_t)((by_window < by_overlay) ? by_window : by_overlay);
+}
+
 /* prepass + whole-file tables: offset_lshift, super-frames, candidate shapes, search groups */
 static double g_trace_t0;
 #define PTRACE(label) do { if (g_trace_on) { fprintf(stderr, "[sla_hip]   prepare +%7.3f ms  %s\n", now_ms() - g_trace_t0, (label)); } } while (0)
@@ -803,7 +815,7 @@ static double g_trace_t0;
 static int build_tables(struct SLAEncoder* e, actx_t* a, const slai_silence* sil)
 {
   const uint32_t C = e->wave_format.num_channels, bps = e->wave_format.bit_per_sample;
-  const uint32_t order = e->encode_param.parcor_order, O1 = order + 1;
+  const uint32_t order = e->encode_param.parcor_order;
   const uint32_t n = e->num_samples, maxb = e->encode_param.max_num_block_samples;
   extern uint32_t sla_hip_lattice_chunk_samples(uint32_t order);
   const uint32_t chunk_samples = sla_hip_lattice_chunk_samples(order);
@@ -885,16 +897,20 @@ static int build_tables(struct SLAEncoder* e, actx_t* a, const slai_silence* sil
   }
 
   PTRACE("candidate + window tables");
-  /* search groups: (super-frame, channel), candidates sliced so that window + r[] fits the LDS budget */
+  /* search groups: (super-frame, channel), candidates sliced so that k_lpc's LDS fits the budget.  One launch serves every
+   * shape, sized by the longest window and the largest slice of the file, so the slice is that of the longest window */
+  a->max_window = 1;
+  for (i = 0; i < a->nsf; i++) {
+    if (a->sf[i].shape != 0xFFFFFFFFu && a->shapes[a->sf[i].shape].window > a->max_window) { a->max_window = a->shapes[a->sf[i].shape].window; }
+  }
   {
     uint32_t total_groups = 1;
     for (i = 0; i < a->nsf; i++) {
       const shape_t* sh;
-      size_t room; uint32_t cpg;
+      uint32_t cpg;
       if (a->sf[i].shape == 0xFFFFFFFFu) { continue; }
       sh = &a->shapes[a->sf[i].shape];
-      room = (SLA_HIP_LDS_BUDGET / 8 > sh->window) ? (SLA_HIP_LDS_BUDGET / 8 - sh->window) : 0;
-      cpg = (uint32_t)(room / O1);
+      cpg = search_cands_per_group(a->max_window, order);
       if (cpg == 0) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
       if (cpg > sh->ncand) { cpg = sh->ncand; }
       total_groups += C * ((sh->ncand + cpg - 1) / cpg);
@@ -906,7 +922,7 @@ static int build_tables(struct SLAEncoder* e, actx_t* a, const slai_silence* sil
    * could not certify -- the exception.  Here they are only counted; search_groups_ready() writes and uploads them for whoever
    * needs them (an hour of stereo: 84 k descriptors, 3.4 MB, built and sent for nothing on every file whose tables are new). */
   e->groups_valid = 0;
-  a->max_window = 1; a->max_cpg = 1; a->max_xcands = 1;
+  a->max_cpg = 1; a->max_xcands = 1;
   /* candidates start on multiples of SLAI_SEARCH_DELTA and end on one or with the window: tile aligned */
   a->exact = (e->search_exact && SLAI_SEARCH_DELTA == SLA_HIP_XTILE && maxb <= SLA_HIP_XTILE * SLA_HIP_XTILES
               && sla_hip_search_exact_lags(order) != 0 && e->h_or[0] != 0);
@@ -917,7 +933,7 @@ static int build_tables(struct SLAEncoder* e, actx_t* a, const slai_silence* sil
     f->grp_lo = f->grp_hi = a->nsgroups;
     if (f->shape == 0xFFFFFFFFu) { continue; }
     sh = &a->shapes[f->shape];
-    cpg = (uint32_t)((SLA_HIP_LDS_BUDGET / 8 - sh->window) / O1);
+    cpg = search_cands_per_group(a->max_window, order);
     if (cpg > sh->ncand) { cpg = sh->ncand; }
     f->slot_base = a->nslots;
     for (ch = 0; ch < C; ch++) {
@@ -950,7 +966,6 @@ static int pipeline_reserve(struct SLAEncoder* e, const actx_t* a);
 static int search_groups_ready(struct SLAEncoder* e, const actx_t* a)
 {
   const uint32_t C = e->wave_format.num_channels, bps = e->wave_format.bit_per_sample;
-  const uint32_t O1 = e->encode_param.parcor_order + 1;
   sla_hip_lpc_group* groups = (sla_hip_lpc_group*)e->h_groups.ptr;
   uint32_t i;
   if (e->groups_valid || a->nsgroups == 0) { return 0; }
@@ -961,7 +976,7 @@ static int search_groups_ready(struct SLAEncoder* e, const actx_t* a)
     uint32_t cpg, ch, first, g = f->grp_lo;
     if (f->shape == 0xFFFFFFFFu) { continue; }
     sh = &a->shapes[f->shape];
-    cpg = (uint32_t)((SLA_HIP_LDS_BUDGET / 8 - sh->window) / O1);
+    cpg = search_cands_per_group(a->max_window, e->encode_param.parcor_order);
     if (cpg > sh->ncand) { cpg = sh->ncand; }
     for (ch = 0; ch < C; ch++) {
       for (first = 0; first < sh->ncand; first += cpg) {
@@ -1509,7 +1524,7 @@ static int search_launch(struct SLAEncoder* e, actx_t* a, uint32_t c)
          * tables are written instead of 40 - 50 us later, when the host has seen the counts and made its first launches;
          * by then it only has to queue the lattice behind them.  (Long files: their idle workgroups would cost more.) */
         a->prelaunched = 0;
-        if (c == 0 && a->nchunks == 1 && e->cert_now && !(e->fuse_lattice && order <= 64) && (uint64_t)a->nsf * C <= SPECULATE_MAX_GROUPS
+        if (c == 0 && a->nchunks == 1 && e->cert_now && !(e->fuse_lattice && order <= SLA_HIP_FUSED_LATTICE_MAX_ORDER) && (uint64_t)a->nsf * C <= SPECULATE_MAX_GROUPS
             && e->device_ltm && e->prelaunch) {
           const uint32_t ms2 = (e->encode_param.ch_process_method == SLA_CHPROCESSMETHOD_STEREO_MS);
           const hipStream_t ps = a->one_stream ? e->stream : e->stream2;      /* the stream blocks_launch will continue on */
@@ -1695,9 +1710,9 @@ static int blocks_launch(struct SLAEncoder* e, actx_t* a, uint32_t c, int mode)
   sla_hip_acf_job* acf_jobs = (sla_hip_acf_job*)e->h_acf_jobs.ptr;
   hipEvent_t* ev = a->ev + (size_t)c * EV_PER_CHUNK;
   uint32_t b, ch, max_window = 1, ng, nl;
-  const int fused = (e->fuse_lattice && order <= 64);
+  const int fused = (e->fuse_lattice && order <= SLA_HIP_FUSED_LATTICE_MAX_ORDER);
   const int use_cert = e->cert_now;
-  const int pre = (use_cert && mode == 1 && c == 0 && a->prelaunched && !(e->fuse_lattice && order <= 64));
+  const int pre = (use_cert && mode == 1 && c == 0 && a->prelaunched && !(e->fuse_lattice && order <= SLA_HIP_FUSED_LATTICE_MAX_ORDER));
   const size_t cnt_base = (size_t)a->blocks_bound * C + 1;      /* h_cert_flag: per-slot flags, then one fallback count per chunk */
   /* option alt_streams: odd chunks run their block stage on the third stream, beside the even chunks' (not when the FFT
    * works in the shared global scratch) */
@@ -2183,7 +2198,7 @@ static int run_pipeline(struct SLAEncoder* e, int preset_blocks)
   e->image_valid = 0;                /* a new analysis: whatever image a pack left belongs to other tables */
   memset(e->ltm_stat, 0, sizeof(e->ltm_stat));
   e->ltm_cert_now = (e->ltm_cert && e->device_ltm && sla_hip_ltm_cert_supported(slai_fft_plan_size(e->fft)));
-  e->cert_now = (e->block_cert && !(e->fuse_lattice && e->encode_param.parcor_order <= 64) && !e->tune.lpc_blocks_chains
+  e->cert_now = (e->block_cert && !(e->fuse_lattice && e->encode_param.parcor_order <= SLA_HIP_FUSED_LATTICE_MAX_ORDER) && !e->tune.lpc_blocks_chains
                  && sla_hip_search_exact_lags(e->encode_param.parcor_order) != 0);
   a.trace = trace; a.t_begin = t_begin;
   a.fast_rice = (!preset_blocks && e->device_ltm && e->single_tail);

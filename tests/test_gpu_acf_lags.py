@@ -100,7 +100,7 @@ def _expected_tiles(w, order, scale):
 
 
 @pytest.mark.parametrize("ms", [0, 1])
-@pytest.mark.parametrize("order", [16, 32, 48, 15, 18, 31])
+@pytest.mark.parametrize("order", [16, 32, 48, 15, 18, 31, 49, 51])
 def test_tile_sums_are_the_exact_integers(hip, noise, order, ms):
     import torch
     L = hip.lib()
@@ -134,6 +134,33 @@ def test_tile_sums_are_the_exact_integers(hip, noise, order, ms):
         assert np.array_equal(got_p.view(np.uint64), P.view(np.uint64)), ("P", order, ms, n, off, ch)
         assert np.array_equal(got_x.view(np.uint64), X.view(np.uint64)), ("X", order, ms, n, off, ch)
         assert (ts[gi, nt:] == sentinel).all(), ("tiles beyond the window", order, ms, n, off, ch)
+
+
+def test_order_51_is_the_last_with_tile_sums(hip, noise):
+    """the widest kernels compute 52 lags, 0 .. 51: order 51 is the last they serve.  At order 52 sla_hip_search_exact_lags says
+    0, and both launchers that need the sums refuse the call before anything is launched or written (the encoder then takes the
+    serial chains: tests/test_gpu_high_orders.py)"""
+    import torch
+    L = hip.lib()
+    assert [L.sla_hip_search_exact_lags(o) for o in (48, 49, 51, 52, 53, 64, 255)] == [52, 52, 52, 0, 0, 0, 0]
+    order, n, sentinel = 52, 4096, -7.25e100
+    _, d_pcm = noise
+    d_g, d_c = _groups_dev([Group(0, n, 0, 0xFFFFFFFF, 16, 0, 1, 0, 0)]), _dev(np.array([(0, n)], np.uint32))
+    d_ts = torch.full((XTILES * 2 * 56,), sentinel, dtype=torch.float64, device="cuda")
+    d_out = torch.full((order + 2,), sentinel, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    rc = L.sla_hip_launch_search_exact_x(_p(d_pcm, 4 * MARGIN), C.c_uint64(PLANE), 0, order, _p(d_g), 1, n, 1, _p(d_c), _p(d_ts), _p(d_out),
+                                         C.c_double(2.0 ** 23), C.c_double(64.0), None, None, None)
+    assert rc == 3                                                # SLA_APIRESULT_EXCEED_HANDLE_CAPACITY
+    d_w = _dev(np.ones(n))
+    d_i = [torch.full((order + 1,), 77, dtype=torch.int32, device="cuda") for _ in range(6)]
+    d_wg = _groups_dev([Group(0, n, 0, 0, 16, 0, 1, 0, 0)])
+    rc = L.sla_hip_launch_lpc_blocks_cert_x(_p(d_pcm, 4 * MARGIN), C.c_uint64(PLANE), 0, order, _p(d_wg), 1, n, _p(d_c), _p(d_w), _p(d_out),
+                                            _p(d_i[0]), _p(d_i[1]), _p(d_i[2]), _p(d_i[3]), _p(d_i[4]), _p(d_i[5]), C.c_double(16.0), 16, None, None)
+    assert rc == 3
+    torch.cuda.synchronize()
+    assert (d_ts.cpu().numpy() == sentinel).all() and (d_out.cpu().numpy() == sentinel).all()
+    assert all((t.cpu().numpy() == 77).all() for t in d_i)
 
 
 # ------------------------------------------------------------------ consumers agree
@@ -240,7 +267,7 @@ def consumers(hip, oracle, order, maxb, nch, ms, seed):
     return status, bad
 
 
-CONSUMER_CASES = [(32, 4096, 2, 1, 12345), (48, 8192, 1, 0, 12345)]
+CONSUMER_CASES = [(32, 4096, 2, 1, 12345), (48, 8192, 1, 0, 12345), (49, 4096, 2, 1, 12345), (51, 8192, 1, 0, 12345)]
 
 
 @pytest.mark.parametrize("order,maxb,nch,ms,seed", CONSUMER_CASES)

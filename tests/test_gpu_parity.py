@@ -1172,14 +1172,16 @@ def test_rice_walk_kernels_agree(oracle, hip, n, kind):
         assert got == want, lanes
 
 
+@pytest.mark.parametrize("order", [48, 49, 51, 52])
 @pytest.mark.parametrize("n,bits,ms", [(8192 * 6 + 333, 24, 0), (8192 * 3 + 40, 16, 0), (4096 * 9 + 1999, 24, 1), (1500, 24, 0)])
-def test_tile_sums_at_52_lags(oracle, hip, n, bits, ms):
-    """orders 33 .. 52 take the tile sums from k_acf_tiles_lds<13> (partners from LDS, tile walked backwards): the oracle's bytes
-    on windows with a short last tile (fewer samples than lags in it), a window shorter than a tile, loud 24-bit material
+def test_tile_sums_at_52_lags(oracle, hip, n, bits, ms, order):
+    """orders 33 .. 51 take the tile sums from k_acf_tiles_lds<13> (partners from LDS, tile walked backwards; order 48 the
+    variant that stops at lag 48, 49 and 51 the one with all 52 lags; 52 is the first order without tile sums): the oracle's
+    bytes on windows with a short last tile (fewer samples than lags in it), a window shorter than a tile, loud 24-bit material
     (certified sums) and 16-bit (exact sums)"""
     nch = 2 if ms else 1
     pcm = W.music_like(nch, n, bits, seed=n % 71, level=1.0)
-    p = S.make_params(nch, bits, 96000, 48, 3, 8, ms, 1, 8192)
+    p = S.make_params(nch, bits, 96000, order, 3, 8, ms, 1, 8192, cap=None if order <= 48 else (8, 16384, 52, 5, 40))
     ret, want = oracle.encode_whole(p, pcm)
     assert ret == 0
     got, _ = _encode_with_options(hip, p, pcm, stream=0)

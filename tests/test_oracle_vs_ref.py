@@ -48,7 +48,7 @@ def test_autocorr_windowed(oracle, ref):
 
 
 @pytest.mark.parametrize("name", W.NAMES)
-@pytest.mark.parametrize("order", [1, 4, 8, 16, 32, 48])
+@pytest.mark.parametrize("order", [1, 4, 8, 16, 32, 48, 49, 51, 52, 53, 64, 65, 128, 255])
 def test_parcor(oracle, ref, name, order):
     x = to_double(W.gen(name, 1, 2048, 16, seed=order)[0])
     ro, po = oracle.parcor(x, order)
@@ -412,6 +412,41 @@ def test_baseline_configs(oracle, ref, cfg, kind):
     compare_traces(ta, tb, p)
     rd, dec, _ = oracle.decode_whole(p, da, n)
     assert rd == 0 and np.array_equal(dec, pcm)
+
+
+HIGH_ORDERS = [49, 51, 52, 53, 64, 65, 128, 255]
+HIGH_ORDER_SHAPES = {
+    # name: (nch, bits, ms, ltm, lms, max_block, samples as a function of the order)
+    "music-1ch-16": (1, 16, 0, 3, 8, 4096, lambda order: 2 * 4096 + order - 1),
+    "music-2ch-24-ms": (2, 24, 1, 3, 16, 8192, lambda order: 8192 + 2048 + order + 1),
+    "wave-2ch-16-ms": (2, 16, 1, 3, 8, 4096, lambda order: 2 * 4096 + order - 1),       # last block one sample shorter than the order
+    "wave-1ch-24": (1, 24, 0, 3, 8, 2048, lambda order: 2048 + order + 1),             # ... and one sample longer
+}
+
+
+def _high_order_cases():
+    for shape in ("music-1ch-16", "music-2ch-24-ms"):
+        yield shape, "music"
+    for shape in ("wave-2ch-16-ms", "wave-1ch-24"):
+        for name in W.NAMES:
+            yield shape, name
+
+
+@pytest.mark.parametrize("shape,kind", list(_high_order_cases()))
+@pytest.mark.parametrize("order", HIGH_ORDERS)
+def test_whole_file_above_order_48(oracle, ref, order, shape, kind):
+    """PARCOR orders above the CLI's capacity of 48, up to the 255 a handle accepts (capacity {channels, max block, 255, 5,
+    32}): return code, bytes and trace of the oracle are the reference's on programme-like material and on the eight waveform
+    families, with last blocks one sample shorter and one sample longer than the order.  (A tail of exactly `order` samples
+    hangs the compiled reference, see test_tiny_and_ragged_lengths.)"""
+    nch, bits, ms, ltm, lms, maxb, length = HIGH_ORDER_SHAPES[shape]
+    n = length(order)
+    pcm = W.music_like(nch, n, bits, seed=order) if kind == "music" else W.gen(kind, nch, n, bits, seed=order)
+    p = S.make_params(nch, bits, 48000, order, ltm, lms, ms, 1, maxb, cap=(nch, maxb, 255, 5, 32))
+    ra, da, ta = oracle.encode_trace(p, pcm)
+    rb, db, tb = ref.encode_trace(p, pcm)
+    assert ra == rb == 0 and da == db
+    compare_traces(ta, tb, p)
 
 
 def test_leading_silence_block_layout(oracle, ref):
