@@ -270,6 +270,14 @@ int sla_hip_launch_lpc_blocks_cert(const int32_t* d_pcm, uint64_t plane_stride, 
                                    double* d_out, int32_t* d_code, int32_t* d_kint, uint32_t* d_rshift,
                                    uint32_t* d_cert_flag, uint32_t* d_fallback_list, uint32_t* d_fallback_count,
                                    double safety, uint32_t bits_per_sample, sla_hip_stream_t stream);
+/* k_acf_blocks alone, in the instantiation sla_hip_launch_lpc_blocks_cert picks for `order`, and nothing behind it: the
+ * launch stores the sums themselves -- d_out[slot * (order + 2) + 1 + lag] = r[lag], lag = 0 .. order (element 0 of the slot
+ * is not written) -- and d_rshift[slot], the quantiser's shift.  For tests that hold the sums against exact ones
+ * (tests/test_gpu_acf_error.py).  The same refusals as sla_hip_launch_lpc_blocks_cert: orders above 51 return
+ * SLA_APIRESULT_EXCEED_HANDLE_CAPACITY before anything is launched. */
+int sla_hip_launch_acf_blocks(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                              const sla_hip_lpc_group* d_groups, uint32_t num_groups, const double* d_window_pool,
+                              double* d_out, uint32_t* d_rshift, sla_hip_stream_t stream);
 
 /* sla_hip_launch_lpc restricted to the groups that sla_hip_launch_search_exact flagged (NaN in r[0] of the group's
  * first slot): everything else returns at once and keeps its result.  *d_rerun_counter (may be NULL) is

@@ -358,8 +358,14 @@ void k_lpc_blocks(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ms,
 // CERT = true: r[] came from k_acf_blocks (any summation order), so the doubles are NOT the reference's bit for bit --
 // but what reaches the bit stream are the quantised codes (16 bits for the first three coefficients, 8 bits for the
 // rest, src/SLAEncoder.c:573-589) and the RAW decision (src/SLAEncoder.c:553-565).  Both are certified per block:
-//   * |r_ref[j] - r[j]| <= delta = (n + 64) * 2^-53 * r[0]: the reference adds <= n/2 + 2 terms c*(a+b) one after the
-//     other (each term two roundings, sum|terms| <= sum|x_i x_(i+lag)| <= r0), k_acf_blocks <= 48 (lane chain, wave tree);
+//   * |r_ref[j] - r[j]| <= delta = (n + max(64, 4 ceil(n/256) + 6)) * 2^-53 * r[0] (acf_blocks_budget).  Counted in roundings
+//     a product passes through, each worth 2^-53 * sum|x_i x_(i+lag)| <= 2^-53 * r0 (tests/acfmodel.py derives the counts):
+//     the reference's lag 0 is n squares added one after the other, n roundings; at a lag >= 1 it adds T terms c*(a+b) (two
+//     roundings each) and leftover products, T + 1 <= n/2 + lag roundings.  k_acf_blocks keeps a lane's accumulators
+//     across all tiles of the block, four FMAs per tile and lag, and runs the wave tree once: 4 ceil(n/256) + 6 (70 at
+//     n = 4096, 262 at 16384; not the 48 this comment used to state).  Lag 0 is the tightest: n + 64 covers both sums only up to
+//     n = 3584, hence the maximum.  tests/test_acf_error_model.py::test_block_budget_covers_both_sums checks the inequality for
+//     every n <= 16384 and lag <= 51, tests/test_gpu_acf_error.py measures the kernel's sums against exact ones;
 //   * to first order the reflection coefficient of stage m moves by
 //        dk_m = -(B' dR A)/e + k_m (A' dR A)/e,   A = (1, a_1 .. a_(m-1), 0), B = A reversed, e = e_(m-1)
 //     (the optimal predictors make the variation of A and B drop out: R A and R B vanish in the middle rows), hence
@@ -375,6 +381,13 @@ void k_lpc_blocks(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ms,
 // (k_lpc_blocks + k_blocks_finish<.., false> in list mode) redo it on the same stream.
 // list mode (list != NULL): the groups to finish are list[0 .. *list_count).
 // ---------------------------------------------------------------------------------------------
+// roundings per lag the certificate allows the reference's sum and k_acf_blocks' together (see above; 256 = ACF_TILE)
+__device__ __forceinline__ double acf_blocks_budget(uint32_t n)
+{
+  const uint32_t own = 4u * ((n + 255u) / 256u) + 6u;
+  return (double)n + (double)((own > 64u) ? own : 64u);
+}
+
 template <int P, bool CERT>           // P >= order
 __global__ __launch_bounds__(64, (P == 32 && CERT) ? 2 : 1)
 void k_blocks_finish(const sla_hip_lpc_group* __restrict__ groups, uint32_t num_groups, uint32_t order,
@@ -398,7 +411,7 @@ void k_blocks_finish(const sla_hip_lpc_group* __restrict__ groups, uint32_t num_
   for (int i = 0; i <= P; i++) { r[i] = ((uint32_t)i <= order) ? o[1 + i] : 0.0; a[i] = 0.0; par[i] = 0.0; }
   const uint32_t rshift = out_rshift[slot];
   const double u = 1.1102230246251565e-16;      // 2^-53
-  const double delta = CERT ? ((double)g.num_samples + 64.0) * u * r[0] : 0.0;
+  const double delta = CERT ? acf_blocks_budget(g.num_samples) * u * r[0] : 0.0;
   bool sure = true;
   double gain = 0.0, gain_w = 0.0;              // sum log2(1 - k^2) and its half width
   // margin test of one coefficient: does Round(k * 2^(q-1)) (half-integers away from zero, then clipped) keep its value

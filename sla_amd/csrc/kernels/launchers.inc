@@ -176,6 +176,42 @@ extern "C" int sla_hip_launch_lpc_blocks(const int32_t* d_pcm, uint64_t plane_st
   return sla_hip_launch_lpc_blocks_x(d_pcm, plane_stride, mid_side, order, d_groups, num_groups, max_window, d_cands, d_window_pool, d_out, d_code, d_kint, d_rshift, d_lattice_residual, stream, nullptr);
 }
 
+// k_acf_blocks in the instantiation that serves `order` (lags = sla_hip_search_exact_lags(order) != 0): the one place that
+// chooses it, for the certified block stage and for sla_hip_launch_acf_blocks, which shows the sums to the tests.
+// The lags that have a reader: order + 1.  The BASELINE orders 16 / 32 / 48 leave three lags of the last block of four without
+// one and get kernels that do not compute them; every other order keeps the full blocks.
+static void launch_acf_blocks(uint32_t lags, const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                              const sla_hip_lpc_group* d_groups, uint32_t num_groups, const double* d_window_pool,
+                              double* d_out, uint32_t* d_rshift, hipStream_t st, unsigned long long* span,
+                              uint32_t* zero_word, const uint32_t* dyn)
+{
+  const dim3 grid((num_groups + 3) / 4), block(256);
+#define SLA_ACFB(NBB, TOPP) do { \
+    if (mid_side) { hipLaunchKernelGGL((k_acf_blocks<NBB, TOPP, true>), grid, block, 0, st, d_pcm, plane_stride, order, d_groups, num_groups, d_window_pool, d_out, d_rshift, span, zero_word, dyn); } \
+    else { hipLaunchKernelGGL((k_acf_blocks<NBB, TOPP, false>), grid, block, 0, st, d_pcm, plane_stride, order, d_groups, num_groups, d_window_pool, d_out, d_rshift, span, zero_word, dyn); } } while (0)
+  switch (lags) {
+    case 12: SLA_ACFB(3, 12); break;
+    case 20: if (order == 16) { SLA_ACFB(5, 17); } else { SLA_ACFB(5, 20); } break;
+    case 36: if (order == 32) { SLA_ACFB(9, 33); } else { SLA_ACFB(9, 36); } break;
+    default: if (order == 48) { SLA_ACFB(13, 49); } else { SLA_ACFB(13, 52); } break;
+  }
+#undef SLA_ACFB
+}
+
+extern "C" int sla_hip_launch_acf_blocks(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                                         const sla_hip_lpc_group* d_groups, uint32_t num_groups, const double* d_window_pool,
+                                         double* d_out, uint32_t* d_rshift, sla_hip_stream_t stream)
+{
+  if (d_pcm == nullptr || d_groups == nullptr || d_window_pool == nullptr || d_out == nullptr || d_rshift == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (order < 1) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  const uint32_t lags = sla_hip_search_exact_lags(order);
+  if (lags == 0) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }      // orders above 51 (more than 52 lags)
+  if (num_groups == 0) { return 0; }
+  launch_acf_blocks(lags, d_pcm, plane_stride, mid_side, order, d_groups, num_groups, d_window_pool, d_out, d_rshift, (hipStream_t)stream,
+                    nullptr, nullptr, nullptr);
+  return hip_rc(hipGetLastError());
+}
+
 extern "C" int sla_hip_launch_lpc_blocks_cert_x(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
                                               const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
                                               const sla_hip_lpc_cand* d_cands, const double* d_window_pool,
@@ -196,19 +232,7 @@ extern "C" int sla_hip_launch_lpc_blocks_cert_x(const int32_t* d_pcm, uint64_t p
   hipError_t e = hipSuccess;
   unsigned long long* span = span_of(extra);
   const uint32_t* dyn = (extra != nullptr) ? extra->d_group_count : nullptr;      // num_groups is then an upper bound, the kernels read the number
-  const dim3 grid((num_groups + 3) / 4), block(256);
-  // the lags that have a reader: order + 1.  The BASELINE orders 16 / 32 / 48 leave three lags of the last block of four without
-  // one and get kernels that do not compute them; every other order keeps the full blocks.
-#define SLA_ACFB(NBB, TOPP) do { \
-    if (mid_side) { hipLaunchKernelGGL((k_acf_blocks<NBB, TOPP, true>), grid, block, 0, st, d_pcm, plane_stride, order, d_groups, num_groups, d_window_pool, d_out, d_rshift, span, d_fallback_count, dyn); } \
-    else { hipLaunchKernelGGL((k_acf_blocks<NBB, TOPP, false>), grid, block, 0, st, d_pcm, plane_stride, order, d_groups, num_groups, d_window_pool, d_out, d_rshift, span, d_fallback_count, dyn); } } while (0)
-  switch (lags) {
-    case 12: SLA_ACFB(3, 12); break;
-    case 20: if (order == 16) { SLA_ACFB(5, 17); } else { SLA_ACFB(5, 20); } break;
-    case 36: if (order == 32) { SLA_ACFB(9, 33); } else { SLA_ACFB(9, 36); } break;
-    default: if (order == 48) { SLA_ACFB(13, 49); } else { SLA_ACFB(13, 52); } break;
-  }
-#undef SLA_ACFB
+  launch_acf_blocks(lags, d_pcm, plane_stride, mid_side, order, d_groups, num_groups, d_window_pool, d_out, d_rshift, st, span, d_fallback_count, dyn);
   e = hipGetLastError();
   if (e != hipSuccess) { return hip_rc(e); }
   const dim3 fgrid((num_groups + 63) / 64), fblock(64);

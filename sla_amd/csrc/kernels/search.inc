@@ -440,7 +440,7 @@ void k_acf_tiles_lds(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t 
   if constexpr (TOP == 17 || TOP == 33) {
     // W = TOP - 1 lags (lag 0 has no such pair) times NP = 64 / W parts of the terms: all 64 lanes work, the chain is W / NP
     // long instead of W, and the parts meet in log2(NP) cross-lane additions.  Exact windows stay exact in any order; for
-    // the others a sum takes at most W / NP + 2 roundings instead of W, inside the certificates' 48.
+    // the others a sum takes at most W / NP + log2(NP) roundings instead of W (tests/acfmodel.py::roundings_tile).
     constexpr uint32_t W = TOP - 1, NP = 64 / W, CH = W / NP;
     const uint32_t lag = (lane & (W - 1)) + 1, part = lane / W;
     const double* e = s_edge[wv] + LAGS + part * CH;
@@ -481,8 +481,11 @@ void k_acf_tiles_lds(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t 
 // block.  The samples are staged as the reference stages them -- x[s] = w[s]*in[s] - 0.96875 * w[s-1]*in[s-1]
 // (src/SLAEncoder.c:505-515, 540-543, src/SLAPredictor.c:1803-1809): the previous windowed sample comes from the lane
 // below (from the last lane of the tile before for lane 0).  Out: slot = { -, r[0..order] } and the quantiser's shift,
-// exactly what k_lpc_blocks hands to k_blocks_finish -- but r[] is the correctly ordered sum only up to the rounding
-// errors of ~48 additions.
+// exactly what k_lpc_blocks hands to k_blocks_finish -- but r[] is the exact sum only up to 4 ceil(N/256) + 6 roundings per
+// lag, each worth 2^-53 * sum|x_i x_(i+lag)|: a lane's chain of four FMAs per tile and the six additions of the wave tree
+// (tests/acfmodel.py::roundings_blocks; k_blocks_finish's delta budgets for them, tests/test_acf_error_model.py::
+// test_block_budget_covers_both_sums; tests/test_gpu_acf_error.py holds the sums against exact ones through
+// sla_hip_launch_acf_blocks).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ double shr1_f64(double v, double first)       // lane t <- lane t-1, lane 0 <- first
 {
@@ -611,9 +614,14 @@ void k_acf_blocks(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ord
 // serially rounded sums bit for bit -- but the search only has to deliver a PARTITION, and the reference's decision
 // can be certified from sums that are merely close (cert > 0):
 //   * the reference's r[lag] differs from the exact sum by at most n*2^-53 * sum|terms| <= n*2^-53 * r0 (recursive
-//     summation of n exactly representable terms), ours by at most 48*2^-53 * (energy of the window) (<= 48 roundings
-//     per lag: lane chain, wave tree, tiles), so the two Toeplitz matrices differ by a symmetric Toeplitz matrix whose
-//     2-norm is at most (2*order+1) * delta;
+//     summation of n exactly representable terms), ours by at most 64*2^-53 * (energy of the window).  The count, in
+//     roundings a product passes through (tests/acfmodel.py::roundings_window): a tile's P takes 4 FMAs per 256-sample
+//     sub-tile and the six additions of the wave tree, 22 (26 in k_acf_tiles<3>: five passes); the candidate's tiles are added
+//     one after the other and the last tile's X subtracted, <= 16; X itself is a chain of up to `lag` <= 51 FMAs, but its
+//     pairs straddle the candidate's end and their magnitudes add up to at most HALF the window's energy, <= 26: 64 in all
+//     at 52 lags and 16 tiles (the 48 this comment used to state left X out: enough up to 33 live lags, not for 36 / 49 / 52;
+//     tests/test_acf_error_model.py::test_search_budget_covers_the_tile_sums).  So the two Toeplitz matrices differ by a
+//     symmetric Toeplitz matrix whose 2-norm is at most (2*order+1) * delta;
 //   * the estimated code length of a candidate depends on its autocorrelation only through the final prediction
 //     error e_p = r0 * prod(1 - k_j^2) = min over a, a_0 = 1, of a'Ra, which is monotone in the Loewner order:
 //     R~ - d*I <= R_ref <= R~ + d*I  implies  e_p(R~ - d*I) <= e_p(R_ref) <= e_p(R~ + d*I);
@@ -624,6 +632,7 @@ void k_acf_blocks(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ord
 // log2(e_p); k_plan adds the widths up along the paths and only accepts a partition no width can change.  Anything
 // else (not positive definite, not finite, cert <= 0) is flagged -- NaN in r[0], or an infinite width -- and redone
 // as serial chains.
+#define SEARCH_ACF_ROUNDINGS 64.0      // roundings per lag of the assembled tile sums, in units of 2^-53 * energy (see above)
 #define XF_BATCH 64          // candidates one pass of the wave takes (at most)
 #define XF_GROUPS 16         // groups one wave takes (at most)
 
@@ -804,7 +813,7 @@ void k_search_finish(uint32_t order, uint32_t lags, uint32_t gpw, uint32_t per,
         const double r0 = rc[0];
         double w = inf, lg = 0.0;
         if (cd.len >= order && r0 > 2.0 * (double)FLT_EPSILON) {     // (the reference zeroes the coefficients below FLT_EPSILON, src/SLAPredictor.c:274)
-          const double delta = ((double)cd.len * u) * r0 + (48.0 * u) * energy;
+          const double delta = ((double)cd.len * u) * r0 + (SEARCH_ACF_ROUNDINGS * u) * energy;
           const double d = cert * (double)(2 * order + 1) * delta;
           // one copy of the unrolled recursion, run for both ends of the bracket (inlined copies do not fit the instruction
           // cache).  The value handed to k_plan is the middle of the bracket in the logarithm, which is where the width applies:
@@ -1132,7 +1141,7 @@ void k_search_cert(uint32_t order, uint32_t lags, uint32_t per_max,
   const double r0 = live ? rc[0] : 1.0;
   const uint32_t len = s_len[cl];
   const bool valid = live && len >= order && r0 > 2.0 * (double)FLT_EPSILON;   // (the reference zeroes the coefficients below FLT_EPSILON, src/SLAPredictor.c:274)
-  const double delta = ((double)len * u) * r0 + (48.0 * u) * s_energy[cl];
+  const double delta = ((double)len * u) * r0 + (SEARCH_ACF_ROUNDINGS * u) * s_energy[cl];
   const double d = cert * (double)(2 * order + 1) * delta;
   double e_mine = nan, g_mine = 1.0;
   if (valid) {
