@@ -751,6 +751,112 @@ typedef struct sla_hip_dec_gather {
 int sla_hip_launch_dec_gather(const sla_hip_dec_gather* d_table, uint32_t num_entries, uint32_t max_bytes,
                               uint8_t* d_image, uint64_t image_bytes, sla_hip_stream_t stream);
 
+/* The block-chain walk for a WINDOW of samples [win_start, min(win_start + win_len, total)) of each file (the end in 64
+ * bits), one file per lane like sla_hip_launch_dec_walk and with its chain checks, in its order and its 32-bit
+ * arithmetic: off > data_size or fewer than 11 bytes left -> INSUFFICIENT_DATA_SIZE, no sync code ->
+ * FAILED_TO_FIND_SYNC_CODE, a wrapped `size field + 6` above the bytes left or below 8 -> INSUFFICIENT_DATA_SIZE.
+ * The walk starts at byte 43, sample 0, or, with seek_byte != 0, at (seek_byte, seek_sample) -- the caller's promise that
+ * a block starts there -- and runs while the sample position (carried in 64 bits, it never wraps) is below the window's
+ * end.  A block with no samples, or one that ends at or before win_start, is PASSED OVER: counted in `skipped`, no row,
+ * no further check.  Every other block is KEPT, unless its sample count exceeds max_block_samples: that stops the walk
+ * with INSUFFICIENT_BUFFER_SIZE and the block is not kept (there are no header-only rows and no capacity test here: the
+ * window is clipped, not the file).  Blocks behind the window are never read.
+ * Result: the blocks kept and passed over, the stop code, the file position (byte, sample) of the first kept block and
+ * the position behind the last one; all four positions 0 when no block was kept.
+ * Write mode (d_blocks, d_block_end and d_crc_field all given; count mode: all NULL) lays the kept blocks out for a pass
+ * that gathered the bytes [base_byte, base_byte + range_bytes) of the file to img_off and gave it the plane region at
+ * plane_off for the samples from base_sample on: row first + k is a sla_hip_dec_block with byte_off = img_off + (off -
+ * base_byte), smp_off = plane_off + (pos - base_sample), flags 0; its block end is img_off + range_bytes; its CRC field
+ * the big-endian 16-bit field at byte 6 of the block.  Nothing is written at or behind first + max_rows; rows the walk
+ * did not reach become empty header-only rows at img_off, as in sla_hip_launch_dec_walk.
+ * The walk reads bytes, at any alignment, and none outside [src, src + data_size), whatever the hint.
+ * INVALID_ARGUMENT before any launch for a NULL file table or result table, or for write mode with a table missing. */
+typedef struct sla_hip_dec_window_file {
+  const uint8_t* src;             /* device: the whole .sla stream */
+  uint64_t img_off;               /* write mode: where the pass image holds the file's byte range */
+  uint32_t data_size;
+  uint32_t total;                 /* the header's num_samples */
+  uint32_t win_start;             /* first sample of the window */
+  uint32_t win_len;               /* its length */
+  uint32_t seek_byte;             /* 0: walk from the header; else the byte of a block's sync code */
+  uint32_t seek_sample;           /* the first sample of that block */
+  uint32_t range_bytes;           /* write mode: bytes of the file's range in the image */
+  uint32_t base_byte;             /* write mode: the file position of the range's first byte */
+  uint32_t base_sample;           /* write mode: the file position of the region's first sample */
+  uint32_t plane_off;             /* write mode: the file's region in the pass planes */
+  uint32_t first;                 /* write mode: the file's first row */
+  uint32_t max_rows;              /* write mode: its rows */
+} sla_hip_dec_window_file;        /* 64 bytes */
+typedef struct sla_hip_dec_window_result {
+  uint32_t num_blocks;            /* blocks kept */
+  uint32_t stop;                  /* SLAApiResult */
+  uint32_t skipped;               /* blocks passed over */
+  uint32_t first_byte;            /* file position of the first kept block */
+  uint32_t first_sample;
+  uint32_t end_byte;              /* file position behind the last kept block */
+  uint32_t end_sample;
+  uint32_t reserved;
+} sla_hip_dec_window_result;      /* 32 bytes */
+int sla_hip_launch_dec_walk_window(const sla_hip_dec_window_file* d_files, uint32_t num_files, uint32_t max_block_samples,
+                                   sla_hip_dec_window_result* d_results, sla_hip_dec_block* d_blocks,
+                                   uint64_t* d_block_end, uint32_t* d_crc_field, sla_hip_stream_t stream);
+
+/* Windows of samples of resident .sla streams decoded into caller-owned device memory: what a pipeline that keeps its
+ * compressed corpus in device memory needs for a crop.  Item i delivers the samples [start, start + length) of its stream,
+ * clipped to the file: sample start + k of channel c goes to element c * channel_stride + k * sample_stride of dst.
+ * Blocks reset their filters and their coder, so a window needs exactly the blocks it overlaps, and the 10-byte chain
+ * headers in front of them to find where they start: only those are read, gathered and decoded.  Consequently damage in
+ * a block the window does not need is NOT SEEN -- neither a flipped bit in a block in front of the window nor anything
+ * behind its last block.
+ * Formats, SLA_HIP_DEC_ZERO_FILL, the strides, the call-level refusals, the per-item source and destination checks (made
+ * on the host before anything of the item is read or written, `length` in the part of `capacity`), the header failures
+ * and format verdicts, the ordering behind `stream` and the handle's wave format and encode parameter afterwards are
+ * sla_hip_decode_batch_resident's.  Per item also INVALID_ARGUMENT (nothing written) for: a seek_byte that is neither 0
+ * nor at least 43, seek_byte == 0 with seek_sample != 0, seek_sample > start, and, once the header is home,
+ * start > num_samples.
+ * A window is delivered whole or not at all.  Result OK: output_num_samples = min(length, num_samples - start) samples
+ * (none, and nothing decoded, for start == num_samples or length == 0); with the flag [output_num_samples, length) of
+ * every channel is zero.  The kept blocks are examined in file order with the whole-file decode's criteria and the first
+ * failure is the item's result: with enable_crc_check a CRC that differs from the stored field ->
+ * DETECT_DATA_CORRUPTION, a block type above 2 -> INVALID_HEADER_FORMAT, a compressed block with an LMS order the
+ * kernels do not run -> FAILED_TO_SYNTHESIZE, a body that does not end where the size field says or a reader that ran
+ * off the end -> DETECT_DATA_CORRUPTION (windows do NO RESYNC: where the whole-file decode would continue from where
+ * its reader stopped, the window fails); after the blocks the walk's stop code.  A failed item gets output_num_samples
+ * 0; with the flag its whole [0, C) x [0, length) is zero, without it nothing of it is written.
+ * The hint: seek_byte / seek_sample name a block start at or before the window (seek_byte 0: none, the walk starts at
+ * the header).  first_block_byte / first_block_sample return the first kept block's position (0, 0 when the walk kept
+ * none), a valid hint for any later window of the same bytes with start >= first_block_sample; a long file is served by
+ * hints the caller keeps, there is no index object.  A hint is the caller's promise: a wrong one gives an error code or
+ * wrong samples, never a read outside the source or a write outside the destination.
+ * The same source may appear in any number of items; each is decoded on its own.
+ * How it runs: the header gather; the window walk in count mode over all items; items grouped by launch parameters and
+ * cut into passes by sla_hip_decode_batch's caps, an item costing the bytes from its first kept block to the end of its
+ * last and the samples of those blocks; per pass one gather of the ranges, the window walk in write mode, the decode
+ * kernels unchanged, the examination, and the emit kernel reading each region from the window's first sample.  A
+ * write-mode walk that differs from the count fails the call.
+ * sla_hip_decoder_last_timing keeps sla_hip_decode_batch_resident's split. */
+typedef struct sla_hip_decode_window_item {
+  const uint8_t* data;            /* in : a whole .sla stream in device memory, any byte alignment */
+  void*    dst;                   /* in : device memory */
+  uint64_t channel_stride;        /* in : elements */
+  uint64_t sample_stride;         /* in : elements (>= 1) */
+  uint32_t data_size;             /* in  */
+  uint32_t start;                 /* in : first sample of the window */
+  uint32_t length;                /* in : samples per channel of the window and of dst */
+  uint32_t seek_byte;             /* in : hint, 0 for none */
+  uint32_t seek_sample;           /* in : hint */
+  uint32_t output_num_samples;    /* out */
+  int32_t  result;                /* out: SLAApiResult */
+  uint32_t first_block_byte;      /* out: a hint for later windows at or behind this one */
+  uint32_t first_block_sample;    /* out */
+  uint32_t reserved;
+} sla_hip_decode_window_item;     /* 72 bytes */
+int sla_hip_decode_windows_resident(struct SLADecoder* decoder, sla_hip_decode_window_item* items, uint32_t num_items,
+                                    uint32_t sample_format, uint32_t flags, sla_hip_stream_t stream);
+/* Summed over the last sla_hip_decode_windows_resident: [0] blocks passed over, [1] blocks decoded, [2] stream bytes
+ * gathered, [3] plane samples per channel reserved.  INVALID_ARGUMENT for a NULL argument. */
+int sla_hip_decoder_last_window_stats(const struct SLADecoder* decoder, uint64_t counters[4]);
+
 /* Decode-and-compare of blocks (option "verify" of the encoder; kernel k_verify_blocks): for every block of the table and
  * every channel, the decoded plane samples [smp_off, smp_off + num_samples) -- what dec_bits / dec_lms / dec_ltm /
  * dec_lattice left, right-justified, mid/side still folded -- are finished as sla_hip_launch_dec_finish_batch finishes them

@@ -114,6 +114,28 @@ class DecGather(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst_off", C.c_uint64), ("bytes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class DecWindowFile(C.Structure):
+    """sla_hip_dec_window_file (include/sla_hip.h): one file of sla_hip_launch_dec_walk_window"""
+    _fields_ = [("src", C.c_void_p), ("img_off", C.c_uint64), ("data_size", C.c_uint32), ("total", C.c_uint32),
+                ("win_start", C.c_uint32), ("win_len", C.c_uint32), ("seek_byte", C.c_uint32), ("seek_sample", C.c_uint32),
+                ("range_bytes", C.c_uint32), ("base_byte", C.c_uint32), ("base_sample", C.c_uint32), ("plane_off", C.c_uint32),
+                ("first", C.c_uint32), ("max_rows", C.c_uint32)]
+
+
+class DecWindowResult(C.Structure):
+    """sla_hip_dec_window_result (include/sla_hip.h): what the window walk returns per file"""
+    _fields_ = [("num_blocks", C.c_uint32), ("stop", C.c_uint32), ("skipped", C.c_uint32), ("first_byte", C.c_uint32),
+                ("first_sample", C.c_uint32), ("end_byte", C.c_uint32), ("end_sample", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DecodeWindowItem(C.Structure):
+    """sla_hip_decode_window_item (include/sla_hip.h): one window of sla_hip_decode_windows_resident"""
+    _fields_ = [("data", u8p), ("dst", C.c_void_p), ("channel_stride", C.c_uint64), ("sample_stride", C.c_uint64),
+                ("data_size", C.c_uint32), ("start", C.c_uint32), ("length", C.c_uint32), ("seek_byte", C.c_uint32),
+                ("seek_sample", C.c_uint32), ("output_num_samples", C.c_uint32), ("result", C.c_int32),
+                ("first_block_byte", C.c_uint32), ("first_block_sample", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class EncodeDeviceItem(C.Structure):
     """sla_hip_encode_device_item (include/sla_hip.h): one file of sla_hip_encode_batch_device"""
     _fields_ = [("src", C.c_void_p), ("channel_stride", C.c_uint64), ("sample_stride", C.c_uint64), ("data", u8p),
@@ -262,6 +284,12 @@ def lib():
             L.sla_hip_launch_dec_walk.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]
             L.sla_hip_launch_dec_gather.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+        if hasattr(L, "sla_hip_decode_windows_resident"):    # (SLA_HIP_LIB may name an older build in an A/B run)
+            L.sla_hip_decode_windows_resident.argtypes = [C.c_void_p, C.POINTER(DecodeWindowItem), C.c_uint32, C.c_uint32,
+                                                          C.c_uint32, C.c_void_p]
+            L.sla_hip_launch_dec_walk_window.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p]
+            L.sla_hip_decoder_last_window_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         if hasattr(L, "sla_hip_encode_batch_resident"):      # (SLA_HIP_LIB may name an older build in an A/B run)
             L.sla_hip_encode_batch_resident.argtypes = [C.c_void_p, C.POINTER(EncodeDeviceItem), C.c_uint32, C.c_uint32,
                                                         C.c_void_p, C.c_uint64, C.c_void_p]
@@ -317,6 +345,8 @@ EXPORTED_SYMBOLS = [
     "sla_hip_decode_batch_device", "sla_hip_launch_dec_emit_batch",
     # batch decode of streams that are in device memory (include/sla_hip.h)
     "sla_hip_decode_batch_resident", "sla_hip_resident_headers", "sla_hip_launch_dec_walk", "sla_hip_launch_dec_gather",
+    # sample windows of streams that are in device memory (include/sla_hip.h)
+    "sla_hip_decode_windows_resident", "sla_hip_launch_dec_walk_window", "sla_hip_decoder_last_window_stats",
     # batch encode from device memory (include/sla_hip.h)
     "sla_hip_encode_batch_device", "sla_hip_launch_enc_ingest_batch",
     # batch encode to .sla streams that stay in device memory (include/sla_hip.h)
@@ -823,6 +853,7 @@ class Decoder:
         dev = C.c_int(0)
         self._lib.hipGetDevice(C.byref(dev))
         self.device_index = dev.value             # the handle's stream lives on the device current at creation
+        self.max_num_block_samples = max_num_block_samples
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1083,6 +1114,170 @@ class Decoder:
                 else:
                     out[b, :, nchs[b]:].zero_()
         return out, [n for _, n in got], [rc for rc, _ in got]
+
+    def decode_windows_into(self, srcs, starts, outs, sample_format, zero_fill=True, hints=None, stream=None, _headers=None):
+        """sample windows of .sla streams whose bytes are in device memory -> caller-owned device tensors
+        (sla_hip_decode_windows_resident): window i is the samples [starts[i], starts[i] + outs[i].shape[1]) of srcs[i],
+        clipped to the file, delivered whole or not at all; only the blocks it overlaps are gathered and decoded.  srcs,
+        outs, sample_format, zero_fill and stream as for decode_resident_into; the same source may appear any number of
+        times.  hints[i]: None or a (byte, sample) pair naming a block start at or before the window, such as an earlier
+        call returned.  Returns [(result code, samples, (first_block_byte, first_block_sample))]."""
+        import torch
+        if sample_format not in self._FORMAT_DTYPE:
+            raise ValueError("unknown sample format %r" % (sample_format,))
+        if len(outs) != len(srcs) or len(starts) != len(srcs) or (hints is not None and len(hints) != len(srcs)):
+            raise ValueError("%d sources, %d starts, %d outputs" % (len(srcs), len(starts), len(outs)))
+        want = getattr(torch, self._FORMAT_DTYPE[sample_format])
+        ps = self._resident_sources(srcs)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        heads = _headers if _headers is not None else self.resident_headers(ps, stream=st)
+        items = (DecodeWindowItem * max(len(ps), 1))()
+        for i, ((ptr, size), out) in enumerate(zip(ps, outs)):
+            if not isinstance(out, torch.Tensor) or out.dim() != 2:
+                raise ValueError("output %d: need a 2-D torch tensor [channel][sample]" % i)
+            if out.dtype != want:
+                raise ValueError("output %d: dtype %s, the format wants %s" % (i, out.dtype, want))
+            if out.device.type != "cuda" or out.device.index != self.device_index:
+                raise ValueError("output %d: on %s, the decoder's device is cuda:%d" % (i, out.device, self.device_index))
+            rc, h = heads[i]
+            nch = h.wave_format.num_channels if rc in (0, 11) else 0
+            if out.shape[0] < nch:
+                raise ValueError("output %d: %d rows for a file of %d channels" % (i, out.shape[0], nch))
+            if out.shape[1] > 0xFFFFFFFF or min(out.stride()) < 0 or (out.shape[1] > 1 and out.stride(1) == 0) \
+                    or (nch > 1 and out.stride(0) == 0):
+                raise ValueError("output %d: unsupported shape %s / strides %s" % (i, tuple(out.shape), out.stride()))
+            start = int(starts[i])
+            hint = hints[i] if hints is not None and hints[i] is not None else (0, 0)
+            if not 0 <= start <= 0xFFFFFFFF or not 0 <= int(hint[0]) <= 0xFFFFFFFF or not 0 <= int(hint[1]) <= 0xFFFFFFFF:
+                raise ValueError("window %d: start %d / hint %r out of range" % (i, start, hint))
+            items[i].data = C.cast(C.c_void_p(ptr or None), u8p)
+            items[i].data_size = size
+            # a window of no samples is answered, not refused: an empty view still names its place in its storage
+            items[i].dst = out.data_ptr() or (out.untyped_storage().data_ptr() + out.storage_offset() * out.element_size()) or None
+            items[i].channel_stride = out.stride(0)
+            items[i].sample_stride = max(out.stride(1), 1)
+            items[i].start = start
+            items[i].length = out.shape[1]
+            items[i].seek_byte, items[i].seek_sample = int(hint[0]), int(hint[1])
+        rc = self._lib.sla_hip_decode_windows_resident(self._h, items, len(ps), sample_format,
+                                                       DEC_ZERO_FILL if zero_fill else 0, C.c_void_p(st.cuda_stream))
+        self._check(rc, "sla_hip_decode_windows_resident")
+        return [(int(items[i].result), int(items[i].output_num_samples),
+                 (int(items[i].first_block_byte), int(items[i].first_block_sample))) for i in range(len(ps))]
+
+    def decode_windows_tensor(self, srcs, starts, length, dtype=None, layout="planar", right_justify=False, index=None):
+        """one window of `length` samples per source -> one device tensor on the handle's device: [B][C][length] (planar)
+        or [B][length][C] (interleaved), C the largest channel count among the headers; dtype, layout and right_justify
+        as for decode_resident_tensor.  Returns (tensor, samples, results); everything past a window's samples, rows past
+        a file's channel count and windows that gave nothing are zero.  index: what block_index_resident(srcs) returned;
+        every window's walk then starts at the last block at or before starts[i] instead of at the header."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype == torch.float32:
+            fmt = PCM_F32
+        elif dtype == torch.int16:
+            fmt = PCM_S16
+        elif dtype == torch.int32:
+            fmt = PCM_S32 if right_justify else PCM_S32_LEFT
+        else:
+            raise ValueError("dtype must be float32, int16 or int32, not %s" % (dtype,))
+        if layout not in ("planar", "interleaved"):
+            raise ValueError("layout must be 'planar' or 'interleaved', not %r" % (layout,))
+        ps = self._resident_sources(srcs)
+        if len(starts) != len(ps) or (index is not None and len(index) != len(ps)):
+            raise ValueError("%d sources, %d starts" % (len(ps), len(starts)))
+        L = int(length)
+        if L < 0 or L > 0xFFFFFFFF:
+            raise ValueError("length %d out of range" % L)
+        heads = self.resident_headers(ps) if ps else []
+        nchs = [h.wave_format.num_channels if rc in (0, 11) else 0 for rc, h in heads]
+        B, Cn = len(ps), max(nchs, default=0)
+        hints = None
+        if index is not None:
+            hints = []
+            for (byte_off, smp_off, _), start in zip(index, starts):
+                k = int(np.searchsorted(smp_off, int(start), side="right")) - 1
+                hints.append((int(byte_off[k]), int(smp_off[k])) if k >= 0 else None)
+        dev = torch.device("cuda", self.device_index)
+        shape = (B, Cn, L) if layout == "planar" else (B, L, Cn)
+        out = torch.empty(shape, dtype=dtype, device=dev)
+        if out.numel() == 0:
+            # nothing can be written: a one-element stand-in keeps the per-item pointers valid, the results are real
+            scratch = torch.empty(1, dtype=dtype, device=dev)
+            outs = [scratch.as_strided((Cn, L), (1, 1)) for _ in range(B)]
+        else:
+            outs = [out[b] if layout == "planar" else out[b].t() for b in range(B)]
+        got = self.decode_windows_into(ps, starts, outs, fmt, zero_fill=True, hints=hints, _headers=heads)
+        # the zero fill covers the rows a header gave; rows no header covers, and windows refused outright, are zeroed here
+        for b in range(B):
+            if out.numel() and (nchs[b] < Cn or got[b][0] == 2):
+                first = 0 if got[b][0] == 2 else nchs[b]
+                if layout == "planar":
+                    out[b, first:].zero_()
+                else:
+                    out[b, :, first:].zero_()
+        return out, [n for _, n, _ in got], [rc for rc, _, _ in got]
+
+    def block_index_resident(self, srcs, stream=None):
+        """the block chain of every resident stream, for hints: [(byte_off, smp_off, stop)] with the file position of
+        every block's sync code and of its first sample as numpy uint32 arrays, and the walk's stop code (0: the chain
+        reaches the header's num_samples).  Two launches of sla_hip_launch_dec_walk, count mode and write mode; a block
+        larger than the handle's max_num_block_samples ends a file's index.  A caller keeps the index next to the bytes
+        and hands it to decode_windows_tensor(index=...)."""
+        import torch
+        ps = self._resident_sources(srcs)
+        nf = len(ps)
+        if nf == 0:
+            return []
+        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        heads = self.resident_headers(ps, stream=st)
+        dev = torch.device("cuda", self.device_index)
+        table = (DecWalkFile * nf)()
+        for i, ((ptr, size), (rc, h)) in enumerate(zip(ps, heads)):
+            table[i].src = ptr or None
+            table[i].data_size = size if rc in (0, 11) else 0
+            table[i].total = h.num_samples if rc in (0, 11) else 0
+            table[i].capacity = 0xFFFFFFFF
+        sp = C.c_void_p(st.cuda_stream)
+
+        def run(rows):
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+            with torch.cuda.stream(st):
+                d_tab = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+                d_res = torch.zeros(nf * C.sizeof(DecWalkResult), dtype=torch.uint8, device=dev)
+                d_blk = torch.zeros(rows * 24, dtype=torch.uint8, device=dev) if rows else None
+                d_end = torch.zeros(rows * 8, dtype=torch.uint8, device=dev) if rows else None
+                d_crc = torch.zeros(rows * 4, dtype=torch.uint8, device=dev) if rows else None
+                self._check(self._lib.sla_hip_launch_dec_walk(ptr(d_tab), nf, self.max_num_block_samples, 0, ptr(d_res), ptr(d_blk),
+                                                              ptr(d_end), ptr(d_crc), sp), "sla_hip_launch_dec_walk")
+                st.synchronize()
+            res = np.frombuffer(d_res.cpu().numpy().tobytes(), np.uint32).reshape(nf, 4)
+            blk = np.frombuffer(d_blk.cpu().numpy().tobytes(), np.dtype([("byte_off", "<u8"), ("byte_len", "<u4"), ("smp_off", "<u4"),
+                                ("num_samples", "<u4"), ("flags", "<u4")])) if rows else None
+            return res, blk
+
+        res, _ = run(0)
+        first = 0
+        for i in range(nf):
+            table[i].first, table[i].max_rows = first, int(res[i][0])
+            first += int(res[i][0])
+        if first == 0:
+            return [(np.zeros(0, np.uint32), np.zeros(0, np.uint32), int(res[i][1])) for i in range(nf)]
+        res2, blk = run(first)
+        if not np.array_equal(res, res2):
+            raise RuntimeError("block_index_resident: the streams changed during the call")
+        out = []
+        for i in range(nf):
+            rows = blk[table[i].first:table[i].first + table[i].max_rows]
+            out.append((rows["byte_off"].astype(np.uint32), rows["smp_off"].astype(np.uint32), int(res[i][1])))
+        return out
+
+    def last_window_stats(self):
+        """(blocks passed over, blocks decoded, stream bytes gathered, plane samples per channel reserved), summed over the
+        last decode_windows_into / decode_windows_tensor (sla_hip_decoder_last_window_stats)"""
+        c = (C.c_uint64 * 4)()
+        self._check(self._lib.sla_hip_decoder_last_window_stats(self._h, c), "sla_hip_decoder_last_window_stats")
+        return tuple(int(v) for v in c)
 
     def decode_device(self, data, image_ptr, planes_ptr, plane_stride):
         """decode an image that already lives in device memory into device planes; returns (rc, samples)"""

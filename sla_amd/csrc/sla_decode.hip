@@ -19,6 +19,7 @@
 //   k_dec_finish_batch   the same for every file of a batch pass, packed [file][ch][n] for one copy home
 //   k_dec_emit_batch     the same, converted and stored to every file's own device destination
 //   k_dec_walk           src/SLADecoder.c:696-722 (the block chain of whole files whose bytes are in device memory)
+//   k_dec_walk_window    the same chain, for the blocks a window of samples overlaps (no counterpart in the reference)
 //   k_dec_gather         the staging copies of a batch pass, for files that are in device memory already
 //   k_verify_blocks      (kernels/verify.inc) k_dec_finish fused with a compare against source planes, per block table
 #include <hip/hip_runtime.h>
@@ -868,6 +869,73 @@ void k_dec_walk(const sla_hip_dec_walk_file* __restrict__ files, uint32_t num_fi
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_dec_walk_window: k_dec_walk for a window of samples (sla_hip_decode_windows_resident).  The same shape -- one file
+// per lane, a workgroup is one wave, ten byte loads per block inside [src + off, src + off + 11) with off + 11 <=
+// data_size checked first -- and the same three chain checks in the same order and 32-bit arithmetic.  What differs:
+// the walk may start at a hint, it ends at the window's end, blocks in front of the window are passed over without a
+// row, and there is neither a capacity test nor a header-only row.  The sample position is carried in 64 bits: it only
+// grows, so a chain (or a wrong hint) cannot bring it back below the window's end.  Every kept block has pos < win_end
+// and num_samples <= cap_n, and the host sizes the plane region from the same walk in count mode.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64)
+void k_dec_walk_window(const sla_hip_dec_window_file* __restrict__ files, uint32_t num_files, uint32_t cap_n,
+                       sla_hip_dec_window_result* __restrict__ results, sla_hip_dec_block* __restrict__ blocks,
+                       uint64_t* __restrict__ block_end, uint32_t* __restrict__ crc_field)
+{
+  const uint32_t f = blockIdx.x * 64u + threadIdx.x;
+  if (f >= num_files) { return; }
+  const sla_hip_dec_window_file fi = files[f];
+  const uint8_t* data = fi.src;
+  const uint32_t data_size = fi.data_size, rows = (blocks != nullptr) ? fi.max_rows : 0u;
+  const uint64_t end = fi.img_off + fi.range_bytes;
+  const uint64_t win_start = fi.win_start;
+  uint64_t win_end = win_start + fi.win_len;
+  if (win_end > fi.total) { win_end = fi.total; }
+  uint32_t off = (fi.seek_byte != 0) ? fi.seek_byte : SLA_HEADER_SIZE;
+  uint64_t pos = (fi.seek_byte != 0) ? fi.seek_sample : 0u;
+  uint32_t nb = 0, skipped = 0, stop = SLA_APIRESULT_OK, first_byte = 0, first_sample = 0, end_byte = 0, end_sample = 0;
+  while (pos < win_end) {
+    if (off > data_size) { stop = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE; break; }
+    const uint32_t left = data_size - off;
+    if (left < DEC_WALK_MIN_HEADER) { stop = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE; break; }
+    const uint8_t* p = data + off;
+    uint32_t h[10];
+#pragma unroll
+    for (int k = 0; k < 10; k++) { h[k] = p[k]; }
+    if (((h[0] << 8) | h[1]) != DEC_WALK_SYNC) { stop = SLA_APIRESULT_FAILED_TO_FIND_SYNC_CODE; break; }
+    const uint32_t bsize = ((h[2] << 24) | (h[3] << 16) | (h[4] << 8) | h[5]) + 6u;
+    const uint32_t n = (h[8] << 8) | h[9];
+    if (bsize > left || bsize < DEC_WALK_CRC_START) { stop = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE; break; }
+    if (n == 0 || pos + n <= win_start) { skipped++; off += bsize; pos += n; continue; }       // in front of the window
+    if (n > cap_n) { stop = SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE; break; }
+    if (nb == 0) { first_byte = off; first_sample = (uint32_t)pos; }
+    if (nb < rows) {
+      sla_hip_dec_block b;
+      b.byte_off = fi.img_off + (uint32_t)(off - fi.base_byte); b.byte_len = bsize;
+      b.smp_off = fi.plane_off + (uint32_t)((uint32_t)pos - fi.base_sample); b.num_samples = n; b.flags = 0;
+      blocks[fi.first + nb] = b;
+      block_end[fi.first + nb] = end;
+      crc_field[fi.first + nb] = (h[6] << 8) | h[7];
+    }
+    nb++;
+    off += bsize; pos += n;
+    end_byte = off; end_sample = (uint32_t)pos;
+  }
+  // rows the walk did not reach (the bytes changed since they were counted): empty, header-only, at the range's start
+  for (uint32_t r = nb; r < rows; r++) {
+    sla_hip_dec_block b;
+    b.byte_off = fi.img_off; b.byte_len = DEC_WALK_CRC_START; b.smp_off = fi.plane_off; b.num_samples = 0; b.flags = SLA_HIP_DEC_HEADER_ONLY;
+    blocks[fi.first + r] = b;
+    block_end[fi.first + r] = end;
+    crc_field[fi.first + r] = 0;
+  }
+  sla_hip_dec_window_result res;
+  res.num_blocks = nb; res.stop = stop; res.skipped = skipped; res.first_byte = first_byte; res.first_sample = first_sample;
+  res.end_byte = end_byte; res.end_sample = end_sample; res.reserved = 0;
+  results[f] = res;
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_dec_gather: files at any byte address into the pass image at 4-byte-aligned offsets, zeros from each file's end to
 // its 4-byte boundary.  blockIdx.y walks the table, the x dimension the aligned 16-byte chunks of the file's
 // destination; a lane makes the four words of its chunk.  A chunk that lies wholly inside the padded destination range
@@ -1128,6 +1196,19 @@ extern "C" int sla_hip_launch_dec_walk(const sla_hip_dec_walk_file* d_files, uin
   if (num_files == 0) { return 0; }
   hipLaunchKernelGGL(k_dec_walk, dim3((num_files + 63) / 64), dim3(64), 0, (hipStream_t)stream, d_files, num_files,
                      max_block_samples, crc_check, d_results, d_blocks, d_block_end, d_crc_field);
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_dec_walk_window(const sla_hip_dec_window_file* d_files, uint32_t num_files, uint32_t max_block_samples,
+                                              sla_hip_dec_window_result* d_results, sla_hip_dec_block* d_blocks,
+                                              uint64_t* d_block_end, uint32_t* d_crc_field, sla_hip_stream_t stream)
+{
+  if (d_files == nullptr || d_results == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if ((d_blocks != nullptr || d_block_end != nullptr || d_crc_field != nullptr)
+      && (d_blocks == nullptr || d_block_end == nullptr || d_crc_field == nullptr)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_files == 0) { return 0; }
+  hipLaunchKernelGGL(k_dec_walk_window, dim3((num_files + 63) / 64), dim3(64), 0, (hipStream_t)stream, d_files, num_files,
+                     max_block_samples, d_results, d_blocks, d_block_end, d_crc_field);
   return hip_rc(hipGetLastError());
 }
 

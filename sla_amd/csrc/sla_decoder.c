@@ -44,6 +44,7 @@ struct SLADecoder {
   uint32_t*                 h_crcf;                     /* every block's stored CRC field, next to h_blocks */
   uint32_t                  h_cap;
   float                     timing[6];
+  uint64_t                  win_stats[4];               /* sla_hip_decode_windows_resident: sla_hip_decoder_last_window_stats */
 };
 
 static double now_ms(void)
@@ -702,6 +703,34 @@ static int emit_run(struct SLADecoder* d, const int32_t* planes, uint64_t stride
   return 0;
 }
 
+/* The decode kernels of a pass, once each over its nb blocks: the table (nb rows, then nb block ends) is in d->d_blocks,
+ * the image in d->d_image, d->d_info is cleared.  The block infos come home to d->h_info[first ...]; waited for, the
+ * kernels' time is added to *kernel_ms. */
+static int pass_kernels(struct SLADecoder* d, const dec_format_t* f, uint32_t nb, uint32_t first, uint64_t img_bytes, uint64_t span,
+                        float* kernel_ms)
+{
+  const sla_hip_dec_block* db = (const sla_hip_dec_block*)d->d_blocks.ptr;
+  const sla_hip_dec_info* di = (const sla_hip_dec_info*)d->d_info.ptr;
+  int32_t* planes = (int32_t*)d->d_planes.ptr;
+  const uint32_t C = f->C;
+  float ms_k = 0.0f;
+  BCHK(hipEventRecord(d->ev[0], d->stream));
+  BRC(sla_hip_launch_dec_bits_x((const uint32_t*)d->d_image.ptr, img_bytes, db, nb, C, f->bps, f->lshift, f->ms, f->order, f->ntaps,
+                                d->cfg.enable_crc_check == 1, planes, span, (sla_hip_dec_info*)d->d_info.ptr,
+                                (sla_hip_dec_chan*)d->d_chan.ptr, (int32_t*)d->d_kint.ptr, d->stream,
+                                (const uint64_t*)(db + nb)));
+  BCHK(hipMemcpyAsync(d->h_info + first, d->d_info.ptr, sizeof(sla_hip_dec_info) * nb, hipMemcpyDeviceToHost, d->stream));
+  if (lms_order_ok(f->lms)) {
+    BRC(sla_hip_launch_dec_lms(planes, span, db, di, nb, C, f->lms, d->stream));
+    BRC(sla_hip_launch_dec_ltm(planes, span, db, di, (const sla_hip_dec_chan*)d->d_chan.ptr, nb, C, f->ntaps, d->cfg.max_num_block_samples, d->stream));
+    BRC(sla_hip_launch_dec_lattice(planes, span, db, di, nb, C, (const int32_t*)d->d_kint.ptr, f->order, 1, d->stream));
+  }
+  BCHK(hipEventRecord(d->ev[1], d->stream));
+  BCHK(hipStreamSynchronize(d->stream));
+  if (hipEventElapsedTime(&ms_k, d->ev[0], d->ev[1]) == hipSuccess) { *kernel_ms += ms_k; }
+  return 0;
+}
+
 /* One pass: files[0, nf), all with the same launch parameters, blocks d->h_blocks[files[0].first ...] contiguous.
  * dev != NULL: the samples go to the caller's device destinations through the emit kernel, nothing comes home.
  * Returns -1 on a device or allocation failure. */
@@ -709,7 +738,7 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
                       const dev_out_t* dev, double* t_up, double* t_walk, double* t_down, float* kernel_ms)
 {
   const dec_format_t* f = &files[0].f;
-  const uint32_t C = f->C, first = files[0].first, cap_n = d->cfg.max_num_block_samples;
+  const uint32_t C = f->C, first = files[0].first;
   const int lms_ok = lms_order_ok(f->lms), res = (dev != NULL && dev->resident);
   uint64_t img_bytes = 0, span = 0, out_elems = 0;
   uint32_t nb = 0, i, k, nfin = 0, max_done = 0;
@@ -771,23 +800,7 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
 
   /* ---- the kernels, once each over all blocks of the pass */
   if (nb > 0) {
-    const sla_hip_dec_block* db = (const sla_hip_dec_block*)d->d_blocks.ptr;
-    const sla_hip_dec_info* di = (const sla_hip_dec_info*)d->d_info.ptr;
-    int32_t* planes = (int32_t*)d->d_planes.ptr;
-    BCHK(hipEventRecord(d->ev[0], d->stream));
-    BRC(sla_hip_launch_dec_bits_x((const uint32_t*)d->d_image.ptr, img_bytes, db, nb, C, f->bps, f->lshift, f->ms, f->order, f->ntaps,
-                                  d->cfg.enable_crc_check == 1, planes, span, (sla_hip_dec_info*)d->d_info.ptr,
-                                  (sla_hip_dec_chan*)d->d_chan.ptr, (int32_t*)d->d_kint.ptr, d->stream,
-                                  (const uint64_t*)(db + nb)));
-    BCHK(hipMemcpyAsync(d->h_info + first, d->d_info.ptr, sizeof(sla_hip_dec_info) * nb, hipMemcpyDeviceToHost, d->stream));
-    if (lms_ok) {
-      BRC(sla_hip_launch_dec_lms(planes, span, db, di, nb, C, f->lms, d->stream));
-      BRC(sla_hip_launch_dec_ltm(planes, span, db, di, (const sla_hip_dec_chan*)d->d_chan.ptr, nb, C, f->ntaps, cap_n, d->stream));
-      BRC(sla_hip_launch_dec_lattice(planes, span, db, di, nb, C, (const int32_t*)d->d_kint.ptr, f->order, 1, d->stream));
-    }
-    BCHK(hipEventRecord(d->ev[1], d->stream));
-    BCHK(hipStreamSynchronize(d->stream));
-    if (hipEventElapsedTime(&ms_k, d->ev[0], d->ev[1]) == hipSuccess) { *kernel_ms += ms_k; }
+    if (pass_kernels(d, f, nb, first, img_bytes, span, kernel_ms) != 0) { return -1; }
     if (res && res_finish_pass(d, files, nf, t_up, t_walk) != 0) { return -1; }
   }
 
@@ -1144,6 +1157,303 @@ int sla_hip_resident_headers(struct SLADecoder* d, const uint8_t* const* d_data,
 out:
   free(ok);
   return rc;
+}
+
+/* ------------------------------------------------------------------------------------------------------------
+ * sla_hip_decode_windows_resident (include/sla_hip.h): sla_hip_decode_batch_resident for a window of samples per item.
+ * The source and destination checks, the header gather and pass, the grouping, the pass caps, the kernels, the
+ * examination criteria and the emit are that call's code; what is the window's own is the walk (k_dec_walk_window: only
+ * the blocks the window overlaps get a row), the gather of each item's byte range in place of its whole file, and the
+ * all-or-nothing outcome: no samples before a failing block, no resync.
+ * ------------------------------------------------------------------------------------------------------------ */
+static void win_walk_entry(sla_hip_dec_window_file* w, const sla_hip_decode_window_item* it, uint32_t total)
+{
+  memset(w, 0, sizeof(*w));
+  w->src = it->data; w->data_size = it->data_size; w->total = total; w->win_start = it->start; w->win_len = it->length;
+  w->seek_byte = it->seek_byte; w->seek_sample = it->seek_sample;
+}
+
+/* The count-mode window walk of files[0, nf): one launch, one small copy home; wres[item] is each item's result, from
+ * which every file's first / nb / walk_err / extent are set, and *nblocks; makes room for that many rows in the host tables. */
+static int win_count_walk(struct SLADecoder* d, const sla_hip_decode_window_item* items, bfile_t* files, uint32_t nf,
+                          sla_hip_dec_window_result* wres, uint32_t* nblocks)
+{
+  sla_hip_dec_window_file* wt;
+  sla_hip_dec_window_result* wr;
+  uint64_t total = 0;
+  uint32_t i;
+  if (nf == 0) { return 0; }
+  if (hbuf_reserve(&d->h_src, (sizeof(*wt) + sizeof(*wr)) * (size_t)nf) != 0 || dbuf_reserve(&d->d_src, sizeof(*wt) * (size_t)nf) != 0
+      || dbuf_reserve(&d->d_wres, sizeof(*wr) * (size_t)nf) != 0) { return -1; }
+  wt = (sla_hip_dec_window_file*)d->h_src.ptr;
+  wr = (sla_hip_dec_window_result*)(wt + nf);
+  for (i = 0; i < nf; i++) { win_walk_entry(&wt[i], &items[files[i].item], files[i].f.total); }
+  BCHK(hipMemcpyAsync(d->d_src.ptr, wt, sizeof(*wt) * nf, hipMemcpyHostToDevice, d->stream));
+  BRC(sla_hip_launch_dec_walk_window((const sla_hip_dec_window_file*)d->d_src.ptr, nf, d->cfg.max_num_block_samples,
+                                     (sla_hip_dec_window_result*)d->d_wres.ptr, NULL, NULL, NULL, d->stream));
+  BCHK(hipMemcpyAsync(wr, d->d_wres.ptr, sizeof(*wr) * nf, hipMemcpyDeviceToHost, d->stream));
+  BCHK(hipStreamSynchronize(d->stream));
+  for (i = 0; i < nf; i++) {
+    /* a walk that kept blocks ends behind where it began, in bytes and in samples: anything else is not this kernel's */
+    if (wr[i].end_byte < wr[i].first_byte || wr[i].end_sample < wr[i].first_sample) { return -1; }
+    wres[files[i].item] = wr[i];
+    files[i].first = (uint32_t)total; files[i].nb = wr[i].num_blocks;
+    files[i].walk_err = (SLAApiResult)wr[i].stop; files[i].extent = wr[i].end_sample - wr[i].first_sample;
+    total += wr[i].num_blocks;
+  }
+  if (total > 0xFFFFFFFFull || host_tables_reserve(d, (uint32_t)total) != 0) { return -1; }
+  *nblocks = (uint32_t)total;
+  return 0;
+}
+
+/* The first failure among a file's kept blocks, in file order, by examine_blocks' criteria; a body that does not end
+ * where its size field says, or a reader that ran off the end, is DETECT_DATA_CORRUPTION here: windows do no resync.
+ * SLA_APIRESULT_NG, which neither the walk nor examine_blocks gives, marks "no failure" on the way. */
+static SLAApiResult win_examine(const struct SLADecoder* d, const bfile_t* fl, int lms_ok)
+{
+  const uint32_t* cf = d->h_crcf + fl->first;
+  const sla_hip_dec_block* bl = d->h_blocks + fl->first;
+  const sla_hip_dec_info* in = d->h_info + fl->first;
+  uint32_t j = 0, done = 0, off = 0, pos = 0;
+  SLAApiResult r;
+  while (j < fl->nb && !in[j].overrun) { j++; }
+  if (examine_blocks(d, cf, bl, in, j, lms_ok, SLA_APIRESULT_NG, NULL, &done, &off, &pos, &r)) { return SLA_APIRESULT_DETECT_DATA_CORRUPTION; }
+  if (r != SLA_APIRESULT_NG) { return r; }
+  if (j < fl->nb) {
+    /* block j's reader ran off the end: the criteria that come before the size comparison decide first */
+    if (!examine_blocks(d, cf + j, bl + j, in + j, 1, lms_ok, SLA_APIRESULT_NG, NULL, &done, &off, &pos, &r) && r != SLA_APIRESULT_NG) { return r; }
+    return SLA_APIRESULT_DETECT_DATA_CORRUPTION;
+  }
+  return fl->walk_err;
+}
+
+/* One pass of windows: files[0, nf) share the launch parameters, their rows are d->h_blocks[files[0].first ...].
+ * dv[item] is the item as a device item of the resident call (capacity = length).  Returns -1 on a device or allocation
+ * failure, or when the write-mode walk differs from the count. */
+static int win_pass(struct SLADecoder* d, sla_hip_decode_window_item* items, const sla_hip_decode_device_item* dv, bfile_t* files,
+                    uint32_t nf, const sla_hip_dec_window_result* wres, uint32_t format, uint32_t zero_fill, double* t_gather,
+                    double* t_walk, double* t_down, float* kernel_ms)
+{
+  const dec_format_t* f = &files[0].f;
+  const uint32_t C = f->C, first = files[0].first;
+  const int lms_ok = lms_order_ok(f->lms);
+  uint64_t img_bytes = 0, span = 0;
+  uint32_t nb = 0, i, ne = 0, max_lim = 0;
+  sla_hip_dec_emit* et;
+  double t;
+
+  for (i = 0; i < nf; i++) {
+    const sla_hip_dec_window_result* r = &wres[files[i].item];
+    files[i].img_off = img_bytes; img_bytes += ((uint64_t)(r->end_byte - r->first_byte) + 3) & ~(uint64_t)3;
+    files[i].plane_off = span; span += ((uint64_t)files[i].extent + DEC_BATCH_ALIGN - 1) / DEC_BATCH_ALIGN * DEC_BATCH_ALIGN;
+    nb += files[i].nb;
+    d->win_stats[2] += r->end_byte - r->first_byte;
+  }
+  d->win_stats[3] += span;
+  if (span == 0) { span = 1; }
+  if (dbuf_reserve(&d->d_image, img_bytes + 16) != 0 || hbuf_reserve(&d->h_ptab, sizeof(sla_hip_dec_emit) * (size_t)nf) != 0
+      || dbuf_reserve(&d->d_blocks, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb) != 0
+      || dbuf_reserve(&d->d_info, sizeof(sla_hip_dec_info) * nb) != 0
+      || dbuf_reserve(&d->d_chan, sizeof(sla_hip_dec_chan) * (size_t)nb * C) != 0
+      || dbuf_reserve(&d->d_kint, sizeof(int32_t) * (size_t)nb * C * (f->order + 1)) != 0
+      || dbuf_reserve(&d->d_planes, sizeof(int32_t) * (size_t)span * C) != 0) { return -1; }
+
+  if (nb > 0) {
+    /* ---- the stage: the byte ranges gathered into the pass image, the walk in write mode; then the kernels */
+    sla_hip_dec_gather* gt;
+    sla_hip_dec_window_file* wt;
+    sla_hip_dec_window_result* wr;
+    sla_hip_dec_block* db;
+    uint32_t ng = 0, max_bytes = 0;
+    float ms = 0.0f;
+    if (hbuf_reserve(&d->h_src, (sizeof(*gt) + sizeof(*wt) + sizeof(*wr)) * (size_t)nf) != 0
+        || dbuf_reserve(&d->d_src, (sizeof(*gt) + sizeof(*wt)) * (size_t)nf) != 0 || dbuf_reserve(&d->d_wres, sizeof(*wr) * (size_t)nf) != 0
+        || dbuf_reserve(&d->d_crcf, sizeof(uint32_t) * (size_t)nb) != 0 || res_events(d) != 0) { return -1; }
+    gt = (sla_hip_dec_gather*)d->h_src.ptr;
+    wt = (sla_hip_dec_window_file*)(gt + nf);
+    wr = (sla_hip_dec_window_result*)(wt + nf);
+    memset(gt, 0, sizeof(*gt) * (size_t)nf);
+    for (i = 0; i < nf; i++) {
+      const sla_hip_decode_window_item* it = &items[files[i].item];
+      const sla_hip_dec_window_result* r = &wres[files[i].item];
+      const uint32_t range = r->end_byte - r->first_byte;
+      if (range > 0) {
+        gt[ng].src = it->data + r->first_byte; gt[ng].dst_off = files[i].img_off; gt[ng].bytes = range; gt[ng].reserved = 0;
+        ng++;
+        if (range > max_bytes) { max_bytes = range; }
+      }
+      win_walk_entry(&wt[i], it, files[i].f.total);
+      wt[i].img_off = files[i].img_off; wt[i].range_bytes = range; wt[i].base_byte = r->first_byte; wt[i].base_sample = r->first_sample;
+      wt[i].plane_off = (uint32_t)files[i].plane_off; wt[i].first = files[i].first - first; wt[i].max_rows = files[i].nb;
+    }
+    db = (sla_hip_dec_block*)d->d_blocks.ptr;
+    BCHK(hipMemcpyAsync(d->d_src.ptr, gt, (sizeof(*gt) + sizeof(*wt)) * (size_t)nf, hipMemcpyHostToDevice, d->stream));
+    BCHK(hipEventRecord(d->ev_src[0], d->stream));
+    BRC(sla_hip_launch_dec_gather((const sla_hip_dec_gather*)d->d_src.ptr, ng, max_bytes, (uint8_t*)d->d_image.ptr, img_bytes, d->stream));
+    BCHK(hipEventRecord(d->ev_src[1], d->stream));
+    BRC(sla_hip_launch_dec_walk_window((const sla_hip_dec_window_file*)((const sla_hip_dec_gather*)d->d_src.ptr + nf), nf,
+                                       d->cfg.max_num_block_samples, (sla_hip_dec_window_result*)d->d_wres.ptr, db, (uint64_t*)(db + nb),
+                                       (uint32_t*)d->d_crcf.ptr, d->stream));
+    BCHK(hipMemcpyAsync(wr, d->d_wres.ptr, sizeof(*wr) * nf, hipMemcpyDeviceToHost, d->stream));
+    BCHK(hipMemcpyAsync(d->h_blocks + first, db, sizeof(*db) * (size_t)nb, hipMemcpyDeviceToHost, d->stream));
+    BCHK(hipMemcpyAsync(d->h_crcf + first, d->d_crcf.ptr, sizeof(uint32_t) * (size_t)nb, hipMemcpyDeviceToHost, d->stream));
+    BCHK(hipEventRecord(d->ev_src[2], d->stream));
+    BCHK(hipMemsetAsync(d->d_info.ptr, 0, sizeof(sla_hip_dec_info) * nb, d->stream));
+    if (pass_kernels(d, f, nb, first, img_bytes, span, kernel_ms) != 0) { return -1; }
+    if (hipEventElapsedTime(&ms, d->ev_src[0], d->ev_src[1]) == hipSuccess) { *t_gather += ms; }
+    if (hipEventElapsedTime(&ms, d->ev_src[1], d->ev_src[2]) == hipSuccess) { *t_walk += ms; }
+    /* a file whose chain changed since it was counted fails the call */
+    for (i = 0; i < nf; i++) { if (memcmp(&wr[i], &wres[files[i].item], sizeof(wr[i])) != 0) { return -1; } }
+  }
+
+  /* ---- every window examined on its own; delivered whole from its first sample in the region, or not at all */
+  t = now_ms();
+  et = (sla_hip_dec_emit*)d->h_ptab.ptr;
+  for (i = 0; i < nf; i++) {
+    sla_hip_decode_window_item* it = &items[files[i].item];
+    const uint32_t rest = files[i].f.total - it->start;
+    uint32_t done = 0;
+    it->result = win_examine(d, &files[i], lms_ok);
+    if (it->result == SLA_APIRESULT_OK) { done = (it->length < rest) ? it->length : rest; }
+    it->output_num_samples = done;
+    ne += emit_entry(et + ne, &dv[files[i].item], zero_fill, files[i].plane_off + (it->start - wres[files[i].item].first_sample), done, C,
+                     f->ms, 32u - f->bps + f->lshift, f->bps, &max_lim);
+  }
+  if (emit_run(d, (const int32_t*)d->d_planes.ptr, span, et, ne, max_lim, format, kernel_ms) != 0) { return -1; }
+  *t_down += now_ms() - t;
+  return 0;
+}
+
+int sla_hip_decode_windows_resident(struct SLADecoder* d, sla_hip_decode_window_item* items, uint32_t num_items,
+                                    uint32_t sample_format, uint32_t flags, sla_hip_stream_t stream)
+{
+  const uint32_t zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u;
+  const uint64_t esize = (sample_format == SLA_HIP_PCM_S16) ? 2u : 4u;
+  sla_hip_decode_device_item* dv;
+  sla_hip_dec_window_result* wres;
+  bfile_t* files;
+  const uint8_t** src;
+  uint32_t *size, *chans;
+  uint8_t *ok, *state;
+  struct SLAWaveFormat wf_after;
+  struct SLAEncodeParameter ep_after;
+  uint32_t flag_after, nf = 0, nblocks = 0, passes = 0, i, p0;
+  int rc = 0;
+  float kernel_ms = 0.0f;
+  double t0 = now_ms(), t_gather = 0.0, t_walk = 0.0, t_down = 0.0, t;
+  if (d == NULL || (items == NULL && num_items > 0) || sample_format > SLA_HIP_PCM_F32 || (flags & ~SLA_HIP_DEC_ZERO_FILL) != 0) {
+    return SLA_APIRESULT_INVALID_ARGUMENT;
+  }
+  memset(d->timing, 0, sizeof(d->timing));
+  memset(d->win_stats, 0, sizeof(d->win_stats));
+  if (num_items == 0) { return 0; }
+  wf_after = d->wave_format; ep_after = d->encode_param; flag_after = d->status_flag;
+  dv = (sla_hip_decode_device_item*)calloc(num_items, sizeof(*dv));
+  wres =(sla_hip_dec_window_result*)calloc(num_items, sizeof(*wres));
+  files = (bfile_t*)calloc(num_items, sizeof(*files));
+  src = (const uint8_t**)calloc(num_items, sizeof(*src));
+  size = (uint32_t*)calloc(num_items, sizeof(*size));
+  chans = (uint32_t*)calloc(num_items, sizeof(*chans));
+  ok = (uint8_t*)calloc(num_items, 1);
+  state = (uint8_t*)calloc(num_items, 1);
+  if (dv == NULL || wres == NULL || files == NULL || src == NULL || size == NULL || chans == NULL || ok == NULL || state == NULL) {
+    rc = SLA_APIRESULT_NG; goto out;
+  }
+  /* the sources and the hints, on the host, before anything of an item is read */
+  for (i = 0; i < num_items; i++) {
+    const sla_hip_decode_window_item* it = &items[i];
+    dv[i].data = it->data; dv[i].dst = it->dst; dv[i].channel_stride = it->channel_stride; dv[i].sample_stride = it->sample_stride;
+    dv[i].data_size = it->data_size; dv[i].capacity = it->length;
+    src[i] = it->data; size[i] = it->data_size;
+    ok[i] = (uint8_t)(src_region_ok(it->data, it->data_size)
+                      && (it->seek_byte == 0 ? it->seek_sample == 0 : it->seek_byte >= SLA_HEADER_SIZE) && it->seek_sample <= it->start);
+  }
+  /* nothing is read or written before the caller's stream has reached this call */
+  if (order_behind(d, stream) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+  t = now_ms();
+  if (res_fetch_headers(d, src, size, ok, num_items) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+  t_gather += now_ms() - t;
+
+  /* ---- headers in item order, as in batch_run; the destinations are checked with each header's channel count first */
+  t = now_ms();
+  for (i = 0; i < num_items; i++) {
+    sla_hip_decode_window_item* it = &items[i];
+    const uint8_t* hdr = (const uint8_t*)d->h_hdr.ptr + (size_t)i * RES_HDR_SLOT;
+    dec_format_t f;
+    SLAApiResult ret;
+    int verdict;
+    it->output_num_samples = 0; it->first_block_byte = 0; it->first_block_sample = 0;
+    state[i] = DEV_REFUSED; it->result = SLA_APIRESULT_INVALID_ARGUMENT;
+    if (!ok[i]) { continue; }
+    chans[i] = header_channels(hdr, it->data_size);
+    if (!dst_region_ok(&dv[i], chans[i], esize)) { continue; }
+    state[i] = DEV_PENDING;
+    if ((ret = file_format(d, hdr, it->data_size, &f)) != SLA_APIRESULT_OK) { it->result = ret; continue; }
+    if (it->start > f.total) { state[i] = DEV_REFUSED; continue; }
+    if ((verdict = format_verdict(&f)) >= 0) { it->result = verdict; continue; }
+    it->result = SLA_APIRESULT_OK;
+    if (it->start == f.total || it->length == 0) { continue; }       /* OK, no samples: nothing is decoded */
+    files[nf].item = i; files[nf].f = f;
+    state[i] = DEV_DECODED;
+    nf++;
+  }
+  wf_after = d->wave_format; ep_after = d->encode_param; flag_after = d->status_flag;
+
+  /* ---- windows that share the launch parameters next to each other, every chain walked up to its window's end */
+  qsort(files, nf, sizeof(*files), bfile_cmp);
+  if (win_count_walk(d, items, files, nf, wres, &nblocks) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+  for (i = 0; i < nf; i++) {
+    const sla_hip_dec_window_result* r = &wres[files[i].item];
+    items[files[i].item].first_block_byte = r->first_byte; items[files[i].item].first_block_sample = r->first_sample;
+    d->win_stats[0] += r->skipped; d->win_stats[1] += r->num_blocks;
+  }
+  t_walk += now_ms() - t;
+
+  /* ---- passes: batch_run's caps, an item costing its byte range and the samples of its kept blocks */
+  for (p0 = 0; p0 < nf; ) {
+    uint64_t smp = 0, bytes = 0;
+    uint32_t p1 = p0;
+    while (p1 < nf && same_launch(&files[p1].f, &files[p0].f)) {
+      const sla_hip_dec_window_result* r = &wres[files[p1].item];
+      const uint64_t s1 = ((uint64_t)files[p1].extent + DEC_BATCH_ALIGN) * files[p1].f.C;
+      const uint64_t b1 = (uint64_t)(r->end_byte - r->first_byte) + 4;
+      if (p1 > p0 && (smp + s1 > SLA_HIP_DEC_BATCH_PASS || bytes + b1 > DEC_BATCH_PASS_BYTES)) { break; }
+      smp += s1; bytes += b1; p1++;
+    }
+    if (win_pass(d, items, dv, files + p0, p1 - p0, wres, sample_format, zero_fill, &t_gather, &t_walk, &t_down, &kernel_ms) != 0) {
+      rc = SLA_APIRESULT_NG; goto out;
+    }
+    passes++;
+    p0 = p1;
+  }
+
+  /* ---- destinations of items whose header gave a channel count but of which nothing was decoded: the zero fill */
+  if (zero_fill) {
+    sla_hip_dec_emit* et = (sla_hip_dec_emit*)calloc(num_items, sizeof(*et));
+    uint32_t ne = 0, max_lim = 0;
+    if (et == NULL) { rc = SLA_APIRESULT_NG; goto out; }
+    t = now_ms();
+    for (i = 0; i < num_items; i++) {
+      if (state[i] == DEV_PENDING) { ne += emit_entry(et + ne, &dv[i], 1, 0, 0, chans[i], 0, 0, 32, &max_lim); }
+    }
+    if (emit_run(d, NULL, 1, et, ne, max_lim, sample_format, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; }
+    free(et);
+    t_down += now_ms() - t;
+  }
+
+out:
+  d->wave_format = wf_after; d->encode_param = ep_after; d->status_flag = flag_after;
+  d->timing[0] = (float)t_gather; d->timing[1] = (float)t_walk; d->timing[2] = kernel_ms; d->timing[3] = (float)t_down;
+  d->timing[4] = (float)(now_ms() - t0); d->timing[5] = (float)passes;
+  free(dv); free(wres); free(files); free((void*)src); free(size); free(chans); free(ok); free(state);
+  return rc;
+}
+
+int sla_hip_decoder_last_window_stats(const struct SLADecoder* decoder, uint64_t counters[4])
+{
+  if (decoder == NULL || counters == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  memcpy(counters, decoder->win_stats, sizeof(decoder->win_stats));
+  return 0;
 }
 
 int sla_hip_decoder_last_timing(const struct SLADecoder* decoder, float* timing_ms)
