@@ -186,6 +186,28 @@ int sla_hip_launch_lpc_blocks_cert_x(const int32_t* d_pcm, uint64_t plane_stride
 int sla_hip_launch_prepass(const int32_t* d_pcm, uint64_t plane_stride, uint32_t num_channels,
                            uint32_t num_samples, uint32_t bits_per_sample, uint32_t mid_side,
                            uint32_t* d_or_mask, uint64_t* d_nz_mask, sla_hip_stream_t stream);
+/* Search beside the prepass (option "search_early"): d_early names SLA_HIP_EARLY_WORDS device words that the prepass and
+ * the kernels started beside it share.  d_early[SLA_HIP_EARLY_CANCEL] must be 0 before either is launched (nothing here
+ * clears it: the encoder clears it with the first search kernel of a launch that does not run beside a prepass); k_prepass
+ * sets it to 1 the moment it meets an all-zero mask word, and one thread behind it on the same stream sets it for an OR
+ * word of 0 or samples wider than bits_per_sample and stores the file's offset_lshift in d_early[SLA_HIP_EARLY_LSHIFT]
+ * (0 in those two cases).  Every kernel of the `_early` launchers below reads the flag once at its start (the tile sums:
+ * once per wave) and returns when it is set; no kernel ever waits for a word in memory.
+ * sla_hip_launch_search_exact_early: exact_limit is the limit of offset_lshift 0; the tile sums are queued at once, then
+ * the stream waits for prepass_done (a hipEvent_t recorded behind sla_hip_launch_prepass_early on its stream) and the
+ * kernels behind the wait scale the limit by 4^offset_lshift.  sla_hip_launch_expand_early: int_shift is the shift of
+ * offset_lshift 0, the kernel adds the stored one; cancelled, it leaves d_run and counts alone.  Both, and
+ * sla_hip_launch_plan_early, must be queued on that stream behind that wait.  d_early == NULL (where allowed: plan, expand)
+ * is the plain launcher.
+ * max_workgroups (0: no limit) caps the prepass's grid, its waves walking on through the file: the tile sums beside it read
+ * the same samples, and a prepass that takes all the memory bandwidth there is slows them by more than it gains. */
+#define SLA_HIP_EARLY_CANCEL 0
+#define SLA_HIP_EARLY_LSHIFT 1
+#define SLA_HIP_EARLY_WORDS  2
+int sla_hip_launch_prepass_early(const int32_t* d_pcm, uint64_t plane_stride, uint32_t num_channels,
+                                 uint32_t num_samples, uint32_t bits_per_sample, uint32_t mid_side,
+                                 uint32_t* d_or_mask, uint64_t* d_nz_mask, uint32_t* d_early, uint32_t max_workgroups,
+                                 sla_hip_stream_t stream);
 /* The same pass that also stores the OR of every 1024-sample tile (d_tile_or: ceil(num_samples / 4096) * 4 words):
  * a batch of files laid out back to back on 1024-sample boundaries gets its offset_lshift per file from them. */
 #define SLA_HIP_PREPASS_TILE 1024u
@@ -321,6 +343,14 @@ int sla_hip_launch_search_exact_x(const int32_t* d_pcm, uint64_t plane_stride, u
                                 const sla_hip_lpc_cand* d_cands, double* d_tile_sums, double* d_out,
                                 double exact_limit, double cert_safety, uint32_t* d_any_exact /* one scratch word, may be NULL */,
                                 sla_hip_stream_t stream, const sla_hip_launch_extra* extra);
+/* (beside the prepass: see sla_hip_launch_prepass_early; num_groups == 0 is refused -- nothing would queue the wait) */
+int sla_hip_launch_search_exact_early(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                                const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                                uint32_t max_cands_per_group,
+                                const sla_hip_lpc_cand* d_cands, double* d_tile_sums, double* d_out,
+                                double exact_limit, double cert_safety, uint32_t* d_any_exact /* one scratch word, may be NULL */,
+                                sla_hip_stream_t stream, const sla_hip_launch_extra* extra,
+                                const uint32_t* d_early, void* prepass_done /* hipEvent_t */);
 
 /* The scalar tail of the partition search on the device: estimated code length per candidate, adjacency
  * matrix, shortest path (reference src/SLAPredictor.c:416-468, 1521-1581, 1615-1692).  d_groups: the groups of
@@ -337,6 +367,10 @@ int sla_hip_launch_plan(const sla_hip_lpc_group* d_groups, uint32_t num_superfra
                         uint32_t order, uint32_t bits_per_sample, const sla_hip_lpc_cand* d_cands,
                         double* d_lpc_out, uint32_t* d_parts, uint32_t* d_num_parts, uint32_t* d_status,
                         sla_hip_stream_t stream);
+int sla_hip_launch_plan_early(const sla_hip_lpc_group* d_groups, uint32_t num_superframes, uint32_t num_channels,
+                              uint32_t order, uint32_t bits_per_sample, const sla_hip_lpc_cand* d_cands,
+                              double* d_lpc_out, uint32_t* d_parts, uint32_t* d_num_parts, uint32_t* d_status,
+                              sla_hip_stream_t stream, const uint32_t* d_early);
 
 /* Block table of one run of super-frames from sla_hip_launch_plan's partitions, written on the device, so that the
  * block-stage kernels can follow the partition search without the host building and uploading their descriptors
@@ -378,6 +412,14 @@ int sla_hip_launch_expand_masked(const sla_hip_superframe* d_superframes, uint32
                           uint32_t* d_run, uint32_t* d_prefix, sla_hip_lpc_group* d_groups, sla_hip_lpc_cand* d_cands,
                           sla_hip_acf_job* d_acf_jobs, uint32_t group_capacity,
                           uint32_t* counts, uint32_t sequence, const uint64_t* d_nonzero_mask, sla_hip_stream_t stream);
+int sla_hip_launch_expand_early(const sla_hip_superframe* d_superframes, uint32_t num_superframes,
+                          const uint32_t* d_parts, const uint32_t* d_num_parts, const uint32_t* d_status,
+                          uint32_t num_channels, uint32_t int_shift,
+                          const uint32_t* d_win_len, const uint32_t* d_win_off, uint32_t num_windows,
+                          uint32_t* d_run, uint32_t* d_prefix, sla_hip_lpc_group* d_groups, sla_hip_lpc_cand* d_cands,
+                          sla_hip_acf_job* d_acf_jobs, uint32_t group_capacity,
+                          uint32_t* counts, uint32_t sequence, const uint64_t* d_nonzero_mask, sla_hip_stream_t stream,
+                          const uint32_t* d_early);
 
 /* Building blocks of the per-call predictor API (include/SLAPredictor.h), also usable on their own:
  *   sla_hip_launch_lpc_f64      sla_hip_launch_lpc in its search form on samples that already are doubles
@@ -1167,6 +1209,15 @@ int sla_hip_get_trace(struct SLAEncoder* encoder, sla_hip_trace* trace);
  * Covers sla_hip_analyze_device / SLAEncoder_EncodeWhole (not streamed), sla_hip_encode_batch (lanes included),
  * sla_hip_encode_batch_device and sla_hip_analyze_batch_device; the pieces of a streamed file, the sla_hip_shard_* calls and
  * SLAEncoder_EncodeBlock keep the mask.  See sla_hip_last_silence; DESIGN section 2e.
+ * "search_early" (1 = default, 0): a single file whose predecessor on this handle had no silence starts its whole search
+ * chain (tile sums, certificate, plan, block tables) BESIDE the prepass, on another stream, instead of behind the host's look
+ * at the prepass result: the chain reads offset_lshift from a device word the prepass stores, and a prepass that finds
+ * silence (or an OR word of 0) raises a device flag at which every kernel of the chain returns at once; the host then
+ * launches the search again with the right tables.  Files of any length.  0: the search follows the prepass (short files:
+ * on the guess "like the last file").  Same bytes either way.  Batches, the sla_hip_shard_* calls and the pieces of a
+ * streamed file are not affected.  See sla_hip_launch_prepass_early, sla_hip_last_search_early; DESIGN section 2.
+ * "early_prepass_groups" (0 = default: three per two compute units; 1..2^20): most workgroups of the prepass that runs beside
+ * such a search (sla_hip_launch_prepass_early's max_workgroups; a value of at least the file's 4096-sample tiles is "no cap").
  * SLAEncoder_EncodeWhole of long files: "stream" (0: never streamed), "stream_piece" (samples per piece, all channels
  * together; default 32 Mi; a file of fewer than two pieces is not streamed), "stream_lanes" (worker lanes, 1..6, default 6; pieces are handed to whichever lane is free),
  * "batch_lanes" (sla_hip_encode_batch: a batch of at least 8 files and 16 Mi samples is dealt out in groups of consecutive files to
@@ -1229,9 +1280,17 @@ int sla_hip_last_silence(const struct SLAEncoder* encoder, uint32_t counters[4])
 /* 4 counters: pipeline chunks of the last analysis whose block stage was launched from device-written tables
  * (sla_hip_launch_expand; option "device_expand"), its pipeline chunks in all; since the handle was created: the analyses
  * that found their search tables kept from the file before (same length and parameters, no silence; option
- * "table_cache"), and those among them whose searches -- launched behind the prepass on the guess that the file is like
- * the last one (short files only) -- had to go out again because the prepass said otherwise. */
+ * "table_cache"), and the analyses whose searches were launched before the host had seen the prepass result -- on the guess
+ * that the file is like the last one -- and whose prepass then said otherwise: silence, or another OR word.  (With option
+ * "search_early" another OR word costs nothing -- the chain reads the shift from the device -- but is still counted here;
+ * the starts that were really thrown away are sla_hip_last_search_early's.) */
 int sla_hip_last_expand(const struct SLAEncoder* encoder, uint32_t* counters);
+
+/* Option "search_early", 4 counters: 1 if the last analysis started its search beside the prepass; since the handle was
+ * created: the analyses that did, and those among them whose start was cancelled (the prepass found silence, an OR word of
+ * 0 or samples wider than declared, or the host found the file's short last super-frame silent) and whose search went out
+ * a second time; 0 (reserved). */
+int sla_hip_last_search_early(const struct SLAEncoder* encoder, uint32_t counters[4]);
 
 /* 4 floats [ms]: execution time of k_lpc_blocks, k_lattice, k_ltm_acf, k_tail in the last analysis, summed over
  * its launches and measured ON the device (first wave in to last wave out, constant 100 MHz clock) -- what

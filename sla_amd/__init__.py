@@ -230,6 +230,8 @@ def lib():
             L.sla_hip_last_silence.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
             L.sla_hip_launch_zero_runs.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                                    C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "sla_hip_last_search_early"):          # (SLA_HIP_LIB may name an older build in an A/B run)
+            L.sla_hip_last_search_early.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.sla_hip_search_exact_lags.restype = C.c_uint32
         L.sla_hip_encoder_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
         L.sla_hip_shard_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, u32p, C.POINTER(C.c_uint64)]
@@ -355,6 +357,9 @@ EXPORTED_SYMBOLS = [
     "sla_hip_launch_verify_blocks", "sla_hip_last_verify", "sla_hip_verify_last_image",
     # silence from a device-written run list (include/sla_hip.h)
     "sla_hip_launch_zero_runs", "sla_hip_last_silence",
+    # search beside the prepass (option "search_early")
+    "sla_hip_launch_prepass_early", "sla_hip_launch_search_exact_early", "sla_hip_launch_plan_early", "sla_hip_launch_expand_early",
+    "sla_hip_last_search_early",
 ]
 
 
@@ -749,6 +754,13 @@ class Encoder:
         bytes downloaded beyond the fixed tail words); a batch's passes and worker lanes are summed (the route: the maximum)"""
         c = (C.c_uint32 * 4)()
         self._check(self._lib.sla_hip_last_silence(self._h, c), "sla_hip_last_silence")
+        return tuple(c)
+
+    def last_search_early(self):
+        """option "search_early": (1 if the last analysis started its search beside the prepass; analyses of this handle
+        that did; those among them whose start was cancelled and whose search went out again; 0)"""
+        c = (C.c_uint32 * 4)()
+        self._check(self._lib.sla_hip_last_search_early(self._h, c), "sla_hip_last_search_early")
         return tuple(c)
 
     def last_verify(self):

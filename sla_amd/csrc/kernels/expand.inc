@@ -46,8 +46,11 @@ void k_expand_scan(const sla_hip_superframe* __restrict__ sf, uint32_t num_sf, c
                    const uint32_t* __restrict__ nparts, const uint32_t* __restrict__ status, uint32_t nch,
                    const uint32_t* __restrict__ win_len, uint32_t num_win,
                    uint32_t* __restrict__ run, uint32_t* __restrict__ prefix, uint32_t capacity,
-                   volatile uint32_t* counts, uint32_t sequence, const uint64_t* __restrict__ nz)
+                   volatile uint32_t* counts, uint32_t sequence, const uint64_t* __restrict__ nz, const uint32_t* early)
 {
+  // started beside the prepass and called off: the running numbers stay where they are and no sequence word is published
+  // (the host launches the whole chain again; the whole workgroup leaves together)
+  if (early_cancelled(early)) { return; }
   __shared__ uint32_t s_has[EXPAND_MAX_LEN / 32 + 1];             // bit per block length: its window table exists
   __shared__ uint32_t s_cb[EXPAND_TILE], s_cl[EXPAND_TILE];       // per super-frame of the tile: blocks, blocks of live super-frames
   __shared__ uint32_t s_wb[EXPAND_THREADS / 64], s_wl[EXPAND_THREADS / 64];
@@ -143,9 +146,14 @@ void k_expand_write(const sla_hip_superframe* __restrict__ sf, uint32_t num_sf, 
                     const uint32_t* __restrict__ win_len, const uint32_t* __restrict__ win_off, uint32_t num_win,
                     const uint32_t* __restrict__ run, const uint32_t* __restrict__ prefix,
                     sla_hip_lpc_group* __restrict__ groups, sla_hip_lpc_cand* __restrict__ cands, sla_hip_acf_job* __restrict__ acf_jobs,
-                    const uint64_t* __restrict__ nz)
+                    const uint64_t* __restrict__ nz, const uint32_t* early)
 {
   __shared__ uint32_t s_wlen[EXPAND_MAX_WINDOWS], s_woff[EXPAND_MAX_WINDOWS];
+  // early (may be NULL): int_shift is the shift of offset_lshift 0, the prepass has stored the file's shift meanwhile
+  if (early != nullptr) {
+    if (early_cancelled(early)) { return; }
+    int_shift += early[SLA_HIP_EARLY_LSHIFT];
+  }
   if (run[2] != 0u) { return; }                        // the scan found this run (or an earlier one) unfit for device tables
   for (uint32_t i = threadIdx.x; i < num_win && i < EXPAND_MAX_WINDOWS; i += blockDim.x) { s_wlen[i] = win_len[i]; s_woff[i] = win_off[i]; }
   __syncthreads();

@@ -55,26 +55,48 @@ static inline int hip_rc(hipError_t e) { return (e == hipSuccess) ? 0 : -(int)e;
 
 static int launch_prepass_impl(const int32_t* d_pcm, uint64_t plane_stride, uint32_t num_channels,
                                uint32_t num_samples, uint32_t bits_per_sample, uint32_t mid_side,
-                               uint32_t* d_or_mask, uint64_t* d_nz_mask, uint32_t* d_tile_or, sla_hip_stream_t stream)
+                               uint32_t* d_or_mask, uint64_t* d_nz_mask, uint32_t* d_tile_or, sla_hip_stream_t stream,
+                               uint32_t* d_early = nullptr, uint32_t max_workgroups = 0)
 {
+  uint32_t* const cancel = (d_early != nullptr) ? d_early + SLA_HIP_EARLY_CANCEL : nullptr;
   if (d_pcm == nullptr || d_or_mask == nullptr || d_nz_mask == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if (num_channels == 0 || num_channels > 8 || bits_per_sample == 0 || bits_per_sample > 32
       || plane_stride < num_samples || (mid_side && num_channels != 2)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(d_or_mask, 0, 2 * sizeof(uint32_t), st);
   if (e != hipSuccess) { return hip_rc(e); }
-  if (num_samples == 0) { return 0; }
+  if (num_samples == 0) {
+    if (d_early != nullptr) { hipLaunchKernelGGL(k_prepass_done, dim3(1), dim3(64), 0, st, (const uint32_t*)d_or_mask, bits_per_sample, d_early); return hip_rc(hipGetLastError()); }
+    return 0;
+  }
   uint64_t nwords = ((uint64_t)num_samples + 63) / 64;
   uint32_t nblocks = (uint32_t)((nwords + 4 * PREPASS_WORDS - 1) / (4 * PREPASS_WORDS));
   const uint32_t shift = 32u - bits_per_sample;
+  uint32_t wave_stride = 0;
+  if (max_workgroups != 0 && max_workgroups < nblocks) { nblocks = max_workgroups; wave_stride = 4u * nblocks; }
   if (num_channels == 1) {
-    hipLaunchKernelGGL(k_prepass<1>, dim3(nblocks), dim3(256), 0, st, d_pcm, plane_stride, num_channels, num_samples, shift, mid_side, d_or_mask, d_nz_mask, d_tile_or);
+    hipLaunchKernelGGL(k_prepass<1>, dim3(nblocks), dim3(256), 0, st, d_pcm, plane_stride, num_channels, num_samples, shift, mid_side, d_or_mask, d_nz_mask, d_tile_or, cancel, wave_stride);
   } else if (num_channels == 2) {
-    hipLaunchKernelGGL(k_prepass<2>, dim3(nblocks), dim3(256), 0, st, d_pcm, plane_stride, num_channels, num_samples, shift, mid_side, d_or_mask, d_nz_mask, d_tile_or);
+    hipLaunchKernelGGL(k_prepass<2>, dim3(nblocks), dim3(256), 0, st, d_pcm, plane_stride, num_channels, num_samples, shift, mid_side, d_or_mask, d_nz_mask, d_tile_or, cancel, wave_stride);
   } else {
-    hipLaunchKernelGGL(k_prepass<0>, dim3(nblocks), dim3(256), 0, st, d_pcm, plane_stride, num_channels, num_samples, shift, mid_side, d_or_mask, d_nz_mask, d_tile_or);
+    hipLaunchKernelGGL(k_prepass<0>, dim3(nblocks), dim3(256), 0, st, d_pcm, plane_stride, num_channels, num_samples, shift, mid_side, d_or_mask, d_nz_mask, d_tile_or, cancel, wave_stride);
+  }
+  if (d_early != nullptr) {
+    e = hipGetLastError();
+    if (e != hipSuccess) { return hip_rc(e); }
+    hipLaunchKernelGGL(k_prepass_done, dim3(1), dim3(64), 0, st, (const uint32_t*)d_or_mask, bits_per_sample, d_early);
   }
   return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_prepass_early(const int32_t* d_pcm, uint64_t plane_stride, uint32_t num_channels,
+                                            uint32_t num_samples, uint32_t bits_per_sample, uint32_t mid_side,
+                                            uint32_t* d_or_mask, uint64_t* d_nz_mask, uint32_t* d_early, uint32_t max_workgroups,
+                                            sla_hip_stream_t stream)
+{
+  if (d_early == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  return launch_prepass_impl(d_pcm, plane_stride, num_channels, num_samples, bits_per_sample, mid_side, d_or_mask, d_nz_mask, nullptr, stream, d_early,
+                             max_workgroups);
 }
 
 extern "C" int sla_hip_launch_prepass(const int32_t* d_pcm, uint64_t plane_stride, uint32_t num_channels,
@@ -392,11 +414,12 @@ extern "C" uint32_t sla_hip_search_exact_lags(uint32_t order)
   return (nb <= 3) ? 12 : (nb <= 5) ? 20 : (nb <= 9) ? 36 : (nb <= 13) ? 52 : 0;
 }
 
-extern "C" int sla_hip_launch_search_exact_x(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+static int launch_search_exact_impl(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
                                            const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
                                            uint32_t max_cands_per_group,
                                            const sla_hip_lpc_cand* d_cands, double* d_tile_sums, double* d_out,
-                                           double exact_limit, double cert_safety, uint32_t* d_any_exact, sla_hip_stream_t stream, const sla_hip_launch_extra* extra)
+                                           double exact_limit, double cert_safety, uint32_t* d_any_exact, sla_hip_stream_t stream, const sla_hip_launch_extra* extra,
+                                           const uint32_t* d_early, void* prepass_done)
 {
   if (d_pcm == nullptr || d_groups == nullptr || d_cands == nullptr || d_tile_sums == nullptr || d_out == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   const uint32_t lags = sla_hip_search_exact_lags(order);
@@ -411,9 +434,9 @@ extern "C" int sla_hip_launch_search_exact_x(const int32_t* d_pcm, uint64_t plan
   const uint32_t waves = num_groups * tiles;
   const dim3 grid((waves + 3) / 4), block(256);
   switch (lags) {
-    case 12: hipLaunchKernelGGL(k_acf_tiles<3>, grid, block, 0, st, d_pcm, plane_stride, mid_side, d_groups, num_groups, tiles, d_tile_sums, cl); break;
+    case 12: hipLaunchKernelGGL(k_acf_tiles<3>, grid, block, 0, st, d_pcm, plane_stride, mid_side, d_groups, num_groups, tiles, d_tile_sums, cl, d_early); break;
     // (lag slots that no order <= `order` reads stay unwritten: orders 16 / 32 / 48 skip the top three of 20 / 36 / 52)
-#define SLA_ACFT(NBB, TOPP) hipLaunchKernelGGL((k_acf_tiles_lds<NBB, TOPP>), grid, block, 0, st, d_pcm, plane_stride, mid_side, d_groups, num_groups, tiles, d_tile_sums, cl)
+#define SLA_ACFT(NBB, TOPP) hipLaunchKernelGGL((k_acf_tiles_lds<NBB, TOPP>), grid, block, 0, st, d_pcm, plane_stride, mid_side, d_groups, num_groups, tiles, d_tile_sums, cl, d_early)
     case 20: if (order == 16) { SLA_ACFT(5, 17); } else { SLA_ACFT(5, 20); } break;
     case 36: if (order == 32) { SLA_ACFT(9, 33); } else { SLA_ACFT(9, 36); } break;
     default: if (order == 48) { SLA_ACFT(13, 49); } else { SLA_ACFT(13, 52); } break;
@@ -421,6 +444,11 @@ extern "C" int sla_hip_launch_search_exact_x(const int32_t* d_pcm, uint64_t plan
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { return hip_rc(e); }
+  if (prepass_done != nullptr) {
+    // the tile sums need nothing from the prepass and run beside it; what follows reads the offset_lshift it stores
+    e = hipStreamWaitEvent(st, (hipEvent_t)prepass_done, 0);
+    if (e != hipSuccess) { return hip_rc(e); }
+  }
   // lanes = (group, candidate): `per` candidate slots per group and pass, `gpw` groups per wave
   const uint32_t per = (max_cands_per_group < XF_BATCH) ? max_cands_per_group : XF_BATCH;
   uint32_t gpw = XF_BATCH / per;
@@ -439,7 +467,7 @@ extern "C" int sla_hip_launch_search_exact_x(const int32_t* d_pcm, uint64_t plan
       e = ensure_dynamic_lds((const void*)k_search_finish<PP, 0>, lds_r); \
       if (e != hipSuccess) { return hip_rc(e); } \
       hipLaunchKernelGGL((k_search_finish<PP, 0>), dim3((num_groups + gpw - 1) / gpw), dim3(64), lds_r, st, order, lags, gpw, per, \
-                         d_groups, num_groups, d_cands, d_tile_sums, d_out, exact_limit, cert_safety, d_any_exact); \
+                         d_groups, num_groups, d_cands, d_tile_sums, d_out, exact_limit, cert_safety, d_any_exact, d_early); \
     } else { \
       e = ensure_dynamic_lds((const void*)k_search_finish<PP, 1>, lds_r); \
       if (e != hipSuccess) { return hip_rc(e); } \
@@ -454,13 +482,13 @@ extern "C" int sla_hip_launch_search_exact_x(const int32_t* d_pcm, uint64_t plan
         const uint32_t win_tiles = (max_window + SLA_HIP_XTILE - 1) / SLA_HIP_XTILE, stage = (win_tiles >= 6u) ? XC_STAGE : 0u; \
         const uint32_t r_doubles = XC_CANDS * (order + 1), lds_doubles = (r_doubles > stage) ? r_doubles : stage; \
         hipLaunchKernelGGL((k_search_cert<PP>), dim3((uint32_t)((slots_bound + XC_CANDS - 1) / XC_CANDS)), dim3(64), sizeof(double) * lds_doubles, st, \
-                           order, lags, max_cands_per_group, d_groups, num_groups, d_cands, d_tile_sums, d_out, exact_limit, cert_safety, d_any_exact, stage ? lds_doubles : 0u); \
+                           order, lags, max_cands_per_group, d_groups, num_groups, d_cands, d_tile_sums, d_out, exact_limit, cert_safety, d_any_exact, stage ? lds_doubles : 0u, d_early); \
       } else { \
       hipLaunchKernelGGL((k_search_finish<PP, 1>), dim3((num_groups + gpw - 1) / gpw), dim3(64), lds_r, st, order, lags, gpw, per, \
-                         d_groups, num_groups, d_cands, d_tile_sums, d_out, exact_limit, cert_safety, d_any_exact); \
+                         d_groups, num_groups, d_cands, d_tile_sums, d_out, exact_limit, cert_safety, d_any_exact, d_early); \
       } \
       hipLaunchKernelGGL((k_search_finish<PP, 2>), dim3((num_groups + gpw - 1) / gpw), dim3(64), lds_r, st, order, lags, gpw, per, \
-                         d_groups, num_groups, d_cands, d_tile_sums, d_out, exact_limit, cert_safety, d_any_exact); \
+                         d_groups, num_groups, d_cands, d_tile_sums, d_out, exact_limit, cert_safety, d_any_exact, d_early); \
     } } while (0)
   switch (pclass) {
     case 16: SLA_FINISH(16); break;
@@ -472,6 +500,29 @@ extern "C" int sla_hip_launch_search_exact_x(const int32_t* d_pcm, uint64_t plan
   return hip_rc(hipGetLastError());
 }
 
+extern "C" int sla_hip_launch_search_exact_x(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                                           const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                                           uint32_t max_cands_per_group,
+                                           const sla_hip_lpc_cand* d_cands, double* d_tile_sums, double* d_out,
+                                           double exact_limit, double cert_safety, uint32_t* d_any_exact, sla_hip_stream_t stream, const sla_hip_launch_extra* extra)
+{
+  return launch_search_exact_impl(d_pcm, plane_stride, mid_side, order, d_groups, num_groups, max_window, max_cands_per_group, d_cands, d_tile_sums, d_out,
+                                  exact_limit, cert_safety, d_any_exact, stream, extra, nullptr, nullptr);
+}
+
+extern "C" int sla_hip_launch_search_exact_early(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                                           const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                                           uint32_t max_cands_per_group,
+                                           const sla_hip_lpc_cand* d_cands, double* d_tile_sums, double* d_out,
+                                           double exact_limit, double cert_safety, uint32_t* d_any_exact, sla_hip_stream_t stream, const sla_hip_launch_extra* extra,
+                                           const uint32_t* d_early, void* prepass_done)
+{
+  // (a launch of no groups would queue no wait: the kernels behind it on the stream would not be ordered behind the prepass)
+  if (d_early == nullptr || prepass_done == nullptr || num_groups == 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  return launch_search_exact_impl(d_pcm, plane_stride, mid_side, order, d_groups, num_groups, max_window, max_cands_per_group, d_cands, d_tile_sums, d_out,
+                                  exact_limit, cert_safety, d_any_exact, stream, extra, d_early, prepass_done);
+}
+
 extern "C" int sla_hip_launch_search_exact(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
                                            const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
                                            uint32_t max_cands_per_group,
@@ -481,10 +532,10 @@ extern "C" int sla_hip_launch_search_exact(const int32_t* d_pcm, uint64_t plane_
   return sla_hip_launch_search_exact_x(d_pcm, plane_stride, mid_side, order, d_groups, num_groups, max_window, max_cands_per_group, d_cands, d_tile_sums, d_out, exact_limit, cert_safety, d_any_exact, stream, nullptr);
 }
 
-extern "C" int sla_hip_launch_plan(const sla_hip_lpc_group* d_groups, uint32_t num_superframes, uint32_t num_channels,
+extern "C" int sla_hip_launch_plan_early(const sla_hip_lpc_group* d_groups, uint32_t num_superframes, uint32_t num_channels,
                                    uint32_t order, uint32_t bits_per_sample, const sla_hip_lpc_cand* d_cands,
                                    double* d_lpc_out, uint32_t* d_parts, uint32_t* d_num_parts, uint32_t* d_status,
-                                   sla_hip_stream_t stream)
+                                   sla_hip_stream_t stream, const uint32_t* d_early)
 {
   if (d_groups == nullptr || d_cands == nullptr || d_lpc_out == nullptr || d_parts == nullptr || d_num_parts == nullptr
       || d_status == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
@@ -492,8 +543,18 @@ extern "C" int sla_hip_launch_plan(const sla_hip_lpc_group* d_groups, uint32_t n
   if (num_superframes == 0) { return 0; }
   hipLaunchKernelGGL(k_plan, dim3((num_superframes + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_groups, num_superframes, num_channels,
                      order, bits_per_sample, d_cands, d_lpc_out, d_parts, d_num_parts, d_status,
-                     (tuning().plan_margin > 0.0) ? tuning().plan_margin : PLAN_MARGIN);   /* tests raise it to force the host path */
+                     (tuning().plan_margin > 0.0) ? tuning().plan_margin : PLAN_MARGIN,   /* tests raise it to force the host path */
+                     d_early);
   return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_plan(const sla_hip_lpc_group* d_groups, uint32_t num_superframes, uint32_t num_channels,
+                                   uint32_t order, uint32_t bits_per_sample, const sla_hip_lpc_cand* d_cands,
+                                   double* d_lpc_out, uint32_t* d_parts, uint32_t* d_num_parts, uint32_t* d_status,
+                                   sla_hip_stream_t stream)
+{
+  return sla_hip_launch_plan_early(d_groups, num_superframes, num_channels, order, bits_per_sample, d_cands, d_lpc_out, d_parts, d_num_parts, d_status,
+                                   stream, nullptr);
 }
 
 extern "C" int sla_hip_launch_expand_masked(const sla_hip_superframe* d_superframes, uint32_t num_superframes,
@@ -525,17 +586,31 @@ extern "C" int sla_hip_launch_expand_masked(const sla_hip_superframe* d_superfra
                                      sla_hip_acf_job* d_acf_jobs, uint32_t group_capacity,
                                      uint32_t* counts, uint32_t sequence, const uint64_t* d_nonzero_mask, sla_hip_stream_t stream)
 {
+  return sla_hip_launch_expand_early(d_superframes, num_superframes, d_parts, d_num_parts, d_status, num_channels, int_shift, d_win_len,
+                                     d_win_off, num_windows, d_run, d_prefix, d_groups, d_cands, d_acf_jobs, group_capacity, counts, sequence,
+                                     d_nonzero_mask, stream, nullptr);
+}
+
+extern "C" int sla_hip_launch_expand_early(const sla_hip_superframe* d_superframes, uint32_t num_superframes,
+                                     const uint32_t* d_parts, const uint32_t* d_num_parts, const uint32_t* d_status,
+                                     uint32_t num_channels, uint32_t int_shift,
+                                     const uint32_t* d_win_len, const uint32_t* d_win_off, uint32_t num_windows,
+                                     uint32_t* d_run, uint32_t* d_prefix, sla_hip_lpc_group* d_groups, sla_hip_lpc_cand* d_cands,
+                                     sla_hip_acf_job* d_acf_jobs, uint32_t group_capacity,
+                                     uint32_t* counts, uint32_t sequence, const uint64_t* d_nonzero_mask, sla_hip_stream_t stream,
+                                     const uint32_t* d_early)
+{
   if (d_superframes == nullptr || d_parts == nullptr || d_num_parts == nullptr || d_status == nullptr || d_run == nullptr
       || d_prefix == nullptr || d_groups == nullptr || d_cands == nullptr || d_acf_jobs == nullptr || counts == nullptr
       || (num_windows != 0 && (d_win_len == nullptr || d_win_off == nullptr))) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if (num_channels == 0 || num_channels > 8 || int_shift > 31) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   hipLaunchKernelGGL(k_expand_scan, dim3(1), dim3(EXPAND_THREADS), 0, (hipStream_t)stream, d_superframes, num_superframes, d_parts,
                      d_num_parts, d_status, num_channels, d_win_len, num_windows, d_run, d_prefix, group_capacity,
-                     (volatile uint32_t*)counts, sequence, d_nonzero_mask);
+                     (volatile uint32_t*)counts, sequence, d_nonzero_mask, d_early);
   if (num_superframes != 0) {
     hipLaunchKernelGGL(k_expand_write, dim3((num_superframes + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_superframes, num_superframes,
                        d_parts, d_num_parts, num_channels, int_shift, d_win_len, d_win_off, num_windows, d_run, d_prefix, d_groups, d_cands,
-                       d_acf_jobs, d_nonzero_mask);
+                       d_acf_jobs, d_nonzero_mask, d_early);
   }
   return hip_rc(hipGetLastError());
 }

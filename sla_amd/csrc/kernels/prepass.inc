@@ -11,12 +11,17 @@ template <int NCH>      // 1, 2 or 0 = any
 __global__ __launch_bounds__(256)
 void k_prepass(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t nch_rt, uint32_t n,
                uint32_t shift, uint32_t ms, uint32_t* __restrict__ or_mask, uint64_t* __restrict__ nz_mask,
-               uint32_t* __restrict__ tile_or)
+               uint32_t* __restrict__ tile_or, uint32_t* __restrict__ cancel, uint32_t wave_stride)
 {
   const uint32_t nch = (NCH != 0) ? (uint32_t)NCH : nch_rt;
   const uint32_t lane = threadIdx.x & 63;
-  const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const uint64_t nwords = ((uint64_t)n + 63) / 64;
+  uint32_t acc_all = 0, zero_all = 0;
+  // wave_stride != 0 (sla_hip_launch_prepass_early with a limit on the workgroups): the grid is smaller than the file and every
+  // wave walks on by that many waves -- a pass that runs BESIDE the search's tile sums, which read the same samples, is not to
+  // take the memory system for itself: its result is not needed before they are done
+  for (;;) {
   uint32_t acc = 0, zero_words = 0;
   // (one or two channels: 16 mask words = 4 KB requested before the first one is looked at -- the kernel is bound by how
   // many bytes the chip has in flight: C2 80 -> 68 us with 8 words)
@@ -65,11 +70,48 @@ void k_prepass(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t nch_rt
       }
     }
   }
-  for (int off = 32; off > 0; off >>= 1) { acc |= __shfl_xor(acc, off); }
+  if (tile_or != nullptr) {       // OR of this wave's 1024 samples (batches: offset_lshift per file)
+    for (int off = 32; off > 0; off >>= 1) { acc |= __shfl_xor(acc, off); }
+    if (lane == 0) { tile_or[wave] = acc; }
+  }
+  // a search that was started beside this kernel (sla_hip_launch_prepass_early) is for nothing: tell it at once
+  if (cancel != nullptr && lane == 0 && zero_words != 0) { __hip_atomic_store(cancel, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  acc_all |= acc; zero_all += zero_words;
+  if (wave_stride == 0u) { break; }
+  wave += wave_stride;
+  if (wave * PREPASS_WORDS >= nwords) { break; }
+  }
+  for (int off = 32; off > 0; off >>= 1) { acc_all |= __shfl_xor(acc_all, off); }
   // thousands of waves, one word: only the few that still add a bit pay for the atomic (a stale read just costs one)
-  if (lane == 0 && (acc & ~__atomic_load_n(or_mask, __ATOMIC_RELAXED)) != 0) { atomicOr(or_mask, acc); }
-  if (lane == 0 && zero_words != 0) { atomicAdd(or_mask + 1, zero_words); }
-  if (tile_or != nullptr && lane == 0) { tile_or[wave] = acc; }       // OR of this wave's 1024 samples (batches: offset_lshift per file)
+  if (lane == 0 && (acc_all & ~__atomic_load_n(or_mask, __ATOMIC_RELAXED)) != 0) { atomicOr(or_mask, acc_all); }
+  if (lane == 0 && zero_all != 0) { atomicAdd(or_mask + 1, zero_all); }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_prepass_done: one thread behind k_prepass on its stream (sla_hip_launch_prepass_early).  early[1] = offset_lshift of the
+// file (src/SLAEncoder.c:425-455, as the host's lshift_of), early[0] is raised when the kernels that were started beside the
+// prepass on the guess "no silence" must not go on: an all-zero mask word, an OR word of 0, samples wider than declared.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64)
+void k_prepass_done(const uint32_t* or_mask, uint32_t bps, uint32_t* early)
+{
+  if (threadIdx.x != 0 || blockIdx.x != 0) { return; }
+  const uint32_t orw = or_mask[0], zeros = or_mask[1];
+  uint32_t lshift = 0;
+  bool stop = (orw == 0u || zeros != 0u);
+  if (orw != 0u) {
+    const uint32_t ntz = (uint32_t)__builtin_ctz(orw);
+    if (bps < 32u - ntz || bps - (32u - ntz) >= bps) { stop = true; } else { lshift = bps - (32u - ntz); }
+  }
+  early[SLA_HIP_EARLY_LSHIFT] = lshift;
+  if (stop) { __hip_atomic_store(early + SLA_HIP_EARLY_CANCEL, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+}
+
+// what a kernel of the early chain asks at its start: has the prepass called the start off?  (past the L1 / scalar caches:
+// the word is raised while the kernel runs)
+__device__ __forceinline__ bool early_cancelled(const uint32_t* early)
+{
+  return early != nullptr && __hip_atomic_load(early + SLA_HIP_EARLY_CANCEL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
 }
 
 // ---------------------------------------------------------------------------------------------

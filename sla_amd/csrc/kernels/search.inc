@@ -209,19 +209,20 @@ template <int NB>
 __global__ __launch_bounds__(256)
 void k_acf_tiles(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ms,
                  const sla_hip_lpc_group* __restrict__ groups, uint32_t num_groups, uint32_t tiles_per_group,
-                 double* __restrict__ tile_sums, clear_list cl)
+                 double* __restrict__ tile_sums, clear_list cl, const uint32_t* early)
 {
   constexpr uint32_t OL = 64 - NB;             // lanes of a pass that own samples
   constexpr uint32_t STEP = OL * 4, PASSES = (SLA_HIP_XTILE + STEP - 1) / STEP, LAGS = NB * 4;
   __shared__ double s_edge[4][2 * LAGS];       // x[t1-LAGS .. t1+LAGS) of each wave's tile end t1
   clear_words(cl);
+  const bool stop = early_cancelled(early);    // (see k_acf_tiles_lds)
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t w = blockIdx.x * 4 + wv;
   const uint32_t gi = w / tiles_per_group, tile = w - gi * tiles_per_group;
   if (gi >= num_groups) { return; }
   const sla_hip_lpc_group g = groups[gi];
   const uint32_t N = g.num_samples, t0 = tile * SLA_HIP_XTILE;
-  if (t0 >= N) { return; }
+  if (t0 >= N || stop) { return; }
   const uint32_t t1 = (t0 + SLA_HIP_XTILE < N) ? (t0 + SLA_HIP_XTILE) : N;
   const double scale = 4.656612873077392578125e-10;   // 2^-31, exact (same arithmetic as load_f64)
 
@@ -324,12 +325,15 @@ template <int NB, int TOP>
 __global__ __launch_bounds__(256, (NB >= 13) ? 3 : 1)
 void k_acf_tiles_lds(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ms,
                      const sla_hip_lpc_group* __restrict__ groups, uint32_t num_groups, uint32_t tiles_per_group,
-                     double* __restrict__ tile_sums, clear_list cl)
+                     double* __restrict__ tile_sums, clear_list cl, const uint32_t* early)
 {
   constexpr uint32_t LAGS = NB * 4, HL = NB + 1;
   __shared__ double2 s_e[4][2][64 + HL], s_o[4][2][64 + HL];
   __shared__ double s_edge[4][2 * LAGS];       // x[t1-LAGS .. t1+LAGS) of each wave's tile end t1 (zero below t0)
   clear_words(cl);
+  // started beside the prepass (sla_hip_launch_search_exact_early) and called off by it: every wave asks once, at its start --
+  // the answer travels while the group's descriptor does and is looked at together with it, before any sample is loaded
+  const bool stop = early_cancelled(early);
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // the same in the wave's 64 lanes: the group, the tile and their bounds live in scalar registers
   const uint32_t w = blockIdx.x * 4 + wv;
@@ -337,7 +341,7 @@ void k_acf_tiles_lds(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t 
   if (gi >= num_groups) { return; }
   const sla_hip_lpc_group g = groups[gi];
   const uint32_t N = g.num_samples, t0 = tile * SLA_HIP_XTILE;
-  if (t0 >= N) { return; }
+  if (t0 >= N || stop) { return; }
   const uint32_t t1 = (t0 + SLA_HIP_XTILE < N) ? (t0 + SLA_HIP_XTILE) : N;
   const double scale = 4.656612873077392578125e-10;   // 2^-31, exact (same arithmetic as load_f64)
   const int32_t* p0 = pcm + (ms ? 0 : (uint64_t)g.channel * stride) + g.pcm_off;
@@ -737,8 +741,15 @@ __global__ __launch_bounds__(64)
 void k_search_finish(uint32_t order, uint32_t lags, uint32_t gpw, uint32_t per,
                      const sla_hip_lpc_group* __restrict__ groups, uint32_t num_groups, const sla_hip_lpc_cand* __restrict__ cands,
                      const double* __restrict__ tile_sums, double* __restrict__ out, double exact_limit, double cert,
-                     uint32_t* __restrict__ any_exact)
+                     uint32_t* __restrict__ any_exact, const uint32_t* early)
 {
+  // early (may be NULL): the launch was queued before the host knew the file's offset_lshift -- exact_limit is the limit of
+  // offset_lshift 0, the prepass has stored the shift meanwhile (the stream waited for it): a unit 2^lshift coarser, a
+  // limit 4^lshift higher, exactly
+  if (early != nullptr) {
+    if (early_cancelled(early)) { return; }
+    exact_limit = ldexp(exact_limit, 2 * (int)early[SLA_HIP_EARLY_LSHIFT]);
+  }
   // any_exact (may be NULL): mode 1 sets the word when it meets a group below the limit, mode 2 returns at once while it is
   // still 0 -- loud material wider than 16 bits has no such group, and the mode-2 launch (70 KiB of LDS per workgroup) cost
   // 0.15 ms per C5-120 s launch just to find that out group by group
@@ -896,10 +907,12 @@ __device__ __forceinline__ double plan_code_length(double sumsq, uint32_t n, uin
 __global__ __launch_bounds__(256)
 void k_plan(const sla_hip_lpc_group* __restrict__ groups, uint32_t num_sf, uint32_t nch, uint32_t order, uint32_t bps,
             const sla_hip_lpc_cand* __restrict__ cands, double* __restrict__ lpc_out,
-            uint32_t* __restrict__ parts, uint32_t* __restrict__ nparts, uint32_t* __restrict__ status, double margin)
+            uint32_t* __restrict__ parts, uint32_t* __restrict__ nparts, uint32_t* __restrict__ status, double margin,
+            const uint32_t* early)
 {
   __shared__ double s_adj[4][PLAN_NODES * PLAN_NODES];
   __shared__ uint32_t s_path[4][PLAN_NODES];
+  if (early_cancelled(early)) { return; }
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t sf = blockIdx.x * 4 + wv;
   if (sf >= num_sf) { return; }
@@ -1018,9 +1031,13 @@ __global__ __launch_bounds__(64)
 void k_search_cert(uint32_t order, uint32_t lags, uint32_t per_max,
                    const sla_hip_lpc_group* __restrict__ groups, uint32_t num_groups, const sla_hip_lpc_cand* __restrict__ cands,
                    const double* __restrict__ tile_sums, double* __restrict__ out, double exact_limit, double cert,
-                   uint32_t* __restrict__ any_exact, uint32_t stage_doubles)
+                   uint32_t* __restrict__ any_exact, uint32_t stage_doubles, const uint32_t* early)
 {
   extern __shared__ __attribute__((aligned(16))) double lds[];          // the wave's tile sums, then r[XC_CANDS][order + 1] in their place
+  if (early != nullptr) {                                                // (see k_search_finish)
+    if (early_cancelled(early)) { return; }
+    exact_limit = ldexp(exact_limit, 2 * (int)early[SLA_HIP_EARLY_LSHIFT]);
+  }
   __shared__ uint32_t s_grp[XC_CANDS], s_start[XC_CANDS], s_len[XC_CANDS], s_live[XC_CANDS], s_nt[XC_CANDS];
   __shared__ double s_energy[XC_CANDS];
   const uint32_t O1 = order + 1, O2 = order + 2;

@@ -112,6 +112,18 @@ struct SLAEncoder {
   uint32_t table_hits;              /* analyses served from the kept tables since the handle was created */
   int      spec_valid; uint32_t spec_or;    /* the last file had no silence / its OR word: the guess for the next one of its shape */
   uint32_t spec_misses;             /* guesses that turned out wrong */
+  /* option "search_early" (1 = default): a single file whose predecessor had no silence starts its search chain BESIDE the
+   * prepass (which moves to the upload stream for that) instead of behind the host's look at its result.  d_or words 3, 4 are
+   * the chain's SLA_HIP_EARLY_WORDS: the cancel flag the prepass raises and the offset_lshift it stores (pipeline_prepare) */
+  int      search_early;
+  /* option "early_prepass_groups": most workgroups of a prepass that runs beside the search, its waves walking on through the
+   * file.  The tile sums read the same samples; a prepass that takes all the memory bandwidth there is slows them by more than
+   * running beside them gains (C3: tile sums 0.86 -> 1.05 ms, profiles/r9_search_early_ab.txt), and its result is not needed
+   * before they are done.  0 (default): three workgroups per two compute units, the best of the sweep in that file */
+  uint32_t early_prepass_groups, early_prepass_auto;
+  int      defer_bc_clear;          /* pipeline_reserve leaves the host result array to its caller, who clears it once the search is queued */
+  int      early_clear;             /* the cancel flag is known to be 0: a launch that did not run beside a prepass has cleared it since it was last seen set */
+  uint32_t early_last, early_starts, early_cancels;      /* sla_hip_last_search_early */
   uint32_t blocks_exact;            /* last analysis: (block, channel) pairs the certificate handed to the exact kernel */
   sla_hip_tuning tune;              /* launcher knobs, named to the launchers at every API entry */
   uint32_t host_planned;            /* last analysis: super-frames whose partition the host had to decide */
@@ -400,7 +412,9 @@ struct SLAEncoder* SLAEncoder_Create(const struct SLAEncoderConfig* config)
   if (hipGetDevice(&e->device) != hipSuccess) { goto fail; }
   if (hipGetDeviceProperties(&prop, e->device) == hipSuccess) {
     snprintf(g_device_name, sizeof(g_device_name), "%.160s (%.80s)", prop.name, prop.gcnArchName);
+    if (prop.multiProcessorCount > 0) { e->early_prepass_auto = 3u * (uint32_t)prop.multiProcessorCount / 2u; }
   }
+  if (e->early_prepass_auto == 0) { e->early_prepass_auto = 384; }
   if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess
       || hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking) != hipSuccess
       || hipStreamCreateWithFlags(&e->stream3, hipStreamNonBlocking) != hipSuccess
@@ -440,6 +454,8 @@ struct SLAEncoder* SLAEncoder_Create(const struct SLAEncoderConfig* config)
   e->tune.ltm_int = 1;  /* that stage's autocorrelation from k_ltm_acf_int (int8 matrix products) instead of k_ltm_acf_fast; lanes copy e->tune */
   e->table_cache = 1;
   e->prelaunch = 1;
+  e->search_early = 1;
+  e->early_prepass_groups = 0;
   e->device_expand = 1; e->expand_silence = 1;
   e->upload24 = 1;      /* profiles/r3_pack24_ab_*.json: plain path +13 % (C3) / +15 % (C5) from pageable memory, streamed path +1..3 % */
   e->stream_mode = 1; e->stream_piece = 32u << 20; e->stream_lanes = 6; e->batch_lanes = 4;
@@ -646,6 +662,10 @@ static int blocks_push(struct SLAEncoder* e, uint32_t start, uint32_t nsmpl, uin
 #define SPAN_ULLS (MAX_CHUNKS * 4 * 2)
 #define SPAN_AREA_ULLS (SPAN_ULLS + MAX_CHUNKS * 2)
 #define LTM_CNT_SLOT(e, c) ((uint32_t*)((unsigned long long*)(e)->d_spans.ptr + SPAN_ULLS) + 4 * (size_t)(c))
+/* d_or: [0] OR word, [1] all-zero mask words, [2] groups rerun as serial chains, [3] [4] the words a search beside the prepass
+ * shares with it (SLA_HIP_EARLY_CANCEL, SLA_HIP_EARLY_LSHIFT), [8 + chunk] "some window is exact" of the chunk's search */
+#define EARLY_WORDS(e) ((uint32_t*)(e)->d_or.ptr + 3)
+typedef char early_words_fit_d_or[(3 + SLA_HIP_EARLY_WORDS <= 8 && SLA_HIP_EARLY_CANCEL == 0) ? 1 : -1];
 #define SPECULATE_MAX_GROUPS 16384u      /* (super-frame, channel) pairs up to which the searches are launched on a guess */
 enum { EV_SEARCH_S, EV_SEARCH_E, EV_SEARCH_DONE, EV_LPCB_S, EV_LPCB_E, EV_LAT_E, EV_ACF_S, EV_ACF_E, EV_BLOCK_DONE,
        EV_TAIL_S, EV_TAIL_E, EV_TAIL_DONE, EV_UPLOADED, EV_PLANNED, EV_UPLOADED2, EV_LPC_DOWN, EV_SOLVED, EV_EXPANDED, EV_JOBS_DOWN, EV_PER_CHUNK };
@@ -684,6 +704,7 @@ typedef struct {
   int borrowed;                                   /* sf / shapes belong to the encoder's table cache */
   int tab_hit;                                    /* ... and were found there                         */
   int spec;                                       /* the searches are in flight on a guess of the prepass result */
+  int early;                                      /* ... beside the prepass, on the guess "no silence" alone: the shift comes from the device, a wrong start is cancelled there */
   int prelaunched;                                /* chunk 0's certified block kernels were queued with the searches (device-side count) */
   int clear_in_kernel;                            /* spans, rerun counter and k_expand's numbers are cleared by the first search kernel */
   uint32_t* clear_ptr[3]; uint32_t clear_words[3]; /* ... these words: handed to the first search launch (sla_hip_launch_extra), then NULL */
@@ -1139,14 +1160,19 @@ static int zruns_reserve(struct SLAEncoder* e, uint64_t span)
 }
 
 /* behind the prepass on the handle's stream: the list kernels, then count and entries on their way home in one copy */
-static int zruns_enqueue(struct SLAEncoder* e, uint32_t span, const uint32_t* d_seg_start, const uint32_t* d_seg_len, uint32_t nsegs)
+static int zruns_enqueue_on(struct SLAEncoder* e, uint32_t span, const uint32_t* d_seg_start, const uint32_t* d_seg_len, uint32_t nsegs, hipStream_t st)
 {
   RCCHK(sla_hip_launch_zero_runs((const uint64_t*)e->d_nz.ptr, span, d_seg_start, d_seg_len, nsegs, SLA_HIP_ZERO_RUN_MIN,
                                  (sla_hip_zero_run*)((uint8_t*)e->d_zruns.ptr + ZRUNS_HEAD), e->silence_runs, (uint32_t*)e->d_zruns.ptr,
-                                 (uint32_t*)e->d_zscratch.ptr, e->stream));
+                                 (uint32_t*)e->d_zscratch.ptr, st));
   HIPCHK(hipMemcpyAsync(e->h_zruns.ptr, e->d_zruns.ptr, ZRUNS_HEAD + sizeof(sla_hip_zero_run) * (size_t)e->silence_runs,
-                        hipMemcpyDeviceToHost, e->stream));
+                        hipMemcpyDeviceToHost, st));
   return 0;
+}
+
+static int zruns_enqueue(struct SLAEncoder* e, uint32_t span, const uint32_t* d_seg_start, const uint32_t* d_seg_len, uint32_t nsegs)
+{
+  return zruns_enqueue_on(e, span, d_seg_start, d_seg_len, nsegs, e->stream);
 }
 
 /* after the wait: the number of runs the device found; when they fit the list, e->sil answers from it (sorted) */
@@ -1195,8 +1221,18 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
   /* (ranges of a longer file, sla_hip_shard_*, keep the mask route) */
   const int want_runs = (e->silence_runs != 0 && e->nsegs == 0 && e->file_or_word == 0 && n <= SLA_HIP_ZERO_RUN_MAX_SPAN);
   int rebuild = 0;
+  /* option "search_early": the search chain starts beside the prepass.  What the handle alone can tell is asked here, before
+   * the prepass goes out (it takes another stream then, and stores the chain's device words): a single file of this handle
+   * itself, the last one without silence, the cancel flag known to be clear, and the one route the chain's kernels have their
+   * hooks on -- tile sums with the certificate, planned on the device.  (Everything else follows the prepass, as before.) */
+  const int early_want = (e->search_early && !e->is_lane && e->nsegs == 0 && e->file_or_word == 0 && !e->skip_prepass && n > 0
+                          && e->spec_valid && e->early_clear && e->device_plan && e->cert_safety > 0.0 && e->search_exact
+                          && SLAI_SEARCH_DELTA == SLA_HIP_XTILE && maxb <= SLA_HIP_XTILE * SLA_HIP_XTILES
+                          && sla_hip_search_exact_lags(e->encode_param.parcor_order) != 0 && bps >= 1 && bps <= 32);
+  const hipStream_t ps = early_want ? e->stream_up : e->stream;      /* the prepass and what comes home behind it */
 
   g_trace_t0 = now_ms();
+  e->early_last = 0;
   if (e->nsegs != 0) {
     /* batch: sla_hip_encode_batch ran the prepass over all files, the whole mask is on the host and the files of
      * this pass share one offset_lshift */
@@ -1223,7 +1259,7 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
   RCCHK(pin_reserve(&e->h_nz, (size_t)(nwords + 2) * 8));
   if (want_runs) { RCCHK(zruns_reserve(e, n)); }
   e->sil_stat[0] = 0; e->sil_stat[1] = 0; e->sil_stat[2] = e->silence_runs; e->sil_stat[3] = 0;
-  HIPCHK(hipEventRecord(e->ev[0], e->stream));
+  HIPCHK(hipEventRecord(e->ev[0], ps));
   /* (one exception keeps the prepass: a last super-frame of fewer than 127 samples can be all zero -- and then is a SILENT
    * block, its minimum length being what is left of the file, src/SLAEncoder.c:401-407 -- without containing an aligned
    * all-zero 64-sample word for the count to see; without silence the super-frames sit on multiples of the block size) */
@@ -1238,8 +1274,13 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
     silence_from_mask(e);
     RCCHK(tables_no_silence(e, a));
   } else {
-  RCCHK(sla_hip_launch_prepass(e->pcm_dev, e->stride, C, n, bps, ms, (uint32_t*)e->d_or.ptr, (uint64_t*)e->d_nz.ptr, e->stream));
-  HIPCHK(hipEventRecord(e->ev[1], e->stream));
+  if (early_want) {
+    RCCHK(sla_hip_launch_prepass_early(e->pcm_dev, e->stride, C, n, bps, ms, (uint32_t*)e->d_or.ptr, (uint64_t*)e->d_nz.ptr,
+                                       EARLY_WORDS(e), e->early_prepass_groups ? e->early_prepass_groups : e->early_prepass_auto, ps));
+  } else {
+    RCCHK(sla_hip_launch_prepass(e->pcm_dev, e->stride, C, n, bps, ms, (uint32_t*)e->d_or.ptr, (uint64_t*)e->d_nz.ptr, ps));
+  }
+  HIPCHK(hipEventRecord(e->ev[1], ps));      /* (search beside the prepass: what the chain's later kernels wait for) */
   {
     int by_runs = 0;
     uint32_t zcount = 0;
@@ -1249,10 +1290,40 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
      * block length never changes a decision). */
     const uint64_t tail_words = (nwords < SLAI_MIN_BLOCK / 64 + 2) ? nwords : (SLAI_MIN_BLOCK / 64 + 2);
     const uint64_t head_words = nwords - tail_words;
-    HIPCHK(hipMemcpyAsync(e->h_or, e->d_or.ptr, 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync((uint64_t*)e->h_nz.ptr + head_words, (uint64_t*)e->d_nz.ptr + head_words, (size_t)tail_words * 8, hipMemcpyDeviceToHost, e->stream));
-    if (want_runs) { RCCHK(zruns_enqueue(e, n, NULL, NULL, 0)); }      /* (count and list come home in the same wait) */
-    HIPCHK(hipEventRecord(e->ev_prep, e->stream));
+    if (early_want) {
+      /* Search beside the prepass.  Nothing the chain's first kernel -- the tile sums, three quarters of the search -- reads
+       * depends on the prepass; what does (the exactness limit, the shift in the block descriptors) is read from the word the
+       * prepass stores, behind a stream wait for ev[1].  The tables are those of a file without silence, kept or just sent;
+       * the routes are decided for offset_lshift 0 (an OR word with bit 32 - bps set), the kernels add the stored shift.  A
+       * prepass that finds silence raises the flag and the chain's kernels return at once; the host sees it below, after the
+       * same wait as ever, and launches the search again.
+       * The chain goes out before anything else the host has to do here: the copies that bring the prepass result home are
+       * queued behind it, and the host's result array is cleared after that (pipeline_reserve leaves it alone). */
+      int rc_tab;
+      e->defer_bc_clear = 1;
+      rc_tab = tables_no_silence(e, a);
+      e->defer_bc_clear = 0;
+      RCCHK(rc_tab);
+      PTRACE("tables (search beside the prepass)");
+      decide_routes(e, a, 1u << (32u - bps), 0);
+      if (a->exact && a->nxg > 0) {
+        e->lshift = 0;
+        a->spec = 1; a->early = 1;
+        e->early_last = 1; e->early_starts++;
+        RCCHK(launch_searches(e, a, 0, a->trace, a->t_begin));
+        PTRACE("search queued beside the prepass");
+      }
+    }
+    /* (search beside the prepass: the cancel flag comes home with the two words -- and the rerun counter between them, which
+     * nobody reads before the end of the analysis brings it again) */
+    e->h_or[3] = 0;
+    HIPCHK(hipMemcpyAsync(e->h_or, e->d_or.ptr, early_want ? 16 : 8, hipMemcpyDeviceToHost, ps));
+    HIPCHK(hipMemcpyAsync((uint64_t*)e->h_nz.ptr + head_words, (uint64_t*)e->d_nz.ptr + head_words, (size_t)tail_words * 8, hipMemcpyDeviceToHost, ps));
+    if (want_runs) { RCCHK(zruns_enqueue_on(e, n, NULL, NULL, 0, ps)); }      /* (count and list come home in the same wait) */
+    HIPCHK(hipEventRecord(e->ev_prep, ps));
+    if (early_want) {
+      memset(e->bc, 0, sizeof(blkch_t) * ((size_t)a->blocks_bound * C + 1));
+    } else {
     /* while the prepass runs: the tables of a file without silence (the usual case; checked below), every buffer of
      * the pipeline, and the tables on their way to the device behind the prepass -- so that the first search kernel
      * can follow the host's look at the prepass result without further copies in between */
@@ -1269,7 +1340,9 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
         RCCHK(launch_searches(e, a, 0, a->trace, a->t_begin));
       }
     }
+    }
     HIPCHK(hipEventSynchronize(e->ev_prep));
+    if (early_want && e->h_or[3] != 0) { e->early_clear = 0; }      /* (until a launch that does not run beside a prepass clears it) */
     if (want_runs) { zcount = zruns_take(e, &by_runs); e->sil_stat[1] = zcount; }
     if (by_runs && (zcount != 0 || e->h_or[1] != 0)) {
       /* silence, and the device's list of it is complete: no mask comes home, no second wait.  The head of h_nz is not
@@ -1303,7 +1376,14 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
   }
   PTRACE("prepass + mask on the host");
 
-  RCCHK(lshift_of(e->h_or[0], bps, &e->lshift));
+  {
+    const int bad = lshift_of(e->h_or[0], bps, &e->lshift);
+    if (bad != 0) {
+      /* (samples wider than declared: nothing may still be running on this file's tables when the caller gets its answer) */
+      if (a->spec) { (void)hipStreamSynchronize(e->stream); (void)hipStreamSynchronize(e->stream2); }
+      return bad;
+    }
+  }
 
   /* without all-zero mask words only the last super-frame can still be silent (its minimum block length is what
    * is left of the file) */
@@ -1326,7 +1406,9 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
   }
   {
     const int silence = (rebuild || e->h_or[1] != 0);
-    if (a->spec && (silence || e->h_or[0] != a->or_word)) {
+    const int wrong = a->early ? (silence || e->h_or[0] == 0 || e->h_or[3] != 0) : (silence || e->h_or[0] != a->or_word);
+    if (a->spec && !wrong && a->early && e->h_or[0] != e->spec_or) { e->spec_misses++; }      /* (not like the last file: counted as ever, costs nothing) */
+    if (a->spec && wrong) {
       /* guessed wrong: the searches go out again.  Whatever the first run queued on the block stream behind its tables (the
        * prelaunched block kernels: they still read the descriptors, counters and candidate slots the second run rewrites) must
        * have drained first: the search stream waits for that stream's tail (the two runs were unordered) */
@@ -1338,8 +1420,10 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
         }
         a->prelaunched = 0;
       }
+      if (a->early) { e->early_cancels++; a->early = 0; }
       a->spec = 0; e->spec_misses++;
     }
+    a->early = 0;                                          /* (from here on the analysis is like any other) */
     decide_routes(e, a, e->h_or[0], silence);
     e->spec_valid = !silence; e->spec_or = e->h_or[0];
   }
@@ -1422,7 +1506,7 @@ static int pipeline_reserve(struct SLAEncoder* e, const actx_t* a)
     e->parcor_exact = (uint8_t*)realloc(e->parcor_exact, e->coef_cap);
   }
   if (e->bc == NULL || e->parcor == NULL || e->code == NULL || e->kint == NULL || e->parcor_exact == NULL) { return SLA_APIRESULT_NG; }
-  memset(e->bc, 0, sizeof(blkch_t) * nslots);
+  if (!e->defer_bc_clear) { memset(e->bc, 0, sizeof(blkch_t) * nslots); }      /* (an hour of stereo: 0.1 ms of host time) */
   /* tables that never change while kernels are in flight */
   if (e->win_dirty) {
     /* (new block lengths since the last file: rare.  win_host is ordinary memory that the next file may realloc, so the
@@ -1482,6 +1566,14 @@ static int search_launch(struct SLAEncoder* e, actx_t* a, uint32_t c)
         int q;
         for (q = 0; q < 3; q++) { xs.clear_ptr[q] = a->clear_ptr[q]; xs.clear_words[q] = a->clear_words[q]; a->clear_ptr[q] = NULL; }
       }
+      if (a->early) {
+        /* beside the prepass: `limit` is that of offset_lshift 0 (a->or_word), the kernels behind the tile sums wait for the
+         * prepass (ev[1]) and scale it by the shift it stored */
+        RCCHK(sla_hip_launch_search_exact_early(e->pcm_dev, e->stride, ms, order, dx, nx, a->max_window, a->max_xcands, (const sla_hip_lpc_cand*)e->d_cands.ptr,
+                                          (double*)e->d_tile_sums.ptr + (size_t)k->xg_lo * SLA_HIP_XTILES * 2 * sla_hip_search_exact_lags(order),
+                                          (double*)e->d_lpc_out.ptr, limit, cert, (uint32_t*)e->d_or.ptr + 8 + c, e->stream, &xs,
+                                          EARLY_WORDS(e), (void*)e->ev[1]));
+      } else
       RCCHK(sla_hip_launch_search_exact_x(e->pcm_dev, e->stride, ms, order, dx, nx, a->max_window, a->max_xcands, (const sla_hip_lpc_cand*)e->d_cands.ptr,
                                           (double*)e->d_tile_sums.ptr + (size_t)k->xg_lo * SLA_HIP_XTILES * 2 * sla_hip_search_exact_lags(order),
                                           (double*)e->d_lpc_out.ptr, limit, cert, (uint32_t*)e->d_or.ptr + 8 + c, e->stream, &xs));
@@ -1501,9 +1593,10 @@ static int search_launch(struct SLAEncoder* e, actx_t* a, uint32_t c)
     if (e->device_plan) {
       /* plan on the device; only the block lengths come back (the candidates' doubles follow on demand) */
       const uint32_t live_lo = k->xg_lo / C, live = nx / C;
-      RCCHK(sla_hip_launch_plan(dx, live, C, order, e->wave_format.bit_per_sample, (const sla_hip_lpc_cand*)e->d_cands.ptr,
+      RCCHK(sla_hip_launch_plan_early(dx, live, C, order, e->wave_format.bit_per_sample, (const sla_hip_lpc_cand*)e->d_cands.ptr,
                                 (double*)e->d_lpc_out.ptr, (uint32_t*)e->d_parts.ptr + (size_t)live_lo * SLA_HIP_PLAN_NODES,
-                                (uint32_t*)e->d_nparts.ptr + live_lo, (uint32_t*)e->d_pstatus.ptr + live_lo, e->stream));
+                                (uint32_t*)e->d_nparts.ptr + live_lo, (uint32_t*)e->d_pstatus.ptr + live_lo, e->stream,
+                                a->early ? EARLY_WORDS(e) : NULL));
       HIPCHK(hipEventRecord(ev[EV_PLANNED], e->stream));
       if (a->expand) {
         /* the chunk's block table, written on the device right behind the plan; two counts (polled in page-locked memory)
@@ -1512,12 +1605,14 @@ static int search_launch(struct SLAEncoder* e, actx_t* a, uint32_t c)
         const uint32_t bps = e->wave_format.bit_per_sample;
         hc[0] = hc[1] = hc[2] = hc[3] = 0;
         if (c == 0 && !a->clear_in_kernel) { HIPCHK(hipMemsetAsync(e->d_run.ptr, 0, 16, e->stream)); }      /* the running block / group numbers restart */
-        RCCHK(sla_hip_launch_expand_masked((const sla_hip_superframe*)e->d_sframes.ptr + k->sf_lo, k->sf_hi - k->sf_lo,
+        /* (beside the prepass: e->lshift is 0 here, the kernel adds the shift the prepass stored) */
+        RCCHK(sla_hip_launch_expand_early((const sla_hip_superframe*)e->d_sframes.ptr + k->sf_lo, k->sf_hi - k->sf_lo,
                                     (const uint32_t*)e->d_parts.ptr, (const uint32_t*)e->d_nparts.ptr, (const uint32_t*)e->d_pstatus.ptr,
                                     C, 32 - bps + e->lshift, (const uint32_t*)e->d_winmap.ptr, (const uint32_t*)e->d_winmap.ptr + e->winmap_entries,
                                     e->winmap_entries, (uint32_t*)e->d_run.ptr, (uint32_t*)e->d_expref.ptr, (sla_hip_lpc_group*)e->d_bgroups.ptr, (sla_hip_lpc_cand*)e->d_bcands.ptr,
                                     (sla_hip_acf_job*)e->d_acf_jobs.ptr, a->blocks_bound * C, (uint32_t*)e->h_counts.ptr + 4 * (size_t)c,
-                                    e->expand_seq, a->silence ? (const uint64_t*)e->d_nz.ptr : NULL, e->stream));
+                                    e->expand_seq, a->silence ? (const uint64_t*)e->d_nz.ptr : NULL, e->stream,
+                                    a->early ? EARLY_WORDS(e) : NULL));
         HIPCHK(hipEventRecord(ev[EV_EXPANDED], e->stream));
         /* Short files: the first two kernels of the block stage go out right here, sized for the most groups the chunk can
          * have and reading the number from the device (sla_hip_launch_extra.d_group_count) -- the device starts on them the moment the
@@ -2167,9 +2262,12 @@ static int launch_searches(struct SLAEncoder* e, actx_t* a, int preset_blocks, i
     if (a->clear_in_kernel) {
       /* (the first search launch of this analysis takes them along: search_launch, chunk 0) */
       a->clear_ptr[0] = (uint32_t*)e->d_spans.ptr; a->clear_words[0] = SPAN_AREA_ULLS * 2;
-      a->clear_ptr[1] = (uint32_t*)e->d_or.ptr + 2; a->clear_words[1] = 1;
+      /* (the rerun counter -- and behind it the flag at which a search started beside the prepass gives up: cleared by every
+       * launch that is not such a search itself) */
+      a->clear_ptr[1] = (uint32_t*)e->d_or.ptr + 2; a->clear_words[1] = a->early ? 1u : 2u;
       a->clear_ptr[2] = a->expand ? (uint32_t*)e->d_run.ptr : NULL; a->clear_words[2] = 4;
-    } else if (hipMemsetAsync((uint32_t*)e->d_or.ptr + 2, 0, sizeof(uint32_t), e->stream) != hipSuccess) { rc = SLA_APIRESULT_NG; }      /* groups rerun as serial chains */
+    } else if (hipMemsetAsync((uint32_t*)e->d_or.ptr + 2, 0, 2 * sizeof(uint32_t), e->stream) != hipSuccess) { rc = SLA_APIRESULT_NG; }      /* groups rerun as serial chains (and the flag, as above) */
+    if (!a->early && rc == 0 && e->d_or.ptr != NULL) { e->early_clear = 1; }
     for (c = 0; c < a->nchunks && rc == 0; c++) { rc = search_launch(e, a, c); }
     TRACE("search launched", a->nchunks);
   } else {
@@ -2469,6 +2567,8 @@ int sla_hip_encoder_set_option(struct SLAEncoder* e, const char* name, double va
   else if (strcmp(name, "silence_runs") == 0)      { OPT_RANGE(0, 65536); e->silence_runs = (uint32_t)iv; }
   else if (strcmp(name, "one_stream") == 0)        { OPT_RANGE(0, 1); e->one_stream = (int)iv; }
   else if (strcmp(name, "prelaunch") == 0)         { OPT_RANGE(0, 1); e->prelaunch = (int)iv; }
+  else if (strcmp(name, "search_early") == 0)      { OPT_RANGE(0, 1); e->search_early = (int)iv; }
+  else if (strcmp(name, "early_prepass_groups") == 0) { OPT_RANGE(0, 1 << 20); e->early_prepass_groups = (uint32_t)iv; }
   else if (strcmp(name, "table_cache") == 0)       { OPT_RANGE(0, 1); e->table_cache = (int)iv; e->tab_valid = 0; e->spec_valid = 0; }
   else if (strcmp(name, "device_ltm") == 0)        { OPT_RANGE(0, 1); e->device_ltm = (int)iv; }
   else if (strcmp(name, "fuse_lattice") == 0)      { OPT_RANGE(0, 1); e->fuse_lattice = (int)iv && !e->tune.lpc_blocks_chains; }
@@ -2680,6 +2780,13 @@ int sla_hip_last_expand(const struct SLAEncoder* e, uint32_t* counters)
 {
   if (e == NULL || counters == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   counters[0] = e->expanded_chunks; counters[1] = (uint32_t)e->timing[9]; counters[2] = e->table_hits; counters[3] = e->spec_misses;
+  return 0;
+}
+
+int sla_hip_last_search_early(const struct SLAEncoder* e, uint32_t counters[4])
+{
+  if (e == NULL || counters == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  counters[0] = e->early_last; counters[1] = e->early_starts; counters[2] = e->early_cancels; counters[3] = 0;
   return 0;
 }
 
