@@ -1381,6 +1381,7 @@ static int pipeline_prepare(struct SLAEncoder* e, actx_t* a)
     if (bad != 0) {
       /* (samples wider than declared: nothing may still be running on this file's tables when the caller gets its answer) */
       if (a->spec) { (void)hipStreamSynchronize(e->stream); (void)hipStreamSynchronize(e->stream2); }
+      if (a->early) { e->early_cancels++; a->early = 0; }   /* (a start the prepass called off, like the ones counted below) */
       return bad;
     }
   }

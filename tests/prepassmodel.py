@@ -43,6 +43,22 @@ def prepass(pcm, bits, mid_side):
     return or_word, mask, int((mask == 0).sum()), tiles
 
 
+def prepass_done(or_word, zero_words, bits):
+    """the two words sla_hip_launch_prepass_early leaves for the kernels started beside the prepass (include/sla_hip.h):
+    (cancel, lshift).  lshift is the reference's offset_lshift (src/SLAEncoder.c:425-455): 0 for an all-zero file, otherwise
+    bits minus the dynamic range 32 - ntz(OR word) -- the number of always-zero bits above the declared unit 2^(32 - bits).
+    The start is called off for an OR word of 0, for any all-zero mask word, and for samples wider than `bits` (a bit below
+    the unit set: the reference asserts there); lshift is 0 in the first and the last of these."""
+    or_word, zero_words, bits = int(or_word), int(zero_words), int(bits)
+    assert 0 <= or_word < 2 ** 32 and zero_words >= 0 and 1 <= bits <= 32
+    if or_word == 0:
+        return 1, 0
+    ntz = (or_word & -or_word).bit_length() - 1                 # trailing zeros
+    if ntz < 32 - bits:                                         # wider than declared
+        return 1, 0
+    return (1 if zero_words else 0), ntz - (32 - bits)
+
+
 def batch_scan(mask, tile_or, starts, lens, max_block):
     """the documented three words per file: OR of the file's own tile words, all-zero WHOLE mask words inside the file, and
     1 when the file's last super-frame has 1 .. 126 samples and all of them are zero"""

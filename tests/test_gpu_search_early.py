@@ -6,7 +6,8 @@ Every case: the packed image with the option on, the same with it off, and the o
 counters say which way the file went (sla_hip_last_search_early: started early, starts, cancelled starts).
 
 Files of 5 x 4096 + 1000 samples (six super-frames, a ragged last one); the case of a silent last super-frame shorter than
-127 samples needs a file that ends in one: 5 x 4096 + 100.
+127 samples needs a file that ends in one: 5 x 4096 + 100.  The prepass of such a file needs six workgroups: option
+"early_prepass_groups" 1 and 2 both cap its grid (its waves walk on), and change neither a byte nor a counter.
 
 Reference: offset_lshift src/SLAEncoder.c:425-455, the super-frame hop over silence src/SLAEncoder.c:846-869, 392-408."""
 import numpy as np
@@ -24,6 +25,7 @@ SHAPES = {
     # nch, bits, order, mid/side, max_block
     "stereo24": (2, 24, 32, 1, 4096),
     "mono16": (1, 16, 16, 0, 4096),
+    "three16": (3, 16, 16, 0, 4096),                            # three channels: the prepass's generic channel path beside a search
 }
 
 
@@ -75,18 +77,20 @@ def _case(shape, name):
     if name == "all_zero":
         pcm[:] = 0
         return pcm, True
-    if name == "lshift3":
-        unit = 32 - bits + 3
-        pcm = ((pcm >> unit) << unit) | np.int32(1 << unit)     # multiples of 8 in the file's unit, bit 3 always set
+    if name in LSHIFTS:
+        unit = 32 - bits + LSHIFTS[name]
+        pcm = ((pcm >> unit) << unit) | np.int32(1 << unit)     # (lshift3:) multiples of 8 in the file's unit, bit 3 always set
         assert _zero_words(pcm) == 0
         return pcm, False
     raise AssertionError(name)
 
 
-def _encoder(hip, p, early):
+def _encoder(hip, p, early, groups=0):
     enc = hip.Encoder(p.cap_channels, p.cap_block_samples, p.cap_parcor_order, p.cap_longterm_order, p.cap_lms_order)
     enc.set_option("stream", 0)
     enc.set_option("search_early", early)
+    if groups:
+        enc.set_option("early_prepass_groups", groups)
     enc.set_wave_format(p.num_channels, p.bits_per_sample, p.sampling_rate)
     enc.set_encode_parameter(p.parcor_order, p.longterm_order, p.lms_order, p.ch_process_method, p.window_type, p.max_block_samples)
     return enc
@@ -108,12 +112,16 @@ def warm(oracle):
     return get
 
 
-CASES = ["plain", "zeros_at_start", "zeros_across_superframes", "silent_short_tail", "all_zero", "lshift3"]
+LSHIFTS = {"lshift1": 1, "lshift3": 3, "lshift8": 8}
+CASES = ["plain", "zeros_at_start", "zeros_across_superframes", "silent_short_tail", "all_zero", "lshift3", "lshift1", "lshift8"]
+# (shape, early_prepass_groups): every shape with the default cap, which no file here reaches; stereo24 also with caps that bind
+RUNS = [pytest.param(shape, 0, id=shape) for shape in sorted(SHAPES)]
+RUNS += [pytest.param("stereo24", g, id="stereo24-groups%d" % g) for g in (1, 2)]
 
 
-@pytest.mark.parametrize("shape", sorted(SHAPES))
+@pytest.mark.parametrize("shape,groups", RUNS)
 @pytest.mark.parametrize("name", CASES)
-def test_early_search_gives_the_same_bytes(oracle, hip, warm, shape, name):
+def test_early_search_gives_the_same_bytes(oracle, hip, warm, shape, groups, name):
     p = _params(shape)
     pcm, cancelled = _case(shape, name)
     ret, want = oracle.encode_whole(p, pcm)
@@ -121,7 +129,7 @@ def test_early_search_gives_the_same_bytes(oracle, hip, warm, shape, name):
     first, first_want = warm(shape, pcm.shape[1])
     got = {}
     for early in (1, 0):
-        enc = _encoder(hip, p, early)
+        enc = _encoder(hip, p, early, groups)
         try:
             assert enc.encode_whole(first) == first_want
             assert enc.last_search_early() == (0, 0, 0, 0)      # a fresh handle has no predecessor to go by
@@ -134,8 +142,39 @@ def test_early_search_gives_the_same_bytes(oracle, hip, warm, shape, name):
             enc.close()
     assert got[1] == got[0]
     assert got[1] == want
-    if name == "lshift3":
-        assert got[1] != first_want and len(got[1]) < len(first_want)      # (three bits per sample less to code)
+    if name in LSHIFTS:
+        assert got[1] != first_want and len(got[1]) < len(first_want)      # (lshift3: three bits per sample less to code)
+        assert got[1][24] == LSHIFTS[name]                      # offset_lshift in the file header (tests/slastream.py)
+
+
+@pytest.mark.parametrize("shape", sorted(SHAPES))
+def test_wide_samples_cancel_the_start_and_are_refused_as_ever(hip, warm, shape):
+    """one sample with a bit below the declared unit set: the prepass beside the search finds the file wider than declared and
+    calls the start off on the device; the handle answers with the result code it gives without the option, counts one start
+    and one cancelled start, and encodes the next file as if nothing had happened"""
+    nch, bits = SHAPES[shape][:2]
+    p = _params(shape)
+    pcm = _plain(shape, N, seed=311)
+    pcm[nch - 1, N // 2] |= np.int32(1 << (32 - bits - 1))
+    assert _zero_words(pcm) == 0
+    first, first_want = warm(shape, N)
+    codes = {}
+    for early in (1, 0):
+        enc = _encoder(hip, p, early)
+        try:
+            assert enc.encode_whole(first) == first_want
+            assert enc.last_search_early() == (0, 0, 0, 0)
+            with pytest.raises(hip.SlaError) as refused:
+                enc.encode_whole(pcm)
+            codes[early] = refused.value.code
+            assert enc.last_search_early() == ((1, 1, 1, 0) if early else (0, 0, 0, 0))
+            assert enc.encode_whole(first) == first_want
+            assert enc.last_search_early()[2] == early
+            assert enc.encode_whole(first) == first_want        # ... and so is the handle's next start beside a prepass
+            assert enc.last_search_early() == ((1, 2, 1, 0) if early else (0, 0, 0, 0))
+        finally:
+            enc.close()
+    assert codes[1] == codes[0] != 0
 
 
 def test_one_handle_through_every_route(oracle, hip):

@@ -1,6 +1,8 @@
-"""The numpy model of the prepass and of the batch scan (tests/prepassmodel.py) on hand-made inputs, and the one value
-it takes from the oracle: what the encoder calls silent at 32 bits with mid/side, where L + R and L - R wrap."""
+"""The numpy model of the prepass and of the batch scan (tests/prepassmodel.py) on hand-made inputs, and the values
+it takes from the oracle: what the encoder calls silent at 32 bits with mid/side, where L + R and L - R wrap, and the
+offset_lshift byte of the file header (prepass_done, the model of the two words of sla_hip_launch_prepass_early)."""
 import numpy as np
+import pytest
 
 import prepassmodel as M
 import slalibs as S
@@ -55,3 +57,61 @@ def test_batch_scan_tail_cases():
                 b2 = bits.copy()
                 b2[p] = True
                 assert M.batch_scan(M.Z.mask_words(b2), np.full(8, 5, np.uint32), [1024], [ln], maxb)[2] == 0
+
+
+def test_prepass_done_by_hand():
+    """(OR word, all-zero mask words, bits) -> (cancel, lshift), every branch"""
+    table = [
+        # nothing to encode: called off, shift 0 -- whatever the count says
+        ((0, 0, 16), (1, 0)), ((0, 5, 16), (1, 0)), ((0, 0, 32), (1, 0)), ((0, 1, 8), (1, 0)),
+        # the lowest bit of the unit is used: shift 0, and the start stands
+        ((1 << 16, 0, 16), (0, 0)), ((0xFFFF0000, 0, 16), (0, 0)), ((1 << 8, 0, 24), (0, 0)), ((1 << 24, 0, 8), (0, 0)),
+        ((1, 0, 32), (0, 0)), ((0xFFFFFFFF, 0, 32), (0, 0)),
+        # always-zero bits above the unit: that many
+        ((1 << 17, 0, 16), (0, 1)), ((0xFFF80000, 0, 16), (0, 3)), ((0xFFF80000, 0, 24), (0, 11)), ((0x00000800, 0, 24), (0, 3)),
+        ((0x50000000, 0, 8), (0, 4)), ((8, 0, 32), (0, 3)), ((0x12345600, 0, 32), (0, 9)),
+        # the largest legal shift, bits - 1: the sign bit alone
+        ((1 << 31, 0, 8), (0, 7)), ((1 << 31, 0, 16), (0, 15)), ((1 << 31, 0, 24), (0, 23)), ((1 << 31, 0, 32), (0, 31)),
+        # silence somewhere: called off, the shift is still the file's
+        ((1 << 16, 1, 16), (1, 0)), ((0xFFF80000, 1000, 16), (1, 3)), ((1 << 31, 2, 32), (1, 31)), ((1 << 31, 1, 24), (1, 23)),
+        # a bit below the unit: wider than declared -- called off, shift 0, with or without silence
+        ((0x0000FFFF, 0, 16), (1, 0)), ((0x00018000, 0, 16), (1, 0)), ((0xFFFF0080, 0, 24), (1, 0)), ((1 << 23, 0, 8), (1, 0)),
+        ((0x80000001, 7, 24), (1, 0)), ((0x00008000, 3, 16), (1, 0)),
+    ]
+    for args, want in table:
+        assert M.prepass_done(*args) == want, (args, want)
+    # bits = 32: no sample can be wider than declared; the lowest set bit is the shift
+    for ntz in range(32):
+        assert M.prepass_done((0xFFFFFFFF << ntz) & 0xFFFFFFFF, 0, 32) == (0, ntz)
+        assert M.prepass_done(1 << ntz, 9, 32) == (1, ntz)
+    # every (bits, lowest set bit): wide below the unit, the distance to the unit at and above it
+    for bits in range(1, 33):
+        for ntz in range(32):
+            want = (1, 0) if ntz < 32 - bits else (0, ntz - (32 - bits))
+            assert M.prepass_done((1 << ntz) | (1 << 31), 0, bits) == want, (bits, ntz)
+
+
+@pytest.mark.parametrize("bits", [8, 16, 24])
+def test_prepass_done_gives_the_oracles_header_byte(oracle, bits):
+    """one channel, one block of 4096 samples, every sample an odd multiple of 2^(32 - bits + L): the oracle's encoder writes
+    offset_lshift into byte 24 of the file header (tests/slastream.py: file_header), the model says the same for the OR word
+    of the samples.  A shift the oracle's encoder refuses is noted and left out; the others still count."""
+    rng = np.random.default_rng(bits)
+    p = S.make_params(1, bits, 48000, 16, 1, 8, 0, 1, 4096)
+    refused, seen = [], []
+    for L in range(bits):
+        half = 1 << (bits - L - 1)                              # odd k in [-half, half)
+        k = rng.integers(-half, half, 4096, dtype=np.int64) | 1 if half > 1 else np.full(4096, -1, np.int64)
+        pcm = (k << (32 - bits + L)).astype(np.int32).reshape(1, 4096)
+        assert (pcm.astype(np.int64) == k << (32 - bits + L)).all()
+        ret, data = oracle.encode_whole(p, pcm)
+        if ret != 0:
+            refused.append((L, ret))
+            continue
+        orw, _, zero, _ = M.prepass(pcm, bits, 0)
+        assert zero == 0
+        assert M.prepass_done(orw, zero, bits) == (0, data[24]), (bits, L)
+        assert data[23] == bits and data[24] == L, (bits, L, data[23], data[24])
+        seen.append(L)
+    print("bits %d: offset_lshift seen %s, refused by the oracle's encoder (shift, result) %s" % (bits, seen, refused))
+    assert 0 in seen and 1 in seen and 3 in seen                # what the GPU tests rely on
