@@ -124,9 +124,10 @@ class AcfJob(C.Structure):
     _fields_ = [("blk_off", C.c_uint64), ("blk_len", C.c_uint32), ("channel", C.c_uint32)]
 
 
-def launch_both(hip, blocks, ntaps, fft_size=8192):
+def launch_both(hip, blocks, ntaps, fft_size=8192, scratch=None, scratch_slots=0):
     """the certified launcher and the exact pair (sla_hip_launch_ltm_acf + sla_hip_launch_ltm_solve) on the same residual
-    blocks: (jobs of the certified call, jobs of the exact pair, counters)"""
+    blocks: (jobs of the certified call, jobs of the exact pair, counters).  scratch: a device tensor of scratch_slots x
+    fft_size doubles for the transform sizes that do not fit the LDS."""
     import torch
     L = hip.lib()
     n = len(blocks)
@@ -160,17 +161,18 @@ def launch_both(hip, blocks, ntaps, fft_size=8192):
     d_jobs2 = torch.full((n * C.sizeof(Job),), 0xAB, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     vp = lambda t: C.c_void_p(t.data_ptr())
+    d_scr = vp(scratch) if scratch is not None else None
     L.sla_hip_launch_ltm_cert_x.restype = C.c_int
     rc = L.sla_hip_launch_ltm_cert_x(vp(d_res), C.c_uint64(len(plane)), vp(d_aj), vp(d_gr), C.c_uint32(n), C.c_uint32(fft_size),
-                                     vp(d_tw), vp(d_ftw), None, C.c_uint32(0), vp(d_rec), vp(d_eps), C.c_uint32(ntaps),
+                                     vp(d_tw), vp(d_ftw), d_scr, C.c_uint32(scratch_slots), vp(d_rec), vp(d_eps), C.c_uint32(ntaps),
                                      C.c_double(16.0), vp(d_jobs), vp(d_list), vp(d_cnt), None, None)
     assert rc == 0
     torch.cuda.synchronize()
     cnt = d_cnt.cpu().numpy().copy()
     eps = d_eps.cpu().numpy().copy()
     lst = d_list.cpu().numpy().copy()
-    rc = L.sla_hip_launch_ltm_acf(vp(d_res), C.c_uint64(len(plane)), vp(d_aj), C.c_uint32(n), C.c_uint32(fft_size), vp(d_tw), None,
-                                  C.c_uint32(0), vp(d_rec), C.c_uint32(12), None)
+    rc = L.sla_hip_launch_ltm_acf(vp(d_res), C.c_uint64(len(plane)), vp(d_aj), C.c_uint32(n), C.c_uint32(fft_size), vp(d_tw), d_scr,
+                                  C.c_uint32(scratch_slots), vp(d_rec), C.c_uint32(12), None)
     assert rc == 0
     rc = L.sla_hip_launch_ltm_solve(vp(d_rec), vp(d_gr), C.c_uint32(n), C.c_uint32(ntaps), vp(d_jobs2), None)
     assert rc == 0
