@@ -1111,6 +1111,132 @@ typedef struct sla_hip_enc_emit {
 int sla_hip_launch_enc_emit_batch(const sla_hip_enc_emit* d_table, uint32_t num_entries, uint32_t max_bytes,
                                   const uint8_t* d_image, uint64_t image_bytes, sla_hip_stream_t stream);
 
+/* ---- WAV files (sla_wav.c; kernels/wav.inc) ------------------------------------------------------------------
+ * A reader and a writer of RIFF/WAVE headers on the host, and the byte work of the data chunk -- unpack, de-interleave,
+ * widen on the way in; finish, narrow, interleave, pack on the way out -- on the device.  With L the left-justified plane
+ * word, little-endian samples, frames interleaved:
+ *     8-bit (unsigned byte u)  L = (u - 128) << 24      u = (L >> 24) + 128
+ *     16-bit                   L = s << 16              s = L >> 16 (arithmetic)
+ *     24-bit                   L = s << 8               s = L >> 8  (arithmetic)
+ *     32-bit                   L = s                    s = L
+ *
+ * sla_hip_wav_parse accepts: `RIFF`, a size field that is ignored, `WAVE`; chunks walked from byte 12 (id, little-endian
+ * size, body, and the pad byte RIFF prescribes after a body of odd size); a `fmt ` chunk of at least 16 bytes somewhere
+ * before `data`, other chunks before and between them skipped; format tag 1, or 0xFFFE (extensible) with the extension
+ * present (chunk >= 40 bytes, cbSize >= 22), a sub-format whose first two bytes are 1 and valid bits equal to the container
+ * bits; 8, 16, 24 or 32 bits; at least one channel.  Byte rate and block align are ignored.  A data chunk that is no whole
+ * number of frames is floored.  Result codes: INVALID_ARGUMENT for a NULL argument; INVALID_HEADER_FORMAT for a missing
+ * signature (a file shorter than 12 bytes has none), `data` before `fmt `, a `fmt ` shorter than 16 bytes, any other tag,
+ * depth, or zero channels; INSUFFICIENT_DATA_SIZE when the chunk chain runs off the end of the file before `data` or the
+ * data chunk claims more bytes than the file holds.  Offsets are computed in 64 bits, no byte outside [data, data + size)
+ * is read.  On any failure *info is zero.
+ * sla_hip_wav_header writes the canonical 44-byte header: `RIFF`, 36 + data_bytes, `WAVEfmt `, 16, tag 1, channels, rate,
+ * byte rate, block align, bits, `data`, data_bytes. */
+#define SLA_HIP_WAV_HEADER_BYTES 44u
+typedef struct sla_hip_wav_info {
+  uint32_t num_channels, bits_per_sample, sampling_rate;
+  uint32_t num_samples;     /* frames = data_bytes / (num_channels * bits_per_sample / 8), floored */
+  uint32_t data_off;        /* file position of the first sample byte */
+  uint32_t data_bytes;      /* num_samples * num_channels * bits_per_sample / 8 */
+} sla_hip_wav_info;
+int sla_hip_wav_parse(const uint8_t* data, uint32_t size, sla_hip_wav_info* info);
+int sla_hip_wav_header(const sla_hip_wav_info* info, uint8_t out[SLA_HIP_WAV_HEADER_BYTES]);
+
+/* The ingest kernel of the WAV encode calls, the mirror of sla_hip_launch_enc_ingest_batch for packed frames.  One launch
+ * serves files that share num_channels (1 .. 8) and bytes_per_sample (1 .. 4).  Sample i of channel c of an entry is the
+ * bytes_per_sample bytes at src + (i * num_channels + c) * bytes_per_sample (src: device, ANY byte alignment); it is
+ * converted as the table above says and stored to d_planes[c * plane_stride + plane_off + i]; [num_samples, fill_end) of
+ * every plane is written zero in the same launch; nothing else is written.  Loads touch only the aligned 16-byte words
+ * that overlap [src, src + num_samples * num_channels * bytes_per_sample): a data chunk may end at the last byte of an
+ * allocation.  plane_off, plane_stride and d_planes aligned to 4 words give 16-byte plane stores.  One and two channels: a
+ * lane takes 4 whole frames from the 2 or 3 aligned words that hold them, realigned in registers; more channels: one frame
+ * per lane, byte loads.  max_samples: the largest max(num_samples, fill_end) of the table (sizes the grid).
+ * INVALID_ARGUMENT before any launch for a NULL table or planes, num_channels outside 1 .. 8, bytes_per_sample outside
+ * 1 .. 4. */
+typedef struct sla_hip_wav_ingest {
+  const uint8_t* src;             /* device: the first byte of frame 0 */
+  uint64_t plane_off;             /* first sample of the file's region in every plane */
+  uint32_t num_samples;           /* frames read from src */
+  uint32_t fill_end;              /* [num_samples, fill_end) is written zero; <= num_samples: nothing */
+} sla_hip_wav_ingest;             /* 24 bytes */
+int sla_hip_launch_wav_ingest_batch(const sla_hip_wav_ingest* d_files, uint32_t num_files, uint32_t max_samples,
+                                    uint32_t num_channels, uint32_t bytes_per_sample, int32_t* d_planes,
+                                    uint64_t plane_stride, sla_hip_stream_t stream);
+
+/* The emit kernel of the WAV decode calls, the mirror of sla_hip_launch_dec_emit_batch and of k_enc_emit for WAV files.
+ * Entry k writes exactly [dst, dst + header_bytes + num_samples * num_channels * bytes_per_sample): byte i is header[i] for
+ * i < header_bytes, then the frames of the file's region of the planes, finished as sla_hip_launch_dec_emit_batch finishes
+ * them (mid/side undone, left shift by `shift`) and converted as the table above says.  No byte outside that range is
+ * written, not even with the value it already holds -- destinations may be packed back to back and share 4-byte words and
+ * 16-byte chunks with neighbours written in the same launch: heads (with the header) and tails go out as guarded byte
+ * stores, interiors as 16-byte stores to 16-byte-aligned chunks.  An entry is skipped whole when header_bytes is neither 0
+ * nor 44 (or dst is NULL).  mid_side (the launch's): 0 = the entries' mid_side fields are ignored, 1 = they apply.
+ * max_samples: the largest num_samples of the table (sizes the grid).
+ * INVALID_ARGUMENT before any launch for a NULL table or planes, num_channels outside 1 .. 8, bytes_per_sample outside
+ * 1 .. 4, mid_side != 0 with num_channels != 2. */
+typedef struct sla_hip_wav_emit {
+  uint64_t plane_off;             /* first sample of the file's region in every plane */
+  uint8_t* dst;                   /* device, any alignment */
+  uint32_t num_samples;           /* frames read from the planes */
+  uint32_t mid_side;              /* 1: planes 0 / 1 are mid / side (two channels only) */
+  uint32_t shift;                 /* left shift of the left-justification: 32 - bits_per_sample + offset_lshift */
+  uint32_t header_bytes;          /* 0 (frames only) or 44 */
+  uint8_t  header[48];            /* the first header_bytes bytes of the file; the rest of the array is ignored */
+} sla_hip_wav_emit;               /* 80 bytes */
+int sla_hip_launch_wav_emit_batch(const int32_t* d_planes, uint64_t plane_stride, const sla_hip_wav_emit* d_table,
+                                  uint32_t num_entries, uint32_t max_samples, uint32_t num_channels,
+                                  uint32_t bytes_per_sample, uint32_t mid_side, sla_hip_stream_t stream);
+
+/* Whole WAV files in, whole .sla files out, and back.  Plain = host memory to host memory, _resident = device memory to
+ * device memory (pointers of any byte alignment).
+ *
+ * Encode.  Host sources are parsed in place; device sources are probed: one sla_hip_launch_dec_gather of the first
+ * min(size, 4096) bytes of every admissible item and one copy home, again at the chunk offset reached for files whose `data`
+ * chunk header lies beyond the probe, in rounds of one gather and one copy for all unresolved files; after 64 rounds an
+ * unresolved file gets INVALID_HEADER_FORMAT.  Per item: the code of sla_hip_wav_parse; INVALID_ARGUMENT for a NULL src, a
+ * NULL dst outside arena mode and, on the resident call, a src or dst that sla_hip_encode_batch_resident's pointer and
+ * allocation checks refuse; EXCEED_HANDLE_CAPACITY for more channels than the handle's max_num_channels or more frames than
+ * the pass cap.  Items are grouped by (channels, bits, rate) in order of first appearance; for each group the call does what
+ * SLAEncoder_SetWaveFormat does and runs the group as sla_hip_encode_batch_device runs a batch, with
+ * sla_hip_launch_wav_ingest_batch as the ingest.  A file of other than two channels is encoded with ch_process_method NONE
+ * when the handle's parameter says STEREO_MS, as the reference's tool does; the handle's encode parameter is unchanged
+ * afterwards, its wave format is the last group's.  The host call stages the data chunks of each pass -- and only those -- in
+ * page-locked memory and brings them to the device in one transfer; from there on it is the resident call with host
+ * delivery.  The resident call reads the data chunk where it lies.
+ * Every item gets exactly the result code, size and bytes that sla_hip_encode_batch on a handle with that wave format and
+ * that parameter gives for the planes of the sample map above: its own offset_lshift, the 43-byte header for an empty data
+ * chunk, INSUFFICIENT_BUFFER_SIZE where that call gives it; options "verify" and "silence_runs" work as on the device
+ * route.  A refused item gets output_size 0 and nothing written.  Arena mode (d_arena non-NULL) is
+ * sla_hip_encode_batch_resident's, group after group: dst and dst_capacity are ignored on input, dst is the file's place
+ * on output (NULL when nothing was delivered).
+ * Returns 0 when the batch ran; INVALID_ARGUMENT for a NULL encoder, NULL items with num_items > 0 or an arena that is not
+ * device memory; PARAMETER_NOT_SET without an encode parameter; what sla_hip_encode_batch gives for a parameter it refuses.
+ *
+ * Decode.  The items go through the batch decode as sla_hip_decode_batch_device / _resident run them, every item's capacity
+ * the num_samples of its header; the last leg is sla_hip_launch_wav_emit_batch -- for the host call into a device staging
+ * image that one download per pass brings home.  A WAV is delivered whole or not at all: when the decode's result is OK and
+ * every sample of the header's num_samples was produced, [dst, dst + 44 + num_samples * C * B) is written, output_size is
+ * that size and num_samples is set; on any decode failure the item carries that failure's code, output_size 0, and nothing
+ * is written.  INSUFFICIENT_BUFFER_SIZE when dst_capacity is smaller than the file (computed in 64 bits: a file of 4 GiB or
+ * more cannot be delivered); INVALID_HEADER_FORMAT for a stream whose bit_per_sample is not 8, 16, 24 or 32;
+ * INVALID_ARGUMENT for NULL src or dst and, on the resident call, what sla_hip_decode_batch_resident's pointer checks
+ * refuse.  The handle's wave format and encode parameter afterwards are what sla_hip_decode_batch_resident leaves;
+ * sla_hip_decoder_last_timing keeps its split with [3] = the WAV emit (and the download). */
+typedef struct sla_hip_wav_item {
+  const uint8_t* src;  uint8_t* dst;
+  uint32_t src_size;   uint32_t dst_capacity;
+  uint32_t output_size;   /* out */
+  int32_t  result;        /* out: SLAApiResult */
+  uint32_t num_samples;   /* out: frames of the file */
+  uint32_t reserved;
+} sla_hip_wav_item;       /* 40 bytes */
+int sla_hip_encode_wav_batch(struct SLAEncoder* encoder, sla_hip_wav_item* items, uint32_t num_items);
+int sla_hip_encode_wav_batch_resident(struct SLAEncoder* encoder, sla_hip_wav_item* items, uint32_t num_items,
+                                      uint8_t* d_arena, uint64_t arena_bytes, sla_hip_stream_t stream);
+int sla_hip_decode_wav_batch(struct SLADecoder* decoder, sla_hip_wav_item* items, uint32_t num_items);
+int sla_hip_decode_wav_batch_resident(struct SLADecoder* decoder, sla_hip_wav_item* items, uint32_t num_items,
+                                      sla_hip_stream_t stream);
+
 /* ---- one file, several GPUs ------------------------------------------------------------------------------
  * Blocks are independent (every filter and the coder reset per block, src/SLAEncoder.c:594-659), so the super-frames
  * of ONE file shard over the GPUs of a node, one process and one encoder handle per GPU.  Three facts of the whole

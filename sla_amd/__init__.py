@@ -148,6 +148,29 @@ class EncEmit(C.Structure):
                 ("header", C.c_uint8 * 48)]
 
 
+class WavInfo(C.Structure):
+    """sla_hip_wav_info (include/sla_hip.h): what sla_hip_wav_parse finds in a RIFF/WAVE file"""
+    _fields_ = [("num_channels", C.c_uint32), ("bits_per_sample", C.c_uint32), ("sampling_rate", C.c_uint32),
+                ("num_samples", C.c_uint32), ("data_off", C.c_uint32), ("data_bytes", C.c_uint32)]
+
+
+class WavItem(C.Structure):
+    """sla_hip_wav_item (include/sla_hip.h): one file of the four WAV calls"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_size", C.c_uint32), ("dst_capacity", C.c_uint32),
+                ("output_size", C.c_uint32), ("result", C.c_int32), ("num_samples", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class WavIngest(C.Structure):
+    """sla_hip_wav_ingest (include/sla_hip.h): one entry of sla_hip_launch_wav_ingest_batch"""
+    _fields_ = [("src", C.c_void_p), ("plane_off", C.c_uint64), ("num_samples", C.c_uint32), ("fill_end", C.c_uint32)]
+
+
+class WavEmit(C.Structure):
+    """sla_hip_wav_emit (include/sla_hip.h): one entry of sla_hip_launch_wav_emit_batch"""
+    _fields_ = [("plane_off", C.c_uint64), ("dst", C.c_void_p), ("num_samples", C.c_uint32), ("mid_side", C.c_uint32),
+                ("shift", C.c_uint32), ("header_bytes", C.c_uint32), ("header", C.c_uint8 * 48)]
+
+
 class LaunchExtra(C.Structure):
     """sla_hip_launch_extra (include/sla_hip.h): optional extras of one launch of an `_x` launcher; all zero = none"""
     _fields_ = [("d_span", C.c_void_p), ("d_group_count", C.c_void_p), ("clear_ptr", C.c_void_p * 3),
@@ -297,8 +320,29 @@ def lib():
                                                         C.c_void_p, C.c_uint64, C.c_void_p]
             L.sla_hip_pack_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, u32p]
             L.sla_hip_launch_enc_emit_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+        if hasattr(L, "sla_hip_wav_parse"):                  # (SLA_HIP_LIB may name an older build in an A/B run)
+            L.sla_hip_wav_parse.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(WavInfo)]
+            L.sla_hip_wav_header.argtypes = [C.POINTER(WavInfo), u8p]
+            L.sla_hip_launch_wav_ingest_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                          C.c_uint64, C.c_void_p]
+            L.sla_hip_launch_wav_emit_batch.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                        C.c_uint32, C.c_uint32, C.c_void_p]
+            L.sla_hip_encode_wav_batch.argtypes = [C.c_void_p, C.POINTER(WavItem), C.c_uint32]
+            L.sla_hip_encode_wav_batch_resident.argtypes = [C.c_void_p, C.POINTER(WavItem), C.c_uint32, C.c_void_p, C.c_uint64,
+                                                            C.c_void_p]
+            L.sla_hip_decode_wav_batch.argtypes = [C.c_void_p, C.POINTER(WavItem), C.c_uint32]
+            L.sla_hip_decode_wav_batch_resident.argtypes = [C.c_void_p, C.POINTER(WavItem), C.c_uint32, C.c_void_p]
         _lib = L
     return _lib
+
+
+def wav_info(data):
+    """(result code, WavInfo) of a RIFF/WAVE file in a bytes-like object (sla_hip_wav_parse)"""
+    buf = np.frombuffer(data, np.uint8)
+    info = WavInfo()
+    rc = lib().sla_hip_wav_parse(buf.ctypes.data if len(buf) else C.cast(C.create_string_buffer(1), C.c_void_p), len(buf),
+                                 C.byref(info))
+    return int(rc), info
 
 
 EXPORTED_SYMBOLS = [
@@ -360,6 +404,10 @@ EXPORTED_SYMBOLS = [
     # search beside the prepass (option "search_early")
     "sla_hip_launch_prepass_early", "sla_hip_launch_search_exact_early", "sla_hip_launch_plan_early", "sla_hip_launch_expand_early",
     "sla_hip_last_search_early",
+    # WAV files (include/sla_hip.h)
+    "sla_hip_wav_parse", "sla_hip_wav_header", "sla_hip_launch_wav_ingest_batch", "sla_hip_launch_wav_emit_batch",
+    "sla_hip_encode_wav_batch", "sla_hip_encode_wav_batch_resident", "sla_hip_decode_wav_batch",
+    "sla_hip_decode_wav_batch_resident",
 ]
 
 
@@ -593,6 +641,64 @@ class Encoder:
                 view = outs[i][:size]
             else:
                 off = (C.cast(items[i].data, C.c_void_p).value or arena.data_ptr()) - arena.data_ptr()
+                view = arena[off:off + size]
+            got.append((int(items[i].result), view))
+        return got
+
+    def encode_wav_batch(self, wavs, capacities=None):
+        """many WAV files (bytes-like, host memory) -> [(result code, .sla bytes)] (sla_hip_encode_wav_batch): the data
+        chunks cross the bus as they are, unpacking and de-interleaving run on the device.  Each file is what encode_batch
+        on a handle of the file's wave format gives for its samples; files of different formats may share a call.  The
+        default capacity is encode_batch's rule, 8 * C * n + 65536, from the file's own header."""
+        n = len(wavs)
+        items, keep = (WavItem * max(n, 1))(), []
+        for i, w in enumerate(wavs):
+            src = np.frombuffer(w, np.uint8)
+            if capacities is not None:
+                cap = capacities[i]
+            else:
+                rc, info = wav_info(w)
+                cap = 8 * info.num_channels * info.num_samples + 65536
+            buf = np.empty(min(cap, 0xFFFFFFFF), np.uint8)
+            keep.append((src, buf))
+            items[i].src = src.ctypes.data if len(src) else None
+            items[i].src_size = len(src)
+            items[i].dst = buf.ctypes.data
+            items[i].dst_capacity = len(buf)
+        self._check(self._lib.sla_hip_encode_wav_batch(self._h, items, n), "sla_hip_encode_wav_batch")
+        return [(int(items[i].result), keep[i][1][:items[i].output_size].tobytes()) for i in range(n)]
+
+    def encode_wav_resident(self, srcs, outs=None, arena=None, stream=None):
+        """encode_wav_batch for WAV files whose bytes are in device memory, the .sla bytes delivered to device memory
+        (sla_hip_encode_wav_batch_resident).  srcs[i] is a 1-D contiguous uint8 CUDA tensor (a slice at any offset is
+        fine) or a (device pointer, bytes) pair; exactly one of outs and arena, as for encode_resident_from.  Returns
+        [(result code, uint8 tensor view of the file's bytes)]; where nothing was delivered the view is empty."""
+        import torch
+        if (outs is None) == (arena is None):
+            raise ValueError("exactly one of outs and arena")
+        ps = Decoder._resident_sources(srcs)
+        n = len(ps)
+        if outs is not None and len(outs) != n:
+            raise ValueError("%d outputs for %d files" % (len(outs), n))
+        items = (WavItem * max(n, 1))()
+        for i, (ptr, size) in enumerate(ps):
+            items[i].src = ptr or None
+            items[i].src_size = size
+            if outs is not None:
+                items[i].dst = outs[i].data_ptr() or None
+                items[i].dst_capacity = min(outs[i].numel(), 0xFFFFFFFF)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        self._check(self._lib.sla_hip_encode_wav_batch_resident(self._h, items, n,
+                                                                C.c_void_p(arena.data_ptr() or None) if arena is not None else None,
+                                                                arena.numel() if arena is not None else 0, C.c_void_p(st.cuda_stream)),
+                    "sla_hip_encode_wav_batch_resident")
+        got = []
+        for i in range(n):
+            size = int(items[i].output_size)
+            if outs is not None:
+                view = outs[i][:size]
+            else:
+                off = (items[i].dst or arena.data_ptr()) - arena.data_ptr()
                 view = arena[off:off + size]
             got.append((int(items[i].result), view))
         return got
@@ -1012,6 +1118,53 @@ class Decoder:
                 else:
                     out[b, :, nchs[b]:].zero_()
         return out, [n for _, n in got], [rc for rc, _ in got]
+
+    def decode_wav_batch(self, slas):
+        """many .sla streams (bytes-like, host memory) -> [(result code, WAV bytes)] (sla_hip_decode_wav_batch): canonical
+        44-byte header and interleaved frames, packed on the device; capacities come from the streams' headers.  A file is
+        delivered whole or not at all (empty bytes)."""
+        n = len(slas)
+        items, keep = (WavItem * max(n, 1))(), []
+        for i, dat in enumerate(slas):
+            src = np.frombuffer(dat, np.uint8)
+            rc, h = decode_header(dat)
+            cap = 44
+            if rc == 0:
+                cap = min(44 + h.num_samples * h.wave_format.num_channels * ((h.wave_format.bit_per_sample + 7) // 8), 0xFFFFFFFF)
+            buf = np.empty(cap, np.uint8)
+            keep.append((src, buf))
+            items[i].src = src.ctypes.data if len(src) else None
+            items[i].src_size = len(src)
+            items[i].dst = buf.ctypes.data
+            items[i].dst_capacity = cap
+        self._check(self._lib.sla_hip_decode_wav_batch(self._h, items, n), "sla_hip_decode_wav_batch")
+        return [(int(items[i].result), keep[i][1][:items[i].output_size].tobytes()) for i in range(n)]
+
+    def decode_wav_resident(self, srcs, outs=None, stream=None):
+        """decode_wav_batch for streams whose bytes are in device memory, the WAV files delivered to device memory
+        (sla_hip_decode_wav_batch_resident).  srcs as for decode_resident_into; outs: 1-D contiguous uint8 CUDA tensors
+        (slices at any offset are fine), allocated from resident_headers when None.  Returns [(result code, uint8 tensor
+        view of the file's bytes)], empty where nothing was delivered."""
+        import torch
+        ps = self._resident_sources(srcs)
+        n = len(ps)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        if outs is None:
+            outs = []
+            for rc, h in self.resident_headers(ps, stream=st):
+                size = 44 + h.num_samples * h.wave_format.num_channels * ((h.wave_format.bit_per_sample + 7) // 8) if rc == 0 else 44
+                outs.append(torch.empty(min(size, 0xFFFFFFFF), dtype=torch.uint8, device="cuda:%d" % self.device_index))
+        if len(outs) != n:
+            raise ValueError("%d outputs for %d files" % (len(outs), n))
+        items = (WavItem * max(n, 1))()
+        for i, (ptr, size) in enumerate(ps):
+            items[i].src = ptr or None
+            items[i].src_size = size
+            items[i].dst = outs[i].data_ptr() or None
+            items[i].dst_capacity = min(outs[i].numel(), 0xFFFFFFFF)
+        self._check(self._lib.sla_hip_decode_wav_batch_resident(self._h, items, n, C.c_void_p(st.cuda_stream)),
+                    "sla_hip_decode_wav_batch_resident")
+        return [(int(items[i].result), outs[i][:items[i].output_size]) for i in range(n)]
 
     @staticmethod
     def _resident_sources(srcs):

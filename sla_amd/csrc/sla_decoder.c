@@ -35,6 +35,7 @@ struct SLADecoder {
   hipEvent_t                ev_order;                   /* sla_hip_decode_batch_device: the caller's stream, recorded */
   dbuf_t                    d_image, d_planes, d_blocks, d_info, d_chan, d_kint;
   dbuf_t                    d_ftab, d_out;              /* sla_hip_decode_batch: file table, packed samples */
+  dbuf_t                    d_wav; hbuf_t h_wav;        /* the WAV calls: the emit table */
   hbuf_t                    h_img, h_ptab, h_out;       /* sla_hip_decode_batch: page-locked staging */
   dbuf_t                    d_src, d_wres, d_crcf;      /* sla_hip_decode_batch_resident: gather / walk tables, walk results, CRC fields */
   hbuf_t                    h_src, h_hdr;               /* the same: tables and results, the headers brought home */
@@ -135,6 +136,7 @@ void SLADecoder_Destroy(struct SLADecoder* d)
   dbuf_free(&d->d_image); dbuf_free(&d->d_planes); dbuf_free(&d->d_blocks);
   dbuf_free(&d->d_info); dbuf_free(&d->d_chan); dbuf_free(&d->d_kint);
   dbuf_free(&d->d_ftab); dbuf_free(&d->d_out);
+  dbuf_free(&d->d_wav); hbuf_free(&d->h_wav);
   hbuf_free(&d->h_img); hbuf_free(&d->h_ptab); hbuf_free(&d->h_out);
   dbuf_free(&d->d_src); dbuf_free(&d->d_wres); dbuf_free(&d->d_crcf);
   hbuf_free(&d->h_src); hbuf_free(&d->h_hdr);
@@ -527,7 +529,22 @@ typedef struct {
   uint32_t* chans;          /* per item: the channel count its header gave, 0 when none */
   int       resident;       /* sla_hip_decode_batch_resident: items[].data are device pointers; the internal items' data
                              * is the host copy of each header, nothing behind byte 43 of it exists */
+  const struct wav_out* wav; /* the WAV calls: whole files through the WAV emit instead (items, format, zero_fill unused unless
+                             * resident, where items[].data are the sources) */
 } dev_out_t;
+
+/* sla_hip_decode_wav_batch / _resident: a file is delivered -- 44-byte header and frames, by sla_hip_launch_wav_emit_batch --
+ * when its decode ended OK with every sample of its header and nothing kept it from delivery beforehand (hold[i] != 0: the
+ * code the item gets, e.g. a destination that is too small; the decode itself still runs, so that the handle's format moves as
+ * under the device calls).  host: the destinations are host memory -- the emit goes into a device staging image (d->d_out)
+ * and one download per pass brings the files home. */
+typedef struct wav_out {
+  sla_hip_wav_item* items;
+  int32_t*  hold;
+  uint32_t* rate;            /* per item: the header's sampling rate */
+  uint8_t*  delivered;       /* out, per item */
+  int       host;
+} wav_out_t;
 
 /* ---- resident sources: the device walk and the gather stand in for walk_chain and the staging copies ---- */
 #define RES_HDR_SLOT 48u     /* bytes of one header in the gathered header image (43, padded, a multiple of 4) */
@@ -703,6 +720,69 @@ static int emit_run(struct SLADecoder* d, const int32_t* planes, uint64_t stride
   return 0;
 }
 
+/* The last leg of the WAV calls for files[0, nf) that share C and bps (a pass, or one file decoded on its own): every file
+ * that is to be delivered (wav_out_t) gets its header and its place in the emit table, one upload, one launch; host
+ * destinations: one download of the staging image and the copies into the callers' buffers.  in_pass: the planes hold the
+ * pass (regions at files[].plane_off, mid/side and shift still to do); otherwise decode_run's finished planes of one file. */
+static int wav_emit_run(struct SLADecoder* d, const dev_out_t* dev, const sla_hip_decode_item* items, const bfile_t* files,
+                        const uint32_t* done, uint32_t nf, int in_pass, const int32_t* planes, uint64_t stride, copy_list_t* cl,
+                        float* kernel_ms)
+{
+  const wav_out_t* w = dev->wav;
+  const dec_format_t* f = &files[0].f;
+  const uint32_t B = f->bps / 8;
+  sla_hip_wav_emit* et;
+  uint64_t stage = 0;
+  uint32_t i, ne = 0, max_n = 0;
+  float ms = 0.0f;
+  if (hbuf_reserve(&d->h_wav, sizeof(*et) * (size_t)nf) != 0 || dbuf_reserve(&d->d_wav, sizeof(*et) * (size_t)nf) != 0) { return -1; }
+  et = (sla_hip_wav_emit*)d->h_wav.ptr;
+  for (i = 0; i < nf; i++) {
+    const uint32_t item = files[i].item;
+    sla_hip_wav_info info;
+    if ((in_pass && files[i].alone) || items[item].result != SLA_APIRESULT_OK || done[i] != files[i].f.total || w->hold[item] != 0) { continue; }
+    memset(&et[ne], 0, sizeof(et[ne]));
+    info.num_channels = f->C; info.bits_per_sample = f->bps; info.sampling_rate = w->rate[item];
+    info.num_samples = done[i]; info.data_off = SLA_HIP_WAV_HEADER_BYTES; info.data_bytes = done[i] * f->C * B;
+    (void)sla_hip_wav_header(&info, et[ne].header);
+    et[ne].plane_off = in_pass ? files[i].plane_off : 0;
+    et[ne].num_samples = done[i];
+    et[ne].mid_side = in_pass ? f->ms : 0;
+    et[ne].shift = in_pass ? 32u - f->bps + f->lshift : 0;
+    et[ne].header_bytes = SLA_HIP_WAV_HEADER_BYTES;
+    et[ne].dst = w->host ? (uint8_t*)(uintptr_t)stage : w->items[item].dst;      /* (host: the offset, until the image is there) */
+    stage += (uint64_t)SLA_HIP_WAV_HEADER_BYTES + info.data_bytes;
+    if (done[i] > max_n) { max_n = done[i]; }
+    w->delivered[item] = 1;
+    ne++;
+  }
+  if (ne == 0) { return 0; }
+  if (w->host) {
+    if (dbuf_reserve(&d->d_out, stage + 16) != 0 || hbuf_reserve(&d->h_out, stage + 16) != 0) { return -1; }
+    for (i = 0; i < ne; i++) { et[i].dst = (uint8_t*)d->d_out.ptr + (uintptr_t)et[i].dst; }
+  }
+  BCHK(hipMemcpyAsync(d->d_wav.ptr, et, sizeof(*et) * ne, hipMemcpyHostToDevice, d->stream));
+  BCHK(hipEventRecord(d->ev[0], d->stream));
+  BRC(sla_hip_launch_wav_emit_batch(planes, stride, (const sla_hip_wav_emit*)d->d_wav.ptr, ne, max_n, f->C, B,
+                                    (in_pass && f->ms && f->C == 2) ? 1u : 0u, d->stream));
+  BCHK(hipEventRecord(d->ev[1], d->stream));
+  if (w->host) { BCHK(hipMemcpyAsync(d->h_out.ptr, d->d_out.ptr, stage, hipMemcpyDeviceToHost, d->stream)); }
+  BCHK(hipStreamSynchronize(d->stream));
+  if (hipEventElapsedTime(&ms, d->ev[0], d->ev[1]) == hipSuccess) { *kernel_ms += ms; }
+  if (w->host) {
+    uint32_t k = 0;
+    for (i = 0; i < nf; i++) {
+      const uint32_t item = files[i].item;
+      if ((in_pass && files[i].alone) || !w->delivered[item]) { continue; }
+      if (copy_add(cl, w->items[item].dst, (const uint8_t*)d->h_out.ptr + ((uintptr_t)et[k].dst - (uintptr_t)d->d_out.ptr),
+                   (size_t)SLA_HIP_WAV_HEADER_BYTES + (size_t)et[k].num_samples * f->C * B) != 0) { return -1; }
+      k++;
+    }
+    copy_run(cl);
+  }
+  return 0;
+}
+
 /* The decode kernels of a pass, once each over its nb blocks: the table (nb rows, then nb block ends) is in d->d_blocks,
  * the image in d->d_image, d->d_info is cleared.  The block infos come home to d->h_info[first ...]; waited for, the
  * kernels' time is added to *kernel_ms. */
@@ -832,7 +912,9 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
   /* ---- mid/side and left-justification of every file, packed, home in one copy, into the caller's planes; or, for
    *      device destinations, converted and stored there by the emit kernel, zero fill included */
   t = now_ms();
-  if (dev != NULL) {
+  if (dev != NULL && dev->wav != NULL) {
+    if (wav_emit_run(d, dev, items, files, done, nf, 1, (const int32_t*)d->d_planes.ptr, span, cl, kernel_ms) != 0) { free(done); return -1; }
+  } else if (dev != NULL) {
     sla_hip_dec_emit* et = (sla_hip_dec_emit*)(tend + nb);
     uint32_t ne = 0, max_lim = 0;
     for (i = 0; i < nf; i++) {
@@ -961,7 +1043,12 @@ static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t 
     }
     it->result = decode_run(d, res ? (const uint8_t*)d->h_img.ptr : it->data, it->data_size, NULL, NULL, 0, it->buffer, it->buffer_num_samples,
                             &it->output_num_samples, NULL);
-    if (dev != NULL) {
+    if (dev != NULL && dev->wav != NULL) {
+      t = now_ms();
+      if (wav_emit_run(d, dev, items, &files[i], &it->output_num_samples, 1, 0, (const int32_t*)d->d_planes.ptr,
+                       run_plane_stride(files[i].f.total, it->buffer_num_samples), &cl, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+      t_down += now_ms() - t;
+    } else if (dev != NULL) {
       sla_hip_dec_emit e;
       uint32_t max_lim = 0, ne;
       t = now_ms();
@@ -1057,7 +1144,7 @@ int sla_hip_decode_batch_device(struct SLADecoder* d, sla_hip_decode_device_item
   }
   if (num_items == 0) { memset(d->timing, 0, sizeof(d->timing)); return 0; }
   bi = (sla_hip_decode_item*)calloc(num_items, sizeof(*bi));
-  dev.items = items; dev.format = sample_format; dev.zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u; dev.resident = 0;
+  dev.items = items; dev.format = sample_format; dev.zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u; dev.resident = 0; dev.wav = NULL;
   dev.state = (uint8_t*)calloc(num_items, 1);
   dev.chans = (uint32_t*)calloc(num_items, sizeof(uint32_t));
   if (bi == NULL || dev.state == NULL || dev.chans == NULL) { rc = SLA_APIRESULT_NG; goto out; }
@@ -1106,7 +1193,7 @@ int sla_hip_decode_batch_resident(struct SLADecoder* d, sla_hip_decode_device_it
   src = (const uint8_t**)calloc(num_items, sizeof(*src));
   size = (uint32_t*)calloc(num_items, sizeof(*size));
   ok = (uint8_t*)calloc(num_items, 1);
-  dev.items = items; dev.format = sample_format; dev.zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u; dev.resident = 1;
+  dev.items = items; dev.format = sample_format; dev.zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u; dev.resident = 1; dev.wav = NULL;
   dev.state = (uint8_t*)calloc(num_items, 1);
   dev.chans = (uint32_t*)calloc(num_items, sizeof(uint32_t));
   if (bi == NULL || src == NULL || size == NULL || ok == NULL || dev.state == NULL || dev.chans == NULL) { rc = SLA_APIRESULT_NG; goto out; }
@@ -1135,6 +1222,110 @@ int sla_hip_decode_batch_resident(struct SLADecoder* d, sla_hip_decode_device_it
 out:
   free(bi); free((void*)src); free(size); free(ok); free(dev.state); free(dev.chans);
   return rc;
+}
+
+/* sla_hip_decode_wav_batch / sla_hip_decode_wav_batch_resident (include/sla_hip.h): the items become device items whose
+ * capacity is the header's num_samples and go through batch_run with the WAV emit as the last leg (wav_out_t). */
+static int decode_wav_impl(struct SLADecoder* d, sla_hip_wav_item* items, uint32_t num_items, int resident, sla_hip_stream_t stream)
+{
+  sla_hip_decode_item* bi;
+  sla_hip_decode_device_item* di;
+  const uint8_t** src;
+  uint32_t *size, *fbytes, *wbits;
+  uint8_t* ok;
+  dev_out_t dev;
+  wav_out_t w;
+  uint32_t i;
+  int rc = 0;
+  double t_hdr = 0.0;
+  if (d == NULL || (items == NULL && num_items > 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_items == 0) { memset(d->timing, 0, sizeof(d->timing)); return 0; }
+  bi = (sla_hip_decode_item*)calloc(num_items, sizeof(*bi));
+  di = (sla_hip_decode_device_item*)calloc(num_items, sizeof(*di));
+  src = (const uint8_t**)calloc(num_items, sizeof(*src));
+  size = (uint32_t*)calloc(num_items, sizeof(*size));
+  fbytes = (uint32_t*)calloc(num_items, sizeof(*fbytes));
+  wbits = (uint32_t*)calloc(num_items, sizeof(*wbits));
+  ok = (uint8_t*)calloc(num_items, 1);
+  memset(&dev, 0, sizeof(dev)); memset(&w, 0, sizeof(w));
+  dev.items = di; dev.resident = resident; dev.wav = &w;
+  dev.state = (uint8_t*)calloc(num_items, 1);
+  dev.chans = (uint32_t*)calloc(num_items, sizeof(uint32_t));
+  w.items = items; w.host = !resident;
+  w.hold = (int32_t*)calloc(num_items, sizeof(int32_t));
+  w.rate = (uint32_t*)calloc(num_items, sizeof(uint32_t));
+  w.delivered = (uint8_t*)calloc(num_items, 1);
+  if (bi == NULL || di == NULL || src == NULL || size == NULL || fbytes == NULL || wbits == NULL || ok == NULL || dev.state == NULL || dev.chans == NULL || w.hold == NULL
+      || w.rate == NULL || w.delivered == NULL) { rc = SLA_APIRESULT_NG; goto out; }
+  /* the sources, on the host, before anything of an item is read */
+  for (i = 0; i < num_items; i++) {
+    src[i] = items[i].src; size[i] = items[i].src_size;
+    ok[i] = (uint8_t)(resident ? src_region_ok(items[i].src, items[i].src_size) : (items[i].src != NULL));
+    items[i].output_size = 0; items[i].num_samples = 0;
+  }
+  /* nothing is read or written before the caller's stream has reached this call */
+  if (order_behind(d, stream) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+  if (resident) {
+    t_hdr = now_ms();
+    if (res_fetch_headers(d, src, size, ok, num_items) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+    t_hdr = now_ms() - t_hdr;
+  }
+  for (i = 0; i < num_items; i++) {
+    const sla_hip_wav_item* it = &items[i];
+    struct SLAHeaderInfo h;
+    SLAApiResult r;
+    uint64_t bytes;
+    di[i].data = it->src; di[i].data_size = it->src_size; di[i].dst = it->dst; di[i].channel_stride = 1; di[i].sample_stride = 1;
+    bi[i].data = resident ? (const uint8_t*)d->h_hdr.ptr + (size_t)i * RES_HDR_SLOT : it->src;
+    bi[i].data_size = it->src_size; bi[i].buffer = NULL;
+    if (!ok[i] || it->dst == NULL) { dev.state[i] = DEV_REFUSED; continue; }
+    r = SLADecoder_DecodeHeader(bi[i].data, it->src_size, &h);
+    if (r != SLA_APIRESULT_OK) { continue; }                    /* (batch_run gives the header's code) */
+    bi[i].buffer_num_samples = di[i].capacity = h.num_samples;
+    dev.chans[i] = h.wave_format.num_channels; w.rate[i] = h.wave_format.sampling_rate;
+    if (!(h.wave_format.bit_per_sample == 8 || h.wave_format.bit_per_sample == 16 || h.wave_format.bit_per_sample == 24
+          || h.wave_format.bit_per_sample == 32)) { w.hold[i] = SLA_APIRESULT_INVALID_HEADER_FORMAT; continue; }
+    bytes = (uint64_t)SLA_HIP_WAV_HEADER_BYTES + (uint64_t)h.num_samples * h.wave_format.num_channels * (h.wave_format.bit_per_sample / 8);
+    if (bytes > 0xFFFFFFFFull || bytes > it->dst_capacity) { w.hold[i] = SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE; continue; }
+    fbytes[i] = (uint32_t)bytes; wbits[i] = h.wave_format.bit_per_sample;
+    if (resident && !slai_device_region_ok(it->dst, 1, 2, 0, bytes - 1, 1, -1)) { dev.state[i] = DEV_REFUSED; }
+  }
+  rc = batch_run(d, bi, num_items, &dev);
+  d->timing[0] += (float)t_hdr;
+  for (i = 0; i < num_items; i++) {
+    items[i].result = (bi[i].result == SLA_APIRESULT_OK && w.hold[i] != 0) ? w.hold[i] : bi[i].result;
+    if (rc == 0 && !w.delivered[i] && items[i].result == SLA_APIRESULT_OK && fbytes[i] == SLA_HIP_WAV_HEADER_BYTES) {
+      /* a file of no samples joins no pass (format_verdict): its WAV is the header alone, written here */
+      uint8_t hdr[SLA_HIP_WAV_HEADER_BYTES];
+      sla_hip_wav_info info;
+      memset(&info, 0, sizeof(info));
+      info.num_channels = dev.chans[i]; info.bits_per_sample = wbits[i]; info.sampling_rate = w.rate[i]; info.data_off = SLA_HIP_WAV_HEADER_BYTES;
+      (void)sla_hip_wav_header(&info, hdr);
+      if (!resident) { memcpy(items[i].dst, hdr, sizeof(hdr)); w.delivered[i] = 1; }
+      else if (hipMemcpyAsync(items[i].dst, hdr, sizeof(hdr), hipMemcpyHostToDevice, d->stream) == hipSuccess
+               && hipStreamSynchronize(d->stream) == hipSuccess) { w.delivered[i] = 1; }
+      else { rc = SLA_APIRESULT_NG; }
+    }
+    if (rc == 0 && w.delivered[i]) {
+      items[i].num_samples = bi[i].output_num_samples;
+      items[i].output_size = fbytes[i];
+    } else if (items[i].result == SLA_APIRESULT_OK) {
+      items[i].result = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE;   /* (an OK decode that stopped short of the header's samples) */
+    }
+  }
+out:
+  free(bi); free(di); free((void*)src); free(size); free(fbytes); free(wbits); free(ok); free(dev.state); free(dev.chans); free(w.hold); free(w.rate); free(w.delivered);
+  return rc;
+}
+
+int sla_hip_decode_wav_batch(struct SLADecoder* d, sla_hip_wav_item* items, uint32_t num_items)
+{
+  return decode_wav_impl(d, items, num_items, 0, NULL);
+}
+
+int sla_hip_decode_wav_batch_resident(struct SLADecoder* d, sla_hip_wav_item* items, uint32_t num_items, sla_hip_stream_t stream)
+{
+  return decode_wav_impl(d, items, num_items, 1, stream);
 }
 
 int sla_hip_resident_headers(struct SLADecoder* d, const uint8_t* const* d_data, const uint32_t* data_size, uint32_t num,

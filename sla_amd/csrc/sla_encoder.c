@@ -176,6 +176,8 @@ struct SLAEncoder {
                                                     (| the ingest kernel's error word, sla_hip_encode_batch_device) */
   devbuf_t d_ingest; pinbuf_t h_ingest;          /* sla_hip_encode_batch_device: the ingest kernel's file table */
   hipEvent_t ev_order;                           /* sla_hip_encode_batch_device: the caller's stream, recorded */
+  devbuf_t d_wav_probe; pinbuf_t h_wav_probe;    /* sla_hip_encode_wav_batch_resident: the gathered header probes */
+  devbuf_t d_wav_data; pinbuf_t h_wav_data;      /* sla_hip_encode_wav_batch: the data chunks of a pass, staged and uploaded */
   int      batch_silence;                        /* the batch has an all-zero mask word or a silent file tail: whole mask on the host, host tables */
   int      mask_absent;                          /* the mask stayed on the device (nothing in it can make a block SILENT): readers take "all ones" */
   uint32_t* tab_segs; uint32_t tab_nsegs;        /* kept search tables of a batch: the file layout they were built for */
@@ -536,6 +538,10 @@ void SLAEncoder_Destroy(struct SLAEncoder* e)
   if (e->d_ingest.ptr != NULL) { (void)hipFree(e->d_ingest.ptr); }
   if (e->h_ingest.ptr != NULL) { (void)hipHostFree(e->h_ingest.ptr); }
   if (e->ev_order != NULL) { (void)hipEventDestroy(e->ev_order); }
+  if (e->d_wav_probe.ptr != NULL) { (void)hipFree(e->d_wav_probe.ptr); }
+  if (e->h_wav_probe.ptr != NULL) { (void)hipHostFree(e->h_wav_probe.ptr); }
+  if (e->d_wav_data.ptr != NULL) { (void)hipFree(e->d_wav_data.ptr); }
+  if (e->h_wav_data.ptr != NULL) { (void)hipHostFree(e->h_wav_data.ptr); }
   if (e->d_emit.ptr != NULL) { (void)hipFree(e->d_emit.ptr); }
   if (e->h_emit.ptr != NULL) { (void)hipHostFree(e->h_emit.ptr); }
   if (e->d_zruns.ptr != NULL) { (void)hipFree(e->d_zruns.ptr); }
@@ -4104,7 +4110,9 @@ static int batch_prepass(struct SLAEncoder* e, uint64_t span, const uint32_t* st
 
 /* Where the samples of a pass come from when they are not host planes: the items of sla_hip_encode_batch_device (the
  * pass's sla_hip_batch_item copies carry their sizes and buffers, a refused item with no samples and no buffer). */
-typedef struct { const sla_hip_encode_device_item* items; uint32_t format; } ingest_src_t;
+/* Or, for the WAV calls (wav_src != NULL): per item the device address of frame 0 of its data chunk, wav_bytes bytes per
+ * sample, frames interleaved -- the ingest is sla_hip_launch_wav_ingest_batch. */
+typedef struct { const sla_hip_encode_device_item* items; uint32_t format; const uint8_t* const* wav_src; uint32_t wav_bytes; } ingest_src_t;
 
 /* The upload leg of a pass of device items, queued on the handle's stream (which already waits for the caller's): the
  * files' error words zeroed, the file table up, one k_enc_ingest_batch writing every file's planes and the zero gap
@@ -4116,6 +4124,30 @@ static int ingest_batch_pass(struct SLAEncoder* e, const ingest_src_t* dev, cons
   sla_hip_enc_ingest* t;
   uint32_t i, max_fill = 0;
   RCCHK(dev_reserve(&e->d_binfo, sizeof(uint32_t) * 6 * (size_t)count + 64));      /* (batch_prepass's size with error words) */
+  if (dev->wav_src != NULL) {
+    /* packed WAV frames: the same leg with the WAV table and kernel (no sample can refuse an item: the error words stay zero) */
+    sla_hip_wav_ingest* w;
+    RCCHK(dev_reserve(&e->d_ingest, sizeof(sla_hip_wav_ingest) * (size_t)count));
+    RCCHK(pin_reserve(&e->h_ingest, sizeof(sla_hip_wav_ingest) * (size_t)count));
+    w = (sla_hip_wav_ingest*)e->h_ingest.ptr;
+    for (i = 0; i < count; i++) {
+      const uint32_t n = items[first + i].num_samples;
+      memset(&w[i], 0, sizeof(w[i]));
+      w[i].plane_off = start[i];
+      w[i].src = (n > 0) ? dev->wav_src[first + i] : NULL;
+      w[i].num_samples = n;
+      w[i].fill_end = (n + SLA_HIP_PREPASS_TILE - 1) / SLA_HIP_PREPASS_TILE * SLA_HIP_PREPASS_TILE;
+      if (w[i].fill_end > max_fill) { max_fill = w[i].fill_end; }
+    }
+    HIPCHK(hipMemsetAsync((uint32_t*)e->d_binfo.ptr + 5 * (size_t)count, 0, sizeof(uint32_t) * count, e->stream));
+    if (max_fill == 0) {
+      HIPCHK(hipMemsetAsync(e->d_pcm.ptr, 0, sizeof(int32_t) * (size_t)C * stride, e->stream));
+      return 0;
+    }
+    HIPCHK(hipMemcpyAsync(e->d_ingest.ptr, w, sizeof(sla_hip_wav_ingest) * (size_t)count, hipMemcpyHostToDevice, e->stream));
+    return sla_hip_launch_wav_ingest_batch((const sla_hip_wav_ingest*)e->d_ingest.ptr, count, max_fill, C, dev->wav_bytes,
+                                           (int32_t*)e->d_pcm.ptr, stride, e->stream);
+  }
   RCCHK(dev_reserve(&e->d_ingest, sizeof(sla_hip_enc_ingest) * (size_t)count));
   RCCHK(pin_reserve(&e->h_ingest, sizeof(sla_hip_enc_ingest) * (size_t)count));
   t = (sla_hip_enc_ingest*)e->h_ingest.ptr;
@@ -4483,7 +4515,7 @@ static int encode_batch_device_impl(struct SLAEncoder* e, sla_hip_encode_device_
   if (hipEventRecord(e->ev_order, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(e->stream, e->ev_order, 0) != hipSuccess) {
     free(bi); return SLA_APIRESULT_NG;
   }
-  dev.items = items; dev.format = sample_format;
+  dev.items = items; dev.format = sample_format; dev.wav_src = NULL; dev.wav_bytes = 0;
   e->resident = resident; e->arena = d_arena; e->arena_bytes = arena_bytes; e->arena_used = 0;
   while (first < num_items) {
     uint64_t span = 0;
@@ -4524,6 +4556,193 @@ int sla_hip_encode_batch_resident(struct SLAEncoder* e, sla_hip_encode_device_it
                                   uint32_t sample_format, uint8_t* d_arena, uint64_t arena_bytes, sla_hip_stream_t stream)
 {
   return encode_batch_device_impl(e, items, num_items, sample_format, stream, (d_arena != NULL) ? 2 : 1, d_arena, arena_bytes);
+}
+
+/* ---- WAV files in, .sla files out (include/sla_hip.h) ----------------------------------------------------------------
+ * The headers of device sources: probes of WAV_PROBE_BYTES bytes at every unresolved file's scan position, one gather and one
+ * copy home per round, until every file's scan (sla_wav.c) has ended. */
+#define WAV_PROBE_BYTES  4096u
+#define WAV_PROBE_ROUNDS 64u
+static int wav_probe_headers(struct SLAEncoder* e, const sla_hip_wav_item* items, uint32_t num_items, const uint8_t* admit,
+                             slai_wav_scan* scan, int32_t* code)
+{
+  uint32_t i, round, *who;
+  RCCHK(dev_reserve(&e->d_wav_probe, (size_t)num_items * WAV_PROBE_BYTES + 16));
+  RCCHK(pin_reserve(&e->h_wav_probe, (size_t)num_items * WAV_PROBE_BYTES + 16));
+  RCCHK(dev_reserve(&e->d_ingest, sizeof(sla_hip_dec_gather) * (size_t)num_items));
+  RCCHK(pin_reserve(&e->h_ingest, (sizeof(sla_hip_dec_gather) + sizeof(uint32_t)) * (size_t)num_items));
+  who = (uint32_t*)((sla_hip_dec_gather*)e->h_ingest.ptr + num_items);
+  for (i = 0; i < num_items; i++) { slai_wav_scan_init(&scan[i]); code[i] = admit[i] ? SLAI_WAV_NEED_MORE : SLA_APIRESULT_INVALID_ARGUMENT; }
+  for (round = 0; round < WAV_PROBE_ROUNDS; round++) {
+    sla_hip_dec_gather* gt = (sla_hip_dec_gather*)e->h_ingest.ptr;
+    uint32_t ng = 0, k;
+    for (i = 0; i < num_items; i++) {
+      uint64_t left;
+      if (code[i] != SLAI_WAV_NEED_MORE) { continue; }
+      left = (scan[i].pos < items[i].src_size) ? items[i].src_size - scan[i].pos : 0;
+      if (left == 0) { code[i] = slai_wav_scan_step(&scan[i], NULL, 0, 0, items[i].src_size); continue; }      /* (ends: nothing is left to read) */
+      memset(&gt[ng], 0, sizeof(gt[ng]));
+      gt[ng].src = items[i].src + scan[i].pos; gt[ng].dst_off = (uint64_t)ng * WAV_PROBE_BYTES;
+      gt[ng].bytes = (left < WAV_PROBE_BYTES) ? (uint32_t)left : WAV_PROBE_BYTES;
+      who[ng++] = i;
+    }
+    if (ng == 0) { break; }
+    HIPCHK(hipMemcpyAsync(e->d_ingest.ptr, gt, sizeof(*gt) * (size_t)ng, hipMemcpyHostToDevice, e->stream));
+    RCCHK(sla_hip_launch_dec_gather((const sla_hip_dec_gather*)e->d_ingest.ptr, ng, WAV_PROBE_BYTES, (uint8_t*)e->d_wav_probe.ptr,
+                                    (uint64_t)ng * WAV_PROBE_BYTES, e->stream));
+    HIPCHK(hipMemcpyAsync(e->h_wav_probe.ptr, e->d_wav_probe.ptr, (size_t)ng * WAV_PROBE_BYTES, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (k = 0; k < ng; k++) {
+      i = who[k];
+      code[i] = slai_wav_scan_step(&scan[i], (const uint8_t*)e->h_wav_probe.ptr + (size_t)k * WAV_PROBE_BYTES, scan[i].pos, gt[k].bytes,
+                                   items[i].src_size);
+    }
+  }
+  for (i = 0; i < num_items; i++) { if (code[i] == SLAI_WAV_NEED_MORE) { code[i] = SLA_APIRESULT_INVALID_HEADER_FORMAT; } }
+  return 0;
+}
+
+/* src_dev: the WAV bytes are device memory (read where they lie), otherwise host memory (the data chunks of a pass are staged
+ * in page-locked memory and uploaded in one transfer).  resident 0: host delivery, 1 / 2: the items' device buffers / the
+ * arena, as encode_batch_device_impl. */
+static int encode_wav_impl(struct SLAEncoder* e, sla_hip_wav_item* items, uint32_t num_items, int src_dev, int resident,
+                           uint8_t* d_arena, uint64_t arena_bytes, sla_hip_stream_t stream)
+{
+  const struct SLAEncodeParameter ep_saved = (e != NULL) ? e->encode_param : (struct SLAEncodeParameter){0};
+  slai_wav_scan* scan = NULL;
+  int32_t* code = NULL;
+  uint8_t* admit = NULL;
+  uint32_t* member = NULL;
+  sla_hip_batch_item* bi = NULL;
+  const uint8_t** wsrc = NULL;
+  uint32_t i;
+  int rc = 0;
+  if (e == NULL || (items == NULL && num_items != 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (!(e->status_flag & STATUS_ENCODE_PARAM)) { return SLA_APIRESULT_PARAMETER_NOT_SET; }
+  if (num_items == 0) { return 0; }
+  RCCHK(enter(e));
+  if (resident == 2 && !device_bytes_ok(d_arena, arena_bytes, e->device)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  verify_clear(e);
+  memset(e->sil_stat, 0, sizeof(e->sil_stat));
+  scan = (slai_wav_scan*)calloc(num_items, sizeof(*scan));
+  code = (int32_t*)calloc(num_items, sizeof(*code));
+  admit = (uint8_t*)calloc(num_items, 1);
+  member = (uint32_t*)calloc(num_items, sizeof(*member));
+  bi = (sla_hip_batch_item*)calloc(num_items, sizeof(*bi));
+  wsrc = (const uint8_t**)calloc(num_items, sizeof(*wsrc));
+  if (scan == NULL || code == NULL || admit == NULL || member == NULL || bi == NULL || wsrc == NULL) { rc = SLA_APIRESULT_NG; goto out; }
+  /* the pointers, on the host, before anything of an item is read or written */
+  for (i = 0; i < num_items; i++) {
+    const sla_hip_wav_item* it = &items[i];
+    int ok = (it->src != NULL && (resident == 2 || it->dst != NULL));
+    if (ok && src_dev) { ok = device_bytes_ok(it->src, it->src_size, e->device); }
+    if (ok && resident == 1) { ok = device_bytes_ok(it->dst, it->dst_capacity, e->device); }
+    admit[i] = (uint8_t)ok;
+    items[i].output_size = 0; items[i].num_samples = 0; items[i].result = SLA_APIRESULT_INVALID_ARGUMENT;
+    if (resident == 2) { items[i].dst = NULL; }
+  }
+  /* nothing is read before the caller's stream has reached this call */
+  if (e->ev_order == NULL && hipEventCreateWithFlags(&e->ev_order, hipEventDisableTiming) != hipSuccess) { e->ev_order = NULL; rc = SLA_APIRESULT_NG; goto out; }
+  if (hipEventRecord(e->ev_order, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(e->stream, e->ev_order, 0) != hipSuccess) {
+    rc = SLA_APIRESULT_NG; goto out;
+  }
+  /* the headers */
+  if (src_dev) {
+    if ((rc = wav_probe_headers(e, items, num_items, admit, scan, code)) != 0) { goto out; }
+  } else {
+    for (i = 0; i < num_items; i++) {
+      code[i] = admit[i] ? sla_hip_wav_parse(items[i].src, items[i].src_size, &scan[i].info) : SLA_APIRESULT_INVALID_ARGUMENT;
+    }
+  }
+  for (i = 0; i < num_items; i++) {
+    const sla_hip_wav_info* wi = &scan[i].info;
+    if (code[i] == SLA_APIRESULT_OK && (wi->num_channels > e->cfg.max_num_channels || wi->num_channels > SLAI_MAX_CHANNELS
+                                        || wi->num_samples > BATCH_MAX_SPAN - SLA_HIP_PREPASS_TILE)) { code[i] = SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
+    items[i].result = code[i];
+    if (code[i] != SLA_APIRESULT_OK) { admit[i] = 0; }
+  }
+  /* groups of equal (channels, bits, rate), in order of first appearance: each runs as a batch of its own wave format */
+  e->resident = resident; e->arena = d_arena; e->arena_bytes = arena_bytes; e->arena_used = 0;
+  for (;;) {
+    const sla_hip_wav_info* g = NULL;
+    struct SLAWaveFormat wf;
+    ingest_src_t dev;
+    uint32_t nm = 0, first = 0;
+    for (i = 0; i < num_items; i++) {
+      const sla_hip_wav_info* wi = &scan[i].info;
+      if (!admit[i]) { continue; }
+      if (g == NULL) { g = wi; }
+      if (wi->num_channels == g->num_channels && wi->bits_per_sample == g->bits_per_sample && wi->sampling_rate == g->sampling_rate) {
+        member[nm++] = i; admit[i] = 0;
+      }
+    }
+    if (g == NULL) { break; }
+    /* what SLAEncoder_SetWaveFormat does; mid/side only for two channels, as the reference's tool decides per file */
+    wf.num_channels = g->num_channels; wf.bit_per_sample = g->bits_per_sample; wf.sampling_rate = g->sampling_rate; wf.offset_lshift = 0;
+    e->wave_format = wf; e->status_flag |= STATUS_WAVE_FORMAT; e->analysed = 0; e->image_valid = 0;
+    e->encode_param = ep_saved;
+    if (ep_saved.ch_process_method == SLA_CHPROCESSMETHOD_STEREO_MS && wf.num_channels != 2) { e->encode_param.ch_process_method = SLA_CHPROCESSMETHOD_NONE; }
+    if ((rc = check_ready(e)) != 0) { break; }
+    for (i = 0; i < nm; i++) {
+      const sla_hip_wav_item* it = &items[member[i]];
+      memset(&bi[i], 0, sizeof(bi[i]));
+      bi[i].num_samples = scan[member[i]].info.num_samples;
+      bi[i].data = (resident == 2) ? d_arena : it->dst;
+      bi[i].data_size = (resident == 2) ? 0xFFFFFFFFu : it->dst_capacity;
+      wsrc[i] = src_dev ? it->src + scan[member[i]].info.data_off : NULL;
+    }
+    dev.items = NULL; dev.format = 0; dev.wav_src = wsrc; dev.wav_bytes = wf.bit_per_sample / 8;
+    while (first < nm) {
+      uint64_t span = 0, bytes = 0;
+      uint32_t count = 0;
+      while (first + count < nm) {
+        const uint64_t add = ((uint64_t)bi[first + count].num_samples + SLA_HIP_PREPASS_TILE - 1) / SLA_HIP_PREPASS_TILE * SLA_HIP_PREPASS_TILE;
+        if (count > 0 && span + add > BATCH_MAX_SPAN) { break; }
+        span += add; count++;
+      }
+      if (!src_dev) {
+        /* the pass's data chunks, and only those: into page-locked staging at 16-byte offsets, over in one transfer */
+        for (i = first; i < first + count; i++) { bytes += ((uint64_t)scan[member[i]].info.data_bytes + 15u) & ~(uint64_t)15; }
+        if ((rc = pin_reserve(&e->h_wav_data, (size_t)bytes + 16)) != 0 || (rc = dev_reserve(&e->d_wav_data, (size_t)bytes + 16)) != 0) { break; }
+        bytes = 0;
+        for (i = first; i < first + count; i++) {
+          const sla_hip_wav_info* wi = &scan[member[i]].info;
+          memcpy((uint8_t*)e->h_wav_data.ptr + bytes, items[member[i]].src + wi->data_off, wi->data_bytes);
+          wsrc[i] = (const uint8_t*)e->d_wav_data.ptr + bytes;
+          bytes += ((uint64_t)wi->data_bytes + 15u) & ~(uint64_t)15;
+        }
+        if (bytes > 0 && hipMemcpyAsync(e->d_wav_data.ptr, e->h_wav_data.ptr, (size_t)bytes, hipMemcpyHostToDevice, e->stream) != hipSuccess) {
+          rc = SLA_APIRESULT_NG; break;
+        }
+      }
+      if ((rc = encode_batch_pass(e, bi, first, count, &dev)) != 0) { break; }
+      for (i = first; i < first + count; i++) {
+        sla_hip_wav_item* it = &items[member[i]];
+        it->result = bi[i].result; it->output_size = bi[i].output_size;
+        it->num_samples = (bi[i].result == 0) ? bi[i].num_samples : 0;
+        if (resident == 2) { it->dst = (bi[i].result == 0) ? bi[i].data : NULL; }
+      }
+      first += count;
+    }
+    if (rc != 0) { break; }
+  }
+  e->resident = 0; e->arena = NULL; e->arena_bytes = 0;
+  e->encode_param = ep_saved;
+out:
+  free(scan); free(code); free(admit); free(member); free(bi); free((void*)wsrc);
+  if (rc != 0) { return (rc > 0) ? rc : SLA_APIRESULT_NG; }
+  return 0;
+}
+
+int sla_hip_encode_wav_batch(struct SLAEncoder* e, sla_hip_wav_item* items, uint32_t num_items)
+{
+  return encode_wav_impl(e, items, num_items, 0, 0, NULL, 0, NULL);
+}
+
+int sla_hip_encode_wav_batch_resident(struct SLAEncoder* e, sla_hip_wav_item* items, uint32_t num_items, uint8_t* d_arena,
+                                      uint64_t arena_bytes, sla_hip_stream_t stream)
+{
+  return encode_wav_impl(e, items, num_items, 1, (d_arena != NULL) ? 2 : 1, d_arena, arena_bytes, stream);
 }
 
 /* One block with the encoder's current offset_lshift; no partition search (src/SLAEncoder.c:458-801). */

@@ -108,4 +108,19 @@ uint32_t slai_verify_tables(const sla_hip_pack_block* pb, uint32_t num_blocks, c
 int      slai_device_region_ok(const void* p, uint32_t C, uint32_t n, uint64_t channel_stride, uint64_t sample_stride,
                                uint64_t esize, int device);
 
+/* ---- sla_wav.c: the RIFF/WAVE reader as a scan over windows of the file (no device calls) --------- */
+/* slai_wav_scan_step reads the window [win_off, win_off + win_len) of a file of file_size bytes and walks the chunk chain
+ * from scan->pos on.  It returns the SLAApiResult of sla_hip_wav_parse (OK: scan->info is filled), or SLAI_WAV_NEED_MORE
+ * when the next chunk header (8 bytes, up to 48 for `fmt `) is inside the file but not inside the window: call again with
+ * a window that starts at scan->pos.  A window that starts at scan->pos and holds min(4096, what is left) bytes always
+ * makes progress. */
+#define SLAI_WAV_NEED_MORE (-1)
+typedef struct slai_wav_scan {
+  uint64_t pos;            /* the next chunk header (0: the signature has not been read) */
+  uint32_t have_fmt;
+  sla_hip_wav_info info;
+} slai_wav_scan;
+void     slai_wav_scan_init(slai_wav_scan* scan);
+int      slai_wav_scan_step(slai_wav_scan* scan, const uint8_t* win, uint64_t win_off, uint32_t win_len, uint64_t file_size);
+
 #endif

@@ -30,6 +30,8 @@
 //   k_block_crc, k_unpack16/24 (pack)     src/SLAEncoder.c:682-798 (block assembly), src/SLAUtility.c:321-339 (CRC16)
 //   k_enc_ingest_batch (ingest)           no counterpart: caller-owned device PCM into the planes of a batch pass
 //   k_enc_emit (emit)                     no counterpart: the files of a pack image into caller-owned device memory, headers in front
+//   k_wav_ingest, k_wav_emit (wav)        no counterpart: packed WAV frames at any byte address into the planes of a batch pass, and decoded
+//                                         planes out as whole WAV files, 44-byte headers in front (the header work: sla_wav.c)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <float.h>
@@ -106,3 +108,4 @@ __device__ __forceinline__ uint32_t umax_wave(uint32_t v)
 #include "kernels/launchers.inc"
 #include "kernels/pack.inc"
 #include "kernels/ingest.inc"
+#include "kernels/wav.inc"
