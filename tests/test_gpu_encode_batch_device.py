@@ -2,7 +2,7 @@
 MI355X): many files whose PCM already lives in device tensors, encoded to .sla bytes without a host copy.
 
 The reference for every item is Encoder.encode_batch on a second handle of the same settings, given the host planes of the
-left-justified words the format's conversion makes (`left` below: the numpy form of the table in include/sla_hip.h); some
+left-justified words the format's conversion makes (`left` of tests/pcmmodel.py: the numpy form of the table in include/sla_hip.h); some
 items also against the oracle's encode.  Covered: C4-shaped clips in every format and layout (planar, interleaved, an
 unaligned interleaved view, every other sample of a wider tensor, a padded batch with lengths); 8-channel 24-bit files;
 round trips through decode_batch_tensor in every dtype; the F32 quantiser on crafted floats and a NaN; the S32 range; the
@@ -15,6 +15,7 @@ import pytest
 
 import slalibs as S
 import test_gpu_batch as GB
+from pcmmodel import elements, left, wrap32
 
 pytestmark = pytest.mark.gpu
 
@@ -35,44 +36,6 @@ def hip():
     import sla_amd
     sla_amd.lib()
     return sla_amd
-
-
-def wrap32(a):
-    """int64 values -> int32 of their low 32 bits"""
-    return (np.asarray(a, np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
-
-
-def left(x, fmt, bps):
-    """the table of sla_hip_encode_batch_device in numpy: elements -> left-justified int32 words; None: the item is refused"""
-    x = np.asarray(x)
-    if fmt == S32_LEFT:
-        return x.astype(np.int32)
-    if fmt == S16:
-        return wrap32(x.astype(np.int64) << 16)
-    if fmt == S32:
-        v = x.astype(np.int64)
-        if (v < -(1 << (bps - 1))).any() or (v > (1 << (bps - 1)) - 1).any():
-            return None
-        return wrap32(v << (32 - bps))
-    v = x.astype(np.float32)
-    if np.isnan(v).any():
-        return None
-    with np.errstate(over="ignore", invalid="ignore"):
-        q = np.rint(v * np.float32(2.0 ** (bps - 1)))            # exact scale, ties to even
-    q = np.clip(q.astype(np.float64), -(2.0 ** (bps - 1)), 2.0 ** (bps - 1) - 1).astype(np.int64)
-    return wrap32(q << (32 - bps))
-
-
-def elements(pcm, fmt, bps):
-    """what a producer holding left-justified PCM hands over in format fmt (the decode side's conversions)"""
-    v = np.asarray(pcm, np.int32)
-    if fmt == S32_LEFT:
-        return v
-    if fmt == S32:
-        return v >> np.int32(32 - bps)
-    if fmt == S16:
-        return (v >> np.int32(16)).astype(np.int16)
-    return v.astype(np.float32) * np.float32(2.0 ** -31)
 
 
 def on_device(a, layout="planar"):

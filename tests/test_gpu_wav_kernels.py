@@ -4,7 +4,8 @@
 Ingest: every bytes-per-sample x channel count, files of lengths around the 4-frame run, the 64-lane wave and the 1024-frame
 workgroup row, their first bytes at every offset 0 .. 15 of a 16-byte word, several files per launch, plane regions at
 4-word-aligned and at odd positions; the extremes of each width among the operands.  The planes are pre-filled with a
-sentinel and compared whole: the converted words, the zero gap [n, fill_end) and every word outside.
+sentinel and compared whole: the converted words, the zero gap [n, fill_end) and every word outside.  One more launch per
+width crosses every source offset 0 .. 15 with every count of frames in a lane's last run (files of 1 .. 9 frames).
 Emit: the same grid, mid/side on and off, the left shifts of every depth, with and without the 44-byte header, the files of
 a launch packed back to back from every start offset 0 .. 15 in a sentinel-filled buffer that is compared whole."""
 import ctypes as C
@@ -91,6 +92,58 @@ def test_ingest_against_the_model(hip, B, nch):
         got = planes.cpu().numpy()
         bad = np.nonzero(got != want)[0]
         assert len(bad) == 0, (variant, bad[:8], got[bad[:8]], want[bad[:8]])
+
+
+@pytest.mark.parametrize("nch", [1, 2])
+@pytest.mark.parametrize("B", [1, 2, 3, 4])
+def test_ingest_every_offset_with_every_tail(hip, B, nch):
+    """k_wav_ingest realigns by the source's byte offset and cuts 1 .. 4 frames out of a lane's last run: every offset 0 .. 15
+    with every n = 1 .. 9 in one launch, the last file ending at the last byte of the source tensor"""
+    import torch
+    L = hip.lib()
+    cases = [(off, n) for off in range(16) for n in range(1, 10)]
+    assert len(cases) == 144
+    for variant in (0, 1):                                   # plane regions 4-word aligned / at odd positions
+        chunks, pos = [], 0
+        for i, (off, n) in enumerate(cases):
+            raw = frames_of(n, nch, B, 5000 + 100 * B + 10 * nch + i)
+            pos = (pos + 15) // 16 * 16 + off
+            chunks.append((pos, raw))
+            pos += len(raw)
+        src = np.full(pos, BYTE_SENTINEL, np.uint8)          # (ends with the last file)
+        for p, raw in chunks:
+            src[p:p + len(raw)] = np.frombuffer(raw, np.uint8)
+        d_src = torch.from_numpy(src).cuda()
+        assert d_src.data_ptr() % 16 == 0 and chunks[-1][0] + len(chunks[-1][1]) == d_src.numel()
+        table = (hip.WavIngest * len(cases))()
+        regions, plane_pos, max_lim = [], 0, 0
+        for i, ((off, n), (p, raw)) in enumerate(zip(cases, chunks)):
+            fill_end = [0, n, n + 1, n + 5, n + 3][i % 5]
+            plane_pos = (plane_pos + 3) // 4 * 4 + (0 if variant == 0 else [1, 3, 2][i % 3])
+            regions.append((plane_pos, n, max(n, fill_end), raw))
+            table[i].src, table[i].plane_off, table[i].num_samples, table[i].fill_end = d_src.data_ptr() + p, plane_pos, n, fill_end
+            plane_pos += max(n, fill_end) + 2                # (two sentinel words between the regions)
+            max_lim = max(max_lim, n, fill_end)
+        assert {(int(table[i].src) % 16, n) for i, (_, n) in enumerate(cases)} == set(cases)
+        stride = (plane_pos + 8 + 3) // 4 * 4 + (0 if variant == 0 else 1)
+        d_table = to_device(table)
+        planes = torch.from_numpy(np.full(nch * stride + 4, SENTINEL, np.uint32).view(np.int32)).cuda()
+        base = planes if variant == 0 else planes[1:]
+        want = np.full(nch * stride + 4, SENTINEL, np.uint32).view(np.int32).copy()
+        wbase = want if variant == 0 else want[1:]
+        for po, n, lim, raw in regions:
+            conv = W.planes_from_frames(raw, nch, 8 * B)
+            for c in range(nch):
+                wbase[c * stride + po:c * stride + po + n] = conv[c]
+                wbase[c * stride + po + n:c * stride + po + lim] = 0
+        rc = L.sla_hip_launch_wav_ingest_batch(d_table.data_ptr(), len(cases), max_lim, nch, B, base.data_ptr(), stride, None)
+        assert rc == 0
+        torch.cuda.synchronize()
+        got = planes.cpu().numpy()
+        bad = np.nonzero(got != want)[0]
+        owner = [i for i, r in enumerate(regions) if bad.size and r[0] <= (bad[0] - variant) % stride]
+        assert len(bad) == 0, (variant, "file (offset, n)", cases[owner[-1]] if owner else None, bad[:8], got[bad[:8]], want[bad[:8]])
+        assert np.array_equal(d_src.cpu().numpy(), src)
 
 
 def finish(planes, ms, shift):
