@@ -151,6 +151,21 @@ SLAStreamingDecoder_Decode(struct SLAStreamingDecoder* decoder,
  * After sla_hip_decode_batch (include/sla_hip.h): the same split for the batch, [5] = the number of passes. */
 int sla_hip_decoder_last_timing(const struct SLADecoder* decoder, float* timing_ms);
 
+/* Options of a decoder handle; none changes a result, only how the work is laid out.
+ *   "wide_walk"        resident calls (sla_hip_decode_batch_resident, sla_hip_decode_wav_batch_resident; include/sla_hip.h):
+ *                      a stream of at least this many bytes has its block chain walked by the whole device
+ *                      (sla_hip_launch_dec_walk_wide) instead of one lane, the 8 longest of a call.  0 = off.  Default
+ *                      16 000 000: the smallest measured stream length at which the wide walk took at most half the
+ *                      lane walk's time (tests/tools/bench_walk_wide.py, profiles/walk_wide.json).
+ *   "wide_walk_nodes"  the node capacity of such a walk.  0 = the default: one node per 256 bytes of the stream and at
+ *                      least 1 << 16.  A stream with more nodes is walked on a lane after all.
+ * Values are whole numbers in [0, 2^32).  INVALID_ARGUMENT for a NULL argument, an unknown name or a value out of range. */
+int sla_hip_decoder_set_option(struct SLADecoder* decoder, const char* name, double value);
+
+/* Summed over the last resident call: [0] files walked wide, [1] wide walks that overflowed their node capacity and went
+ * to a lane, [2] nodes found, [3] doubling rounds launched (count and write mode).  INVALID_ARGUMENT for a NULL argument. */
+int sla_hip_decoder_last_walk(const struct SLADecoder* decoder, uint64_t counters[4]);
+
 /* The same decode on an image that already lives in device memory, planes left on the device:
  * d_planes = [num_channels][plane_stride] int32 (plane_stride >= header.num_samples + 65535 or the caller's
  * capacity), no PCIe traffic except the 10-byte-per-block walk, which reads `host_data` (the same bytes). */

@@ -727,7 +727,11 @@ int sla_hip_launch_dec_emit_batch(const int32_t* d_planes, uint64_t plane_stride
  * in the pass's one wait and are examined with the host call's code; a file that needs a resync is copied to the host
  * and decoded again on its own.  A single long file walks its blocks serially on one lane, about 0.7 us per block and
  * walk on an MI355X (two walks: 10 ms of the 16 ms a ten-minute file takes; 125 ten-second clips: 0.4 ms of 9.3 ms;
- * DESIGN section 4b).  That is accepted; there is no second walker for long files.
+ * DESIGN section 4b).  For such a file there is a second walker, sla_hip_launch_dec_walk_wide below: with the handle
+ * option "wide_walk" (sla_hip_decoder_set_option, include/SLADecoder.h; default 16 000 000 bytes) the call sends the streams of at
+ * least that many bytes, at most the 8 longest, through it in both modes -- the lane launch carries them with total = 0
+ * and writes their empty result and rows, the wide launches behind it overwrite both -- and a count whose nodes overflow
+ * the capacity is repeated on a lane.  Results, codes and samples are the same; sla_hip_decoder_last_walk counts the route.
  * The handle's stream waits on an event recorded on `stream` before the first read of any source and before the first
  * write; the call returns when every write has completed and no kernel reads a source any more.
  * sla_hip_decoder_last_timing: [0] = the gathers, [1] = the walks (kernels and their copies), the rest as for
@@ -777,6 +781,45 @@ typedef struct sla_hip_dec_walk_result {
 int sla_hip_launch_dec_walk(const sla_hip_dec_walk_file* d_files, uint32_t num_files, uint32_t max_block_samples,
                             uint32_t crc_check, sla_hip_dec_walk_result* d_results, sla_hip_dec_block* d_blocks,
                             uint64_t* d_block_end, uint32_t* d_crc_field, sla_hip_stream_t stream);
+
+/* The wide walk: the same table for ONE file, built by the whole device instead of one lane -- for the long file whose
+ * thousands of blocks sla_hip_launch_dec_walk follows one dependent load at a time.  `file` is a HOST struct (its src a
+ * device pointer); d_result[0] and the rows [first, first + max_rows) of the three tables are byte for byte what
+ * sla_hip_launch_dec_walk writes for the same file, max_block_samples and crc_check, in count mode (all three tables
+ * NULL) and in write mode: num_blocks, stop, extent, reserved 0, img_off / plane_off, the header-only row of a block
+ * that fails the capacity test under crc_check 1, the empty header-only rows of rows not reached, nothing at or behind
+ * first + max_rows.
+ * How: every byte position is tested on its own for "a block could start here" (a NODE: 43 <= p, p + 11 <= data_size,
+ * FF FF at p, 8 <= size field + 6 mod 2^32 <= data_size - p); the nodes are numbered by a scan, each gets its successor
+ * (the node at p + size field + 6, strictly ahead, or none), and the path from byte 43 is ranked by pointer doubling
+ * in sla_hip_dec_wide_rounds(data_size, node_capacity) launches -- about log2 of the block count -- before a last
+ * kernel cuts the ranked path where the lane walk would stop and writes the rows in rank order.  Sample positions are
+ * 64-bit sums.  Launches on `stream` are the only ordering: no kernel waits for another workgroup, the launcher issues
+ * no memset and no synchronisation, and every loop runs a count known on entry.
+ * Reads are byte-exact in effect: wide loads touch only the aligned 16-byte words that overlap [src, src + data_size).
+ * OVERFLOW: a stream with more nodes than node_capacity yields {0, OK, 0, SLA_HIP_DEC_WIDE_OVERFLOW} and, in write
+ * mode, max_rows empty header-only rows; the caller walks that file on a lane.  The node count is exact beyond the
+ * capacity: once the launches have completed, the first 16 bytes of d_scratch are a sla_hip_dec_wide_info.
+ * d_scratch: SLA_HIP_DEC_WIDE_SCRATCH_BYTES(data_size, node_capacity) bytes, 16-byte aligned, contents arbitrary; it
+ * may be reused by the next launch on the same stream.  A file with total == 0 or data_size < 54 launches one kernel.
+ * INVALID_ARGUMENT before any launch for a NULL file, result or scratch, node_capacity 0, write mode with a table
+ * missing, a scratch that is not 16-byte aligned, or a NULL src of a file that has to be read. */
+#define SLA_HIP_DEC_WIDE_OVERFLOW 1u     /* sla_hip_dec_walk_result.reserved */
+#define SLA_HIP_DEC_WIDE_TILES(data_size) ((((uint64_t)(data_size) + 46u) / 32u + 255u) / 256u)   /* tiles of 256 32-byte words */
+#define SLA_HIP_DEC_WIDE_SCRATCH_BYTES(data_size, node_capacity) \
+  (64u + SLA_HIP_DEC_WIDE_TILES(data_size) * 2048u + ((SLA_HIP_DEC_WIDE_TILES(data_size) * 4u + 15u) & ~(uint64_t)15) \
+   + (((uint64_t)(node_capacity) + 3u) & ~(uint64_t)3) * 64u)
+typedef struct sla_hip_dec_wide_info {
+  uint32_t nodes;                 /* nodes of the stream, exact also above node_capacity */
+  uint32_t path_len;              /* nodes on the path from byte 43 (0 after an overflow) */
+  uint32_t cut;                   /* 0xFFFFFFFF: the whole path is kept; else rank * 2 + (1: a capacity stop) of the cut */
+  uint32_t reserved;
+} sla_hip_dec_wide_info;          /* 16 bytes */
+int sla_hip_launch_dec_walk_wide(const sla_hip_dec_walk_file* file, uint32_t max_block_samples, uint32_t crc_check,
+                                 sla_hip_dec_walk_result* d_result, sla_hip_dec_block* d_blocks, uint64_t* d_block_end,
+                                 uint32_t* d_crc_field, uint32_t node_capacity, void* d_scratch, sla_hip_stream_t stream);
+uint64_t sla_hip_dec_wide_scratch_bytes(uint32_t data_size, uint32_t node_capacity);   /* the macro, for callers without it */
+uint32_t sla_hip_dec_wide_rounds(uint32_t data_size, uint32_t node_capacity);          /* doubling rounds a launch issues */
 
 /* The byte-granular gather into an image: entry k copies `bytes` bytes from src (device, any alignment) to
  * d_image + dst_off (dst_off a multiple of 4) and writes zeros from there to the next 4-byte boundary.  Nothing outside

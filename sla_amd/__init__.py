@@ -109,6 +109,11 @@ class DecWalkResult(C.Structure):
     _fields_ = [("num_blocks", C.c_uint32), ("stop", C.c_uint32), ("extent", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class DecWideInfo(C.Structure):
+    """sla_hip_dec_wide_info (include/sla_hip.h): the first 16 bytes of the wide walk's scratch, once it has run"""
+    _fields_ = [("nodes", C.c_uint32), ("path_len", C.c_uint32), ("cut", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class DecGather(C.Structure):
     """sla_hip_dec_gather (include/sla_hip.h): one entry of sla_hip_launch_dec_gather"""
     _fields_ = [("src", C.c_void_p), ("dst_off", C.c_uint64), ("bytes", C.c_uint32), ("reserved", C.c_uint32)]
@@ -315,6 +320,15 @@ def lib():
             L.sla_hip_launch_dec_walk_window.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                          C.c_void_p, C.c_void_p]
             L.sla_hip_decoder_last_window_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        if hasattr(L, "sla_hip_launch_dec_walk_wide"):       # (SLA_HIP_LIB may name an older build in an A/B run)
+            L.sla_hip_launch_dec_walk_wide.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.sla_hip_dec_wide_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+            L.sla_hip_dec_wide_scratch_bytes.restype = C.c_uint64
+            L.sla_hip_dec_wide_rounds.argtypes = [C.c_uint32, C.c_uint32]
+            L.sla_hip_dec_wide_rounds.restype = C.c_uint32
+            L.sla_hip_decoder_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
+            L.sla_hip_decoder_last_walk.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         if hasattr(L, "sla_hip_encode_batch_resident"):      # (SLA_HIP_LIB may name an older build in an A/B run)
             L.sla_hip_encode_batch_resident.argtypes = [C.c_void_p, C.POINTER(EncodeDeviceItem), C.c_uint32, C.c_uint32,
                                                         C.c_void_p, C.c_uint64, C.c_void_p]
@@ -393,6 +407,9 @@ EXPORTED_SYMBOLS = [
     "sla_hip_decode_batch_resident", "sla_hip_resident_headers", "sla_hip_launch_dec_walk", "sla_hip_launch_dec_gather",
     # sample windows of streams that are in device memory (include/sla_hip.h)
     "sla_hip_decode_windows_resident", "sla_hip_launch_dec_walk_window", "sla_hip_decoder_last_window_stats",
+    # the block table of one long resident stream, built by the whole device (include/sla_hip.h, include/SLADecoder.h)
+    "sla_hip_launch_dec_walk_wide", "sla_hip_dec_wide_scratch_bytes", "sla_hip_dec_wide_rounds", "sla_hip_decoder_set_option",
+    "sla_hip_decoder_last_walk",
     # batch encode from device memory (include/sla_hip.h)
     "sla_hip_encode_batch_device", "sla_hip_launch_enc_ingest_batch",
     # batch encode to .sla streams that stay in device memory (include/sla_hip.h)
@@ -956,6 +973,9 @@ def shard_join(shard_images):
     return out.tobytes() + b"".join(bytes(img[43:]) for img in shard_images)
 
 
+WIDE_WALK_DEFAULT = 16000000     # the handle option "wide_walk" as SLADecoder_Create sets it (sla_decoder.c: DEC_WIDE_WALK_DEFAULT)
+
+
 class Decoder:
     """Python face of ``struct SLADecoder`` (reference src/include/public/SLADecoder.h)."""
 
@@ -972,6 +992,7 @@ class Decoder:
         self._lib.hipGetDevice(C.byref(dev))
         self.device_index = dev.value             # the handle's stream lives on the device current at creation
         self.max_num_block_samples = max_num_block_samples
+        self._wide_walk, self._wide_nodes, self._index_walk = WIDE_WALK_DEFAULT, 0, None
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1162,6 +1183,7 @@ class Decoder:
             items[i].src_size = size
             items[i].dst = outs[i].data_ptr() or None
             items[i].dst_capacity = min(outs[i].numel(), 0xFFFFFFFF)
+        self._index_walk = None              # last_walk() speaks of this call from here on
         self._check(self._lib.sla_hip_decode_wav_batch_resident(self._h, items, n, C.c_void_p(st.cuda_stream)),
                     "sla_hip_decode_wav_batch_resident")
         return [(int(items[i].result), outs[i][:items[i].output_size]) for i in range(n)]
@@ -1232,6 +1254,7 @@ class Decoder:
             items[i].channel_stride = out.stride(0)
             items[i].sample_stride = max(out.stride(1), 1)
             items[i].capacity = out.shape[1]
+        self._index_walk = None              # last_walk() speaks of this call from here on
         rc = self._lib.sla_hip_decode_batch_resident(self._h, items, len(ps), sample_format,
                                                      DEC_ZERO_FILL if zero_fill else 0, C.c_void_p(st.cuda_stream))
         self._check(rc, "sla_hip_decode_batch_resident")
@@ -1383,12 +1406,34 @@ class Decoder:
                     out[b, :, first:].zero_()
         return out, [n for _, n, _ in got], [rc for rc, _, _ in got]
 
-    def block_index_resident(self, srcs, stream=None):
+    def set_option(self, name, value):
+        """a handle option (sla_hip_decoder_set_option): "wide_walk" -- resident streams of at least that many bytes have
+        their block chain walked by the whole device, 0 = off, default WIDE_WALK_DEFAULT -- and "wide_walk_nodes", the node capacity of such a walk
+        (0 = by stream size)"""
+        self._check(self._lib.sla_hip_decoder_set_option(self._h, name.encode(), float(value)), "sla_hip_decoder_set_option")
+        if name == "wide_walk":
+            self._wide_walk = int(value)
+        elif name == "wide_walk_nodes":
+            self._wide_nodes = int(value)
+
+    def last_walk(self):
+        """(files walked wide, wide walks that overflowed and went to a lane, nodes found, doubling rounds launched), summed
+        over the last resident decode (sla_hip_decoder_last_walk) or the last block_index_resident"""
+        if self._index_walk is not None:
+            return self._index_walk
+        c = (C.c_uint64 * 4)()
+        self._check(self._lib.sla_hip_decoder_last_walk(self._h, c), "sla_hip_decoder_last_walk")
+        return tuple(int(v) for v in c)
+
+    def block_index_resident(self, srcs, stream=None, wide=None):
         """the block chain of every resident stream, for hints: [(byte_off, smp_off, stop)] with the file position of
         every block's sync code and of its first sample as numpy uint32 arrays, and the walk's stop code (0: the chain
         reaches the header's num_samples).  Two launches of sla_hip_launch_dec_walk, count mode and write mode; a block
         larger than the handle's max_num_block_samples ends a file's index.  A caller keeps the index next to the bytes
-        and hands it to decode_windows_tensor(index=...)."""
+        and hands it to decode_windows_tensor(index=...).
+        wide: True walks every stream with sla_hip_launch_dec_walk_wide (the whole device on one file, for long files),
+        False none, None those of at least the handle's "wide_walk" bytes (at most the 8 longest).  The index is the same
+        either way; a wide walk whose nodes overflow the capacity falls back to the lane and shows in last_walk()."""
         import torch
         ps = self._resident_sources(srcs)
         nf = len(ps)
@@ -1421,14 +1466,74 @@ class Decoder:
                                 ("num_samples", "<u4"), ("flags", "<u4")])) if rows else None
             return res, blk
 
-        res, _ = run(0)
+        # the streams that go wide: the lane launch sees them with total = 0, their wide launches come behind it
+        threshold = self._wide_walk
+        if wide is None:
+            cand = [i for i in range(nf) if threshold and table[i].data_size >= threshold]
+            cand = sorted(cand, key=lambda i: (-table[i].data_size, i))[:8]
+        else:
+            cand = list(range(nf)) if wide else []
+        stats = [0, 0, 0, 0]
+        ncap = lambda size: self._wide_nodes or max(1 << 16, size // 256)
+
+        def run_wide(rows, which):
+            """the lane launch with `which` blanked, then their wide launches; -> results, rows, the wide files' info"""
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+            totals = {i: table[i].total for i in which}
+            with torch.cuda.stream(st):
+                for i in which:
+                    table[i].total = 0
+                d_tab = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+                for i in which:
+                    table[i].total = totals[i]
+                d_res = torch.zeros(nf * C.sizeof(DecWalkResult), dtype=torch.uint8, device=dev)
+                d_blk = torch.zeros(rows * 24, dtype=torch.uint8, device=dev) if rows else None
+                d_end = torch.zeros(rows * 8, dtype=torch.uint8, device=dev) if rows else None
+                d_crc = torch.zeros(rows * 4, dtype=torch.uint8, device=dev) if rows else None
+                need = max([self._lib.sla_hip_dec_wide_scratch_bytes(table[i].data_size, ncap(table[i].data_size)) for i in which] + [16])
+                d_scr = torch.empty(need, dtype=torch.uint8, device=dev)
+                d_inf = torch.zeros(max(len(which), 1) * 16, dtype=torch.uint8, device=dev)
+                self._check(self._lib.sla_hip_launch_dec_walk(ptr(d_tab), nf, self.max_num_block_samples, 0, ptr(d_res), ptr(d_blk),
+                                                              ptr(d_end), ptr(d_crc), sp), "sla_hip_launch_dec_walk")
+                for k, i in enumerate(which):
+                    size = table[i].data_size
+                    self._check(self._lib.sla_hip_launch_dec_walk_wide(C.byref(table[i]), self.max_num_block_samples, 0,
+                                                                       C.c_void_p(d_res.data_ptr() + 16 * i), ptr(d_blk), ptr(d_end),
+                                                                       ptr(d_crc), ncap(size), ptr(d_scr), sp),
+                                "sla_hip_launch_dec_walk_wide")
+                    d_inf[16 * k:16 * k + 16].copy_(d_scr[:16])
+                    stats[3] += int(self._lib.sla_hip_dec_wide_rounds(size, ncap(size)))
+                st.synchronize()
+            res = np.frombuffer(d_res.cpu().numpy().tobytes(), np.uint32).reshape(nf, 4).copy()
+            blk = np.frombuffer(d_blk.cpu().numpy().tobytes(), np.dtype([("byte_off", "<u8"), ("byte_len", "<u4"), ("smp_off", "<u4"),
+                                ("num_samples", "<u4"), ("flags", "<u4")])) if rows else None
+            return res, blk, np.frombuffer(d_inf.cpu().numpy().tobytes(), np.uint32).reshape(-1, 4)
+
+        if cand:
+            res, _, info = run_wide(0, cand)
+            stats[0] = len(cand)
+            stats[2] = int(sum(int(info[k][0]) for k in range(len(cand))))
+            over = [i for i in cand if int(res[i][3]) != 0]
+            stats[1] = len(over)
+            cand = [i for i in cand if i not in over]
+            if over:                                     # more nodes than the capacity: those on lanes after all
+                res_lane, _ = run(0)
+                for i in over:
+                    res[i] = res_lane[i]
+        else:
+            res, _ = run(0)
         first = 0
         for i in range(nf):
             table[i].first, table[i].max_rows = first, int(res[i][0])
             first += int(res[i][0])
+        self._index_walk = tuple(stats)
         if first == 0:
             return [(np.zeros(0, np.uint32), np.zeros(0, np.uint32), int(res[i][1])) for i in range(nf)]
-        res2, blk = run(first)
+        if cand:
+            res2, blk, _ = run_wide(first, cand)
+            self._index_walk = tuple(stats)
+        else:
+            res2, blk = run(first)
         if not np.array_equal(res, res2):
             raise RuntimeError("block_index_resident: the streams changed during the call")
         out = []

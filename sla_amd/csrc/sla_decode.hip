@@ -20,6 +20,7 @@
 //   k_dec_emit_batch     the same, converted and stored to every file's own device destination
 //   k_dec_walk           src/SLADecoder.c:696-722 (the block chain of whole files whose bytes are in device memory)
 //   k_dec_walk_window    the same chain, for the blocks a window of samples overlaps (no counterpart in the reference)
+//   k_wide_*             kernels/walk_wide.inc: the block table of one long file, found and ranked by the whole device
 //   k_dec_gather         the staging copies of a batch pass, for files that are in device memory already
 //   k_verify_blocks      (kernels/verify.inc) k_dec_finish fused with a compare against source planes, per block table
 #include <hip/hip_runtime.h>
@@ -1011,6 +1012,7 @@ void k_dec_gather(const sla_hip_dec_gather* __restrict__ table, uint32_t num_ent
   }
 }
 
+#include "kernels/walk_wide.inc"
 #include "kernels/verify.inc"
 
 }  // namespace
@@ -1196,6 +1198,76 @@ extern "C" int sla_hip_launch_dec_walk(const sla_hip_dec_walk_file* d_files, uin
   if (num_files == 0) { return 0; }
   hipLaunchKernelGGL(k_dec_walk, dim3((num_files + 63) / 64), dim3(64), 0, (hipStream_t)stream, d_files, num_files,
                      max_block_samples, crc_check, d_results, d_blocks, d_block_end, d_crc_field);
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" uint64_t sla_hip_dec_wide_scratch_bytes(uint32_t data_size, uint32_t node_capacity)
+{
+  return SLA_HIP_DEC_WIDE_SCRATCH_BYTES(data_size, node_capacity);
+}
+
+extern "C" uint32_t sla_hip_dec_wide_rounds(uint32_t data_size, uint32_t node_capacity)
+{
+  // blocks are at least 8 bytes long and the last starts 11 bytes before the end: a path has no more nodes than that,
+  // and no more than the capacity
+  uint64_t longest = (data_size < 54u) ? 0u : (uint64_t)(data_size - 54u) / 8u + 1u;
+  uint32_t r = 0;
+  if (longest > node_capacity) { longest = node_capacity; }
+  while (((uint64_t)1 << r) < longest) { r++; }
+  return r;
+}
+
+extern "C" int sla_hip_launch_dec_walk_wide(const sla_hip_dec_walk_file* file, uint32_t max_block_samples, uint32_t crc_check,
+                                            sla_hip_dec_walk_result* d_result, sla_hip_dec_block* d_blocks,
+                                            uint64_t* d_block_end, uint32_t* d_crc_field, uint32_t node_capacity,
+                                            void* d_scratch, sla_hip_stream_t stream)
+{
+  if (file == nullptr || d_result == nullptr || d_scratch == nullptr || node_capacity == 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if ((d_blocks != nullptr || d_block_end != nullptr || d_crc_field != nullptr)
+      && (d_blocks == nullptr || d_block_end == nullptr || d_crc_field == nullptr)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (((uintptr_t)d_scratch & 15u) != 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  const sla_hip_dec_walk_file fi = *file;
+  const hipStream_t st = (hipStream_t)stream;
+  const uint32_t rows = (d_blocks != nullptr) ? fi.max_rows : 0u;
+  if (fi.total == 0 || fi.data_size < SLA_HEADER_SIZE + DEC_WALK_MIN_HEADER) {
+    const uint32_t g = (rows > 256u * 1024u) ? 1024u : (rows + 255u) / 256u;
+    hipLaunchKernelGGL(k_wide_none, dim3(g ? g : 1u), dim3(256), 0, st, fi, (sla_hip_dec_wide_info*)d_scratch, d_result, d_blocks,
+                       d_block_end, d_crc_field);
+    return hip_rc(hipGetLastError());
+  }
+  if (fi.src == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  // the scratch, carved as SLA_HIP_DEC_WIDE_SCRATCH_BYTES counts it (every part a multiple of 16 bytes)
+  const uint32_t head = (uint32_t)((uintptr_t)fi.src & 15u);
+  const uint32_t words = (uint32_t)(((uint64_t)head + fi.data_size + 31u) >> 5), tiles = (words + WIDE_TILE - 1u) / WIDE_TILE;
+  const uint64_t max_tiles = SLA_HIP_DEC_WIDE_TILES(fi.data_size), capa = ((uint64_t)node_capacity + 3u) & ~(uint64_t)3;
+  uint8_t* s = (uint8_t*)d_scratch;
+  wide_arrays A;
+  A.info = (sla_hip_dec_wide_info*)s;                      s += 64;
+  A.mask = (uint32_t*)s;                                   s += max_tiles * WIDE_TILE * 4u;
+  A.word_first = (uint32_t*)s;                             s += max_tiles * WIDE_TILE * 4u;
+  A.tile = (uint32_t*)s;                                   s += (max_tiles * 4u + 15u) & ~(uint64_t)15;
+  for (int k = 0; k < 2; k++) { A.sum[k] = (uint64_t*)s;   s += capa * 8u; }
+  for (int k = 0; k < 2; k++) { A.spos[k] = (uint64_t*)s;  s += capa * 8u; }
+  for (int k = 0; k < 2; k++) { A.jump[k] = (uint32_t*)s;  s += capa * 4u; }
+  for (int k = 0; k < 2; k++) { A.rank[k] = (uint32_t*)s;  s += capa * 4u; }
+  A.pos = (uint32_t*)s;                                    s += capa * 4u;
+  A.bsize = (uint32_t*)s;                                  s += capa * 4u;
+  A.ncrc = (uint32_t*)s;                                   s += capa * 4u;
+  A.succ = (uint32_t*)s;
+  const uint32_t rounds = sla_hip_dec_wide_rounds(fi.data_size, node_capacity);
+  const uint32_t gn = (node_capacity > 256u * 1024u) ? 1024u : (node_capacity + 255u) / 256u;
+  const uint32_t most = (rows > node_capacity) ? rows : node_capacity;
+  const uint32_t gr = (most > 256u * 1024u) ? 1024u : (most + 255u) / 256u;
+  hipLaunchKernelGGL(k_wide_find, dim3(tiles), dim3(WIDE_TILE), 0, st, fi.src, fi.data_size, words, A.mask, A.tile);
+  hipLaunchKernelGGL(k_wide_scan, dim3(1), dim3(1024), 0, st, A.tile, tiles, A.info);
+  hipLaunchKernelGGL(k_wide_index, dim3(tiles), dim3(WIDE_TILE), 0, st, A.mask, words, A.tile, A.word_first);
+  hipLaunchKernelGGL(k_wide_nodes, dim3(tiles), dim3(WIDE_TILE), 0, st, fi.src, fi.data_size, words, node_capacity, A);
+  for (uint32_t r = 0; r < rounds; r++) {
+    hipLaunchKernelGGL(k_wide_round, dim3(gn), dim3(256), 0, st, node_capacity, 1u << r, A, r & 1u);
+  }
+  hipLaunchKernelGGL(k_wide_cut, dim3(gn), dim3(256), 0, st, fi, max_block_samples, node_capacity, A, rounds & 1u);
+  hipLaunchKernelGGL(k_wide_rows, dim3(gr), dim3(256), 0, st, fi, crc_check, node_capacity, A, rounds & 1u, d_result, d_blocks,
+                     d_block_end, d_crc_field);
   return hip_rc(hipGetLastError());
 }
 

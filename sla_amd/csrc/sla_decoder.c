@@ -21,6 +21,11 @@
 #define DEC_MIN_BLOCK_HEADER  11u        /* SLA_MINIMUM_BLOCK_HEADER_SIZE, reference src/include/private/SLAInternal.h:35 */
 #define STATUS_WAVE_FORMAT    1u
 #define STATUS_ENCODE_PARAM   2u
+/* Resident files of at least this many bytes have their block chain walked by sla_hip_launch_dec_walk_wide (0 = none).
+ * The smallest rung of the ladder of tests/tools/bench_walk_wide.py (0.25, 1, 4, 16, 82 MB) at which the wide walk took at
+ * most half the lane walk's time on an MI355X (profiles/walk_wide.json: 0.075 ms against 0.58 ms; at 4 MB 0.078 against
+ * 0.139).  Half and not break-even: in a batch a file's lane walk runs beside the others', wide launches add up. */
+#define DEC_WIDE_WALK_DEFAULT 16000000u
 
 typedef struct { void* ptr; size_t cap; } dbuf_t;
 typedef struct { void* ptr; size_t cap; } hbuf_t;
@@ -46,6 +51,9 @@ struct SLADecoder {
   uint32_t                  h_cap;
   float                     timing[6];
   uint64_t                  win_stats[4];               /* sla_hip_decode_windows_resident: sla_hip_decoder_last_window_stats */
+  dbuf_t                    d_wide; hbuf_t h_wide;      /* the wide walk of long resident files: its scratch; info words and rerun results home */
+  uint32_t                  wide_walk, wide_nodes;      /* options "wide_walk" (bytes, 0 = off) and "wide_walk_nodes" (0 = by file size) */
+  uint64_t                  walk_stats[4];              /* sla_hip_decoder_last_walk */
 };
 
 static double now_ms(void)
@@ -124,6 +132,7 @@ struct SLADecoder* SLADecoder_Create(const struct SLADecoderConfig* config)
   d = (struct SLADecoder*)calloc(1, sizeof(*d));
   if (d == NULL) { return NULL; }
   d->cfg = *config;
+  d->wide_walk = DEC_WIDE_WALK_DEFAULT;
   if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) { free(d); return NULL; }
   if (hipEventCreate(&d->ev[0]) != hipSuccess || hipEventCreate(&d->ev[1]) != hipSuccess) { (void)hipStreamDestroy(d->stream); free(d); return NULL; }
   return d;
@@ -140,6 +149,7 @@ void SLADecoder_Destroy(struct SLADecoder* d)
   hbuf_free(&d->h_img); hbuf_free(&d->h_ptab); hbuf_free(&d->h_out);
   dbuf_free(&d->d_src); dbuf_free(&d->d_wres); dbuf_free(&d->d_crcf);
   hbuf_free(&d->h_src); hbuf_free(&d->h_hdr);
+  dbuf_free(&d->d_wide); hbuf_free(&d->h_wide);
   { int k; for (k = 0; k < 3; k++) { if (d->ev_src[k] != NULL) { (void)hipEventDestroy(d->ev_src[k]); } } }
   if (d->h_blocks != NULL) { (void)hipHostFree(d->h_blocks); }
   if (d->h_info != NULL) { (void)hipHostFree(d->h_info); }
@@ -494,6 +504,7 @@ typedef struct {
   SLAApiResult walk_err;
   uint32_t     extent;      /* samples per channel its blocks write */
   int          alone;       /* decoded on its own through decode_run */
+  int          wide;        /* resident: its chain is walked by sla_hip_launch_dec_walk_wide, not on a lane */
   uint64_t     img_off;     /* its image in the pass image */
   uint64_t     plane_off;   /* its region in the pass planes */
 } bfile_t;
@@ -588,15 +599,77 @@ static int res_fetch_headers(struct SLADecoder* d, const uint8_t* const* src, co
   return 0;
 }
 
+/* ---- long files: the wide walk (sla_hip_launch_dec_walk_wide) in place of a lane ----
+ * Files of at least d->wide_walk bytes, the RES_WIDE_MAX longest of a call (ties: item order), are walked by the whole
+ * device one after the other behind the lane launch, in whose table they stand with total = 0: the lane writes their
+ * empty result and rows, the wide launches overwrite both.  The launches of a file are serial, so more of them would
+ * only queue up, and a batch of many mid-size files is what the lane walk is good at. */
+#define RES_WIDE_MAX 8u
+
+/* node capacity of a file's wide walk: the option, or one node per 256 stream bytes and at least 1 << 16 */
+static uint32_t res_wide_capacity(const struct SLADecoder* d, uint32_t data_size)
+{
+  const uint32_t by_size = data_size / 256u;
+  if (d->wide_nodes != 0) { return d->wide_nodes; }
+  return (by_size < (1u << 16)) ? (1u << 16) : by_size;
+}
+
+/* the files of files[0, nf) that go wide, longest first -> pick[], their number */
+static uint32_t res_pick_wide(const struct SLADecoder* d, const sla_hip_decode_item* items, const bfile_t* files, uint32_t nf,
+                              uint32_t pick[RES_WIDE_MAX])
+{
+  uint32_t n = 0, i, k;
+  if (d->wide_walk == 0) { return 0; }
+  for (i = 0; i < nf; i++) {
+    const uint32_t size = items[files[i].item].data_size;
+    if (size < d->wide_walk) { continue; }
+    for (k = n; k > 0; k--) {
+      const uint32_t ps = items[files[pick[k - 1]].item].data_size;
+      if (ps > size || (ps == size && files[pick[k - 1]].item < files[i].item)) { break; }
+      if (k < RES_WIDE_MAX) { pick[k] = pick[k - 1]; }
+    }
+    if (k < RES_WIDE_MAX) { pick[k] = i; if (n < RES_WIDE_MAX) { n++; } }
+  }
+  return n;
+}
+
+/* room for the wide walks of the listed table entries: one scratch for the largest, the words that come home */
+static int res_wide_reserve(struct SLADecoder* d, const sla_hip_dec_walk_file* wt, const uint32_t* list, uint32_t n)
+{
+  uint64_t need = 0;
+  uint32_t j;
+  for (j = 0; j < n; j++) {
+    const uint32_t size = wt[list[j]].data_size;
+    const uint64_t b = SLA_HIP_DEC_WIDE_SCRATCH_BYTES(size, res_wide_capacity(d, size));
+    if (b > need) { need = b; }
+  }
+  return (dbuf_reserve(&d->d_wide, (size_t)need) != 0
+          || hbuf_reserve(&d->h_wide, (sizeof(sla_hip_dec_wide_info) + sizeof(sla_hip_dec_walk_result)) * RES_WIDE_MAX) != 0) ? -1 : 0;
+}
+
+/* one file's wide walk queued on the handle's stream: its result to d->d_wres[slot], rows (write mode) to the tables;
+ * info != NULL: the scratch's info words go home to it */
+static int res_wide_launch(struct SLADecoder* d, const sla_hip_dec_walk_file* wf, uint32_t slot, sla_hip_dec_block* db,
+                           uint64_t* dend, uint32_t* dcrc, sla_hip_dec_wide_info* info)
+{
+  const uint32_t cap = res_wide_capacity(d, wf->data_size);
+  BRC(sla_hip_launch_dec_walk_wide(wf, d->cfg.max_num_block_samples, d->cfg.enable_crc_check, (sla_hip_dec_walk_result*)d->d_wres.ptr + slot,
+                                   db, dend, dcrc, cap, d->d_wide.ptr, d->stream));
+  if (info != NULL) { BCHK(hipMemcpyAsync(info, d->d_wide.ptr, sizeof(*info), hipMemcpyDeviceToHost, d->stream)); }
+  d->walk_stats[3] += sla_hip_dec_wide_rounds(wf->data_size, cap);
+  return 0;
+}
+
 /* The count-mode walk of files[0, nf): one launch, one small copy home; sets every file's first / nb / walk_err / extent
- * and *nblocks, and makes room for that many rows in the host tables. */
+ * and *nblocks, and makes room for that many rows in the host tables.  Long files go wide behind the lane launch; one
+ * whose nodes overflow the capacity is walked on a lane after all, in a second launch, and stays on the lane. */
 static int res_count_walk(struct SLADecoder* d, const sla_hip_decode_item* items, const dev_out_t* dev, bfile_t* files, uint32_t nf,
                           uint32_t* nblocks)
 {
   sla_hip_dec_walk_file* wt;
   sla_hip_dec_walk_result* wr;
   uint64_t total = 0;
-  uint32_t i;
+  uint32_t i, j, npick, nover = 0, pick[RES_WIDE_MAX], over[RES_WIDE_MAX];
   if (nf == 0) { return 0; }
   if (hbuf_reserve(&d->h_src, (sizeof(*wt) + sizeof(*wr)) * (size_t)nf) != 0 || dbuf_reserve(&d->d_src, sizeof(*wt) * (size_t)nf) != 0
       || dbuf_reserve(&d->d_wres, sizeof(*wr) * (size_t)nf) != 0) { return -1; }
@@ -608,11 +681,39 @@ static int res_count_walk(struct SLADecoder* d, const sla_hip_decode_item* items
     wt[i].src = dev->items[files[i].item].data; wt[i].data_size = it->data_size;
     wt[i].total = files[i].f.total; wt[i].capacity = it->buffer_num_samples;
   }
+  npick = res_pick_wide(d, items, files, nf, pick);
+  if (npick > 0 && res_wide_reserve(d, wt, pick, npick) != 0) { return -1; }
+  for (j = 0; j < npick; j++) { wt[pick[j]].total = 0; }
   BCHK(hipMemcpyAsync(d->d_src.ptr, wt, sizeof(*wt) * nf, hipMemcpyHostToDevice, d->stream));
   BRC(sla_hip_launch_dec_walk((const sla_hip_dec_walk_file*)d->d_src.ptr, nf, d->cfg.max_num_block_samples, d->cfg.enable_crc_check,
                               (sla_hip_dec_walk_result*)d->d_wres.ptr, NULL, NULL, NULL, d->stream));
+  for (j = 0; j < npick; j++) {
+    sla_hip_dec_walk_file wf = wt[pick[j]];               /* (a copy: the table is on its way to the device) */
+    wf.total = files[pick[j]].f.total;
+    if (res_wide_launch(d, &wf, pick[j], NULL, NULL, NULL, (sla_hip_dec_wide_info*)d->h_wide.ptr + j) != 0) { return -1; }
+  }
   BCHK(hipMemcpyAsync(wr, d->d_wres.ptr, sizeof(*wr) * nf, hipMemcpyDeviceToHost, d->stream));
   BCHK(hipStreamSynchronize(d->stream));
+  for (j = 0; j < npick; j++) {
+    d->walk_stats[0]++;
+    d->walk_stats[2] += ((const sla_hip_dec_wide_info*)d->h_wide.ptr)[j].nodes;
+    if (wr[pick[j]].reserved == SLA_HIP_DEC_WIDE_OVERFLOW) { d->walk_stats[1]++; over[nover++] = pick[j]; }
+    else { files[pick[j]].wide = 1; }
+  }
+  if (nover > 0) {
+    /* more nodes than the capacity: those files on lanes, in a launch of their own (the tables are free again) */
+    sla_hip_dec_walk_file* ot = (sla_hip_dec_walk_file*)d->h_src.ptr;
+    sla_hip_dec_walk_result* orr = (sla_hip_dec_walk_result*)((sla_hip_dec_wide_info*)d->h_wide.ptr + RES_WIDE_MAX);
+    sla_hip_dec_walk_file keep[RES_WIDE_MAX];
+    for (j = 0; j < nover; j++) { keep[j] = wt[over[j]]; keep[j].total = files[over[j]].f.total; }
+    for (j = 0; j < nover; j++) { ot[j] = keep[j]; }
+    BCHK(hipMemcpyAsync(d->d_src.ptr, ot, sizeof(*ot) * nover, hipMemcpyHostToDevice, d->stream));
+    BRC(sla_hip_launch_dec_walk((const sla_hip_dec_walk_file*)d->d_src.ptr, nover, d->cfg.max_num_block_samples, d->cfg.enable_crc_check,
+                                (sla_hip_dec_walk_result*)d->d_wres.ptr, NULL, NULL, NULL, d->stream));
+    BCHK(hipMemcpyAsync(orr, d->d_wres.ptr, sizeof(*orr) * nover, hipMemcpyDeviceToHost, d->stream));
+    BCHK(hipStreamSynchronize(d->stream));
+    for (j = 0; j < nover; j++) { wr[over[j]] = orr[j]; }
+  }
   for (i = 0; i < nf; i++) {
     files[i].first = (uint32_t)total; files[i].nb = wr[i].num_blocks;
     files[i].walk_err = (SLAApiResult)wr[i].stop; files[i].extent = wr[i].extent;
@@ -636,6 +737,7 @@ static int res_stage_pass(struct SLADecoder* d, const sla_hip_decode_item* items
   sla_hip_dec_block* db;
   const uint32_t first = files[0].first;
   uint32_t i, max_bytes = 0;
+  int any_wide = 0;
   if (nb == 0) { return 0; }
   if (hbuf_reserve(&d->h_src, (sizeof(*gt) + sizeof(*wt) + sizeof(*wr)) * (size_t)nf) != 0
       || dbuf_reserve(&d->d_src, (sizeof(*gt) + sizeof(*wt)) * (size_t)nf) != 0 || dbuf_reserve(&d->d_wres, sizeof(*wr) * (size_t)nf) != 0
@@ -650,6 +752,10 @@ static int res_stage_pass(struct SLADecoder* d, const sla_hip_decode_item* items
     wt[i].capacity = it->buffer_num_samples; wt[i].first = files[i].first - first; wt[i].max_rows = files[i].nb;
     wt[i].plane_off = (uint32_t)files[i].plane_off;
     if (it->data_size > max_bytes) { max_bytes = it->data_size; }
+    if (files[i].wide) {
+      if (res_wide_reserve(d, wt, &i, 1) != 0) { return -1; }
+      wt[i].total = 0; any_wide = 1;
+    }
   }
   db = (sla_hip_dec_block*)d->d_blocks.ptr;
   BCHK(hipMemcpyAsync(d->d_src.ptr, gt, (sizeof(*gt) + sizeof(*wt)) * (size_t)nf, hipMemcpyHostToDevice, d->stream));
@@ -659,6 +765,12 @@ static int res_stage_pass(struct SLADecoder* d, const sla_hip_decode_item* items
   BRC(sla_hip_launch_dec_walk((const sla_hip_dec_walk_file*)((const sla_hip_dec_gather*)d->d_src.ptr + nf), nf, d->cfg.max_num_block_samples,
                               d->cfg.enable_crc_check, (sla_hip_dec_walk_result*)d->d_wres.ptr, db, (uint64_t*)(db + nb),
                               (uint32_t*)d->d_crcf.ptr, d->stream));
+  for (i = 0; any_wide && i < nf; i++) {
+    if (!files[i].wide) { continue; }
+    sla_hip_dec_walk_file wf = wt[i];      /* (a copy: the table is on its way to the device) */
+    wf.total = files[i].f.total;
+    if (res_wide_launch(d, &wf, i, db, (uint64_t*)(db + nb), (uint32_t*)d->d_crcf.ptr, NULL) != 0) { return -1; }
+  }
   BCHK(hipMemcpyAsync(wr, d->d_wres.ptr, sizeof(*wr) * nf, hipMemcpyDeviceToHost, d->stream));
   BCHK(hipMemcpyAsync(d->h_blocks + first, db, sizeof(*db) * (size_t)nb, hipMemcpyDeviceToHost, d->stream));
   BCHK(hipMemcpyAsync(d->h_crcf + first, d->d_crcf.ptr, sizeof(uint32_t) * (size_t)nb, hipMemcpyDeviceToHost, d->stream));
@@ -678,7 +790,8 @@ static int res_finish_pass(struct SLADecoder* d, const bfile_t* files, uint32_t 
   if (hipEventElapsedTime(&ms, d->ev_src[0], d->ev_src[1]) == hipSuccess) { *t_gather += ms; }
   if (hipEventElapsedTime(&ms, d->ev_src[1], d->ev_src[2]) == hipSuccess) { *t_walk += ms; }
   for (i = 0; i < nf; i++) {
-    if (wr[i].num_blocks != files[i].nb || wr[i].stop != (uint32_t)files[i].walk_err || wr[i].extent != files[i].extent) { return -1; }
+    if (wr[i].num_blocks != files[i].nb || wr[i].stop != (uint32_t)files[i].walk_err || wr[i].extent != files[i].extent
+        || wr[i].reserved != 0) { return -1; }                 /* reserved: a wide walk that overflowed since the count */
     for (b = 0; b < files[i].nb; b++) {
       d->h_blocks[files[i].first + b].byte_off -= files[i].img_off;
       d->h_blocks[files[i].first + b].smp_off -= (uint32_t)files[i].plane_off;
@@ -966,6 +1079,7 @@ static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t 
   double t0 = now_ms(), t_walk = 0.0, t_up = 0.0, t_down = 0.0, t;
 
   memset(d->timing, 0, sizeof(d->timing));
+  if (res) { memset(d->walk_stats, 0, sizeof(d->walk_stats)); }
   if (num_items == 0) { return 0; }
   files = (bfile_t*)calloc(num_items, sizeof(*files));
   if (files == NULL) { return SLA_APIRESULT_NG; }
@@ -1644,6 +1758,24 @@ int sla_hip_decoder_last_window_stats(const struct SLADecoder* decoder, uint64_t
 {
   if (decoder == NULL || counters == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   memcpy(counters, decoder->win_stats, sizeof(decoder->win_stats));
+  return 0;
+}
+
+int sla_hip_decoder_set_option(struct SLADecoder* decoder, const char* name, double value)
+{
+  if (decoder == NULL || name == NULL || !(value >= 0.0) || value > 4294967295.0 || (double)(uint32_t)value != value) {
+    return SLA_APIRESULT_INVALID_ARGUMENT;
+  }
+  if (strcmp(name, "wide_walk") == 0) { decoder->wide_walk = (uint32_t)value; }
+  else if (strcmp(name, "wide_walk_nodes") == 0) { decoder->wide_nodes = (uint32_t)value; }
+  else { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  return 0;
+}
+
+int sla_hip_decoder_last_walk(const struct SLADecoder* decoder, uint64_t counters[4])
+{
+  if (decoder == NULL || counters == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  memcpy(counters, decoder->walk_stats, sizeof(decoder->walk_stats));
   return 0;
 }
 
