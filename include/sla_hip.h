@@ -821,6 +821,145 @@ int sla_hip_launch_dec_walk_wide(const sla_hip_dec_walk_file* file, uint32_t max
 uint64_t sla_hip_dec_wide_scratch_bytes(uint32_t data_size, uint32_t node_capacity);   /* the macro, for callers without it */
 uint32_t sla_hip_dec_wide_rounds(uint32_t data_size, uint32_t node_capacity);          /* doubling rounds a launch issues */
 
+/* Decode THROUGH damage: one resident .sla stream salvaged on the device.  Every other decode call stops at the first block
+ * that fails, as the reference does; this one delivers all N samples of the header, each either decoded or zero, and says
+ * which ranges are silence and why.  It can, because every block resets its filters and its coder and carries a CRC16 over
+ * its own bytes.  Nothing that the other calls return changes.
+ *
+ * THE RULE (executable: tests/salvagemodel.py).  S = data_size; N, C from the header.
+ *   NODE         the wide walk's: 43 <= p, p + 11 <= S, FF FF at p, 8 <= size field + 6 (mod 2^32) <= S - p.
+ *   SOUND BLOCK  a node whose sample count n (bytes p + 8..9) is <= the handle's max_num_block_samples, whose byte length
+ *                is <= SLA_HIP_SALVAGE_MAX_BLOCK_BYTES(C, n) = 64 + 16 C max(n, 1) -- four times a RAW block of 32-bit
+ *                samples: no block an encoder writes is longer, and the cap bounds the CRC work that the size field of
+ *                a decoy (FF FF in a payload) can cause -- and whose CRC16 over [p + 8, p + length) equals the field at
+ *                p + 6.  Soundness is always judged with the CRC, whatever the handle's enable_crc_check says.
+ *   MODE 1, chain intact: the plain walk from byte 43 with capacity N stops with OK and extent N.  Every block of the
+ *                chain keeps its position.  A block whose stored CRC differs is not entropy-decoded at all (its row is
+ *                SLA_HIP_DEC_HEADER_ONLY) and becomes n samples of silence, reason CRC; a block whose CRC holds and whose
+ *                decode fails by the whole-file decode's criteria -- type > 2, reader overrun, a body that does not end
+ *                where the size field says -- becomes silence, reason UNDECODABLE.  Decoding goes on at the next block of
+ *                the chain: there is no resync from where a reader stopped.
+ *   MODE 2, chain broken (everything else): two anchored pieces are delivered, what lies between them is lost.
+ *                PREFIX: from byte 43, sample 0, sound blocks while one starts exactly where the one before ended and
+ *                s + n <= N; it ends at byte p0, sample s0.  SUFFIX: over links from a sound block to the sound block
+ *                that starts exactly at its end, the smallest sound q >= p0 whose chain ends exactly at byte S with a
+ *                sample sum T <= N - s0; it is placed at sample N - T.  [s0, N - T) is one range of silence, reason GAP
+ *                ([s0, N) when no q qualifies).  Prefix and suffix blocks that then fail in the decoder are concealed as
+ *                in mode 1.
+ * The chain is trusted for positions (mode 1) only when it accounts for exactly N samples: sample counts and size fields
+ * are chain data, and a damaged one that still leads somewhere would shift everything behind it.
+ * ACCEPTED LIMITS.  A second break in the middle loses the sound blocks between the two breaks.  Bytes appended behind
+ * the last block defeat the right anchor (no suffix).  A CRC16 passes a decoy with probability 2^-16.  A complete valid
+ * block embedded in another block's payload and chained to the end can be picked as q when the block around it is not
+ * sound: its samples are then delivered, right-aligned with the suffix.
+ *
+ * THE CALL.  d_data / data_size: the stream in device memory, any alignment, only read.  dst, channel_stride,
+ * sample_stride, capacity, sample_format: as an item of sla_hip_decode_batch_resident, and so are the source and
+ * destination checks (INVALID_ARGUMENT, nothing read or written), the header's failures and format verdicts (that call's
+ * code and nothing else; a file of no samples is OK) and the ordering behind `stream`; the handle's wave format and encode
+ * parameter become the stream's.  An LMS order the kernels do not run is refused whole: FAILED_TO_SYNTHESIZE, nothing
+ * written.  capacity < N: INSUFFICIENT_BUFFER_SIZE, nothing written.  Otherwise exactly [0, C) x [0, N) is written, and
+ * nothing outside it.  Returns OK when nothing was concealed or lost -- dst then equals sla_hip_decode_batch_resident's
+ * bit for bit -- and DETECT_DATA_CORRUPTION when something was; the data is delivered either way.  NG: a device failure.
+ * INVALID_ARGUMENT before anything else for a NULL decoder, d_data, dst or report, an unknown format, or NULL ranges
+ * with range_capacity > 0.
+ * report: see the struct.  ranges: the first min(num_ranges, range_capacity) silent ranges in ascending order, one per
+ * concealed block that has samples and one for the gap; num_ranges is exact beyond the capacity.
+ * How it runs: header gather; the lane walk in count mode (the wide walk from the handle's "wide_walk" size on) decides the
+ * mode.  Mode 1: gather, walk in write mode, k_salvage_crc flags the rows whose CRC differs.  Mode 2: the salvage scan
+ * below in count mode (repeated once with the exact capacity when the nodes overflow the handle's), the gather, the scan
+ * in write mode.  Then the decode kernels unchanged; the infos come home in that wait, the list of silent regions goes up,
+ * k_dec_conceal zeroes them in the planes (zero planes stay zero through mid/side and shift) and the emit kernel writes
+ * dst.  No byte of the stream behind its header is copied to the host.
+ * sla_hip_decoder_last_timing: [0] the gathers, [1] the count walk and the count-mode scan, [2] the decode kernels, [3]
+ * conceal and emit, [4] the call.  sla_hip_decoder_last_walk: the count walk's figures and, in mode 2, one more walk, the
+ * scan's nodes and two sets of doubling rounds per scan; [1] counts a scan whose nodes overflowed. */
+#define SLA_HIP_SALVAGE_MAX_BLOCK_BYTES(C, n) (64u + 16u * (uint32_t)(C) * (((uint32_t)(n) > 1u) ? (uint32_t)(n) : 1u))
+#define SLA_HIP_SALVAGE_CRC         1u    /* sla_hip_salvage_range.reason: the block's stored CRC differs */
+#define SLA_HIP_SALVAGE_UNDECODABLE 2u    /* the CRC holds, the decoder failed on the block */
+#define SLA_HIP_SALVAGE_GAP         3u    /* mode 2: between prefix and suffix */
+typedef struct sla_hip_salvage_report {
+  uint32_t mode;                  /* 0: nothing decoded (refused, or no samples), 1: chain intact, 2: chain broken */
+  uint32_t blocks_decoded;
+  uint32_t blocks_concealed;
+  uint32_t samples_lost;          /* per channel: the sum of the ranges' lengths */
+  uint32_t num_ranges;            /* exact, also beyond range_capacity */
+  uint32_t prefix_blocks;         /* mode 2 from here on; 0 in mode 1 */
+  uint32_t suffix_blocks;
+  uint32_t suffix_byte;           /* q; 0: no suffix */
+  uint32_t suffix_sample;         /* N - T; 0 without a suffix */
+  uint32_t nodes;
+  uint32_t sound_nodes;
+  uint32_t reserved;
+} sla_hip_salvage_report;         /* 48 bytes */
+typedef struct sla_hip_salvage_range {
+  uint32_t start;                 /* first sample */
+  uint32_t length;
+  uint32_t reason;                /* SLA_HIP_SALVAGE_* */
+} sla_hip_salvage_range;          /* 12 bytes */
+struct SLADecoder;
+int sla_hip_salvage_resident(struct SLADecoder* decoder, const uint8_t* d_data, uint32_t data_size,
+                             void* dst, uint64_t channel_stride, uint64_t sample_stride, uint32_t capacity,
+                             uint32_t sample_format, sla_hip_salvage_report* report,
+                             sla_hip_salvage_range* ranges, uint32_t range_capacity, sla_hip_stream_t stream);
+
+/* The salvage scan: mode 2 of the rule above for ONE stream, by the whole device.  `file` is a HOST struct as for
+ * sla_hip_launch_dec_walk_wide (src, data_size, total = N; capacity is not read; write mode: img_off, first, max_rows,
+ * plane_off).  d_result[0] receives the prefix, the suffix and the counts.  Count mode (all three tables NULL) writes
+ * nothing else; write mode puts the prefix rows and behind them the suffix rows -- flags 0, smp_off the block's sample
+ * position + plane_off, the suffix at N - T -- into rows [first, first + max_rows) of the three tables as
+ * sla_hip_launch_dec_walk does, rows behind the last block become empty header-only rows, and nothing is written at or
+ * behind first + max_rows, which the caller sets to prefix_blocks + suffix_blocks of a count-mode scan.
+ * How: the node bitmap, scan and numbering of the wide walk; one wave per node judges soundness (the n test and the
+ * length cap first, then the CRC16 of the block by crc16_wave); sound-successor links are doubled to the END in
+ * sla_hip_dec_wide_rounds(data_size, node_capacity) launches, after which every sound node knows the last node of its
+ * all-sound chain, that chain's end byte and its 64-bit sample sum, and the path from byte 43 is ranked; a cut ends the
+ * prefix; an atomicMin over the qualifying nodes picks q; a second set of rounds ranks q's chain; a last kernel writes the
+ * rows and the result.  Launches on `stream` are the only ordering: no kernel waits for another workgroup, the launcher
+ * issues no memset and no synchronisation, every loop runs a count known on entry.  Reads touch only the aligned 16-byte
+ * words that overlap [src, src + data_size).
+ * OVERFLOW: more nodes than node_capacity yield overflow = 1, the exact node count, every other field as for an empty
+ * scan and, in write mode, empty rows only; the caller repeats with that capacity.
+ * d_scratch: SLA_HIP_DEC_SALVAGE_SCRATCH_BYTES(data_size, node_capacity) bytes, 16-byte aligned, contents arbitrary,
+ * reusable by the next launch on the same stream.  A stream of fewer than 54 bytes launches one kernel.
+ * INVALID_ARGUMENT before any launch for a NULL file, result or scratch, node_capacity 0, num_channels 0 or > 8, write
+ * mode with a table missing, a scratch that is not 16-byte aligned, or a NULL src of a file that has to be read. */
+#define SLA_HIP_DEC_SALVAGE_SCRATCH_BYTES(data_size, node_capacity) \
+  (SLA_HIP_DEC_WIDE_SCRATCH_BYTES(data_size, node_capacity) + 64u + (((uint64_t)(node_capacity) + 3u) & ~(uint64_t)3) * 28u)
+typedef struct sla_hip_salvage_scan {
+  uint32_t prefix_blocks;
+  uint32_t prefix_samples;        /* s0 */
+  uint32_t prefix_end;            /* p0: the byte behind the prefix, 43 when it is empty */
+  uint32_t suffix_byte;           /* q; 0: no suffix */
+  uint32_t suffix_samples;        /* T */
+  uint32_t suffix_blocks;
+  uint32_t nodes;                 /* exact, also above node_capacity */
+  uint32_t sound_nodes;
+  uint32_t overflow;              /* 1: nodes > node_capacity, nothing else was found */
+  uint32_t reserved[3];
+} sla_hip_salvage_scan;           /* 48 bytes */
+int sla_hip_launch_dec_salvage_scan(const sla_hip_dec_walk_file* file, uint32_t num_channels, uint32_t max_block_samples,
+                                    sla_hip_salvage_scan* d_result, sla_hip_dec_block* d_blocks, uint64_t* d_block_end,
+                                    uint32_t* d_crc_field, uint32_t node_capacity, void* d_scratch, sla_hip_stream_t stream);
+uint64_t sla_hip_dec_salvage_scratch_bytes(uint32_t data_size, uint32_t node_capacity);   /* the macro, for callers without it */
+
+/* Mode 1's CRC pass over a block table in a pass image (kernel k_salvage_crc): row b gets d_bad[b] = 1 and the flag
+ * SLA_HIP_DEC_HEADER_ONLY when the CRC16 of its bytes [byte_off + 8, byte_off + byte_len) of the image differs from
+ * d_crc_field[b], else d_bad[b] = 0.  INVALID_ARGUMENT before any launch for a NULL pointer. */
+int sla_hip_launch_salvage_crc(const uint8_t* d_image, sla_hip_dec_block* d_blocks, const uint32_t* d_crc_field,
+                               uint32_t num_blocks, uint32_t* d_bad, sla_hip_stream_t stream);
+
+/* Silence in the decode planes (kernel k_dec_conceal): samples [smp_off, smp_off + num_samples) of all num_channels planes
+ * are written zero for every entry of the device list, clipped to plane_stride.  Launched before the emit kernel: zero
+ * planes stay zero through mid/side and the left shift.  max_samples: the largest num_samples of the list (sizes the
+ * grid).  INVALID_ARGUMENT before any launch for a NULL pointer, num_channels 0 or > 8. */
+typedef struct sla_hip_dec_conceal {
+  uint32_t smp_off;
+  uint32_t num_samples;
+} sla_hip_dec_conceal;            /* 8 bytes */
+int sla_hip_launch_dec_conceal(int32_t* d_planes, uint64_t plane_stride, uint32_t num_channels,
+                               const sla_hip_dec_conceal* d_list, uint32_t count, uint32_t max_samples, sla_hip_stream_t stream);
+
 /* The byte-granular gather into an image: entry k copies `bytes` bytes from src (device, any alignment) to
  * d_image + dst_off (dst_off a multiple of 4) and writes zeros from there to the next 4-byte boundary.  Nothing outside
  * each entry's padded range is written; an entry whose dst_off is no multiple of 4 or whose padded range does not lie

@@ -176,6 +176,28 @@ class WavEmit(C.Structure):
                 ("shift", C.c_uint32), ("header_bytes", C.c_uint32), ("header", C.c_uint8 * 48)]
 
 
+class SalvageReport(C.Structure):
+    """sla_hip_salvage_report (include/sla_hip.h): what sla_hip_salvage_resident did"""
+    _fields_ = [(n, C.c_uint32) for n in ("mode", "blocks_decoded", "blocks_concealed", "samples_lost", "num_ranges", "prefix_blocks",
+                                           "suffix_blocks", "suffix_byte", "suffix_sample", "nodes", "sound_nodes", "reserved")]
+
+
+class SalvageRange(C.Structure):
+    """sla_hip_salvage_range (include/sla_hip.h): one silent range of a salvaged stream"""
+    _fields_ = [("start", C.c_uint32), ("length", C.c_uint32), ("reason", C.c_uint32)]
+
+
+class SalvageScan(C.Structure):
+    """sla_hip_salvage_scan (include/sla_hip.h): what sla_hip_launch_dec_salvage_scan returns"""
+    _fields_ = [(n, C.c_uint32) for n in ("prefix_blocks", "prefix_samples", "prefix_end", "suffix_byte", "suffix_samples",
+                                           "suffix_blocks", "nodes", "sound_nodes", "overflow")] + [("reserved", C.c_uint32 * 3)]
+
+
+class DecConceal(C.Structure):
+    """sla_hip_dec_conceal (include/sla_hip.h): one entry of sla_hip_launch_dec_conceal"""
+    _fields_ = [("smp_off", C.c_uint32), ("num_samples", C.c_uint32)]
+
+
 class LaunchExtra(C.Structure):
     """sla_hip_launch_extra (include/sla_hip.h): optional extras of one launch of an `_x` launcher; all zero = none"""
     _fields_ = [("d_span", C.c_void_p), ("d_group_count", C.c_void_p), ("clear_ptr", C.c_void_p * 3),
@@ -185,6 +207,9 @@ class LaunchExtra(C.Structure):
 # sample formats of sla_hip_decode_batch_device / sla_hip_encode_batch_device, flag of the former
 PCM_S32_LEFT, PCM_S32, PCM_S16, PCM_F32 = range(4)
 DEC_ZERO_FILL = 1
+# sla_hip_salvage_range.reason
+SALVAGE_CRC, SALVAGE_UNDECODABLE, SALVAGE_GAP = 1, 2, 3
+SALVAGE_REASON = {SALVAGE_CRC: "crc", SALVAGE_UNDECODABLE: "undecodable", SALVAGE_GAP: "gap"}
 
 
 class SlaError(RuntimeError):
@@ -346,6 +371,16 @@ def lib():
                                                             C.c_void_p]
             L.sla_hip_decode_wav_batch.argtypes = [C.c_void_p, C.POINTER(WavItem), C.c_uint32]
             L.sla_hip_decode_wav_batch_resident.argtypes = [C.c_void_p, C.POINTER(WavItem), C.c_uint32, C.c_void_p]
+        if hasattr(L, "sla_hip_salvage_resident"):           # (SLA_HIP_LIB may name an older build in an A/B run)
+            L.sla_hip_salvage_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                   C.c_uint32, C.POINTER(SalvageReport), C.POINTER(SalvageRange), C.c_uint32,
+                                                   C.c_void_p]
+            L.sla_hip_launch_dec_salvage_scan.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.sla_hip_dec_salvage_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+            L.sla_hip_dec_salvage_scratch_bytes.restype = C.c_uint64
+            L.sla_hip_launch_salvage_crc.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.sla_hip_launch_dec_conceal.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         _lib = L
     return _lib
 
@@ -425,6 +460,9 @@ EXPORTED_SYMBOLS = [
     "sla_hip_wav_parse", "sla_hip_wav_header", "sla_hip_launch_wav_ingest_batch", "sla_hip_launch_wav_emit_batch",
     "sla_hip_encode_wav_batch", "sla_hip_encode_wav_batch_resident", "sla_hip_decode_wav_batch",
     "sla_hip_decode_wav_batch_resident",
+    # one resident stream decoded through damage (include/sla_hip.h)
+    "sla_hip_salvage_resident", "sla_hip_launch_dec_salvage_scan", "sla_hip_dec_salvage_scratch_bytes",
+    "sla_hip_launch_salvage_crc", "sla_hip_launch_dec_conceal",
 ]
 
 
@@ -1302,6 +1340,63 @@ class Decoder:
                 else:
                     out[b, :, nchs[b]:].zero_()
         return out, [n for _, n in got], [rc for rc, _ in got]
+
+    def salvage_resident_tensor(self, src, dtype=None, layout="planar", right_justify=False, range_capacity=64):
+        """one .sla stream whose bytes are in device memory decoded THROUGH damage (sla_hip_salvage_resident): all N samples
+        of its header, each decoded or zero.  src as one source of decode_resident_into; dtype, layout and right_justify as
+        for decode_resident_tensor.  Returns (tensor [C][N] or [N][C], report, ranges): report is a dict of the fields of
+        sla_hip_salvage_report plus "result" (0 when nothing was concealed or lost, 11 = DETECT_DATA_CORRUPTION when
+        something was), ranges the list of (start, length, reason) of the silent ranges, reason "crc", "undecodable" or
+        "gap".  Raises SlaError for every other code: nothing was delivered then."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype == torch.float32:
+            fmt = PCM_F32
+        elif dtype == torch.int16:
+            fmt = PCM_S16
+        elif dtype == torch.int32:
+            fmt = PCM_S32 if right_justify else PCM_S32_LEFT
+        else:
+            raise ValueError("dtype must be float32, int16 or int32, not %s" % (dtype,))
+        if layout not in ("planar", "interleaved"):
+            raise ValueError("layout must be 'planar' or 'interleaved', not %r" % (layout,))
+        (ptr, size), = self._resident_sources([src])
+        (rc, h), = self.resident_headers([(ptr, size)])
+        if rc != 0:
+            raise SlaError(rc, "sla_hip_salvage_resident (header)")
+        nch, n = h.wave_format.num_channels, h.num_samples
+        dev = torch.device("cuda", self.device_index)
+        out = torch.empty((nch, n) if layout == "planar" else (n, nch), dtype=dtype, device=dev)
+        view = out if layout == "planar" else out.t()
+        # nothing can be written to an empty tensor: a one-element stand-in keeps the pointer valid, the result is real
+        base = out if out.numel() else torch.empty(1, dtype=dtype, device=dev)
+        report, ranges = SalvageReport(), (SalvageRange * max(range_capacity, 1))()
+        while True:
+            st = torch.cuda.current_stream(self.device_index)
+            self._index_walk = None          # last_walk() speaks of this call from here on
+            rc = self._lib.sla_hip_salvage_resident(self._h, C.c_void_p(ptr or None), size, C.c_void_p(base.data_ptr()),
+                                                    view.stride(0), max(view.stride(1), 1), n, fmt, C.byref(report), ranges,
+                                                    len(ranges), C.c_void_p(st.cuda_stream))
+            if rc not in (0, 11):
+                raise SlaError(rc, "sla_hip_salvage_resident")
+            if report.num_ranges <= len(ranges):
+                break
+            ranges = (SalvageRange * report.num_ranges)()     # more silent ranges than room: once more with room for all
+        rep = {name: int(getattr(report, name)) for name, _ in SalvageReport._fields_ if name != "reserved"}
+        rep["result"] = rc
+        return out, rep, [(int(r.start), int(r.length), SALVAGE_REASON.get(int(r.reason), int(r.reason)))
+                          for r in ranges[:report.num_ranges]]
+
+    def salvage(self, data, dtype=None, layout="planar", right_justify=False):
+        """salvage_resident_tensor for a stream in host memory: the bytes are uploaded, the samples come back as a numpy
+        array; -> (array, report, ranges)"""
+        import torch
+        buf = np.frombuffer(bytes(data), np.uint8)
+        if len(buf) == 0:
+            raise SlaError(9, "sla_hip_salvage_resident (header)")
+        src = torch.from_numpy(buf.copy()).to(torch.device("cuda", self.device_index))
+        out, rep, ranges = self.salvage_resident_tensor(src, dtype, layout, right_justify)
+        return out.cpu().numpy(), rep, ranges
 
     def decode_windows_into(self, srcs, starts, outs, sample_format, zero_fill=True, hints=None, stream=None, _headers=None):
         """sample windows of .sla streams whose bytes are in device memory -> caller-owned device tensors

@@ -21,6 +21,7 @@
 //   k_dec_walk           src/SLADecoder.c:696-722 (the block chain of whole files whose bytes are in device memory)
 //   k_dec_walk_window    the same chain, for the blocks a window of samples overlaps (no counterpart in the reference)
 //   k_wide_*             kernels/walk_wide.inc: the block table of one long file, found and ranked by the whole device
+//   k_salvage_* / k_dec_conceal   kernels/salvage.inc: the decodable blocks of a damaged stream; silence in the planes
 //   k_dec_gather         the staging copies of a batch pass, for files that are in device memory already
 //   k_verify_blocks      (kernels/verify.inc) k_dec_finish fused with a compare against source planes, per block table
 #include <hip/hip_runtime.h>
@@ -1013,6 +1014,7 @@ void k_dec_gather(const sla_hip_dec_gather* __restrict__ table, uint32_t num_ent
 }
 
 #include "kernels/walk_wide.inc"
+#include "kernels/salvage.inc"
 #include "kernels/verify.inc"
 
 }  // namespace
@@ -1217,6 +1219,27 @@ extern "C" uint32_t sla_hip_dec_wide_rounds(uint32_t data_size, uint32_t node_ca
   return r;
 }
 
+// the wide walk's scratch, carved as SLA_HIP_DEC_WIDE_SCRATCH_BYTES counts it (every part a multiple of 16 bytes); returns
+// the byte behind it
+static uint8_t* wide_carve(void* d_scratch, uint32_t data_size, uint32_t node_capacity, wide_arrays& A)
+{
+  const uint64_t max_tiles = SLA_HIP_DEC_WIDE_TILES(data_size), capa = ((uint64_t)node_capacity + 3u) & ~(uint64_t)3;
+  uint8_t* s = (uint8_t*)d_scratch;
+  A.info = (sla_hip_dec_wide_info*)s;                      s += 64;
+  A.mask = (uint32_t*)s;                                   s += max_tiles * WIDE_TILE * 4u;
+  A.word_first = (uint32_t*)s;                             s += max_tiles * WIDE_TILE * 4u;
+  A.tile = (uint32_t*)s;                                   s += (max_tiles * 4u + 15u) & ~(uint64_t)15;
+  for (int k = 0; k < 2; k++) { A.sum[k] = (uint64_t*)s;   s += capa * 8u; }
+  for (int k = 0; k < 2; k++) { A.spos[k] = (uint64_t*)s;  s += capa * 8u; }
+  for (int k = 0; k < 2; k++) { A.jump[k] = (uint32_t*)s;  s += capa * 4u; }
+  for (int k = 0; k < 2; k++) { A.rank[k] = (uint32_t*)s;  s += capa * 4u; }
+  A.pos = (uint32_t*)s;                                    s += capa * 4u;
+  A.bsize = (uint32_t*)s;                                  s += capa * 4u;
+  A.ncrc = (uint32_t*)s;                                   s += capa * 4u;
+  A.succ = (uint32_t*)s;                                   s += capa * 4u;
+  return s;
+}
+
 extern "C" int sla_hip_launch_dec_walk_wide(const sla_hip_dec_walk_file* file, uint32_t max_block_samples, uint32_t crc_check,
                                             sla_hip_dec_walk_result* d_result, sla_hip_dec_block* d_blocks,
                                             uint64_t* d_block_end, uint32_t* d_crc_field, uint32_t node_capacity,
@@ -1236,24 +1259,10 @@ extern "C" int sla_hip_launch_dec_walk_wide(const sla_hip_dec_walk_file* file, u
     return hip_rc(hipGetLastError());
   }
   if (fi.src == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
-  // the scratch, carved as SLA_HIP_DEC_WIDE_SCRATCH_BYTES counts it (every part a multiple of 16 bytes)
   const uint32_t head = (uint32_t)((uintptr_t)fi.src & 15u);
   const uint32_t words = (uint32_t)(((uint64_t)head + fi.data_size + 31u) >> 5), tiles = (words + WIDE_TILE - 1u) / WIDE_TILE;
-  const uint64_t max_tiles = SLA_HIP_DEC_WIDE_TILES(fi.data_size), capa = ((uint64_t)node_capacity + 3u) & ~(uint64_t)3;
-  uint8_t* s = (uint8_t*)d_scratch;
   wide_arrays A;
-  A.info = (sla_hip_dec_wide_info*)s;                      s += 64;
-  A.mask = (uint32_t*)s;                                   s += max_tiles * WIDE_TILE * 4u;
-  A.word_first = (uint32_t*)s;                             s += max_tiles * WIDE_TILE * 4u;
-  A.tile = (uint32_t*)s;                                   s += (max_tiles * 4u + 15u) & ~(uint64_t)15;
-  for (int k = 0; k < 2; k++) { A.sum[k] = (uint64_t*)s;   s += capa * 8u; }
-  for (int k = 0; k < 2; k++) { A.spos[k] = (uint64_t*)s;  s += capa * 8u; }
-  for (int k = 0; k < 2; k++) { A.jump[k] = (uint32_t*)s;  s += capa * 4u; }
-  for (int k = 0; k < 2; k++) { A.rank[k] = (uint32_t*)s;  s += capa * 4u; }
-  A.pos = (uint32_t*)s;                                    s += capa * 4u;
-  A.bsize = (uint32_t*)s;                                  s += capa * 4u;
-  A.ncrc = (uint32_t*)s;                                   s += capa * 4u;
-  A.succ = (uint32_t*)s;
+  (void)wide_carve(d_scratch, fi.data_size, node_capacity, A);
   const uint32_t rounds = sla_hip_dec_wide_rounds(fi.data_size, node_capacity);
   const uint32_t gn = (node_capacity > 256u * 1024u) ? 1024u : (node_capacity + 255u) / 256u;
   const uint32_t most = (rows > node_capacity) ? rows : node_capacity;
@@ -1268,6 +1277,91 @@ extern "C" int sla_hip_launch_dec_walk_wide(const sla_hip_dec_walk_file* file, u
   hipLaunchKernelGGL(k_wide_cut, dim3(gn), dim3(256), 0, st, fi, max_block_samples, node_capacity, A, rounds & 1u);
   hipLaunchKernelGGL(k_wide_rows, dim3(gr), dim3(256), 0, st, fi, crc_check, node_capacity, A, rounds & 1u, d_result, d_blocks,
                      d_block_end, d_crc_field);
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" uint64_t sla_hip_dec_salvage_scratch_bytes(uint32_t data_size, uint32_t node_capacity)
+{
+  return SLA_HIP_DEC_SALVAGE_SCRATCH_BYTES(data_size, node_capacity);
+}
+
+extern "C" int sla_hip_launch_dec_salvage_scan(const sla_hip_dec_walk_file* file, uint32_t num_channels, uint32_t max_block_samples,
+                                               sla_hip_salvage_scan* d_result, sla_hip_dec_block* d_blocks, uint64_t* d_block_end,
+                                               uint32_t* d_crc_field, uint32_t node_capacity, void* d_scratch, sla_hip_stream_t stream)
+{
+  if (file == nullptr || d_result == nullptr || d_scratch == nullptr || node_capacity == 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_channels == 0 || num_channels > 8) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if ((d_blocks != nullptr || d_block_end != nullptr || d_crc_field != nullptr)
+      && (d_blocks == nullptr || d_block_end == nullptr || d_crc_field == nullptr)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (((uintptr_t)d_scratch & 15u) != 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  const sla_hip_dec_walk_file fi = *file;
+  const hipStream_t st = (hipStream_t)stream;
+  const uint32_t rows = (d_blocks != nullptr) ? fi.max_rows : 0u;
+  if (fi.data_size < SLA_HEADER_SIZE + DEC_WALK_MIN_HEADER) {
+    const uint32_t g = (rows > 256u * 1024u) ? 1024u : (rows + 255u) / 256u;
+    hipLaunchKernelGGL(k_salvage_none, dim3(g ? g : 1u), dim3(256), 0, st, fi, (sla_hip_dec_wide_info*)d_scratch, d_result, d_blocks,
+                       d_block_end, d_crc_field);
+    return hip_rc(hipGetLastError());
+  }
+  if (fi.src == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  const uint32_t head = (uint32_t)((uintptr_t)fi.src & 15u);
+  const uint32_t words = (uint32_t)(((uint64_t)head + fi.data_size + 31u) >> 5), tiles = (words + WIDE_TILE - 1u) / WIDE_TILE;
+  const uint64_t capa = ((uint64_t)node_capacity + 3u) & ~(uint64_t)3;
+  wide_arrays A;
+  salvage_arrays B;
+  // the salvage arrays behind the wide walk's, as SLA_HIP_DEC_SALVAGE_SCRATCH_BYTES counts them
+  uint8_t* s = wide_carve(d_scratch, fi.data_size, node_capacity, A);
+  B.info = (salvage_info*)s;                               s += 64;
+  B.csum = (uint64_t*)s;                                   s += capa * 8u;
+  for (int k = 0; k < 2; k++) { B.last[k] = (uint32_t*)s;  s += capa * 4u; }
+  B.sound = (uint32_t*)s;                                  s += capa * 4u;
+  B.ssucc = (uint32_t*)s;                                  s += capa * 4u;
+  B.cend = (uint32_t*)s;
+  const uint32_t rounds = sla_hip_dec_wide_rounds(fi.data_size, node_capacity), fin = rounds & 1u;
+  const uint32_t gn = (node_capacity > 256u * 1024u) ? 1024u : (node_capacity + 255u) / 256u;
+  const uint32_t gw = (node_capacity > 4u * 4096u) ? 4096u : (node_capacity + 3u) / 4u;      // one wave per node, four per workgroup
+  const uint32_t most = (rows > node_capacity) ? rows : node_capacity;
+  const uint32_t gr = (most > 256u * 1024u) ? 1024u : (most + 255u) / 256u;
+  hipLaunchKernelGGL(k_salvage_init, dim3(1), dim3(64), 0, st, B.info);
+  hipLaunchKernelGGL(k_wide_find, dim3(tiles), dim3(WIDE_TILE), 0, st, fi.src, fi.data_size, words, A.mask, A.tile);
+  hipLaunchKernelGGL(k_wide_scan, dim3(1), dim3(1024), 0, st, A.tile, tiles, A.info);
+  hipLaunchKernelGGL(k_wide_index, dim3(tiles), dim3(WIDE_TILE), 0, st, A.mask, words, A.tile, A.word_first);
+  hipLaunchKernelGGL(k_wide_nodes, dim3(tiles), dim3(WIDE_TILE), 0, st, fi.src, fi.data_size, words, node_capacity, A);
+  hipLaunchKernelGGL(k_salvage_sound, dim3(gw), dim3(256), 0, st, fi.src, num_channels, max_block_samples, node_capacity, A, B);
+  for (uint32_t pass = 0; pass < 2; pass++) {
+    hipLaunchKernelGGL(k_salvage_link, dim3(gn), dim3(256), 0, st, node_capacity, A, B, pass);
+    for (uint32_t r = 0; r < rounds; r++) {
+      hipLaunchKernelGGL(k_salvage_round, dim3(gn), dim3(256), 0, st, node_capacity, 1u << r, A, B, r & 1u);
+    }
+    hipLaunchKernelGGL(k_salvage_cut, dim3(gn), dim3(256), 0, st, fi.total, node_capacity, A, B, fin, pass);
+    if (pass == 0) {
+      hipLaunchKernelGGL(k_salvage_prefix, dim3(gn), dim3(256), 0, st, fi, node_capacity, A, B, fin, d_blocks, d_block_end, d_crc_field);
+      hipLaunchKernelGGL(k_salvage_pick, dim3(gn), dim3(256), 0, st, fi, node_capacity, A, B);
+    }
+  }
+  hipLaunchKernelGGL(k_salvage_rows, dim3(gr), dim3(256), 0, st, fi, node_capacity, A, B, fin, d_result, d_blocks, d_block_end, d_crc_field);
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_salvage_crc(const uint8_t* d_image, sla_hip_dec_block* d_blocks, const uint32_t* d_crc_field,
+                                          uint32_t num_blocks, uint32_t* d_bad, sla_hip_stream_t stream)
+{
+  if (d_image == nullptr || d_blocks == nullptr || d_crc_field == nullptr || d_bad == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_blocks == 0) { return 0; }
+  hipLaunchKernelGGL(k_salvage_crc, dim3((num_blocks + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_image, d_blocks, d_crc_field,
+                     num_blocks, d_bad);
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_dec_conceal(int32_t* d_planes, uint64_t plane_stride, uint32_t num_channels,
+                                          const sla_hip_dec_conceal* d_list, uint32_t count, uint32_t max_samples, sla_hip_stream_t stream)
+{
+  if (d_planes == nullptr || d_list == nullptr || num_channels == 0 || num_channels > 8) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (count == 0 || max_samples == 0) { return 0; }
+  uint32_t gx = (max_samples + 255u) / 256u;
+  if (gx > 1024u) { gx = 1024u; }
+  hipLaunchKernelGGL(k_dec_conceal, dim3(gx, (count < 65535u) ? count : 65535u), dim3(256), 0, (hipStream_t)stream, d_planes, plane_stride,
+                     num_channels, d_list, count);
   return hip_rc(hipGetLastError());
 }
 

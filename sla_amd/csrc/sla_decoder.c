@@ -1338,6 +1338,190 @@ out:
   return rc;
 }
 
+/* ---- sla_hip_salvage_resident (include/sla_hip.h): one resident stream decoded through damage ----
+ * The stages are those of a resident pass of one file -- res_count_walk, res_stage_pass, pass_kernels, emit_run -- with
+ * three additions: the mode decision behind the count, the salvage scan in place of the walk when the chain is broken,
+ * and the silence (k_salvage_crc before the decode kernels, k_dec_conceal before the emit). */
+
+/* one silent region: into the conceal list, the report and, while there is room, the caller's ranges */
+static void salvage_note(sla_hip_salvage_report* rep, sla_hip_salvage_range* ranges, uint32_t range_capacity, sla_hip_dec_conceal* cl,
+                         uint32_t* ncl, uint32_t* max_len, uint32_t start, uint32_t length, uint32_t reason)
+{
+  if (length == 0) { return; }
+  cl[*ncl].smp_off = start; cl[*ncl].num_samples = length; (*ncl)++;
+  if (length > *max_len) { *max_len = length; }
+  if (rep->num_ranges < range_capacity) {
+    ranges[rep->num_ranges].start = start; ranges[rep->num_ranges].length = length; ranges[rep->num_ranges].reason = reason;
+  }
+  rep->num_ranges++;
+  rep->samples_lost += length;
+}
+
+/* the salvage scan of one stream queued on the handle's stream, its result on the way home to `home` (page-locked) */
+static int salvage_scan_launch(struct SLADecoder* d, const sla_hip_dec_walk_file* wf, uint32_t C, uint32_t cap, uint32_t slot,
+                               sla_hip_dec_block* db, uint64_t* dend, uint32_t* dcrc, sla_hip_salvage_scan* home)
+{
+  sla_hip_salvage_scan* dres = (sla_hip_salvage_scan*)d->d_wres.ptr + slot;
+  BRC(sla_hip_launch_dec_salvage_scan(wf, C, d->cfg.max_num_block_samples, dres, db, dend, dcrc, cap, d->d_wide.ptr, d->stream));
+  BCHK(hipMemcpyAsync(home, dres, sizeof(*home), hipMemcpyDeviceToHost, d->stream));
+  return 0;
+}
+
+int sla_hip_salvage_resident(struct SLADecoder* d, const uint8_t* d_data, uint32_t data_size, void* dst, uint64_t channel_stride,
+                             uint64_t sample_stride, uint32_t capacity, uint32_t sample_format, sla_hip_salvage_report* report,
+                             sla_hip_salvage_range* ranges, uint32_t range_capacity, sla_hip_stream_t stream)
+{
+  sla_hip_decode_device_item di;
+  sla_hip_decode_item bi;
+  sla_hip_salvage_scan* scan;           /* [0] the count-mode scan, [1] the write-mode scan (page-locked) */
+  sla_hip_dec_walk_file wf;
+  sla_hip_dec_conceal* cl;
+  sla_hip_dec_emit e;
+  dev_out_t dev;
+  bfile_t file;
+  dec_format_t f;
+  SLAApiResult ret;
+  const uint8_t* src = d_data;
+  const uint8_t* hdr;
+  uint32_t* hbad;
+  uint8_t ok = 1;
+  uint32_t C, N, nb = 0, nblocks = 0, mode, k, ncl = 0, max_len = 0, max_lim = 0, P = 0, scan_cap = 0;
+  uint64_t span, img_bytes;
+  int verdict;
+  float kernel_ms = 0.0f;
+  double t0 = now_ms(), t_up = 0.0, t_walk = 0.0, t_emit;
+
+  if (d == NULL || d_data == NULL || dst == NULL || report == NULL || sample_format > SLA_HIP_PCM_F32
+      || (ranges == NULL && range_capacity > 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  memset(report, 0, sizeof(*report));
+  memset(d->timing, 0, sizeof(d->timing));
+  memset(d->walk_stats, 0, sizeof(d->walk_stats));
+  /* the source, on the host, before anything is read; nothing is read or written before the caller's stream is here */
+  if (!src_region_ok(d_data, data_size)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (order_behind(d, stream) != 0 || res_fetch_headers(d, &src, &data_size, &ok, 1) != 0) { return SLA_APIRESULT_NG; }
+  hdr = (const uint8_t*)d->h_hdr.ptr;
+  memset(&di, 0, sizeof(di));
+  di.data = d_data; di.dst = dst; di.channel_stride = channel_stride; di.sample_stride = sample_stride;
+  di.data_size = data_size; di.capacity = capacity;
+  /* the destination, with the header's channel count, before anything is written */
+  if (!dst_region_ok(&di, header_channels(hdr, data_size), (sample_format == SLA_HIP_PCM_S16) ? 2u : 4u)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if ((ret = file_format(d, hdr, data_size, &f)) != SLA_APIRESULT_OK) { return ret; }
+  if ((verdict = format_verdict(&f)) >= 0) { return verdict; }
+  if (!lms_order_ok(f.lms)) { return SLA_APIRESULT_FAILED_TO_SYNTHESIZE; }
+  C = f.C; N = f.total;
+  if (capacity < N) { return SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE; }
+
+  /* ---- the chain, counted with capacity N: intact when it accounts for exactly N samples */
+  memset(&bi, 0, sizeof(bi)); memset(&dev, 0, sizeof(dev)); memset(&file, 0, sizeof(file));
+  bi.data = hdr; bi.data_size = data_size; bi.buffer_num_samples = N;
+  dev.items = &di; dev.format = sample_format; dev.resident = 1;
+  file.f = f;
+  if (res_count_walk(d, &bi, &dev, &file, 1, &nblocks) != 0) { return SLA_APIRESULT_NG; }
+  mode = (file.walk_err == SLA_APIRESULT_OK && file.extent == N) ? 1u : 2u;
+  report->mode = mode;
+  if (hbuf_reserve(&d->h_wide, (sizeof(sla_hip_dec_wide_info) + sizeof(sla_hip_dec_walk_result)) * RES_WIDE_MAX + 2 * sizeof(*scan)) != 0) {
+    return SLA_APIRESULT_NG;
+  }
+  scan = (sla_hip_salvage_scan*)((uint8_t*)d->h_wide.ptr + (sizeof(sla_hip_dec_wide_info) + sizeof(sla_hip_dec_walk_result)) * RES_WIDE_MAX);
+  memset(&wf, 0, sizeof(wf));
+  wf.src = d_data; wf.data_size = data_size; wf.total = N; wf.capacity = N;
+  if (mode == 1u) {
+    nb = file.nb;
+  } else {
+    /* the scan in count mode; nodes beyond the handle's capacity: once more with the exact count */
+    uint32_t cap = res_wide_capacity(d, data_size), attempt;
+    for (attempt = 0; ; attempt++) {
+      if (dbuf_reserve(&d->d_wide, (size_t)SLA_HIP_DEC_SALVAGE_SCRATCH_BYTES(data_size, cap)) != 0
+          || dbuf_reserve(&d->d_wres, 2 * sizeof(*scan)) != 0) { return SLA_APIRESULT_NG; }
+      if (salvage_scan_launch(d, &wf, C, cap, 0, NULL, NULL, NULL, &scan[0]) != 0
+          || hipStreamSynchronize(d->stream) != hipSuccess) { return SLA_APIRESULT_NG; }
+      d->walk_stats[0]++; d->walk_stats[2] += scan[0].nodes; d->walk_stats[3] += 2 * sla_hip_dec_wide_rounds(data_size, cap);
+      if (!scan[0].overflow) { break; }
+      d->walk_stats[1]++;
+      if (attempt == 1 || scan[0].nodes == 0) { return SLA_APIRESULT_NG; }
+      cap = scan[0].nodes;
+    }
+    P = scan[0].prefix_blocks;
+    nb = P + scan[0].suffix_blocks;
+    report->prefix_blocks = P; report->suffix_blocks = scan[0].suffix_blocks; report->suffix_byte = scan[0].suffix_byte;
+    report->suffix_sample = (scan[0].suffix_byte != 0) ? N - scan[0].suffix_samples : 0;
+    report->nodes = scan[0].nodes; report->sound_nodes = scan[0].sound_nodes;
+    wf.max_rows = nb;
+    scan_cap = cap;
+  }
+  t_walk = now_ms() - t0;
+
+  /* ---- the pass: one file, image at 0, planes at 0 */
+  span = ((uint64_t)N + DEC_BATCH_ALIGN - 1) / DEC_BATCH_ALIGN * DEC_BATCH_ALIGN;
+  img_bytes = ((uint64_t)data_size + 3) & ~(uint64_t)3;
+  if (dbuf_reserve(&d->d_image, img_bytes + 16) != 0
+      || hbuf_reserve(&d->h_ptab, sizeof(uint32_t) * (size_t)nb + sizeof(*cl) * ((size_t)nb + 1)) != 0
+      || dbuf_reserve(&d->d_blocks, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb + 16) != 0
+      || dbuf_reserve(&d->d_info, sizeof(sla_hip_dec_info) * (size_t)nb + 16) != 0
+      || dbuf_reserve(&d->d_chan, sizeof(sla_hip_dec_chan) * (size_t)nb * C + 16) != 0
+      || dbuf_reserve(&d->d_kint, sizeof(int32_t) * (size_t)nb * C * (f.order + 1) + 16) != 0
+      || dbuf_reserve(&d->d_planes, sizeof(int32_t) * (size_t)span * C) != 0
+      || dbuf_reserve(&d->d_crcf, sizeof(uint32_t) * 2 * (size_t)nb + 16) != 0
+      || host_tables_reserve(d, nb) != 0 || res_events(d) != 0) { return SLA_APIRESULT_NG; }
+  hbad = (uint32_t*)d->h_ptab.ptr;
+  cl = (sla_hip_dec_conceal*)(hbad + nb);
+  if (nb > 0 && mode == 1u) {
+    sla_hip_dec_block* db = (sla_hip_dec_block*)d->d_blocks.ptr;
+    uint32_t* dbad = (uint32_t*)d->d_crcf.ptr + nb;
+    file.first = 0;
+    if (res_stage_pass(d, &bi, &dev, &file, 1, nb, img_bytes) != 0
+        || sla_hip_launch_salvage_crc((const uint8_t*)d->d_image.ptr, db, (const uint32_t*)d->d_crcf.ptr, nb, dbad, d->stream) != 0
+        || hipMemcpyAsync(hbad, dbad, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, d->stream) != hipSuccess
+        || pass_kernels(d, &f, nb, 0, img_bytes, span, &kernel_ms) != 0
+        || res_finish_pass(d, &file, 1, &t_up, &t_walk) != 0) { return SLA_APIRESULT_NG; }
+  } else if (nb > 0) {
+    sla_hip_dec_block* db = (sla_hip_dec_block*)d->d_blocks.ptr;
+    sla_hip_dec_gather* gt;
+    if (hbuf_reserve(&d->h_src, sizeof(*gt)) != 0 || dbuf_reserve(&d->d_src, sizeof(*gt)) != 0) { return SLA_APIRESULT_NG; }
+    gt = (sla_hip_dec_gather*)d->h_src.ptr;
+    gt->src = d_data; gt->dst_off = 0; gt->bytes = data_size; gt->reserved = 0;
+    if (hipMemcpyAsync(d->d_src.ptr, gt, sizeof(*gt), hipMemcpyHostToDevice, d->stream) != hipSuccess
+        || sla_hip_launch_dec_gather((const sla_hip_dec_gather*)d->d_src.ptr, 1, data_size, (uint8_t*)d->d_image.ptr, img_bytes, d->stream) != 0
+        || salvage_scan_launch(d, &wf, C, scan_cap, 1, db, (uint64_t*)(db + nb), (uint32_t*)d->d_crcf.ptr, &scan[1]) != 0
+        || hipMemcpyAsync(d->h_blocks, db, sizeof(*db) * (size_t)nb, hipMemcpyDeviceToHost, d->stream) != hipSuccess
+        || hipMemsetAsync(d->d_info.ptr, 0, sizeof(sla_hip_dec_info) * nb, d->stream) != hipSuccess
+        || pass_kernels(d, &f, nb, 0, img_bytes, span, &kernel_ms) != 0) { return SLA_APIRESULT_NG; }
+    d->walk_stats[3] += 2 * sla_hip_dec_wide_rounds(data_size, scan_cap);
+    /* a stream that changed between the two scans fails the call, as a walk that differs from its count does */
+    if (memcmp(&scan[0], &scan[1], sizeof(scan[0])) != 0) { return SLA_APIRESULT_NG; }
+    memset(hbad, 0, sizeof(uint32_t) * nb);
+  }
+
+  /* ---- every row examined with the whole-file decode's criteria; what fails becomes silence */
+  for (k = 0; k < nb; k++) {
+    const sla_hip_dec_block* b = &d->h_blocks[k];
+    const sla_hip_dec_info* in = &d->h_info[k];
+    uint32_t reason = 0;
+    if (mode == 2u && k == P) { salvage_note(report, ranges, range_capacity, cl, &ncl, &max_len, scan[0].prefix_samples, N - scan[0].suffix_samples - scan[0].prefix_samples, SLA_HIP_SALVAGE_GAP); }
+    if (hbad[k]) { reason = SLA_HIP_SALVAGE_CRC; }
+    else if (in->type > 2 || in->overrun || in->used_bytes != b->byte_len) { reason = SLA_HIP_SALVAGE_UNDECODABLE; }
+    if (reason == 0) { report->blocks_decoded++; continue; }
+    report->blocks_concealed++;
+    salvage_note(report, ranges, range_capacity, cl, &ncl, &max_len, b->smp_off, b->num_samples, reason);
+  }
+  if (mode == 2u && P == nb) { salvage_note(report, ranges, range_capacity, cl, &ncl, &max_len, scan[0].prefix_samples, N - scan[0].suffix_samples - scan[0].prefix_samples, SLA_HIP_SALVAGE_GAP); }
+
+  /* ---- silence into the planes, then the emit of all N samples */
+  t_emit = now_ms();
+  if (ncl > 0) {
+    if (dbuf_reserve(&d->d_src, sizeof(*cl) * ncl) != 0
+        || hipMemcpyAsync(d->d_src.ptr, cl, sizeof(*cl) * ncl, hipMemcpyHostToDevice, d->stream) != hipSuccess
+        || sla_hip_launch_dec_conceal((int32_t*)d->d_planes.ptr, span, C, (const sla_hip_dec_conceal*)d->d_src.ptr, ncl, max_len, d->stream) != 0) {
+      return SLA_APIRESULT_NG;
+    }
+  }
+  if (emit_entry(&e, &di, 0, 0, N, C, f.ms, 32u - f.bps + f.lshift, f.bps, &max_lim) != 0
+      && emit_run(d, (const int32_t*)d->d_planes.ptr, span, &e, 1, max_lim, sample_format, &kernel_ms) != 0) { return SLA_APIRESULT_NG; }
+  d->timing[0] = (float)t_up; d->timing[1] = (float)t_walk; d->timing[2] = kernel_ms; d->timing[3] = (float)(now_ms() - t_emit);
+  d->timing[4] = (float)(now_ms() - t0); d->timing[5] = 1.0f;
+  return (report->blocks_concealed != 0 || report->samples_lost != 0) ? SLA_APIRESULT_DETECT_DATA_CORRUPTION : SLA_APIRESULT_OK;
+}
+
 /* sla_hip_decode_wav_batch / sla_hip_decode_wav_batch_resident (include/sla_hip.h): the items become device items whose
  * capacity is the header's num_samples and go through batch_run with the WAV emit as the last leg (wav_out_t). */
 static int decode_wav_impl(struct SLADecoder* d, sla_hip_wav_item* items, uint32_t num_items, int resident, sla_hip_stream_t stream)
