@@ -84,6 +84,10 @@ static int hbuf_reserve(hbuf_t* b, size_t bytes)
 }
 static void hbuf_free(hbuf_t* b) { if (b->ptr != NULL) { (void)hipHostFree(b->ptr); } b->ptr = NULL; b->cap = 0; }
 
+/* the time between two recorded events that the stream has passed (0 when the runtime cannot tell), added to *acc */
+static float ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0.0f; return (hipEventElapsedTime(&ms, a, b) == hipSuccess) ? ms : 0.0f; }
+#define ev_add_ms(acc, a, b) (*(acc) += ev_ms(a, b))
+
 static uint32_t rd_be16(const uint8_t* p) { return ((uint32_t)p[0] << 8) | p[1]; }
 static uint32_t rd_be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 
@@ -269,9 +273,7 @@ static int examine_blocks(const struct SLADecoder* d, const uint32_t* crc_field,
 
 /* The kernel launch parameters of a file, from its header; SLA_APIRESULT_OK when the kernels can run on it.  Sets the
  * handle's wave format and encode parameter as it goes, as the reference's DecodeWhole does. */
-typedef struct {
-  uint32_t C, total, bps, lshift, order, ntaps, lms, ms;
-} dec_format_t;
+typedef slai_dec_format dec_format_t;
 
 static SLAApiResult file_format(struct SLADecoder* d, const uint8_t* data, uint32_t data_size, dec_format_t* f)
 {
@@ -371,7 +373,6 @@ static SLAApiResult decode_run(struct SLADecoder* d, const uint8_t* data, uint32
 
     /* ---- all blocks of the batch through the kernels */
     if (nb > 0) {
-      float ms_batch = 0.0f;
       if (dbuf_reserve(&d->d_blocks, sizeof(sla_hip_dec_block) * nb) != 0 || dbuf_reserve(&d->d_info, sizeof(sla_hip_dec_info) * nb) != 0
           || dbuf_reserve(&d->d_chan, sizeof(sla_hip_dec_chan) * (size_t)nb * C) != 0
           || dbuf_reserve(&d->d_kint, sizeof(int32_t) * (size_t)nb * C * (order + 1)) != 0) { return SLA_APIRESULT_NG; }
@@ -392,7 +393,7 @@ static SLAApiResult decode_run(struct SLADecoder* d, const uint8_t* data, uint32
       }
       HIPCHK(hipEventRecord(d->ev[1], d->stream));
       HIPCHK(hipStreamSynchronize(d->stream));
-      if (hipEventElapsedTime(&ms_batch, d->ev[0], d->ev[1]) == hipSuccess) { kernel_ms += ms_batch; }
+      ev_add_ms(&kernel_ms, d->ev[0], d->ev[1]);
     }
 
     /* ---- examine the blocks in file order: the first failure decides */
@@ -401,7 +402,6 @@ static SLAApiResult decode_run(struct SLADecoder* d, const uint8_t* data, uint32
 
   /* ---- mid/side, left-justification, copy-out of everything before the failing block */
   if (done_samples > 0) {
-    float ms_fin = 0.0f;
     HIPCHK(hipEventRecord(d->ev[0], d->stream));
     RCCHK(sla_hip_launch_dec_finish(d_planes, stride, C, done_samples, ms, 32u - bps + lshift, d->stream));
     HIPCHK(hipEventRecord(d->ev[1], d->stream));
@@ -412,7 +412,7 @@ static SLAApiResult decode_run(struct SLADecoder* d, const uint8_t* data, uint32
       }
     }
     HIPCHK(hipStreamSynchronize(d->stream));
-    if (hipEventElapsedTime(&ms_fin, d->ev[0], d->ev[1]) == hipSuccess) { kernel_ms += ms_fin; }
+    ev_add_ms(&kernel_ms, d->ev[0], d->ev[1]);
     d->timing[3] = (float)(now_ms() - t1);
   }
   *output_num_samples = done_samples;
@@ -438,19 +438,26 @@ SLAApiResult sla_hip_decode_device(struct SLADecoder* decoder, const uint8_t* ho
 }
 
 /* ------------------------------------------------------------------------------------------------------------
- * sla_hip_decode_batch (include/sla_hip.h): the blocks of many files through the kernels together.  The headers and
- * the block walk are those of decode_run, file by file; files that share the kernels' launch parameters share a pass;
- * a pass uploads its images (concatenated at 4-byte offsets, each block's reader bounded by the end of its own file:
- * sla_hip_launch_dec_bits_x) and its block table once, runs each kernel once over one set of planes in which every
- * file has a region of its own, and brings the finished samples of all its files home in one copy
- * (sla_hip_launch_dec_finish_batch).  The results are then examined file by file with decode_run's code.
- * With resident sources (sla_hip_decode_batch_resident) the streams are in device memory and the host never reads them:
- * the headers come home through a gather, the walk runs on the device (count mode before the passes are cut, write mode
- * in each pass), the gather fills the pass image in place of staging and upload, and the examination reads the table
- * and the stored CRC fields the pass brought home.
+ * The batch calls (include/sla_hip.h): the blocks of many files through the kernels together.  One pipeline, its
+ * arithmetic in sla_dec_plan.c: the headers in item order with decode_run's code (the handle's format moves as under
+ * DecodeWhole of one item after the other; fmt_mark / call_close leave it there); every file's block chain walked into rows
+ * of the host tables; the files sorted so that equal launch parameters are neighbours and cut into passes (pass_cut).  A
+ * pass lays its files out and reserves its scratch (pass_begin: images at 4-byte offsets, each block's reader bounded by the
+ * end of its own file, a plane region per file), stages image and block table, runs each kernel once (pass_kernels),
+ * examines every file with decode_run's code and delivers.  A file with a block body that does not end where its size
+ * field says is decoded again, alone, through decode_run.  What each call adds:
+ *   sla_hip_decode_batch           host sources and destinations: walk_chain, staging copies, one upload and one packed
+ *                                  download (sla_hip_launch_dec_finish_batch) per pass.
+ *   sla_hip_decode_batch_device    device destinations, written by the emit kernel (emit_run), zero fill included -- for items
+ *                                  that reached no pass in a launch of its own (zero_fill_pending).
+ *   sla_hip_decode_batch_resident  device sources the host never reads: the headers come home through a gather
+ *                                  (res_fetch_headers), the walk runs on the device: in count mode before the passes are cut
+ *                                  (res_count_walk), in write mode in each pass behind the gather that fills the pass image.
+ *                                  That is the resident stage (stage_tables, stage_queue), one for whole files, windows and
+ *                                  salvage; the examination reads the rows and stored CRC fields it brought home.
+ * Device-destination calls keep their per-item arrays in one allocation (call_mem_t) and open with call_open.
  * ------------------------------------------------------------------------------------------------------------ */
 #define DEC_BATCH_PASS_BYTES (1ull << 30)    /* stream bytes of one pass (staging and device image) */
-#define DEC_BATCH_ALIGN      64u             /* samples: every file's plane region starts on a 256-byte boundary */
 #define DEC_COPY_THREADS     4u              /* host threads of a staging copy, the caller's own among them */
 #define DEC_COPY_PIECE       ((size_t)4 << 20)
 
@@ -497,36 +504,31 @@ static void copy_run(copy_list_t* l)
   l->n = 0; l->bytes = 0;
 }
 
-typedef struct {
-  uint32_t     item;        /* index into the caller's items */
-  dec_format_t f;
-  uint32_t     first, nb;   /* its blocks: d->h_blocks[first, first + nb), positions in the file */
-  SLAApiResult walk_err;
-  uint32_t     extent;      /* samples per channel its blocks write */
-  int          alone;       /* decoded on its own through decode_run */
-  int          wide;        /* resident: its chain is walked by sla_hip_launch_dec_walk_wide, not on a lane */
-  uint64_t     img_off;     /* its image in the pass image */
-  uint64_t     plane_off;   /* its region in the pass planes */
-} bfile_t;
+typedef slai_dec_file bfile_t;       /* a file of a call: its rows are d->h_blocks[first, first + nb) */
 
-static int bfile_cmp(const void* pa, const void* pb)
-{
-  const bfile_t* a = (const bfile_t*)pa;
-  const bfile_t* b = (const bfile_t*)pb;
-  const uint32_t ka[8] = { a->alone, a->f.C, a->f.bps, a->f.ms, a->f.order, a->f.ntaps, a->f.lms, a->f.lshift };
-  const uint32_t kb[8] = { b->alone, b->f.C, b->f.bps, b->f.ms, b->f.order, b->f.ntaps, b->f.lms, b->f.lshift };
-  int k;
-  for (k = 0; k < 8; k++) { if (ka[k] != kb[k]) { return (ka[k] < kb[k]) ? -1 : 1; } }
-  return (a->item < b->item) ? -1 : (a->item > b->item);
-}
-static int same_launch(const dec_format_t* a, const dec_format_t* b)
-{
-  return a->C == b->C && a->bps == b->bps && a->ms == b->ms && a->order == b->order && a->ntaps == b->ntaps
-         && a->lms == b->lms && a->lshift == b->lshift;
-}
+/* where the pass that starts at files[p0] ends; files[0, n) are the sorted files that are not alone */
+#define pass_cut(files, p0, n) slai_dec_cut(files, p0, n, SLA_HIP_DEC_BATCH_PASS, DEC_BATCH_PASS_BYTES)
 
 #define BCHK(call) do { if ((call) != hipSuccess) { return -1; } } while (0)
 #define BRC(call)  do { if ((call) != 0) { return -1; } } while (0)
+
+/* The layout of the pass files[0, nf) (slai_dec_layout; planes of no sample still get one) and its scratch: the image, the
+ * block table (nb rows, then nb block ends), infos, channel records, PARCOR integers, planes, CRC words (the stored fields
+ * and, for salvage, as many verdicts).  The slack lets a kernel's last vector access run over. */
+typedef struct { uint64_t img_bytes, regions, span; uint32_t nb; } pass_t;      /* regions: their sum; span: the plane stride */
+static int pass_begin(struct SLADecoder* d, bfile_t* files, uint32_t nf, pass_t* p)
+{
+  const size_t nb_C = (size_t)files[0].f.C;
+  slai_dec_layout(files, nf, &p->img_bytes, &p->regions, &p->nb);
+  p->span = (p->regions == 0) ? 1 : p->regions;
+  return (dbuf_reserve(&d->d_image, p->img_bytes + 16) != 0
+          || dbuf_reserve(&d->d_blocks, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)p->nb + 16) != 0
+          || dbuf_reserve(&d->d_info, sizeof(sla_hip_dec_info) * (size_t)p->nb + 16) != 0
+          || dbuf_reserve(&d->d_chan, sizeof(sla_hip_dec_chan) * (size_t)p->nb * nb_C + 16) != 0
+          || dbuf_reserve(&d->d_kint, sizeof(int32_t) * (size_t)p->nb * nb_C * (files[0].f.order + 1) + 16) != 0
+          || dbuf_reserve(&d->d_planes, sizeof(int32_t) * (size_t)p->span * nb_C) != 0
+          || dbuf_reserve(&d->d_crcf, sizeof(uint32_t) * 2 * (size_t)p->nb + 16) != 0) ? -1 : 0;
+}
 
 /* sla_hip_decode_batch_device: where the samples go.  The internal items (sla_hip_decode_item, buffer NULL) are the
  * caller's device items one to one. */
@@ -536,12 +538,8 @@ static int same_launch(const dec_format_t* a, const dec_format_t* b)
 typedef struct {
   const sla_hip_decode_device_item* items;
   uint32_t  format, zero_fill;
-  uint8_t*  state;          /* DEV_* per item */
-  uint32_t* chans;          /* per item: the channel count its header gave, 0 when none */
-  int       resident;       /* sla_hip_decode_batch_resident: items[].data are device pointers; the internal items' data
-                             * is the host copy of each header, nothing behind byte 43 of it exists */
-  const struct wav_out* wav; /* the WAV calls: whole files through the WAV emit instead (items, format, zero_fill unused unless
-                             * resident, where items[].data are the sources) */
+  int       resident;        /* items[].data are device pointers; the internal items' data is the host copy of each header */
+  const struct wav_out* wav; /* the WAV calls: whole files through the WAV emit instead (format, zero_fill unused) */
 } dev_out_t;
 
 /* sla_hip_decode_wav_batch / _resident: a file is delivered -- 44-byte header and frames, by sla_hip_launch_wav_emit_batch --
@@ -557,15 +555,42 @@ typedef struct wav_out {
   int       host;
 } wav_out_t;
 
+/* The per-item arrays of one call, each num_items long and zero, in one allocation (call_mem_new); free(m.base) ends them. */
+typedef struct {
+  void* base;
+  sla_hip_decode_item*        bi;       /* batch_run's items, where the caller's are of another kind */
+  sla_hip_decode_device_item* dv;       /* the items as device items, likewise */
+  sla_hip_dec_emit*           fill;     /* zero_fill_pending's table */
+  bfile_t*                    files;
+  const uint8_t**             src;      /* call_open: what res_fetch_headers reads */
+  sla_hip_dec_window_result*  wres;     /* windows: every item's count-mode walk */
+  uint32_t *size, *chans, *done;        /* chans: the channel count the item's header gave, 0 when none; done: by files[] */
+  uint32_t *rate, *fbytes, *wbits; int32_t* hold;      /* the WAV calls: from each header; wav_out_t */
+  uint8_t  *ok, *state, *delivered;     /* ok: the source may be read; state: DEV_* */
+} call_mem_t;
+
+static int call_mem_new(call_mem_t* m, uint32_t n)
+{
+  uint8_t* p;
+  memset(m, 0, sizeof(*m));
+  p = (uint8_t*)calloc(n, sizeof(*m->bi) + sizeof(*m->dv) + sizeof(*m->fill) + sizeof(*m->files) + sizeof(*m->src) + sizeof(*m->wres)
+                          + 6 * sizeof(uint32_t) + sizeof(*m->hold) + 3);
+  if ((m->base = p) == NULL) { return -1; }
+#define CARVE(field) do { m->field = (void*)p; p += sizeof(*m->field) * (size_t)n; } while (0)
+  CARVE(bi); CARVE(dv); CARVE(fill); CARVE(files); CARVE(src);      /* (sizes that are multiples of 8 first) */
+  CARVE(wres); CARVE(size); CARVE(chans); CARVE(done); CARVE(rate); CARVE(fbytes); CARVE(wbits); CARVE(hold);
+  CARVE(ok); CARVE(state); CARVE(delivered);
+#undef CARVE
+  return 0;
+}
+
 /* ---- resident sources: the device walk and the gather stand in for walk_chain and the staging copies ---- */
 #define RES_HDR_SLOT 48u     /* bytes of one header in the gathered header image (43, padded, a multiple of 4) */
 
 static int res_events(struct SLADecoder* d)
 {
   int k;
-  for (k = 0; k < 3; k++) {
-    if (d->ev_src[k] == NULL && hipEventCreate(&d->ev_src[k]) != hipSuccess) { d->ev_src[k] = NULL; return -1; }
-  }
+  for (k = 0; k < 3; k++) { if (d->ev_src[k] == NULL && hipEventCreate(&d->ev_src[k]) != hipSuccess) { d->ev_src[k] = NULL; return -1; } }
   return 0;
 }
 
@@ -600,38 +625,12 @@ static int res_fetch_headers(struct SLADecoder* d, const uint8_t* const* src, co
 }
 
 /* ---- long files: the wide walk (sla_hip_launch_dec_walk_wide) in place of a lane ----
- * Files of at least d->wide_walk bytes, the RES_WIDE_MAX longest of a call (ties: item order), are walked by the whole
- * device one after the other behind the lane launch, in whose table they stand with total = 0: the lane writes their
- * empty result and rows, the wide launches overwrite both.  The launches of a file are serial, so more of them would
- * only queue up, and a batch of many mid-size files is what the lane walk is good at. */
-#define RES_WIDE_MAX 8u
-
-/* node capacity of a file's wide walk: the option, or one node per 256 stream bytes and at least 1 << 16 */
-static uint32_t res_wide_capacity(const struct SLADecoder* d, uint32_t data_size)
-{
-  const uint32_t by_size = data_size / 256u;
-  if (d->wide_nodes != 0) { return d->wide_nodes; }
-  return (by_size < (1u << 16)) ? (1u << 16) : by_size;
-}
-
-/* the files of files[0, nf) that go wide, longest first -> pick[], their number */
-static uint32_t res_pick_wide(const struct SLADecoder* d, const sla_hip_decode_item* items, const bfile_t* files, uint32_t nf,
-                              uint32_t pick[RES_WIDE_MAX])
-{
-  uint32_t n = 0, i, k;
-  if (d->wide_walk == 0) { return 0; }
-  for (i = 0; i < nf; i++) {
-    const uint32_t size = items[files[i].item].data_size;
-    if (size < d->wide_walk) { continue; }
-    for (k = n; k > 0; k--) {
-      const uint32_t ps = items[files[pick[k - 1]].item].data_size;
-      if (ps > size || (ps == size && files[pick[k - 1]].item < files[i].item)) { break; }
-      if (k < RES_WIDE_MAX) { pick[k] = pick[k - 1]; }
-    }
-    if (k < RES_WIDE_MAX) { pick[k] = i; if (n < RES_WIDE_MAX) { n++; } }
-  }
-  return n;
-}
+ * Files of at least d->wide_walk bytes, the RES_WIDE_MAX longest of a call (ties: item order; slai_dec_pick_wide), are
+ * walked by the whole device one after the other behind the lane launch, in whose table they stand with total = 0: the lane
+ * writes their empty result and rows, the wide launches overwrite both.  The launches of a file are serial, so more of them
+ * would only queue up, and a batch of many mid-size files is what the lane walk is good at.  A file's node capacity is
+ * slai_dec_wide_capacity of the option "wide_walk_nodes" and its size. */
+#define RES_WIDE_MAX SLAI_DEC_WIDE_MAX
 
 /* room for the wide walks of the listed table entries: one scratch for the largest, the words that come home */
 static int res_wide_reserve(struct SLADecoder* d, const sla_hip_dec_walk_file* wt, const uint32_t* list, uint32_t n)
@@ -640,7 +639,7 @@ static int res_wide_reserve(struct SLADecoder* d, const sla_hip_dec_walk_file* w
   uint32_t j;
   for (j = 0; j < n; j++) {
     const uint32_t size = wt[list[j]].data_size;
-    const uint64_t b = SLA_HIP_DEC_WIDE_SCRATCH_BYTES(size, res_wide_capacity(d, size));
+    const uint64_t b = SLA_HIP_DEC_WIDE_SCRATCH_BYTES(size, slai_dec_wide_capacity(d->wide_nodes, size));
     if (b > need) { need = b; }
   }
   return (dbuf_reserve(&d->d_wide, (size_t)need) != 0
@@ -652,7 +651,7 @@ static int res_wide_reserve(struct SLADecoder* d, const sla_hip_dec_walk_file* w
 static int res_wide_launch(struct SLADecoder* d, const sla_hip_dec_walk_file* wf, uint32_t slot, sla_hip_dec_block* db,
                            uint64_t* dend, uint32_t* dcrc, sla_hip_dec_wide_info* info)
 {
-  const uint32_t cap = res_wide_capacity(d, wf->data_size);
+  const uint32_t cap = slai_dec_wide_capacity(d->wide_nodes, wf->data_size);
   BRC(sla_hip_launch_dec_walk_wide(wf, d->cfg.max_num_block_samples, d->cfg.enable_crc_check, (sla_hip_dec_walk_result*)d->d_wres.ptr + slot,
                                    db, dend, dcrc, cap, d->d_wide.ptr, d->stream));
   if (info != NULL) { BCHK(hipMemcpyAsync(info, d->d_wide.ptr, sizeof(*info), hipMemcpyDeviceToHost, d->stream)); }
@@ -681,7 +680,7 @@ static int res_count_walk(struct SLADecoder* d, const sla_hip_decode_item* items
     wt[i].src = dev->items[files[i].item].data; wt[i].data_size = it->data_size;
     wt[i].total = files[i].f.total; wt[i].capacity = it->buffer_num_samples;
   }
-  npick = res_pick_wide(d, items, files, nf, pick);
+  npick = slai_dec_pick_wide(files, nf, d->wide_walk, pick);
   if (npick > 0 && res_wide_reserve(d, wt, pick, npick) != 0) { return -1; }
   for (j = 0; j < npick; j++) { wt[pick[j]].total = 0; }
   BCHK(hipMemcpyAsync(d->d_src.ptr, wt, sizeof(*wt) * nf, hipMemcpyHostToDevice, d->stream));
@@ -724,27 +723,90 @@ static int res_count_walk(struct SLADecoder* d, const sla_hip_decode_item* items
   return 0;
 }
 
-/* A pass's stage for resident sources, queued and not waited for: the gather fills the pass image, the walk in write mode
- * the block table (d->d_blocks: nb rows, then nb ends) and d->d_crcf; rows, CRC fields and the walk's results are on their
- * way home (d->h_blocks / d->h_crcf from the pass's first row, the results behind the tables in d->h_src) and d->d_info is
- * cleared.  Nothing when the pass has no block. */
+/* ---- the resident stage of a pass: what stands in for staging copies, upload and walk_chain when the sources are in
+ * device memory; one for whole files (batch, WAV, salvage) and windows, up to the kind of walk. ----
+ * Its tables lie in d->h_src (page-locked) and d->d_src: the gather table and behind it the walk table (sla_hip_dec_walk_file
+ * or sla_hip_dec_window_file per file), over in one copy; behind them, on the host only, the write-mode walk's results
+ * (sla_hip_dec_walk_result / _window_result), home after the pass's wait.  Only stage_tables knows where each lies. */
+typedef struct {
+  sla_hip_dec_gather* gt; void* wt; void* wr;                  /* host */
+  const sla_hip_dec_gather* d_gt; const void* d_wt;            /* device */
+  size_t up_bytes, wr_bytes;
+} stage_t;
+
+static int stage_tables(struct SLADecoder* d, uint32_t nf, size_t wt_size, size_t wr_size, stage_t* st)
+{
+  st->up_bytes = (sizeof(*st->gt) + wt_size) * (size_t)nf; st->wr_bytes = wr_size * (size_t)nf;
+  if (hbuf_reserve(&d->h_src, st->up_bytes + st->wr_bytes) != 0 || dbuf_reserve(&d->d_src, st->up_bytes) != 0
+      || dbuf_reserve(&d->d_wres, st->wr_bytes) != 0 || res_events(d) != 0) { return -1; }
+  st->gt = (sla_hip_dec_gather*)d->h_src.ptr; st->wt = st->gt + nf; st->wr = (uint8_t*)st->wt + wt_size * (size_t)nf;
+  st->d_gt = (const sla_hip_dec_gather*)d->d_src.ptr; st->d_wt = st->d_gt + nf;
+  memset(st->gt, 0, st->up_bytes);
+  return 0;
+}
+
+/* the first half of the stage: the tables over, the first ng gather entries (the longest max_bytes) into the pass image */
+static int stage_gather(struct SLADecoder* d, const stage_t* st, uint32_t ng, uint32_t max_bytes, uint64_t img_bytes)
+{
+  BCHK(hipMemcpyAsync(d->d_src.ptr, st->gt, st->up_bytes, hipMemcpyHostToDevice, d->stream));
+  BCHK(hipEventRecord(d->ev_src[0], d->stream));
+  BRC(sla_hip_launch_dec_gather(st->d_gt, ng, max_bytes, (uint8_t*)d->d_image.ptr, img_bytes, d->stream));
+  BCHK(hipEventRecord(d->ev_src[1], d->stream));
+  return 0;
+}
+
+/* The stage of the pass files[0, nf), queued on the handle's stream and not waited for: stage_gather, then the walk in write
+ * mode -- of windows, or of whole files with the wide walks of the long ones behind the lane launch -- into the block table
+ * (d->d_blocks: nb rows, then nb ends) and d->d_crcf.  The walk's results (st->wr), the rows and the CRC fields
+ * (d->h_blocks / d->h_crcf from the pass's first row) are on their way home, d->d_info is cleared. */
+static int stage_queue(struct SLADecoder* d, const stage_t* st, const bfile_t* files, uint32_t nf, int windows, uint32_t ng,
+                       uint32_t max_bytes, const pass_t* p)
+{
+  sla_hip_dec_block* db = (sla_hip_dec_block*)d->d_blocks.ptr;
+  uint64_t* dend = (uint64_t*)(db + p->nb);
+  uint32_t* dcrc = (uint32_t*)d->d_crcf.ptr;
+  const uint32_t first = files[0].first;
+  uint32_t i;
+  if (stage_gather(d, st, ng, max_bytes, p->img_bytes) != 0) { return -1; }
+  if (windows) {
+    BRC(sla_hip_launch_dec_walk_window((const sla_hip_dec_window_file*)st->d_wt, nf, d->cfg.max_num_block_samples,
+                                       (sla_hip_dec_window_result*)d->d_wres.ptr, db, dend, dcrc, d->stream));
+  } else {
+    BRC(sla_hip_launch_dec_walk((const sla_hip_dec_walk_file*)st->d_wt, nf, d->cfg.max_num_block_samples, d->cfg.enable_crc_check,
+                                (sla_hip_dec_walk_result*)d->d_wres.ptr, db, dend, dcrc, d->stream));
+    for (i = 0; i < nf; i++) {
+      if (!files[i].wide) { continue; }
+      sla_hip_dec_walk_file wf = ((const sla_hip_dec_walk_file*)st->wt)[i];      /* (a copy: the table is on its way to the device) */
+      wf.total = files[i].f.total;
+      if (res_wide_launch(d, &wf, i, db, dend, dcrc, NULL) != 0) { return -1; }
+    }
+  }
+  BCHK(hipMemcpyAsync(st->wr, d->d_wres.ptr, st->wr_bytes, hipMemcpyDeviceToHost, d->stream));
+  BCHK(hipMemcpyAsync(d->h_blocks + first, db, sizeof(*db) * (size_t)p->nb, hipMemcpyDeviceToHost, d->stream));
+  BCHK(hipMemcpyAsync(d->h_crcf + first, dcrc, sizeof(uint32_t) * (size_t)p->nb, hipMemcpyDeviceToHost, d->stream));
+  BCHK(hipEventRecord(d->ev_src[2], d->stream));
+  BCHK(hipMemsetAsync(d->d_info.ptr, 0, sizeof(sla_hip_dec_info) * p->nb, d->stream));
+  return 0;
+}
+
+/* after the pass's wait: the stage's times */
+static void stage_times(struct SLADecoder* d, double* t_gather, double* t_walk)
+{
+  ev_add_ms(t_gather, d->ev_src[0], d->ev_src[1]); ev_add_ms(t_walk, d->ev_src[1], d->ev_src[2]);
+}
+
+/* The tables of a pass of whole resident files (source i is src[files[i].item]) and its stage queued; nothing when the pass
+ * has no block. */
 static int res_stage_pass(struct SLADecoder* d, const sla_hip_decode_item* items, const dev_out_t* dev, const bfile_t* files,
-                          uint32_t nf, uint32_t nb, uint64_t img_bytes)
+                          uint32_t nf, const pass_t* p, stage_t* st)
 {
   sla_hip_dec_gather* gt;
   sla_hip_dec_walk_file* wt;
-  sla_hip_dec_walk_result* wr;
-  sla_hip_dec_block* db;
   const uint32_t first = files[0].first;
   uint32_t i, max_bytes = 0;
-  int any_wide = 0;
-  if (nb == 0) { return 0; }
-  if (hbuf_reserve(&d->h_src, (sizeof(*gt) + sizeof(*wt) + sizeof(*wr)) * (size_t)nf) != 0
-      || dbuf_reserve(&d->d_src, (sizeof(*gt) + sizeof(*wt)) * (size_t)nf) != 0 || dbuf_reserve(&d->d_wres, sizeof(*wr) * (size_t)nf) != 0
-      || dbuf_reserve(&d->d_crcf, sizeof(uint32_t) * (size_t)nb) != 0 || res_events(d) != 0) { return -1; }
-  gt = (sla_hip_dec_gather*)d->h_src.ptr;
-  wt = (sla_hip_dec_walk_file*)(gt + nf);
-  wr = (sla_hip_dec_walk_result*)(wt + nf);
+  if (p->nb == 0) { return 0; }
+  if (stage_tables(d, nf, sizeof(*wt), sizeof(sla_hip_dec_walk_result), st) != 0) { return -1; }
+  gt = st->gt; wt = (sla_hip_dec_walk_file*)st->wt;
   for (i = 0; i < nf; i++) {
     const sla_hip_decode_item* it = &items[files[i].item];
     gt[i].src = dev->items[files[i].item].data; gt[i].dst_off = files[i].img_off; gt[i].bytes = it->data_size; gt[i].reserved = 0;
@@ -754,41 +816,19 @@ static int res_stage_pass(struct SLADecoder* d, const sla_hip_decode_item* items
     if (it->data_size > max_bytes) { max_bytes = it->data_size; }
     if (files[i].wide) {
       if (res_wide_reserve(d, wt, &i, 1) != 0) { return -1; }
-      wt[i].total = 0; any_wide = 1;
+      wt[i].total = 0;
     }
   }
-  db = (sla_hip_dec_block*)d->d_blocks.ptr;
-  BCHK(hipMemcpyAsync(d->d_src.ptr, gt, (sizeof(*gt) + sizeof(*wt)) * (size_t)nf, hipMemcpyHostToDevice, d->stream));
-  BCHK(hipEventRecord(d->ev_src[0], d->stream));
-  BRC(sla_hip_launch_dec_gather((const sla_hip_dec_gather*)d->d_src.ptr, nf, max_bytes, (uint8_t*)d->d_image.ptr, img_bytes, d->stream));
-  BCHK(hipEventRecord(d->ev_src[1], d->stream));
-  BRC(sla_hip_launch_dec_walk((const sla_hip_dec_walk_file*)((const sla_hip_dec_gather*)d->d_src.ptr + nf), nf, d->cfg.max_num_block_samples,
-                              d->cfg.enable_crc_check, (sla_hip_dec_walk_result*)d->d_wres.ptr, db, (uint64_t*)(db + nb),
-                              (uint32_t*)d->d_crcf.ptr, d->stream));
-  for (i = 0; any_wide && i < nf; i++) {
-    if (!files[i].wide) { continue; }
-    sla_hip_dec_walk_file wf = wt[i];      /* (a copy: the table is on its way to the device) */
-    wf.total = files[i].f.total;
-    if (res_wide_launch(d, &wf, i, db, (uint64_t*)(db + nb), (uint32_t*)d->d_crcf.ptr, NULL) != 0) { return -1; }
-  }
-  BCHK(hipMemcpyAsync(wr, d->d_wres.ptr, sizeof(*wr) * nf, hipMemcpyDeviceToHost, d->stream));
-  BCHK(hipMemcpyAsync(d->h_blocks + first, db, sizeof(*db) * (size_t)nb, hipMemcpyDeviceToHost, d->stream));
-  BCHK(hipMemcpyAsync(d->h_crcf + first, d->d_crcf.ptr, sizeof(uint32_t) * (size_t)nb, hipMemcpyDeviceToHost, d->stream));
-  BCHK(hipEventRecord(d->ev_src[2], d->stream));
-  BCHK(hipMemsetAsync(d->d_info.ptr, 0, sizeof(sla_hip_dec_info) * nb, d->stream));
-  return 0;
+  return stage_queue(d, st, files, nf, 0, nf, max_bytes, p);
 }
 
 /* After the pass's wait: the stage's times, the rows brought back to positions in their own files (what examine_blocks
  * reads), and the write-mode walk checked against the count: a file whose chain changed in between fails the call. */
-static int res_finish_pass(struct SLADecoder* d, const bfile_t* files, uint32_t nf, double* t_gather, double* t_walk)
+static int res_finish_pass(struct SLADecoder* d, const stage_t* st, const bfile_t* files, uint32_t nf, double* t_gather, double* t_walk)
 {
-  const sla_hip_dec_walk_result* wr = (const sla_hip_dec_walk_result*)((const uint8_t*)d->h_src.ptr
-                                      + (sizeof(sla_hip_dec_gather) + sizeof(sla_hip_dec_walk_file)) * (size_t)nf);
-  float ms = 0.0f;
+  const sla_hip_dec_walk_result* wr = (const sla_hip_dec_walk_result*)st->wr;
   uint32_t i, b;
-  if (hipEventElapsedTime(&ms, d->ev_src[0], d->ev_src[1]) == hipSuccess) { *t_gather += ms; }
-  if (hipEventElapsedTime(&ms, d->ev_src[1], d->ev_src[2]) == hipSuccess) { *t_walk += ms; }
+  stage_times(d, t_gather, t_walk);
   for (i = 0; i < nf; i++) {
     if (wr[i].num_blocks != files[i].nb || wr[i].stop != (uint32_t)files[i].walk_err || wr[i].extent != files[i].extent
         || wr[i].reserved != 0) { return -1; }                 /* reserved: a wide walk that overflowed since the count */
@@ -817,7 +857,6 @@ static uint32_t emit_entry(sla_hip_dec_emit* e, const sla_hip_decode_device_item
 static int emit_run(struct SLADecoder* d, const int32_t* planes, uint64_t stride, const sla_hip_dec_emit* et, uint32_t ne,
                     uint32_t max_lim, uint32_t format, float* kernel_ms)
 {
-  float ms = 0.0f;
   if (ne == 0) { return 0; }
   if (dbuf_reserve(&d->d_ftab, sizeof(*et) * ne) != 0) { return -1; }
   if (planes == NULL) {               /* a table of zero fills only: the kernel reads no plane, but takes a valid pointer */
@@ -829,8 +868,24 @@ static int emit_run(struct SLADecoder* d, const int32_t* planes, uint64_t stride
   BRC(sla_hip_launch_dec_emit_batch(planes, stride, (const sla_hip_dec_emit*)d->d_ftab.ptr, ne, max_lim, format, d->stream));
   BCHK(hipEventRecord(d->ev[1], d->stream));
   BCHK(hipStreamSynchronize(d->stream));
-  if (hipEventElapsedTime(&ms, d->ev[0], d->ev[1]) == hipSuccess) { *kernel_ms += ms; }
+  ev_add_ms(kernel_ms, d->ev[0], d->ev[1]);
   return 0;
+}
+
+/* device destinations of items whose header gave a channel count but of which nothing was decoded (DEV_PENDING): the zero
+ * fill, all of them in one launch of the emit kernel */
+static int zero_fill_pending(struct SLADecoder* d, const call_mem_t* m, const sla_hip_decode_device_item* items, uint32_t num_items,
+                             uint32_t format, float* kernel_ms, double* t_down)
+{
+  const double t = now_ms();
+  uint32_t i, ne = 0, max_lim = 0;
+  int rc;
+  for (i = 0; i < num_items; i++) {
+    if (m->state[i] == DEV_PENDING) { ne += emit_entry(m->fill + ne, &items[i], 1, 0, 0, m->chans[i], 0, 0, 32, &max_lim); }
+  }
+  rc = emit_run(d, NULL, 1, m->fill, ne, max_lim, format, kernel_ms);
+  *t_down += now_ms() - t;
+  return rc;
 }
 
 /* The last leg of the WAV calls for files[0, nf) that share C and bps (a pass, or one file decoded on its own): every file
@@ -847,7 +902,6 @@ static int wav_emit_run(struct SLADecoder* d, const dev_out_t* dev, const sla_hi
   sla_hip_wav_emit* et;
   uint64_t stage = 0;
   uint32_t i, ne = 0, max_n = 0;
-  float ms = 0.0f;
   if (hbuf_reserve(&d->h_wav, sizeof(*et) * (size_t)nf) != 0 || dbuf_reserve(&d->d_wav, sizeof(*et) * (size_t)nf) != 0) { return -1; }
   et = (sla_hip_wav_emit*)d->h_wav.ptr;
   for (i = 0; i < nf; i++) {
@@ -881,7 +935,7 @@ static int wav_emit_run(struct SLADecoder* d, const dev_out_t* dev, const sla_hi
   BCHK(hipEventRecord(d->ev[1], d->stream));
   if (w->host) { BCHK(hipMemcpyAsync(d->h_out.ptr, d->d_out.ptr, stage, hipMemcpyDeviceToHost, d->stream)); }
   BCHK(hipStreamSynchronize(d->stream));
-  if (hipEventElapsedTime(&ms, d->ev[0], d->ev[1]) == hipSuccess) { *kernel_ms += ms; }
+  ev_add_ms(kernel_ms, d->ev[0], d->ev[1]);
   if (w->host) {
     uint32_t k = 0;
     for (i = 0; i < nf; i++) {
@@ -906,7 +960,6 @@ static int pass_kernels(struct SLADecoder* d, const dec_format_t* f, uint32_t nb
   const sla_hip_dec_info* di = (const sla_hip_dec_info*)d->d_info.ptr;
   int32_t* planes = (int32_t*)d->d_planes.ptr;
   const uint32_t C = f->C;
-  float ms_k = 0.0f;
   BCHK(hipEventRecord(d->ev[0], d->stream));
   BRC(sla_hip_launch_dec_bits_x((const uint32_t*)d->d_image.ptr, img_bytes, db, nb, C, f->bps, f->lshift, f->ms, f->order, f->ntaps,
                                 d->cfg.enable_crc_check == 1, planes, span, (sla_hip_dec_info*)d->d_info.ptr,
@@ -920,51 +973,40 @@ static int pass_kernels(struct SLADecoder* d, const dec_format_t* f, uint32_t nb
   }
   BCHK(hipEventRecord(d->ev[1], d->stream));
   BCHK(hipStreamSynchronize(d->stream));
-  if (hipEventElapsedTime(&ms_k, d->ev[0], d->ev[1]) == hipSuccess) { *kernel_ms += ms_k; }
+  ev_add_ms(kernel_ms, d->ev[0], d->ev[1]);
   return 0;
 }
 
 /* One pass: files[0, nf), all with the same launch parameters, blocks d->h_blocks[files[0].first ...] contiguous.
  * dev != NULL: the samples go to the caller's device destinations through the emit kernel, nothing comes home.
  * Returns -1 on a device or allocation failure. */
-static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t* files, uint32_t nf, copy_list_t* cl,
+static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t* files, uint32_t* done, uint32_t nf, copy_list_t* cl,
                       const dev_out_t* dev, double* t_up, double* t_walk, double* t_down, float* kernel_ms)
 {
   const dec_format_t* f = &files[0].f;
   const uint32_t C = f->C, first = files[0].first;
   const int lms_ok = lms_order_ok(f->lms), res = (dev != NULL && dev->resident);
-  uint64_t img_bytes = 0, span = 0, out_elems = 0;
-  uint32_t nb = 0, i, k, nfin = 0, max_done = 0;
-  uint32_t* done;
+  uint64_t img_bytes, span, out_elems = 0;
+  uint32_t nb, i, k, nfin = 0, max_done = 0;
   sla_hip_dec_block* tb;
   uint64_t* tend;
   sla_hip_dec_file* ft;
-  float ms_k = 0.0f;
+  pass_t p; stage_t st;
   double t;
-
-  for (i = 0; i < nf; i++) {
-    files[i].img_off = img_bytes; img_bytes += ((uint64_t)items[files[i].item].data_size + 3) & ~(uint64_t)3;
-    files[i].plane_off = span; span += ((uint64_t)files[i].extent + DEC_BATCH_ALIGN - 1) / DEC_BATCH_ALIGN * DEC_BATCH_ALIGN;
-    nb += files[i].nb;
-  }
-  if (span == 0) { span = 1; }
 
   /* ---- images into staging (the bytes after each file up to its 4-byte boundary are zero) and over in one copy,
    *      the block table -- positions in the pass, then every block's end of stream -- likewise */
   t = now_ms();
-  if ((!res && hbuf_reserve(&d->h_img, img_bytes + 16) != 0) || dbuf_reserve(&d->d_image, img_bytes + 16) != 0
+  if (pass_begin(d, files, nf, &p) != 0) { return -1; }
+  img_bytes = p.img_bytes; span = p.span; nb = p.nb;
+  if ((!res && hbuf_reserve(&d->h_img, img_bytes + 16) != 0)
       || hbuf_reserve(&d->h_ptab, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb + sizeof(sla_hip_dec_emit) * nf) != 0
-      || dbuf_reserve(&d->d_blocks, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb) != 0
-      || dbuf_reserve(&d->d_info, sizeof(sla_hip_dec_info) * nb) != 0
-      || dbuf_reserve(&d->d_chan, sizeof(sla_hip_dec_chan) * (size_t)nb * C) != 0
-      || dbuf_reserve(&d->d_kint, sizeof(int32_t) * (size_t)nb * C * (f->order + 1)) != 0
-      || dbuf_reserve(&d->d_planes, sizeof(int32_t) * (size_t)span * C) != 0
       || dbuf_reserve(&d->d_ftab, sizeof(sla_hip_dec_file) * nf) != 0) { return -1; }
   tb = (sla_hip_dec_block*)d->h_ptab.ptr;
   tend = (uint64_t*)(tb + nb);
   if (res) {
     /* resident sources: the gather and the walk in write mode do on the device what the rest of this stage does here */
-    if (res_stage_pass(d, items, dev, files, nf, nb, img_bytes) != 0) { return -1; }
+    if (res_stage_pass(d, items, dev, files, nf, &p, &st) != 0) { return -1; }
   } else {
     for (i = 0; i < nf; i++) {
       const sla_hip_decode_item* it = &items[files[i].item];
@@ -994,12 +1036,10 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
   /* ---- the kernels, once each over all blocks of the pass */
   if (nb > 0) {
     if (pass_kernels(d, f, nb, first, img_bytes, span, kernel_ms) != 0) { return -1; }
-    if (res && res_finish_pass(d, files, nf, t_up, t_walk) != 0) { return -1; }
+    if (res && res_finish_pass(d, &st, files, nf, t_up, t_walk) != 0) { return -1; }
   }
 
-  /* ---- every file examined on its own, in file order, with decode_run's code */
-  done = (uint32_t*)calloc(nf, sizeof(uint32_t));
-  if (done == NULL) { return -1; }
+  /* ---- every file examined on its own, in file order, with decode_run's code (done[]: zero on entry) */
   ft = (sla_hip_dec_file*)(tend + nb);
   for (i = 0; i < nf; i++) {
     sla_hip_decode_item* it = &items[files[i].item];
@@ -1026,7 +1066,7 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
    *      device destinations, converted and stored there by the emit kernel, zero fill included */
   t = now_ms();
   if (dev != NULL && dev->wav != NULL) {
-    if (wav_emit_run(d, dev, items, files, done, nf, 1, (const int32_t*)d->d_planes.ptr, span, cl, kernel_ms) != 0) { free(done); return -1; }
+    if (wav_emit_run(d, dev, items, files, done, nf, 1, (const int32_t*)d->d_planes.ptr, span, cl, kernel_ms) != 0) { return -1; }
   } else if (dev != NULL) {
     sla_hip_dec_emit* et = (sla_hip_dec_emit*)(tend + nb);
     uint32_t ne = 0, max_lim = 0;
@@ -1035,44 +1075,53 @@ static int batch_pass(struct SLADecoder* d, sla_hip_decode_item* items, bfile_t*
       ne += emit_entry(et + ne, &dev->items[files[i].item], dev->zero_fill, files[i].plane_off, done[i], C, f->ms,
                        32u - f->bps + f->lshift, f->bps, &max_lim);
     }
-    if (emit_run(d, (const int32_t*)d->d_planes.ptr, span, et, ne, max_lim, dev->format, kernel_ms) != 0) { free(done); return -1; }
+    if (emit_run(d, (const int32_t*)d->d_planes.ptr, span, et, ne, max_lim, dev->format, kernel_ms) != 0) { return -1; }
   } else if (nfin > 0) {
     uint64_t o = 0;
-    if (dbuf_reserve(&d->d_out, sizeof(int32_t) * out_elems) != 0 || hbuf_reserve(&d->h_out, sizeof(int32_t) * out_elems) != 0) { free(done); return -1; }
+    if (dbuf_reserve(&d->d_out, sizeof(int32_t) * out_elems) != 0 || hbuf_reserve(&d->h_out, sizeof(int32_t) * out_elems) != 0) { return -1; }
     if (hipMemcpyAsync(d->d_ftab.ptr, ft, sizeof(sla_hip_dec_file) * nfin, hipMemcpyHostToDevice, d->stream) != hipSuccess
         || hipEventRecord(d->ev[0], d->stream) != hipSuccess
         || sla_hip_launch_dec_finish_batch((const int32_t*)d->d_planes.ptr, span, C, (const sla_hip_dec_file*)d->d_ftab.ptr, nfin,
                                            max_done, (int32_t*)d->d_out.ptr, d->stream) != 0
         || hipEventRecord(d->ev[1], d->stream) != hipSuccess
         || hipMemcpyAsync(d->h_out.ptr, d->d_out.ptr, sizeof(int32_t) * out_elems, hipMemcpyDeviceToHost, d->stream) != hipSuccess
-        || hipStreamSynchronize(d->stream) != hipSuccess) { free(done); return -1; }
-    if (hipEventElapsedTime(&ms_k, d->ev[0], d->ev[1]) == hipSuccess) { *kernel_ms += ms_k; }
+        || hipStreamSynchronize(d->stream) != hipSuccess) { return -1; }
+    ev_add_ms(kernel_ms, d->ev[0], d->ev[1]);
     for (i = 0; i < nf; i++) {
       sla_hip_decode_item* it = &items[files[i].item];
       uint32_t c;
       if (files[i].alone || done[i] == 0) { continue; }
       for (c = 0; c < C; c++) {
-        if (copy_add(cl, it->buffer[c], (const int32_t*)d->h_out.ptr + o + (uint64_t)c * done[i], sizeof(int32_t) * (size_t)done[i]) != 0) {
-          free(done); return -1;
-        }
+        if (copy_add(cl, it->buffer[c], (const int32_t*)d->h_out.ptr + o + (uint64_t)c * done[i], sizeof(int32_t) * (size_t)done[i]) != 0) { return -1; }
       }
       o += (uint64_t)done[i] * C;
     }
     copy_run(cl);
   }
   for (i = 0; i < nf; i++) { if (!files[i].alone) { items[files[i].item].output_num_samples = done[i]; } }
-  free(done);
   *t_down += now_ms() - t;
   return 0;
 }
 
-static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t num_items, const dev_out_t* dev)
+/* The handle's format as the headers of a call left it, and the close of a call: the format is put back there (m != NULL:
+ * decode_run on an `alone` file moves it out of item order) and timing[0..5] written (sla_hip_decoder_last_timing). */
+typedef struct { struct SLAWaveFormat wf; struct SLAEncodeParameter ep; uint32_t flag; } fmt_mark_t;
+static void fmt_mark(const struct SLADecoder* d, fmt_mark_t* m) { m->wf = d->wave_format; m->ep = d->encode_param; m->flag = d->status_flag; }
+static void call_close(struct SLADecoder* d, const fmt_mark_t* m, double t0, double t_in, double t_walk, float kernel_ms, double t_out,
+                       uint32_t passes)
 {
-  bfile_t* files;
+  if (m != NULL) { d->wave_format = m->wf; d->encode_param = m->ep; d->status_flag = m->flag; }
+  d->timing[0] = (float)t_in; d->timing[1] = (float)t_walk; d->timing[2] = kernel_ms; d->timing[3] = (float)t_out;
+  d->timing[4] = (float)(now_ms() - t0); d->timing[5] = (float)passes;
+}
+
+/* num_items > 0; m: the call's arrays (files, done, fill; with dev also state and chans, as call_open left them) */
+static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t num_items, const dev_out_t* dev, call_mem_t* m)
+{
+  bfile_t* files = m->files;
   copy_list_t cl;
-  struct SLAWaveFormat wf_after;
-  struct SLAEncodeParameter ep_after;
-  uint32_t flag_after, nf = 0, nblocks = 0, passes = 0, i, p0;
+  fmt_mark_t after;
+  uint32_t nf = 0, npass, nblocks = 0, passes = 0, i, p0;
   const int res = (dev != NULL && dev->resident);
   int rc = 0;
   float kernel_ms = 0.0f;
@@ -1080,9 +1129,6 @@ static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t 
 
   memset(d->timing, 0, sizeof(d->timing));
   if (res) { memset(d->walk_stats, 0, sizeof(d->walk_stats)); }
-  if (num_items == 0) { return 0; }
-  files = (bfile_t*)calloc(num_items, sizeof(*files));
-  if (files == NULL) { return SLA_APIRESULT_NG; }
   memset(&cl, 0, sizeof(cl));
 
   /* ---- headers in item order: the handle's format moves exactly as under DecodeWhole of one item after the other */
@@ -1094,19 +1140,20 @@ static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t 
     int verdict;
     uint32_t c;
     it->output_num_samples = 0;
-    if (dev != NULL ? dev->state[i] == DEV_REFUSED : (it->data == NULL || it->buffer == NULL)) { it->result = SLA_APIRESULT_INVALID_ARGUMENT; continue; }
+    if (dev != NULL ? m->state[i] == DEV_REFUSED : (it->data == NULL || it->buffer == NULL)) { it->result = SLA_APIRESULT_INVALID_ARGUMENT; continue; }
     if ((ret = file_format(d, it->data, it->data_size, &f)) != SLA_APIRESULT_OK) { it->result = ret; continue; }
     if ((verdict = format_verdict(&f)) >= 0) { it->result = verdict; continue; }
     it->result = SLA_APIRESULT_OK;
-    files[nf].item = i; files[nf].f = f;
-    if (dev != NULL) { dev->state[i] = DEV_DECODED; }
+    files[nf].item = i; files[nf].f = f; files[nf].bytes = it->data_size;
+    if (dev != NULL) { m->state[i] = DEV_DECODED; }
     else { for (c = 0; c < f.C; c++) { if (it->buffer[c] == NULL) { files[nf].alone = 1; } } }     /* fails there as DecodeWhole does */
     nf++;
   }
-  wf_after = d->wave_format; ep_after = d->encode_param; flag_after = d->status_flag;
+  fmt_mark(d, &after);
 
   /* ---- files that share the launch parameters next to each other, each one's block chain walked */
-  qsort(files, nf, sizeof(*files), bfile_cmp);
+  qsort(files, nf, sizeof(*files), slai_dec_file_cmp);
+  for (npass = 0; npass < nf && !files[npass].alone; npass++) { }
   if (res) {
     /* on the device, all files in one launch (none is `alone` yet: that is decided for NULL planes, which device
      * destinations do not have) */
@@ -1130,16 +1177,9 @@ static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t 
   t_walk += now_ms() - t;
 
   /* ---- passes: runs of equal launch parameters, cut at SLA_HIP_DEC_BATCH_PASS sample-channels / DEC_BATCH_PASS_BYTES */
-  for (p0 = 0; p0 < nf && !files[p0].alone; ) {
-    uint64_t smp = 0, bytes = 0;
-    uint32_t p1 = p0;
-    while (p1 < nf && !files[p1].alone && same_launch(&files[p1].f, &files[p0].f)) {
-      const uint64_t s1 = ((uint64_t)files[p1].extent + DEC_BATCH_ALIGN) * files[p1].f.C;
-      const uint64_t b1 = (uint64_t)items[files[p1].item].data_size + 4;
-      if (p1 > p0 && (smp + s1 > SLA_HIP_DEC_BATCH_PASS || bytes + b1 > DEC_BATCH_PASS_BYTES)) { break; }
-      smp += s1; bytes += b1; p1++;
-    }
-    if (batch_pass(d, items, files + p0, p1 - p0, &cl, dev, &t_up, &t_walk, &t_down, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+  for (p0 = 0; p0 < npass; ) {
+    const uint32_t p1 = pass_cut(files, p0, npass);
+    if (batch_pass(d, items, files + p0, m->done + p0, p1 - p0, &cl, dev, &t_up, &t_walk, &t_down, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; goto out; }
     passes++;
     p0 = p1;
   }
@@ -1157,49 +1197,41 @@ static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t 
     }
     it->result = decode_run(d, res ? (const uint8_t*)d->h_img.ptr : it->data, it->data_size, NULL, NULL, 0, it->buffer, it->buffer_num_samples,
                             &it->output_num_samples, NULL);
-    if (dev != NULL && dev->wav != NULL) {
-      t = now_ms();
-      if (wav_emit_run(d, dev, items, &files[i], &it->output_num_samples, 1, 0, (const int32_t*)d->d_planes.ptr,
-                       run_plane_stride(files[i].f.total, it->buffer_num_samples), &cl, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; goto out; }
-      t_down += now_ms() - t;
-    } else if (dev != NULL) {
+    if (dev != NULL) {
+      const int32_t* planes = (const int32_t*)d->d_planes.ptr;
+      const uint64_t stride = run_plane_stride(files[i].f.total, it->buffer_num_samples);
       sla_hip_dec_emit e;
       uint32_t max_lim = 0, ne;
       t = now_ms();
-      ne = emit_entry(&e, &dev->items[files[i].item], dev->zero_fill, 0, it->output_num_samples, files[i].f.C, 0, 0, files[i].f.bps, &max_lim);
-      if (emit_run(d, (const int32_t*)d->d_planes.ptr, run_plane_stride(files[i].f.total, it->buffer_num_samples), &e, ne, max_lim,
-                   dev->format, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+      if (dev->wav != NULL) { rc = wav_emit_run(d, dev, items, &files[i], &it->output_num_samples, 1, 0, planes, stride, &cl, &kernel_ms); }
+      else {
+        ne = emit_entry(&e, &dev->items[files[i].item], dev->zero_fill, 0, it->output_num_samples, files[i].f.C, 0, 0, files[i].f.bps, &max_lim);
+        rc = emit_run(d, planes, stride, &e, ne, max_lim, dev->format, &kernel_ms);
+      }
+      if (rc != 0) { rc = SLA_APIRESULT_NG; goto out; }
       t_down += now_ms() - t;
     }
   }
 
   /* ---- device destinations of items whose header gave a channel count but that were not decoded: the zero fill */
-  if (dev != NULL && dev->zero_fill) {
-    sla_hip_dec_emit* et = (sla_hip_dec_emit*)calloc(num_items, sizeof(*et));
-    uint32_t ne = 0, max_lim = 0;
-    if (et == NULL) { rc = SLA_APIRESULT_NG; goto out; }
-    t = now_ms();
-    for (i = 0; i < num_items; i++) {
-      if (dev->state[i] == DEV_PENDING) { ne += emit_entry(et + ne, &dev->items[i], 1, 0, 0, dev->chans[i], 0, 0, 32, &max_lim); }
-    }
-    if (emit_run(d, NULL, 1, et, ne, max_lim, dev->format, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; }
-    free(et);
-    t_down += now_ms() - t;
-  }
+  if (dev != NULL && dev->zero_fill && zero_fill_pending(d, m, dev->items, num_items, dev->format, &kernel_ms, &t_down) != 0) { rc = SLA_APIRESULT_NG; }
 
 out:
-  d->wave_format = wf_after; d->encode_param = ep_after; d->status_flag = flag_after;
-  d->timing[0] = (float)t_up; d->timing[1] = (float)t_walk; d->timing[2] = kernel_ms; d->timing[3] = (float)t_down;
-  d->timing[4] = (float)(now_ms() - t0); d->timing[5] = (float)passes;
+  call_close(d, &after, t0, t_up, t_walk, kernel_ms, t_down, passes);
   free(cl.v);
-  free(files);
   return rc;
 }
 
 int sla_hip_decode_batch(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t num_items)
 {
+  call_mem_t m;
+  int rc;
   if (d == NULL || (items == NULL && num_items > 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
-  return batch_run(d, items, num_items, NULL);
+  if (num_items == 0) { memset(d->timing, 0, sizeof(d->timing)); return 0; }
+  if (call_mem_new(&m, num_items) != 0) { return SLA_APIRESULT_NG; }
+  rc = batch_run(d, items, num_items, NULL, &m);
+  free(m.base);
+  return rc;
 }
 
 /* the channel count a file's header gives (its fields are delivered also when only the header CRC fails), 0 when none */
@@ -1246,40 +1278,6 @@ static int dst_region_ok(const sla_hip_decode_device_item* it, uint32_t C, uint6
   return slai_device_region_ok(it->dst, C, it->capacity, it->channel_stride, it->sample_stride, esize, -1);
 }
 
-int sla_hip_decode_batch_device(struct SLADecoder* d, sla_hip_decode_device_item* items, uint32_t num_items,
-                                uint32_t sample_format, uint32_t flags, sla_hip_stream_t stream)
-{
-  sla_hip_decode_item* bi;
-  dev_out_t dev;
-  uint32_t i;
-  int rc = 0;
-  if (d == NULL || (items == NULL && num_items > 0) || sample_format > SLA_HIP_PCM_F32 || (flags & ~SLA_HIP_DEC_ZERO_FILL) != 0) {
-    return SLA_APIRESULT_INVALID_ARGUMENT;
-  }
-  if (num_items == 0) { memset(d->timing, 0, sizeof(d->timing)); return 0; }
-  bi = (sla_hip_decode_item*)calloc(num_items, sizeof(*bi));
-  dev.items = items; dev.format = sample_format; dev.zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u; dev.resident = 0; dev.wav = NULL;
-  dev.state = (uint8_t*)calloc(num_items, 1);
-  dev.chans = (uint32_t*)calloc(num_items, sizeof(uint32_t));
-  if (bi == NULL || dev.state == NULL || dev.chans == NULL) { rc = SLA_APIRESULT_NG; goto out; }
-  for (i = 0; i < num_items; i++) {
-    const sla_hip_decode_device_item* it = &items[i];
-    bi[i].data = it->data; bi[i].data_size = it->data_size; bi[i].buffer_num_samples = it->capacity; bi[i].buffer = NULL;
-    dev.chans[i] = header_channels(it->data, it->data_size);
-    if (!dst_region_ok(it, dev.chans[i], (sample_format == SLA_HIP_PCM_S16) ? 2u : 4u)) { dev.state[i] = DEV_REFUSED; }
-  }
-  /* nothing is written before the caller's stream has reached this call */
-  if (d->ev_order == NULL && hipEventCreateWithFlags(&d->ev_order, hipEventDisableTiming) != hipSuccess) { d->ev_order = NULL; rc = SLA_APIRESULT_NG; goto out; }
-  if (hipEventRecord(d->ev_order, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(d->stream, d->ev_order, 0) != hipSuccess) {
-    rc = SLA_APIRESULT_NG; goto out;
-  }
-  rc = batch_run(d, bi, num_items, &dev);
-  for (i = 0; i < num_items; i++) { items[i].result = bi[i].result; items[i].output_num_samples = bi[i].output_num_samples; }
-out:
-  free(bi); free(dev.state); free(dev.chans);
-  return rc;
-}
-
 /* the handle's stream behind what the caller's stream holds at this moment */
 static int order_behind(struct SLADecoder* d, sla_hip_stream_t stream)
 {
@@ -1288,60 +1286,84 @@ static int order_behind(struct SLADecoder* d, sla_hip_stream_t stream)
   return 0;
 }
 
-int sla_hip_decode_batch_resident(struct SLADecoder* d, sla_hip_decode_device_item* items, uint32_t num_items,
-                                  uint32_t sample_format, uint32_t flags, sla_hip_stream_t stream)
+/* The opening of every device-destination call, on the arrays of m.  In: dv[i], the item as a device item, and ok[i], 0
+ * where a check of the call's own has refused the item already.  In this order: resident sources are checked on the host
+ * (ok[i]) before anything of an item is read; the handle's stream goes behind the caller's, so that nothing is read or
+ * written before the caller's stream has reached the call; resident: the headers come home (*t_hdr: ms that took, else 0);
+ * bi[i] becomes the item as batch_run reads it, its data the header brought home or the caller's host stream; esize != 0:
+ * the destinations, elements of esize bytes, are checked with each header's channel count (chans[i]) before anything is
+ * written.  state[i] is DEV_REFUSED where a check failed, else DEV_PENDING. */
+static int call_open(struct SLADecoder* d, call_mem_t* m, uint32_t num_items, int resident, uint64_t esize, sla_hip_stream_t stream,
+                     double* t_hdr)
 {
-  sla_hip_decode_item* bi;
-  const uint8_t** src;
-  uint32_t* size;
-  uint8_t* ok;
+  uint32_t i;
+  *t_hdr = 0.0;
+  for (i = 0; i < num_items; i++) {
+    m->src[i] = m->dv[i].data; m->size[i] = m->dv[i].data_size;
+    if (resident && m->ok[i]) { m->ok[i] = (uint8_t)src_region_ok(m->dv[i].data, m->dv[i].data_size); }
+  }
+  if (order_behind(d, stream) != 0) { return -1; }
+  if (resident) {
+    const double t = now_ms();
+    if (res_fetch_headers(d, m->src, m->size, m->ok, num_items) != 0) { return -1; }
+    *t_hdr = now_ms() - t;
+  }
+  for (i = 0; i < num_items; i++) {
+    const sla_hip_decode_device_item* it = &m->dv[i];
+    m->bi[i].data = resident ? (const uint8_t*)d->h_hdr.ptr + (size_t)i * RES_HDR_SLOT : it->data;
+    m->bi[i].data_size = it->data_size; m->bi[i].buffer_num_samples = it->capacity; m->bi[i].buffer = NULL;
+    if (!m->ok[i]) { m->state[i] = DEV_REFUSED; continue; }
+    if (esize == 0) { continue; }
+    m->chans[i] = header_channels(m->bi[i].data, it->data_size);
+    if (!dst_region_ok(it, m->chans[i], esize)) { m->state[i] = DEV_REFUSED; }
+  }
+  return 0;
+}
+
+static uint64_t pcm_esize(uint32_t sample_format) { return (sample_format == SLA_HIP_PCM_S16) ? 2u : 4u; }
+
+/* sla_hip_decode_batch_device and sla_hip_decode_batch_resident */
+static int decode_batch_dev(struct SLADecoder* d, sla_hip_decode_device_item* items, uint32_t num_items, uint32_t sample_format,
+                            uint32_t flags, sla_hip_stream_t stream, int resident)
+{
+  call_mem_t m;
   dev_out_t dev;
   uint32_t i;
-  int rc = 0;
+  int rc = SLA_APIRESULT_NG;
   double t_hdr;
   if (d == NULL || (items == NULL && num_items > 0) || sample_format > SLA_HIP_PCM_F32 || (flags & ~SLA_HIP_DEC_ZERO_FILL) != 0) {
     return SLA_APIRESULT_INVALID_ARGUMENT;
   }
   if (num_items == 0) { memset(d->timing, 0, sizeof(d->timing)); return 0; }
-  bi = (sla_hip_decode_item*)calloc(num_items, sizeof(*bi));
-  src = (const uint8_t**)calloc(num_items, sizeof(*src));
-  size = (uint32_t*)calloc(num_items, sizeof(*size));
-  ok = (uint8_t*)calloc(num_items, 1);
-  dev.items = items; dev.format = sample_format; dev.zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u; dev.resident = 1; dev.wav = NULL;
-  dev.state = (uint8_t*)calloc(num_items, 1);
-  dev.chans = (uint32_t*)calloc(num_items, sizeof(uint32_t));
-  if (bi == NULL || src == NULL || size == NULL || ok == NULL || dev.state == NULL || dev.chans == NULL) { rc = SLA_APIRESULT_NG; goto out; }
-  /* the sources, on the host, before anything of an item is read */
-  for (i = 0; i < num_items; i++) {
-    src[i] = items[i].data; size[i] = items[i].data_size;
-    ok[i] = (uint8_t)src_region_ok(items[i].data, items[i].data_size);
+  if (call_mem_new(&m, num_items) != 0) { return SLA_APIRESULT_NG; }
+  dev.items = items; dev.format = sample_format; dev.zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u; dev.resident = resident; dev.wav = NULL;
+  for (i = 0; i < num_items; i++) { m.dv[i] = items[i]; m.ok[i] = 1; }
+  if (call_open(d, &m, num_items, resident, pcm_esize(sample_format), stream, &t_hdr) == 0) {
+    rc = batch_run(d, m.bi, num_items, &dev, &m);
+    d->timing[0] += (float)t_hdr;
+    for (i = 0; i < num_items; i++) { items[i].result = m.bi[i].result; items[i].output_num_samples = m.bi[i].output_num_samples; }
   }
-  /* nothing is read or written before the caller's stream has reached this call */
-  if (order_behind(d, stream) != 0) { rc = SLA_APIRESULT_NG; goto out; }
-  t_hdr = now_ms();
-  if (res_fetch_headers(d, src, size, ok, num_items) != 0) { rc = SLA_APIRESULT_NG; goto out; }
-  t_hdr = now_ms() - t_hdr;
-  /* the destinations, with each header's channel count, before anything is written */
-  for (i = 0; i < num_items; i++) {
-    const sla_hip_decode_device_item* it = &items[i];
-    bi[i].data = (const uint8_t*)d->h_hdr.ptr + (size_t)i * RES_HDR_SLOT; bi[i].data_size = it->data_size;
-    bi[i].buffer_num_samples = it->capacity; bi[i].buffer = NULL;
-    if (!ok[i]) { dev.state[i] = DEV_REFUSED; continue; }
-    dev.chans[i] = header_channels(bi[i].data, it->data_size);
-    if (!dst_region_ok(it, dev.chans[i], (sample_format == SLA_HIP_PCM_S16) ? 2u : 4u)) { dev.state[i] = DEV_REFUSED; }
-  }
-  rc = batch_run(d, bi, num_items, &dev);
-  d->timing[0] += (float)t_hdr;
-  for (i = 0; i < num_items; i++) { items[i].result = bi[i].result; items[i].output_num_samples = bi[i].output_num_samples; }
-out:
-  free(bi); free((void*)src); free(size); free(ok); free(dev.state); free(dev.chans);
+  free(m.base);
   return rc;
 }
 
+int sla_hip_decode_batch_device(struct SLADecoder* d, sla_hip_decode_device_item* items, uint32_t num_items, uint32_t sample_format,
+                                uint32_t flags, sla_hip_stream_t stream)
+{
+  return decode_batch_dev(d, items, num_items, sample_format, flags, stream, 0);
+}
+
+int sla_hip_decode_batch_resident(struct SLADecoder* d, sla_hip_decode_device_item* items, uint32_t num_items,
+                                  uint32_t sample_format, uint32_t flags, sla_hip_stream_t stream)
+{
+  return decode_batch_dev(d, items, num_items, sample_format, flags, stream, 1);
+}
+
 /* ---- sla_hip_salvage_resident (include/sla_hip.h): one resident stream decoded through damage ----
- * The stages are those of a resident pass of one file -- res_count_walk, res_stage_pass, pass_kernels, emit_run -- with
- * three additions: the mode decision behind the count, the salvage scan in place of the walk when the chain is broken,
- * and the silence (k_salvage_crc before the decode kernels, k_dec_conceal before the emit). */
+ * A resident call of one item (call_open on arrays of one) and one pass of one file (res_count_walk, pass_begin, the resident
+ * stage, pass_kernels, emit_run), with three additions: the mode decision behind the count; the salvage scan in place of the
+ * walk, behind the stage's gather half, when the chain is broken; and the silence (k_salvage_crc before the decode kernels,
+ * k_dec_conceal before the emit).  The handle's format stays where the stream's header put it. */
 
 /* one silent region: into the conceal list, the report and, while there is room, the caller's ranges */
 static void salvage_note(sla_hip_salvage_report* rep, sla_hip_salvage_range* ranges, uint32_t range_capacity, sla_hip_dec_conceal* cl,
@@ -1378,33 +1400,34 @@ int sla_hip_salvage_resident(struct SLADecoder* d, const uint8_t* d_data, uint32
   sla_hip_dec_conceal* cl;
   sla_hip_dec_emit e;
   dev_out_t dev;
+  call_mem_t m;
   bfile_t file;
   dec_format_t f;
+  pass_t p; stage_t st;
   SLAApiResult ret;
-  const uint8_t* src = d_data;
-  const uint8_t* hdr;
+  const uint8_t *src, *hdr;
   uint32_t* hbad;
-  uint8_t ok = 1;
-  uint32_t C, N, nb = 0, nblocks = 0, mode, k, ncl = 0, max_len = 0, max_lim = 0, P = 0, scan_cap = 0;
+  uint8_t ok = 1, state = DEV_PENDING;
+  uint32_t C, N, nb = 0, nblocks = 0, mode, k, ncl = 0, max_len = 0, max_lim = 0, P = 0, scan_cap = 0, size, chans = 0;
   uint64_t span, img_bytes;
   int verdict;
   float kernel_ms = 0.0f;
-  double t0 = now_ms(), t_up = 0.0, t_walk = 0.0, t_emit;
+  double t0 = now_ms(), t_up = 0.0, t_walk = 0.0, t_emit, t_hdr;
 
   if (d == NULL || d_data == NULL || dst == NULL || report == NULL || sample_format > SLA_HIP_PCM_F32
       || (ranges == NULL && range_capacity > 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   memset(report, 0, sizeof(*report));
   memset(d->timing, 0, sizeof(d->timing));
   memset(d->walk_stats, 0, sizeof(d->walk_stats));
-  /* the source, on the host, before anything is read; nothing is read or written before the caller's stream is here */
-  if (!src_region_ok(d_data, data_size)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
-  if (order_behind(d, stream) != 0 || res_fetch_headers(d, &src, &data_size, &ok, 1) != 0) { return SLA_APIRESULT_NG; }
-  hdr = (const uint8_t*)d->h_hdr.ptr;
   memset(&di, 0, sizeof(di));
   di.data = d_data; di.dst = dst; di.channel_stride = channel_stride; di.sample_stride = sample_stride;
   di.data_size = data_size; di.capacity = capacity;
-  /* the destination, with the header's channel count, before anything is written */
-  if (!dst_region_ok(&di, header_channels(hdr, data_size), (sample_format == SLA_HIP_PCM_S16) ? 2u : 4u)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  /* the opening of a resident call, on arrays of one item */
+  memset(&m, 0, sizeof(m));
+  m.dv = &di; m.bi = &bi; m.src = &src; m.size = &size; m.ok = &ok; m.state = &state; m.chans = &chans;
+  if (call_open(d, &m, 1, 1, pcm_esize(sample_format), stream, &t_hdr) != 0) { return SLA_APIRESULT_NG; }
+  if (state == DEV_REFUSED) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  hdr = (const uint8_t*)d->h_hdr.ptr;
   if ((ret = file_format(d, hdr, data_size, &f)) != SLA_APIRESULT_OK) { return ret; }
   if ((verdict = format_verdict(&f)) >= 0) { return verdict; }
   if (!lms_order_ok(f.lms)) { return SLA_APIRESULT_FAILED_TO_SYNTHESIZE; }
@@ -1415,7 +1438,7 @@ int sla_hip_salvage_resident(struct SLADecoder* d, const uint8_t* d_data, uint32
   memset(&bi, 0, sizeof(bi)); memset(&dev, 0, sizeof(dev)); memset(&file, 0, sizeof(file));
   bi.data = hdr; bi.data_size = data_size; bi.buffer_num_samples = N;
   dev.items = &di; dev.format = sample_format; dev.resident = 1;
-  file.f = f;
+  file.f = f; file.bytes = data_size;
   if (res_count_walk(d, &bi, &dev, &file, 1, &nblocks) != 0) { return SLA_APIRESULT_NG; }
   mode = (file.walk_err == SLA_APIRESULT_OK && file.extent == N) ? 1u : 2u;
   report->mode = mode;
@@ -1429,7 +1452,7 @@ int sla_hip_salvage_resident(struct SLADecoder* d, const uint8_t* d_data, uint32
     nb = file.nb;
   } else {
     /* the scan in count mode; nodes beyond the handle's capacity: once more with the exact count */
-    uint32_t cap = res_wide_capacity(d, data_size), attempt;
+    uint32_t cap = slai_dec_wide_capacity(d->wide_nodes, data_size), attempt;
     for (attempt = 0; ; attempt++) {
       if (dbuf_reserve(&d->d_wide, (size_t)SLA_HIP_DEC_SALVAGE_SCRATCH_BYTES(data_size, cap)) != 0
           || dbuf_reserve(&d->d_wres, 2 * sizeof(*scan)) != 0) { return SLA_APIRESULT_NG; }
@@ -1451,37 +1474,27 @@ int sla_hip_salvage_resident(struct SLADecoder* d, const uint8_t* d_data, uint32
   }
   t_walk = now_ms() - t0;
 
-  /* ---- the pass: one file, image at 0, planes at 0 */
-  span = ((uint64_t)N + DEC_BATCH_ALIGN - 1) / DEC_BATCH_ALIGN * DEC_BATCH_ALIGN;
-  img_bytes = ((uint64_t)data_size + 3) & ~(uint64_t)3;
-  if (dbuf_reserve(&d->d_image, img_bytes + 16) != 0
+  /* ---- the pass: one file of nb rows and N samples, image at 0, planes at 0 */
+  file.first = 0; file.nb = nb; file.extent = N;
+  if (pass_begin(d, &file, 1, &p) != 0
       || hbuf_reserve(&d->h_ptab, sizeof(uint32_t) * (size_t)nb + sizeof(*cl) * ((size_t)nb + 1)) != 0
-      || dbuf_reserve(&d->d_blocks, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb + 16) != 0
-      || dbuf_reserve(&d->d_info, sizeof(sla_hip_dec_info) * (size_t)nb + 16) != 0
-      || dbuf_reserve(&d->d_chan, sizeof(sla_hip_dec_chan) * (size_t)nb * C + 16) != 0
-      || dbuf_reserve(&d->d_kint, sizeof(int32_t) * (size_t)nb * C * (f.order + 1) + 16) != 0
-      || dbuf_reserve(&d->d_planes, sizeof(int32_t) * (size_t)span * C) != 0
-      || dbuf_reserve(&d->d_crcf, sizeof(uint32_t) * 2 * (size_t)nb + 16) != 0
-      || host_tables_reserve(d, nb) != 0 || res_events(d) != 0) { return SLA_APIRESULT_NG; }
+      || host_tables_reserve(d, nb) != 0) { return SLA_APIRESULT_NG; }
+  span = p.span; img_bytes = p.img_bytes;
   hbad = (uint32_t*)d->h_ptab.ptr;
   cl = (sla_hip_dec_conceal*)(hbad + nb);
   if (nb > 0 && mode == 1u) {
     sla_hip_dec_block* db = (sla_hip_dec_block*)d->d_blocks.ptr;
     uint32_t* dbad = (uint32_t*)d->d_crcf.ptr + nb;
-    file.first = 0;
-    if (res_stage_pass(d, &bi, &dev, &file, 1, nb, img_bytes) != 0
+    if (res_stage_pass(d, &bi, &dev, &file, 1, &p, &st) != 0
         || sla_hip_launch_salvage_crc((const uint8_t*)d->d_image.ptr, db, (const uint32_t*)d->d_crcf.ptr, nb, dbad, d->stream) != 0
         || hipMemcpyAsync(hbad, dbad, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, d->stream) != hipSuccess
         || pass_kernels(d, &f, nb, 0, img_bytes, span, &kernel_ms) != 0
-        || res_finish_pass(d, &file, 1, &t_up, &t_walk) != 0) { return SLA_APIRESULT_NG; }
+        || res_finish_pass(d, &st, &file, 1, &t_up, &t_walk) != 0) { return SLA_APIRESULT_NG; }
   } else if (nb > 0) {
     sla_hip_dec_block* db = (sla_hip_dec_block*)d->d_blocks.ptr;
-    sla_hip_dec_gather* gt;
-    if (hbuf_reserve(&d->h_src, sizeof(*gt)) != 0 || dbuf_reserve(&d->d_src, sizeof(*gt)) != 0) { return SLA_APIRESULT_NG; }
-    gt = (sla_hip_dec_gather*)d->h_src.ptr;
-    gt->src = d_data; gt->dst_off = 0; gt->bytes = data_size; gt->reserved = 0;
-    if (hipMemcpyAsync(d->d_src.ptr, gt, sizeof(*gt), hipMemcpyHostToDevice, d->stream) != hipSuccess
-        || sla_hip_launch_dec_gather((const sla_hip_dec_gather*)d->d_src.ptr, 1, data_size, (uint8_t*)d->d_image.ptr, img_bytes, d->stream) != 0
+    if (stage_tables(d, 1, sizeof(sla_hip_dec_walk_file), sizeof(sla_hip_dec_walk_result), &st) != 0) { return SLA_APIRESULT_NG; }
+    st.gt->src = d_data; st.gt->dst_off = 0; st.gt->bytes = data_size;
+    if (stage_gather(d, &st, 1, data_size, img_bytes) != 0
         || salvage_scan_launch(d, &wf, C, scan_cap, 1, db, (uint64_t*)(db + nb), (uint32_t*)d->d_crcf.ptr, &scan[1]) != 0
         || hipMemcpyAsync(d->h_blocks, db, sizeof(*db) * (size_t)nb, hipMemcpyDeviceToHost, d->stream) != hipSuccess
         || hipMemsetAsync(d->d_info.ptr, 0, sizeof(sla_hip_dec_info) * nb, d->stream) != hipSuccess
@@ -1517,8 +1530,7 @@ int sla_hip_salvage_resident(struct SLADecoder* d, const uint8_t* d_data, uint32
   }
   if (emit_entry(&e, &di, 0, 0, N, C, f.ms, 32u - f.bps + f.lshift, f.bps, &max_lim) != 0
       && emit_run(d, (const int32_t*)d->d_planes.ptr, span, &e, 1, max_lim, sample_format, &kernel_ms) != 0) { return SLA_APIRESULT_NG; }
-  d->timing[0] = (float)t_up; d->timing[1] = (float)t_walk; d->timing[2] = kernel_ms; d->timing[3] = (float)(now_ms() - t_emit);
-  d->timing[4] = (float)(now_ms() - t0); d->timing[5] = 1.0f;
+  call_close(d, NULL, t0, t_up, t_walk, kernel_ms, now_ms() - t_emit, 1);
   return (report->blocks_concealed != 0 || report->samples_lost != 0) ? SLA_APIRESULT_DETECT_DATA_CORRUPTION : SLA_APIRESULT_OK;
 }
 
@@ -1526,11 +1538,9 @@ int sla_hip_salvage_resident(struct SLADecoder* d, const uint8_t* d_data, uint32
  * capacity is the header's num_samples and go through batch_run with the WAV emit as the last leg (wav_out_t). */
 static int decode_wav_impl(struct SLADecoder* d, sla_hip_wav_item* items, uint32_t num_items, int resident, sla_hip_stream_t stream)
 {
+  call_mem_t m;
   sla_hip_decode_item* bi;
   sla_hip_decode_device_item* di;
-  const uint8_t** src;
-  uint32_t *size, *fbytes, *wbits;
-  uint8_t* ok;
   dev_out_t dev;
   wav_out_t w;
   uint32_t i;
@@ -1538,66 +1548,46 @@ static int decode_wav_impl(struct SLADecoder* d, sla_hip_wav_item* items, uint32
   double t_hdr = 0.0;
   if (d == NULL || (items == NULL && num_items > 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if (num_items == 0) { memset(d->timing, 0, sizeof(d->timing)); return 0; }
-  bi = (sla_hip_decode_item*)calloc(num_items, sizeof(*bi));
-  di = (sla_hip_decode_device_item*)calloc(num_items, sizeof(*di));
-  src = (const uint8_t**)calloc(num_items, sizeof(*src));
-  size = (uint32_t*)calloc(num_items, sizeof(*size));
-  fbytes = (uint32_t*)calloc(num_items, sizeof(*fbytes));
-  wbits = (uint32_t*)calloc(num_items, sizeof(*wbits));
-  ok = (uint8_t*)calloc(num_items, 1);
+  if (call_mem_new(&m, num_items) != 0) { return SLA_APIRESULT_NG; }
+  bi = m.bi; di = m.dv;
   memset(&dev, 0, sizeof(dev)); memset(&w, 0, sizeof(w));
   dev.items = di; dev.resident = resident; dev.wav = &w;
-  dev.state = (uint8_t*)calloc(num_items, 1);
-  dev.chans = (uint32_t*)calloc(num_items, sizeof(uint32_t));
-  w.items = items; w.host = !resident;
-  w.hold = (int32_t*)calloc(num_items, sizeof(int32_t));
-  w.rate = (uint32_t*)calloc(num_items, sizeof(uint32_t));
-  w.delivered = (uint8_t*)calloc(num_items, 1);
-  if (bi == NULL || di == NULL || src == NULL || size == NULL || fbytes == NULL || wbits == NULL || ok == NULL || dev.state == NULL || dev.chans == NULL || w.hold == NULL
-      || w.rate == NULL || w.delivered == NULL) { rc = SLA_APIRESULT_NG; goto out; }
-  /* the sources, on the host, before anything of an item is read */
+  w.items = items; w.host = !resident; w.hold = m.hold; w.rate = m.rate; w.delivered = m.delivered;
   for (i = 0; i < num_items; i++) {
-    src[i] = items[i].src; size[i] = items[i].src_size;
-    ok[i] = (uint8_t)(resident ? src_region_ok(items[i].src, items[i].src_size) : (items[i].src != NULL));
+    const sla_hip_wav_item* it = &items[i];
+    di[i].data = it->src; di[i].data_size = it->src_size; di[i].dst = it->dst; di[i].channel_stride = 1; di[i].sample_stride = 1;
+    m.ok[i] = (it->src != NULL);
     items[i].output_size = 0; items[i].num_samples = 0;
   }
-  /* nothing is read or written before the caller's stream has reached this call */
-  if (order_behind(d, stream) != 0) { rc = SLA_APIRESULT_NG; goto out; }
-  if (resident) {
-    t_hdr = now_ms();
-    if (res_fetch_headers(d, src, size, ok, num_items) != 0) { rc = SLA_APIRESULT_NG; goto out; }
-    t_hdr = now_ms() - t_hdr;
-  }
+  /* the destinations are this call's to check: they hold what each header says */
+  if (call_open(d, &m, num_items, resident, 0, stream, &t_hdr) != 0) { rc = SLA_APIRESULT_NG; goto out; }
   for (i = 0; i < num_items; i++) {
     const sla_hip_wav_item* it = &items[i];
     struct SLAHeaderInfo h;
     SLAApiResult r;
     uint64_t bytes;
-    di[i].data = it->src; di[i].data_size = it->src_size; di[i].dst = it->dst; di[i].channel_stride = 1; di[i].sample_stride = 1;
-    bi[i].data = resident ? (const uint8_t*)d->h_hdr.ptr + (size_t)i * RES_HDR_SLOT : it->src;
-    bi[i].data_size = it->src_size; bi[i].buffer = NULL;
-    if (!ok[i] || it->dst == NULL) { dev.state[i] = DEV_REFUSED; continue; }
+    if (m.state[i] == DEV_REFUSED || it->dst == NULL) { m.state[i] = DEV_REFUSED; continue; }
     r = SLADecoder_DecodeHeader(bi[i].data, it->src_size, &h);
     if (r != SLA_APIRESULT_OK) { continue; }                    /* (batch_run gives the header's code) */
     bi[i].buffer_num_samples = di[i].capacity = h.num_samples;
-    dev.chans[i] = h.wave_format.num_channels; w.rate[i] = h.wave_format.sampling_rate;
+    m.chans[i] = h.wave_format.num_channels; w.rate[i] = h.wave_format.sampling_rate;
     if (!(h.wave_format.bit_per_sample == 8 || h.wave_format.bit_per_sample == 16 || h.wave_format.bit_per_sample == 24
           || h.wave_format.bit_per_sample == 32)) { w.hold[i] = SLA_APIRESULT_INVALID_HEADER_FORMAT; continue; }
     bytes = (uint64_t)SLA_HIP_WAV_HEADER_BYTES + (uint64_t)h.num_samples * h.wave_format.num_channels * (h.wave_format.bit_per_sample / 8);
     if (bytes > 0xFFFFFFFFull || bytes > it->dst_capacity) { w.hold[i] = SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE; continue; }
-    fbytes[i] = (uint32_t)bytes; wbits[i] = h.wave_format.bit_per_sample;
-    if (resident && !slai_device_region_ok(it->dst, 1, 2, 0, bytes - 1, 1, -1)) { dev.state[i] = DEV_REFUSED; }
+    m.fbytes[i] = (uint32_t)bytes; m.wbits[i] = h.wave_format.bit_per_sample;
+    if (resident && !slai_device_region_ok(it->dst, 1, 2, 0, bytes - 1, 1, -1)) { m.state[i] = DEV_REFUSED; }
   }
-  rc = batch_run(d, bi, num_items, &dev);
+  rc = batch_run(d, bi, num_items, &dev, &m);
   d->timing[0] += (float)t_hdr;
   for (i = 0; i < num_items; i++) {
     items[i].result = (bi[i].result == SLA_APIRESULT_OK && w.hold[i] != 0) ? w.hold[i] : bi[i].result;
-    if (rc == 0 && !w.delivered[i] && items[i].result == SLA_APIRESULT_OK && fbytes[i] == SLA_HIP_WAV_HEADER_BYTES) {
+    if (rc == 0 && !w.delivered[i] && items[i].result == SLA_APIRESULT_OK && m.fbytes[i] == SLA_HIP_WAV_HEADER_BYTES) {
       /* a file of no samples joins no pass (format_verdict): its WAV is the header alone, written here */
       uint8_t hdr[SLA_HIP_WAV_HEADER_BYTES];
       sla_hip_wav_info info;
       memset(&info, 0, sizeof(info));
-      info.num_channels = dev.chans[i]; info.bits_per_sample = wbits[i]; info.sampling_rate = w.rate[i]; info.data_off = SLA_HIP_WAV_HEADER_BYTES;
+      info.num_channels = m.chans[i]; info.bits_per_sample = m.wbits[i]; info.sampling_rate = w.rate[i]; info.data_off = SLA_HIP_WAV_HEADER_BYTES;
       (void)sla_hip_wav_header(&info, hdr);
       if (!resident) { memcpy(items[i].dst, hdr, sizeof(hdr)); w.delivered[i] = 1; }
       else if (hipMemcpyAsync(items[i].dst, hdr, sizeof(hdr), hipMemcpyHostToDevice, d->stream) == hipSuccess
@@ -1606,13 +1596,13 @@ static int decode_wav_impl(struct SLADecoder* d, sla_hip_wav_item* items, uint32
     }
     if (rc == 0 && w.delivered[i]) {
       items[i].num_samples = bi[i].output_num_samples;
-      items[i].output_size = fbytes[i];
+      items[i].output_size = m.fbytes[i];
     } else if (items[i].result == SLA_APIRESULT_OK) {
       items[i].result = SLA_APIRESULT_INSUFFICIENT_DATA_SIZE;   /* (an OK decode that stopped short of the header's samples) */
     }
   }
 out:
-  free(bi); free(di); free((void*)src); free(size); free(fbytes); free(wbits); free(ok); free(dev.state); free(dev.chans); free(w.hold); free(w.rate); free(w.delivered);
+  free(m.base);
   return rc;
 }
 
@@ -1650,9 +1640,10 @@ out:
 
 /* ------------------------------------------------------------------------------------------------------------
  * sla_hip_decode_windows_resident (include/sla_hip.h): sla_hip_decode_batch_resident for a window of samples per item.
- * The source and destination checks, the header gather and pass, the grouping, the pass caps, the kernels, the
- * examination criteria and the emit are that call's code; what is the window's own is the walk (k_dec_walk_window: only
- * the blocks the window overlaps get a row), the gather of each item's byte range in place of its whole file, and the
+ * The opening (call_open), the grouping and the pass caps (pass_cut), the layout and reserve (pass_begin), the resident
+ * stage, the kernels, the examination criteria, the emit and the zero fill are that call's code.  The window's own: the
+ * walk (k_dec_walk_window: only the blocks the window overlaps get a row), so that a file's bytes in a pass are the byte
+ * range of its kept blocks and not its whole stream; the refusal of bad hints and of a start behind the file; and the
  * all-or-nothing outcome: no samples before a failing block, no resync.
  * ------------------------------------------------------------------------------------------------------------ */
 static void win_walk_entry(sla_hip_dec_window_file* w, const sla_hip_decode_window_item* it, uint32_t total)
@@ -1663,7 +1654,7 @@ static void win_walk_entry(sla_hip_dec_window_file* w, const sla_hip_decode_wind
 }
 
 /* The count-mode window walk of files[0, nf): one launch, one small copy home; wres[item] is each item's result, from
- * which every file's first / nb / walk_err / extent are set, and *nblocks; makes room for that many rows in the host tables. */
+ * which every file's first / nb / walk_err / extent / bytes are set, and *nblocks; makes room for that many rows in the host tables. */
 static int win_count_walk(struct SLADecoder* d, const sla_hip_decode_window_item* items, bfile_t* files, uint32_t nf,
                           sla_hip_dec_window_result* wres, uint32_t* nblocks)
 {
@@ -1688,6 +1679,7 @@ static int win_count_walk(struct SLADecoder* d, const sla_hip_decode_window_item
     wres[files[i].item] = wr[i];
     files[i].first = (uint32_t)total; files[i].nb = wr[i].num_blocks;
     files[i].walk_err = (SLAApiResult)wr[i].stop; files[i].extent = wr[i].end_sample - wr[i].first_sample;
+    files[i].bytes = wr[i].end_byte - wr[i].first_byte;
     total += wr[i].num_blocks;
   }
   if (total > 0xFFFFFFFFull || host_tables_reserve(d, (uint32_t)total) != 0) { return -1; }
@@ -1726,46 +1718,32 @@ static int win_pass(struct SLADecoder* d, sla_hip_decode_window_item* items, con
   const dec_format_t* f = &files[0].f;
   const uint32_t C = f->C, first = files[0].first;
   const int lms_ok = lms_order_ok(f->lms);
-  uint64_t img_bytes = 0, span = 0;
-  uint32_t nb = 0, i, ne = 0, max_lim = 0;
+  uint64_t img_bytes, span;
+  uint32_t nb, i, ne = 0, max_lim = 0;
   sla_hip_dec_emit* et;
+  pass_t p;
   double t;
 
-  for (i = 0; i < nf; i++) {
-    const sla_hip_dec_window_result* r = &wres[files[i].item];
-    files[i].img_off = img_bytes; img_bytes += ((uint64_t)(r->end_byte - r->first_byte) + 3) & ~(uint64_t)3;
-    files[i].plane_off = span; span += ((uint64_t)files[i].extent + DEC_BATCH_ALIGN - 1) / DEC_BATCH_ALIGN * DEC_BATCH_ALIGN;
-    nb += files[i].nb;
-    d->win_stats[2] += r->end_byte - r->first_byte;
-  }
-  d->win_stats[3] += span;
-  if (span == 0) { span = 1; }
-  if (dbuf_reserve(&d->d_image, img_bytes + 16) != 0 || hbuf_reserve(&d->h_ptab, sizeof(sla_hip_dec_emit) * (size_t)nf) != 0
-      || dbuf_reserve(&d->d_blocks, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb) != 0
-      || dbuf_reserve(&d->d_info, sizeof(sla_hip_dec_info) * nb) != 0
-      || dbuf_reserve(&d->d_chan, sizeof(sla_hip_dec_chan) * (size_t)nb * C) != 0
-      || dbuf_reserve(&d->d_kint, sizeof(int32_t) * (size_t)nb * C * (f->order + 1)) != 0
-      || dbuf_reserve(&d->d_planes, sizeof(int32_t) * (size_t)span * C) != 0) { return -1; }
+  if (pass_begin(d, files, nf, &p) != 0 || hbuf_reserve(&d->h_ptab, sizeof(sla_hip_dec_emit) * (size_t)nf) != 0) { return -1; }
+  img_bytes = p.img_bytes; span = p.span; nb = p.nb;
+  for (i = 0; i < nf; i++) { d->win_stats[2] += files[i].bytes; }
+  d->win_stats[3] += p.regions;
 
   if (nb > 0) {
     /* ---- the stage: the byte ranges gathered into the pass image, the walk in write mode; then the kernels */
+    stage_t st;
     sla_hip_dec_gather* gt;
     sla_hip_dec_window_file* wt;
-    sla_hip_dec_window_result* wr;
-    sla_hip_dec_block* db;
+    const sla_hip_dec_window_result* wr;
     uint32_t ng = 0, max_bytes = 0;
-    float ms = 0.0f;
-    if (hbuf_reserve(&d->h_src, (sizeof(*gt) + sizeof(*wt) + sizeof(*wr)) * (size_t)nf) != 0
-        || dbuf_reserve(&d->d_src, (sizeof(*gt) + sizeof(*wt)) * (size_t)nf) != 0 || dbuf_reserve(&d->d_wres, sizeof(*wr) * (size_t)nf) != 0
-        || dbuf_reserve(&d->d_crcf, sizeof(uint32_t) * (size_t)nb) != 0 || res_events(d) != 0) { return -1; }
-    gt = (sla_hip_dec_gather*)d->h_src.ptr;
-    wt = (sla_hip_dec_window_file*)(gt + nf);
-    wr = (sla_hip_dec_window_result*)(wt + nf);
-    memset(gt, 0, sizeof(*gt) * (size_t)nf);
+    if (stage_tables(d, nf, sizeof(*wt), sizeof(*wr), &st) != 0) { return -1; }
+    gt = st.gt;
+    wt = (sla_hip_dec_window_file*)st.wt;
+    wr = (const sla_hip_dec_window_result*)st.wr;
     for (i = 0; i < nf; i++) {
       const sla_hip_decode_window_item* it = &items[files[i].item];
       const sla_hip_dec_window_result* r = &wres[files[i].item];
-      const uint32_t range = r->end_byte - r->first_byte;
+      const uint32_t range = files[i].bytes;
       if (range > 0) {
         gt[ng].src = it->data + r->first_byte; gt[ng].dst_off = files[i].img_off; gt[ng].bytes = range; gt[ng].reserved = 0;
         ng++;
@@ -1775,22 +1753,8 @@ static int win_pass(struct SLADecoder* d, sla_hip_decode_window_item* items, con
       wt[i].img_off = files[i].img_off; wt[i].range_bytes = range; wt[i].base_byte = r->first_byte; wt[i].base_sample = r->first_sample;
       wt[i].plane_off = (uint32_t)files[i].plane_off; wt[i].first = files[i].first - first; wt[i].max_rows = files[i].nb;
     }
-    db = (sla_hip_dec_block*)d->d_blocks.ptr;
-    BCHK(hipMemcpyAsync(d->d_src.ptr, gt, (sizeof(*gt) + sizeof(*wt)) * (size_t)nf, hipMemcpyHostToDevice, d->stream));
-    BCHK(hipEventRecord(d->ev_src[0], d->stream));
-    BRC(sla_hip_launch_dec_gather((const sla_hip_dec_gather*)d->d_src.ptr, ng, max_bytes, (uint8_t*)d->d_image.ptr, img_bytes, d->stream));
-    BCHK(hipEventRecord(d->ev_src[1], d->stream));
-    BRC(sla_hip_launch_dec_walk_window((const sla_hip_dec_window_file*)((const sla_hip_dec_gather*)d->d_src.ptr + nf), nf,
-                                       d->cfg.max_num_block_samples, (sla_hip_dec_window_result*)d->d_wres.ptr, db, (uint64_t*)(db + nb),
-                                       (uint32_t*)d->d_crcf.ptr, d->stream));
-    BCHK(hipMemcpyAsync(wr, d->d_wres.ptr, sizeof(*wr) * nf, hipMemcpyDeviceToHost, d->stream));
-    BCHK(hipMemcpyAsync(d->h_blocks + first, db, sizeof(*db) * (size_t)nb, hipMemcpyDeviceToHost, d->stream));
-    BCHK(hipMemcpyAsync(d->h_crcf + first, d->d_crcf.ptr, sizeof(uint32_t) * (size_t)nb, hipMemcpyDeviceToHost, d->stream));
-    BCHK(hipEventRecord(d->ev_src[2], d->stream));
-    BCHK(hipMemsetAsync(d->d_info.ptr, 0, sizeof(sla_hip_dec_info) * nb, d->stream));
-    if (pass_kernels(d, f, nb, first, img_bytes, span, kernel_ms) != 0) { return -1; }
-    if (hipEventElapsedTime(&ms, d->ev_src[0], d->ev_src[1]) == hipSuccess) { *t_gather += ms; }
-    if (hipEventElapsedTime(&ms, d->ev_src[1], d->ev_src[2]) == hipSuccess) { *t_walk += ms; }
+    if (stage_queue(d, &st, files, nf, 1, ng, max_bytes, &p) != 0 || pass_kernels(d, f, nb, first, img_bytes, span, kernel_ms) != 0) { return -1; }
+    stage_times(d, t_gather, t_walk);
     /* a file whose chain changed since it was counted fails the call */
     for (i = 0; i < nf; i++) { if (memcmp(&wr[i], &wres[files[i].item], sizeof(wr[i])) != 0) { return -1; } }
   }
@@ -1817,16 +1781,10 @@ int sla_hip_decode_windows_resident(struct SLADecoder* d, sla_hip_decode_window_
                                     uint32_t sample_format, uint32_t flags, sla_hip_stream_t stream)
 {
   const uint32_t zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u;
-  const uint64_t esize = (sample_format == SLA_HIP_PCM_S16) ? 2u : 4u;
-  sla_hip_decode_device_item* dv;
-  sla_hip_dec_window_result* wres;
+  call_mem_t m;
   bfile_t* files;
-  const uint8_t** src;
-  uint32_t *size, *chans;
-  uint8_t *ok, *state;
-  struct SLAWaveFormat wf_after;
-  struct SLAEncodeParameter ep_after;
-  uint32_t flag_after, nf = 0, nblocks = 0, passes = 0, i, p0;
+  fmt_mark_t after;
+  uint32_t nf = 0, nblocks = 0, passes = 0, i, p0;
   int rc = 0;
   float kernel_ms = 0.0f;
   double t0 = now_ms(), t_gather = 0.0, t_walk = 0.0, t_down = 0.0, t;
@@ -1836,63 +1794,45 @@ int sla_hip_decode_windows_resident(struct SLADecoder* d, sla_hip_decode_window_
   memset(d->timing, 0, sizeof(d->timing));
   memset(d->win_stats, 0, sizeof(d->win_stats));
   if (num_items == 0) { return 0; }
-  wf_after = d->wave_format; ep_after = d->encode_param; flag_after = d->status_flag;
-  dv = (sla_hip_decode_device_item*)calloc(num_items, sizeof(*dv));
-  wres =(sla_hip_dec_window_result*)calloc(num_items, sizeof(*wres));
-  files = (bfile_t*)calloc(num_items, sizeof(*files));
-  src = (const uint8_t**)calloc(num_items, sizeof(*src));
-  size = (uint32_t*)calloc(num_items, sizeof(*size));
-  chans = (uint32_t*)calloc(num_items, sizeof(*chans));
-  ok = (uint8_t*)calloc(num_items, 1);
-  state = (uint8_t*)calloc(num_items, 1);
-  if (dv == NULL || wres == NULL || files == NULL || src == NULL || size == NULL || chans == NULL || ok == NULL || state == NULL) {
-    rc = SLA_APIRESULT_NG; goto out;
-  }
-  /* the sources and the hints, on the host, before anything of an item is read */
+  fmt_mark(d, &after);
+  if (call_mem_new(&m, num_items) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+  files = m.files;
+  /* the items as device items of the resident call (capacity = length); a bad hint refuses an item as a bad source does */
   for (i = 0; i < num_items; i++) {
     const sla_hip_decode_window_item* it = &items[i];
-    dv[i].data = it->data; dv[i].dst = it->dst; dv[i].channel_stride = it->channel_stride; dv[i].sample_stride = it->sample_stride;
-    dv[i].data_size = it->data_size; dv[i].capacity = it->length;
-    src[i] = it->data; size[i] = it->data_size;
-    ok[i] = (uint8_t)(src_region_ok(it->data, it->data_size)
-                      && (it->seek_byte == 0 ? it->seek_sample == 0 : it->seek_byte >= SLA_HEADER_SIZE) && it->seek_sample <= it->start);
+    sla_hip_decode_device_item* dv = &m.dv[i];
+    dv->data = it->data; dv->dst = it->dst; dv->channel_stride = it->channel_stride; dv->sample_stride = it->sample_stride;
+    dv->data_size = it->data_size; dv->capacity = it->length;
+    m.ok[i] = (uint8_t)((it->seek_byte == 0 ? it->seek_sample == 0 : it->seek_byte >= SLA_HEADER_SIZE) && it->seek_sample <= it->start);
   }
-  /* nothing is read or written before the caller's stream has reached this call */
-  if (order_behind(d, stream) != 0) { rc = SLA_APIRESULT_NG; goto out; }
-  t = now_ms();
-  if (res_fetch_headers(d, src, size, ok, num_items) != 0) { rc = SLA_APIRESULT_NG; goto out; }
-  t_gather += now_ms() - t;
+  if (call_open(d, &m, num_items, 1, pcm_esize(sample_format), stream, &t_gather) != 0) { rc = SLA_APIRESULT_NG; goto out; }
 
-  /* ---- headers in item order, as in batch_run; the destinations are checked with each header's channel count first */
+  /* ---- headers in item order, as in batch_run */
   t = now_ms();
   for (i = 0; i < num_items; i++) {
     sla_hip_decode_window_item* it = &items[i];
-    const uint8_t* hdr = (const uint8_t*)d->h_hdr.ptr + (size_t)i * RES_HDR_SLOT;
+    const uint8_t* hdr = m.bi[i].data;
     dec_format_t f;
     SLAApiResult ret;
     int verdict;
     it->output_num_samples = 0; it->first_block_byte = 0; it->first_block_sample = 0;
-    state[i] = DEV_REFUSED; it->result = SLA_APIRESULT_INVALID_ARGUMENT;
-    if (!ok[i]) { continue; }
-    chans[i] = header_channels(hdr, it->data_size);
-    if (!dst_region_ok(&dv[i], chans[i], esize)) { continue; }
-    state[i] = DEV_PENDING;
+    it->result = SLA_APIRESULT_INVALID_ARGUMENT;
+    if (m.state[i] == DEV_REFUSED) { continue; }
     if ((ret = file_format(d, hdr, it->data_size, &f)) != SLA_APIRESULT_OK) { it->result = ret; continue; }
-    if (it->start > f.total) { state[i] = DEV_REFUSED; continue; }
+    if (it->start > f.total) { m.state[i] = DEV_REFUSED; continue; }
     if ((verdict = format_verdict(&f)) >= 0) { it->result = verdict; continue; }
     it->result = SLA_APIRESULT_OK;
     if (it->start == f.total || it->length == 0) { continue; }       /* OK, no samples: nothing is decoded */
-    files[nf].item = i; files[nf].f = f;
-    state[i] = DEV_DECODED;
+    files[nf].item = i; files[nf].f = f; m.state[i] = DEV_DECODED;
     nf++;
   }
-  wf_after = d->wave_format; ep_after = d->encode_param; flag_after = d->status_flag;
+  fmt_mark(d, &after);
 
   /* ---- windows that share the launch parameters next to each other, every chain walked up to its window's end */
-  qsort(files, nf, sizeof(*files), bfile_cmp);
-  if (win_count_walk(d, items, files, nf, wres, &nblocks) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+  qsort(files, nf, sizeof(*files), slai_dec_file_cmp);
+  if (win_count_walk(d, items, files, nf, m.wres, &nblocks) != 0) { rc = SLA_APIRESULT_NG; goto out; }
   for (i = 0; i < nf; i++) {
-    const sla_hip_dec_window_result* r = &wres[files[i].item];
+    const sla_hip_dec_window_result* r = &m.wres[files[i].item];
     items[files[i].item].first_block_byte = r->first_byte; items[files[i].item].first_block_sample = r->first_sample;
     d->win_stats[0] += r->skipped; d->win_stats[1] += r->num_blocks;
   }
@@ -1900,16 +1840,8 @@ int sla_hip_decode_windows_resident(struct SLADecoder* d, sla_hip_decode_window_
 
   /* ---- passes: batch_run's caps, an item costing its byte range and the samples of its kept blocks */
   for (p0 = 0; p0 < nf; ) {
-    uint64_t smp = 0, bytes = 0;
-    uint32_t p1 = p0;
-    while (p1 < nf && same_launch(&files[p1].f, &files[p0].f)) {
-      const sla_hip_dec_window_result* r = &wres[files[p1].item];
-      const uint64_t s1 = ((uint64_t)files[p1].extent + DEC_BATCH_ALIGN) * files[p1].f.C;
-      const uint64_t b1 = (uint64_t)(r->end_byte - r->first_byte) + 4;
-      if (p1 > p0 && (smp + s1 > SLA_HIP_DEC_BATCH_PASS || bytes + b1 > DEC_BATCH_PASS_BYTES)) { break; }
-      smp += s1; bytes += b1; p1++;
-    }
-    if (win_pass(d, items, dv, files + p0, p1 - p0, wres, sample_format, zero_fill, &t_gather, &t_walk, &t_down, &kernel_ms) != 0) {
+    const uint32_t p1 = pass_cut(files, p0, nf);
+    if (win_pass(d, items, m.dv, files + p0, p1 - p0, m.wres, sample_format, zero_fill, &t_gather, &t_walk, &t_down, &kernel_ms) != 0) {
       rc = SLA_APIRESULT_NG; goto out;
     }
     passes++;
@@ -1917,24 +1849,11 @@ int sla_hip_decode_windows_resident(struct SLADecoder* d, sla_hip_decode_window_
   }
 
   /* ---- destinations of items whose header gave a channel count but of which nothing was decoded: the zero fill */
-  if (zero_fill) {
-    sla_hip_dec_emit* et = (sla_hip_dec_emit*)calloc(num_items, sizeof(*et));
-    uint32_t ne = 0, max_lim = 0;
-    if (et == NULL) { rc = SLA_APIRESULT_NG; goto out; }
-    t = now_ms();
-    for (i = 0; i < num_items; i++) {
-      if (state[i] == DEV_PENDING) { ne += emit_entry(et + ne, &dv[i], 1, 0, 0, chans[i], 0, 0, 32, &max_lim); }
-    }
-    if (emit_run(d, NULL, 1, et, ne, max_lim, sample_format, &kernel_ms) != 0) { rc = SLA_APIRESULT_NG; }
-    free(et);
-    t_down += now_ms() - t;
-  }
+  if (zero_fill && zero_fill_pending(d, &m, m.dv, num_items, sample_format, &kernel_ms, &t_down) != 0) { rc = SLA_APIRESULT_NG; }
 
 out:
-  d->wave_format = wf_after; d->encode_param = ep_after; d->status_flag = flag_after;
-  d->timing[0] = (float)t_gather; d->timing[1] = (float)t_walk; d->timing[2] = kernel_ms; d->timing[3] = (float)t_down;
-  d->timing[4] = (float)(now_ms() - t0); d->timing[5] = (float)passes;
-  free(dv); free(wres); free(files); free((void*)src); free(size); free(chans); free(ok); free(state);
+  call_close(d, &after, t0, t_gather, t_walk, kernel_ms, t_down, passes);
+  free(m.base);
   return rc;
 }
 

@@ -101,6 +101,29 @@ uint32_t slai_verify_tables(const sla_hip_pack_block* pb, uint32_t num_blocks, c
                             sla_hip_verify_expect* expect, uint32_t* seg_of_block, uint64_t* compared,
                             uint32_t* max_block_samples);
 
+/* ---- sla_dec_plan.c: the pass arithmetic of the batch decoder (no device calls) --------- */
+#define SLAI_DEC_BATCH_ALIGN 64u         /* samples: every file's plane region starts on a 256-byte boundary */
+#define SLAI_DEC_WIDE_MAX    8u          /* resident files of one call that are walked wide, at most */
+typedef struct slai_dec_format { uint32_t C, total, bps, lshift, order, ntaps, lms, ms; } slai_dec_format;
+typedef struct slai_dec_file {
+  uint32_t        item;       /* index into the caller's items */
+  slai_dec_format f;          /* from its header */
+  uint32_t        bytes;      /* what a pass image holds of it: the whole stream, or the byte range of a window */
+  uint32_t        first, nb;  /* its blocks: rows [first, first + nb) of the host tables, positions in the file */
+  SLAApiResult    walk_err;
+  uint32_t        extent;     /* samples per channel its blocks write */
+  int             alone;      /* decoded on its own, in no pass */
+  int             wide;       /* resident: its chain is walked by sla_hip_launch_dec_walk_wide, not on a lane */
+  uint64_t        img_off;    /* its bytes in the pass image */
+  uint64_t        plane_off;  /* its region in the pass planes */
+} slai_dec_file;              /* 80 bytes */
+int      slai_dec_same_launch(const slai_dec_format* a, const slai_dec_format* b);
+int      slai_dec_file_cmp(const void* a, const void* b);
+uint32_t slai_dec_cut(const slai_dec_file* files, uint32_t p0, uint32_t n, uint64_t cap_samples, uint64_t cap_bytes);
+void     slai_dec_layout(slai_dec_file* files, uint32_t nf, uint64_t* img_bytes, uint64_t* span, uint32_t* nb);
+uint32_t slai_dec_wide_capacity(uint32_t option, uint32_t data_size);
+uint32_t slai_dec_pick_wide(const slai_dec_file* files, uint32_t nf, uint32_t threshold, uint32_t pick[SLAI_DEC_WIDE_MAX]);
+
 /* ---- sla_decoder.c: caller-owned device memory of the batch calls --------- */
 /* 1 when [0, C) x [0, n) of esize-byte elements at p (element (c, i) at c * channel_stride + i * sample_stride) is aligned,
  * its byte extent does not overflow, the runtime reports p as device memory (of `device` when >= 0) and the region lies

@@ -324,3 +324,70 @@ def test_empty_call(hip):
         assert dec.last_timing() == [0.0] * 6
     finally:
         dec.close()
+
+
+# ------------------------------------------------------------------ one pipeline behind every route
+
+def _every_route(dec, datas, caps):
+    """the batch through the host-source, the resident and the window route of ONE handle, windows being the whole clips
+    -> per route (results, the bits of every destination, passes)"""
+    srcs, keep = resident(datas)
+    routes = []
+    for route in ("host", "resident", "windows"):
+        outs = [TD.alloc((2, cap), S32_LEFT) for cap in caps]
+        if route == "host":
+            got = dec.decode_batch_into(datas, outs, S32_LEFT)
+        elif route == "resident":
+            got = dec.decode_resident_into(srcs, outs, S32_LEFT)
+        else:
+            got = [g[:2] for g in dec.decode_windows_into(srcs, [0] * len(datas), outs, S32_LEFT)]
+        routes.append((got, [TD.bits_of(o.cpu().numpy()) for o in outs], dec.last_timing()[5]))
+    return routes, srcs, keep
+
+
+def _same_on_every_route(routes):
+    (want, want_bits, want_passes), others = routes[0], routes[1:]
+    for got, bits, passes in others:
+        assert got == want and passes == want_passes
+        for i, (a, b) in enumerate(zip(bits, want_bits)):
+            assert a.shape == b.shape and np.array_equal(a, b), ("item", i)
+    return want, want_bits, want_passes
+
+
+def test_same_samples_on_every_route_and_handle_reuse_across_routes(hip):
+    """six short ragged clips in two formats (two passes), one with a header whose CRC fails (zero fill alone) and one whose
+    destination is refused (an empty tensor has no pointer): the host-source, the resident and the window route, windows
+    being the whole clips, deliver every item whole, refused or zero-filled -- the same bytes, codes and pass count on each.
+    The handle then takes a smaller batch through each route, and one intact clip through the salvage call."""
+    import torch
+    other = S.make_params(2, 16, 48000, 8, 1, 8, 1, 1, 4096, cap=(2, 4096, 16, 1, 8))       # PARCOR order 8: another launch key
+    lens = [2048, 5000, 9001, 12345, 16385, 20000]
+    pcms = [S.synth_pcm(2, n, 16, 48000, seed=950 + i) for i, n in enumerate(lens)]
+    even, odd = TB.encode_clips(hip, TB.C4, pcms[0::2]), TB.encode_clips(hip, other, pcms[1::2])
+    datas = [bytearray((even if i % 2 == 0 else odd)[i // 2]) for i in range(6)]
+    datas[1][20] ^= 0x04                                       # a header field changed, its CRC not: the fields are still delivered
+    datas = [bytes(d) for d in datas]
+    caps = list(lens)
+    caps[4] = 0                                                # no destination at all: refused before anything is read
+    dec = TB.make_decoder(hip)
+    try:
+        routes, srcs, keep = _every_route(dec, datas, caps)
+        got, bits, passes = _same_on_every_route(routes)
+        assert got == [(OK, 2048), (11, 0), (OK, 9001), (OK, 12345), (INVALID_ARGUMENT, 0), (OK, 20000)]
+        assert passes == 2
+        for i in (0, 2, 3, 5):
+            assert np.array_equal(bits[i], pcms[i])
+        assert bits[1].shape == (2, 5000) and not bits[1].any()
+        # the same handle, a smaller batch: scratch and tables cut for the larger one
+        small = [5, 0, 3]
+        routes2, srcs2, keep2 = _every_route(dec, [datas[i] for i in small], [lens[i] for i in small])
+        got2, bits2, passes2 = _same_on_every_route(routes2)
+        assert got2 == [(OK, lens[i]) for i in small] and passes2 == 2
+        for k, i in enumerate(small):
+            assert np.array_equal(bits2[k], pcms[i])
+        # and an intact clip through the salvage call of that handle
+        t, rep, ranges = dec.salvage_resident_tensor(srcs[2], dtype=torch.int32)
+        assert rep["result"] == OK and rep["mode"] == 1 and ranges == []
+        assert np.array_equal(t.cpu().numpy(), bits[2])
+    finally:
+        dec.close()
