@@ -1050,8 +1050,9 @@ int sla_hip_launch_dec_walk_window(const sla_hip_dec_window_file* d_files, uint3
  * The hint: seek_byte / seek_sample name a block start at or before the window (seek_byte 0: none, the walk starts at
  * the header).  first_block_byte / first_block_sample return the first kept block's position (0, 0 when the walk kept
  * none), a valid hint for any later window of the same bytes with start >= first_block_sample; a long file is served by
- * hints the caller keeps, there is no index object.  A hint is the caller's promise: a wrong one gives an error code or
- * wrong samples, never a read outside the source or a write outside the destination.
+ * hints the caller keeps (this call takes no index object: sla_hip_decode_windows_indexed does).  A hint is the caller's
+ * promise: a wrong one gives an error code or wrong samples, never a read outside the source or a write outside the
+ * destination.
  * The same source may appear in any number of items; each is decoded on its own.
  * How it runs: the header gather; the window walk in count mode over all items; items grouped by launch parameters and
  * cut into passes by sla_hip_decode_batch's caps, an item costing the bytes from its first kept block to the end of its
@@ -1080,6 +1081,143 @@ int sla_hip_decode_windows_resident(struct SLADecoder* decoder, sla_hip_decode_w
 /* Summed over the last sla_hip_decode_windows_resident: [0] blocks passed over, [1] blocks decoded, [2] stream bytes
  * gathered, [3] plane samples per channel reserved.  INVALID_ARGUMENT for a NULL argument. */
 int sla_hip_decoder_last_window_stats(const struct SLADecoder* decoder, uint64_t counters[4]);
+
+/* ---- A block index, and windows decoded from it without a host wait ----
+ * sla_hip_index is the block chain of one .sla stream, kept on the host: opaque, immutable, shareable between threads and
+ * handles.  It holds the stream's data_size, its first 43 bytes (fewer for a shorter stream), what SLADecoder_DecodeHeader
+ * made of them (result and SLAHeaderInfo), and -- when the header could be read (OK or DETECT_DATA_CORRUPTION) -- the chain
+ * walked from byte 43 by the whole-file walk's rules (sla_hip_launch_dec_walk) with capacity = the header's num_samples,
+ * NO cap on the block length (the format's 65 535) and enable_crc_check 0: rows {byte_off, byte_len, smp_off, num_samples} in
+ * file positions, no header-only rows, the walk's stop code and extent.
+ *   sla_hip_index_build           from host bytes; pure host code, no device.
+ *   sla_hip_index_build_resident  from device bytes, on the handle's stream behind `stream`: the header gather, then the walk
+ *                                 in count and in write mode; a stream of at least the handle's "wide_walk" bytes is walked
+ *                                 by sla_hip_launch_dec_walk_wide, an overflow of its nodes falls back to the lane.  Waits
+ *                                 for the device (it brings rows home).  INVALID_ARGUMENT for a source that is not device
+ *                                 memory or not inside its allocation.
+ * Both give byte-identical serialisations for the same bytes.  Return 0 and *index, INVALID_ARGUMENT for a NULL argument,
+ * NG for a device or allocation failure.
+ *   sla_hip_index_info            gives a sla_hip_index_summary; sla_hip_index_blocks copies rows [first, first + count)
+ *                                 (INVALID_ARGUMENT when that is not inside [0, num_blocks)); sla_hip_index_destroy (NULL
+ *                                 allowed).
+ *   sla_hip_index_serialized_bytes / _serialize / _deserialize: a little-endian blob, so that a data set can keep a sidecar
+ *   next to each file: magic "SLAX", version 1, data_size, header bytes held, header result, stop, extent, num_blocks, the 43
+ *   header bytes (zero padded to 44), the rows, and in its last two bytes the library's CRC16 (slai_crc16) of everything
+ *   before them.  _serialize returns the bytes written, 0 when `capacity` is too small.
+ * Deserialise refuses with INVALID_ARGUMENT, and keeps no allocation, for: a wrong magic or version; a wrong checksum; a
+ * truncated (or over-long) blob; rows that are not strictly ascending in bytes WITHOUT OVERLAP (a row starts at or behind the
+ * end of the one before it, so that the byte range from a window's first row to the end of its last holds every row of it
+ * whole) and cumulative in samples from sample 0; a row with byte_off < 43, byte_len < 11 or byte_off + byte_len > data_size;
+ * num_samples > 65535; an extent that is not the end of the last row or lies above the header's total; header fields that
+ * are not what DecodeHeader makes of the stored bytes.
+ * After this an index can be wrong about the bytes it is used with; it can never name a range outside [0, data_size).
+ * The shortest block: the builders follow the walk, which keeps a block whose size field + 6 is 8, 9 or 10 when 11 bytes are
+ * left (no encoder writes one; no decoder decodes one).  An index with such a row is built, read and used like any other,
+ * and serialises; its blob is one the deserialiser refuses (byte_len < 11), so it has no sidecar. */
+typedef struct sla_hip_index sla_hip_index;
+typedef struct sla_hip_index_block {
+  uint32_t byte_off;              /* the block's sync code in the file */
+  uint32_t byte_len;              /* size field + 6 */
+  uint32_t smp_off;               /* its first sample in the file */
+  uint32_t num_samples;
+} sla_hip_index_block;            /* 16 bytes */
+typedef struct sla_hip_index_summary {
+  uint32_t data_size;
+  uint32_t header_bytes;          /* bytes of the stream's head held: min(data_size, 43) */
+  int32_t  header_result;         /* SLADecoder_DecodeHeader's SLAApiResult */
+  uint32_t stop;                  /* why the walk ended: an SLAApiResult, OK when it reached the header's num_samples */
+  uint32_t extent;                /* samples per channel the rows cover */
+  uint32_t num_blocks;
+  struct SLAHeaderInfo header;    /* zero unless header_result is OK or DETECT_DATA_CORRUPTION */
+} sla_hip_index_summary;
+int      sla_hip_index_build(const uint8_t* data, uint32_t data_size, sla_hip_index** index);
+int      sla_hip_index_build_resident(struct SLADecoder* decoder, const uint8_t* d_data, uint32_t data_size,
+                                      sla_hip_stream_t stream, sla_hip_index** index);
+int      sla_hip_index_info(const sla_hip_index* index, sla_hip_index_summary* info);
+int      sla_hip_index_blocks(const sla_hip_index* index, uint32_t first, uint32_t count, sla_hip_index_block* out);
+void     sla_hip_index_destroy(sla_hip_index* index);
+uint64_t sla_hip_index_serialized_bytes(const sla_hip_index* index);
+uint64_t sla_hip_index_serialize(const sla_hip_index* index, uint8_t* out, uint64_t capacity);
+int      sla_hip_index_deserialize(const uint8_t* blob, uint64_t blob_bytes, sla_hip_index** index);
+
+/* The judge kernel of sla_hip_decode_windows_indexed (k_dec_judge): the examination of the synchronous window call, on the
+ * device.  One wave per item over its rows [first, first + nb) of the pass table.  A row's code is that of the first rule
+ * that applies:
+ *   1. stale index: the ten chain-header bytes at d_image + byte_off are not FF FF, size field + 6 == byte_len, sample
+ *      count == num_samples, or do not lie inside [0, image_bytes)                  -> DETECT_DATA_CORRUPTION
+ *   2. crc_check != 0 and d_info.crc != the big-endian field at byte 6              -> DETECT_DATA_CORRUPTION
+ *   3. d_info.type > 2                                                              -> INVALID_HEADER_FORMAT
+ *   4. d_info.type == 0 and lms_ok == 0                                             -> FAILED_TO_SYNTHESIZE
+ *   5. d_info.overrun or d_info.used_bytes != byte_len                              -> DETECT_DATA_CORRUPTION
+ * The item's result is the code of its LOWEST failing row, with none its `stop`; d_outcomes[outcome] = {result, result == OK
+ * ? ok_samples : 0}.  A failed item's emit entry d_emit[emit] (emit = 0xFFFFFFFF: it has none) gets done = 0 and fill_end =
+ * the item's fill_end, so that sla_hip_launch_dec_emit_batch behind it delivers nothing of it but the zero fill; entries of
+ * clean items are not touched.  Items with nb = 0 get their stop code.  An item whose rows do not lie inside [0, num_blocks)
+ * is judged NG; an outcome or emit position outside its table is not written.
+ * INVALID_ARGUMENT before any launch for a NULL item or outcome table, a NULL emit table with num_emit > 0, or a NULL image,
+ * block or info table with num_blocks > 0. */
+typedef struct sla_hip_window_outcome { int32_t result; uint32_t output_num_samples; } sla_hip_window_outcome;   /* 8 bytes */
+typedef struct sla_hip_dec_judge_item {
+  uint32_t first;                 /* the item's rows in d_blocks / d_info: [first, first + nb) */
+  uint32_t nb;
+  uint32_t stop;                  /* its result when no row fails: an SLAApiResult */
+  uint32_t ok_samples;            /* its output_num_samples when the result is OK */
+  uint32_t outcome;               /* where in d_outcomes */
+  uint32_t emit;                  /* its entry of d_emit, 0xFFFFFFFF for none */
+  uint32_t fill_end;              /* what a failed item's emit entry gets: the window's length with the zero fill, else 0 */
+  uint32_t reserved;
+} sla_hip_dec_judge_item;         /* 32 bytes */
+int sla_hip_launch_dec_judge(const uint8_t* d_image, uint64_t image_bytes, const sla_hip_dec_block* d_blocks,
+                             const sla_hip_dec_info* d_info, uint32_t num_blocks, const sla_hip_dec_judge_item* d_items,
+                             uint32_t num_items, uint32_t crc_check, uint32_t lms_ok, sla_hip_dec_emit* d_emit,
+                             uint32_t num_emit, sla_hip_window_outcome* d_outcomes, uint32_t num_outcomes,
+                             sla_hip_stream_t stream);
+
+/* sla_hip_decode_windows_resident from block indexes, QUEUED: the call returns when its work is enqueued, not when it has
+ * run.  Item i names a resident stream, its index (sla_hip_index_build* of those bytes, or a sidecar) and a window; d_outcomes
+ * is device memory for num_items outcomes.
+ * Contract: once the work `stream` holds at the time of the call has run, d_outcomes[i] and item i's destination hold exactly
+ * what sla_hip_decode_windows_resident gives the same bytes, window, format, flags and handle configuration, provided the
+ * index was built from those bytes: result and output_num_samples, every bit of [0, C) x [0, length), the zero fill, nothing
+ * written outside that region, whole-or-nothing delivery, no resync, enable_crc_check honoured, the per-item refusals (source
+ * and destination checks, start > num_samples, header failures, format verdicts, an LMS order the kernels do not run), and the
+ * handle's wave format and encode parameter afterwards.  The header is the index's, not the device's: the host reads no byte
+ * of the stream.  Also per item INVALID_ARGUMENT (nothing written) for a NULL index or index->data_size != data_size.
+ * A needed block longer than the handle's max_num_block_samples ends the item's rows there with INSUFFICIENT_BUFFER_SIZE, as
+ * the window walk does; for a window that reaches past the index's extent the index's stop code plays the walk's part.
+ * Outcomes the host knows at once (refusals, empty windows) travel through d_outcomes too: the caller reads one place.
+ * AN INDEX IS THE CALLER'S PROMISE, as a seek hint is.  Blocks in front of the window are not looked at.  Every needed
+ * block's chain header is compared with its row on the device (k_dec_judge, rule 1), so bytes that changed under an old index
+ * fail the window with DETECT_DATA_CORRUPTION or decode a block that still parses; whatever the index says, nothing outside
+ * [data, data + data_size) is read and nothing outside the destination is written.
+ * Ordering: the handle's stream waits on an event of `stream` before it reads or writes anything of the call; `stream` then
+ * waits on the handle's closing event, so work queued on `stream` after the call sees the destinations and outcomes written.
+ * How it runs, per pass (grouping and caps as in sla_hip_decode_windows_resident): the host lays out the gather table (one
+ * range per item, first needed block to the end of the last), the block rows and ends, the judge and the emit table straight
+ * from the indexes, into one slot of a ring of SLA_HIP_DEC_QUEUE_SLOTS page-locked staging slots, each guarded by an event; it
+ * queues the table upload, the gather, the decode kernels, the judge, the emit.  No stream synchronisation, no copy home.
+ * THE HOST MAY WAIT in two places only: a call that finds every ring slot still in flight waits for the oldest slot's
+ * upload; a call that must grow a device buffer (or a staging slot) waits for the device as the allocator does.  Every OTHER
+ * entry point of the handle first drains the handle's queued work: their staging is not ring-guarded.
+ * sla_hip_decoder_last_timing: [4] = the host's queueing time, zeros elsewhere.
+ * Returns 0; INVALID_ARGUMENT (nothing queued, nothing written) for a NULL decoder, a NULL d_outcomes or NULL items with
+ * num_items > 0, an unknown format or flag, d_outcomes that is not device memory for num_items outcomes; NG on a device or
+ * allocation failure. */
+#define SLA_HIP_DEC_QUEUE_SLOTS 4u
+typedef struct sla_hip_indexed_window_item {
+  const uint8_t* data;            /* in : a whole .sla stream in device memory, any byte alignment */
+  void*    dst;                   /* in : device memory */
+  uint64_t channel_stride;        /* in : elements */
+  uint64_t sample_stride;         /* in : elements (>= 1) */
+  const sla_hip_index* index;     /* in : the stream's block index */
+  uint32_t data_size;             /* in  */
+  uint32_t start;                 /* in : first sample of the window */
+  uint32_t length;                /* in : samples per channel of the window and of dst */
+  uint32_t reserved;
+} sla_hip_indexed_window_item;    /* 56 bytes */
+int sla_hip_decode_windows_indexed(struct SLADecoder* decoder, const sla_hip_indexed_window_item* items, uint32_t num_items,
+                                   uint32_t sample_format, uint32_t flags, sla_hip_window_outcome* d_outcomes,
+                                   sla_hip_stream_t stream);
 
 /* Decode-and-compare of blocks (option "verify" of the encoder; kernel k_verify_blocks): for every block of the table and
  * every channel, the decoded plane samples [smp_off, smp_off + num_samples) -- what dec_bits / dec_lms / dec_ltm /

@@ -141,6 +141,42 @@ class DecodeWindowItem(C.Structure):
                 ("first_block_byte", C.c_uint32), ("first_block_sample", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class IndexBlock(C.Structure):
+    """sla_hip_index_block (include/sla_hip.h): one row of a block index, positions in the file"""
+    _fields_ = [("byte_off", C.c_uint32), ("byte_len", C.c_uint32), ("smp_off", C.c_uint32), ("num_samples", C.c_uint32)]
+
+
+class IndexSummary(C.Structure):
+    """sla_hip_index_summary (include/sla_hip.h): what sla_hip_index_info returns"""
+    _fields_ = [("data_size", C.c_uint32), ("header_bytes", C.c_uint32), ("header_result", C.c_int32), ("stop", C.c_uint32),
+                ("extent", C.c_uint32), ("num_blocks", C.c_uint32), ("header", SLAHeaderInfo)]
+
+
+class IndexedWindowItem(C.Structure):
+    """sla_hip_indexed_window_item (include/sla_hip.h): one window of sla_hip_decode_windows_indexed"""
+    _fields_ = [("data", u8p), ("dst", C.c_void_p), ("channel_stride", C.c_uint64), ("sample_stride", C.c_uint64),
+                ("index", C.c_void_p), ("data_size", C.c_uint32), ("start", C.c_uint32), ("length", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class WindowOutcome(C.Structure):
+    """sla_hip_window_outcome (include/sla_hip.h): what sla_hip_decode_windows_indexed leaves per item, in device memory"""
+    _fields_ = [("result", C.c_int32), ("output_num_samples", C.c_uint32)]
+
+
+class DecJudgeItem(C.Structure):
+    """sla_hip_dec_judge_item (include/sla_hip.h): one item of sla_hip_launch_dec_judge"""
+    _fields_ = [("first", C.c_uint32), ("nb", C.c_uint32), ("stop", C.c_uint32), ("ok_samples", C.c_uint32),
+                ("outcome", C.c_uint32), ("emit", C.c_uint32), ("fill_end", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DecEmit(C.Structure):
+    """sla_hip_dec_emit (include/sla_hip.h): one entry of sla_hip_launch_dec_emit_batch"""
+    _fields_ = [("plane_off", C.c_uint64), ("channel_stride", C.c_uint64), ("sample_stride", C.c_uint64), ("dst", C.c_void_p),
+                ("done", C.c_uint32), ("fill_end", C.c_uint32), ("num_channels", C.c_uint32), ("mid_side", C.c_uint32),
+                ("shift", C.c_uint32), ("bits_per_sample", C.c_uint32)]
+
+
 class EncodeDeviceItem(C.Structure):
     """sla_hip_encode_device_item (include/sla_hip.h): one file of sla_hip_encode_batch_device"""
     _fields_ = [("src", C.c_void_p), ("channel_stride", C.c_uint64), ("sample_stride", C.c_uint64), ("data", u8p),
@@ -207,6 +243,7 @@ class LaunchExtra(C.Structure):
 # sample formats of sla_hip_decode_batch_device / sla_hip_encode_batch_device, flag of the former
 PCM_S32_LEFT, PCM_S32, PCM_S16, PCM_F32 = range(4)
 DEC_ZERO_FILL = 1
+DEC_QUEUE_SLOTS = 4              # SLA_HIP_DEC_QUEUE_SLOTS (include/sla_hip.h): the staging ring of sla_hip_decode_windows_indexed
 # sla_hip_salvage_range.reason
 SALVAGE_CRC, SALVAGE_UNDECODABLE, SALVAGE_GAP = 1, 2, 3
 SALVAGE_REASON = {SALVAGE_CRC: "crc", SALVAGE_UNDECODABLE: "undecodable", SALVAGE_GAP: "gap"}
@@ -381,6 +418,22 @@ def lib():
             L.sla_hip_dec_salvage_scratch_bytes.restype = C.c_uint64
             L.sla_hip_launch_salvage_crc.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
             L.sla_hip_launch_dec_conceal.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        if hasattr(L, "sla_hip_decode_windows_indexed"):     # (SLA_HIP_LIB may name an older build in an A/B run)
+            L.sla_hip_index_build.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+            L.sla_hip_index_build_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p)]
+            L.sla_hip_index_info.argtypes = [C.c_void_p, C.POINTER(IndexSummary)]
+            L.sla_hip_index_blocks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.sla_hip_index_destroy.argtypes = [C.c_void_p]
+            L.sla_hip_index_destroy.restype = None
+            L.sla_hip_index_serialized_bytes.argtypes = [C.c_void_p]
+            L.sla_hip_index_serialized_bytes.restype = C.c_uint64
+            L.sla_hip_index_serialize.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+            L.sla_hip_index_serialize.restype = C.c_uint64
+            L.sla_hip_index_deserialize.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+            L.sla_hip_decode_windows_indexed.argtypes = [C.c_void_p, C.POINTER(IndexedWindowItem), C.c_uint32, C.c_uint32,
+                                                         C.c_uint32, C.c_void_p, C.c_void_p]
+            L.sla_hip_launch_dec_judge.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                   C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
         _lib = L
     return _lib
 
@@ -463,6 +516,10 @@ EXPORTED_SYMBOLS = [
     # one resident stream decoded through damage (include/sla_hip.h)
     "sla_hip_salvage_resident", "sla_hip_launch_dec_salvage_scan", "sla_hip_dec_salvage_scratch_bytes",
     "sla_hip_launch_salvage_crc", "sla_hip_launch_dec_conceal",
+    # block indexes and the windows decoded from them, queued (include/sla_hip.h)
+    "sla_hip_index_build", "sla_hip_index_build_resident", "sla_hip_index_info", "sla_hip_index_blocks", "sla_hip_index_destroy",
+    "sla_hip_index_serialized_bytes", "sla_hip_index_serialize", "sla_hip_index_deserialize", "sla_hip_launch_dec_judge",
+    "sla_hip_decode_windows_indexed",
 ]
 
 
@@ -1011,6 +1068,101 @@ def shard_join(shard_images):
     return out.tobytes() + b"".join(bytes(img[43:]) for img in shard_images)
 
 
+INDEX_BLOCK_DTYPE = np.dtype([("byte_off", "<u4"), ("byte_len", "<u4"), ("smp_off", "<u4"), ("num_samples", "<u4")])
+
+
+class Index:
+    """the block index of one .sla stream (sla_hip_index, include/sla_hip.h): host memory, immutable.  Index.build(data)
+    walks host bytes, Decoder.index_resident device bytes; to_bytes / from_bytes are the sidecar format."""
+
+    def __init__(self, handle):
+        self._lib = lib()
+        self._h = handle
+        info = IndexSummary()
+        rc = self._lib.sla_hip_index_info(self._h, C.byref(info))
+        if rc != 0:
+            raise SlaError(rc, "sla_hip_index_info")
+        self._info = info
+
+    @classmethod
+    def build(cls, data):
+        """the index of a whole .sla stream in a bytes-like object (sla_hip_index_build: pure host code)"""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        h = C.c_void_p()
+        rc = lib().sla_hip_index_build(buf.ctypes.data if len(buf) else C.cast(C.create_string_buffer(1), C.c_void_p), len(buf),
+                                       C.byref(h))
+        if rc != 0:
+            raise SlaError(rc, "sla_hip_index_build")
+        return cls(h)
+
+    @classmethod
+    def from_bytes(cls, blob):
+        """an index from to_bytes' blob (sla_hip_index_deserialize); SlaError INVALID_ARGUMENT for one it refuses"""
+        buf = np.frombuffer(bytes(blob), np.uint8)
+        h = C.c_void_p()
+        rc = lib().sla_hip_index_deserialize(buf.ctypes.data if len(buf) else C.cast(C.create_string_buffer(1), C.c_void_p),
+                                             len(buf), C.byref(h))
+        if rc != 0:
+            raise SlaError(rc, "sla_hip_index_deserialize")
+        return cls(h)
+
+    def to_bytes(self):
+        n = int(self._lib.sla_hip_index_serialized_bytes(self._h))
+        out = np.zeros(n, np.uint8)
+        if int(self._lib.sla_hip_index_serialize(self._h, out.ctypes.data, n)) != n:
+            raise SlaError(1, "sla_hip_index_serialize")
+        return out.tobytes()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.sla_hip_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def data_size(self):
+        return int(self._info.data_size)
+
+    @property
+    def header(self):
+        """the SLAHeaderInfo DecodeHeader delivered, None when it delivered none"""
+        return self._info.header if self._info.header_result in (0, 11) else None
+
+    @property
+    def header_result(self):
+        return int(self._info.header_result)
+
+    @property
+    def stop(self):
+        return int(self._info.stop)
+
+    @property
+    def extent(self):
+        return int(self._info.extent)
+
+    @property
+    def num_blocks(self):
+        return int(self._info.num_blocks)
+
+    def blocks(self, first=0, count=None):
+        """rows [first, first + count) as a structured numpy array (INDEX_BLOCK_DTYPE)"""
+        count = self.num_blocks - first if count is None else count
+        out = np.zeros(max(count, 0), INDEX_BLOCK_DTYPE)
+        rc = self._lib.sla_hip_index_blocks(self._h, first, count, out.ctypes.data if count > 0 else None)
+        if rc != 0:
+            raise SlaError(rc, "sla_hip_index_blocks")
+        return out
+
+
 WIDE_WALK_DEFAULT = 16000000     # the handle option "wide_walk" as SLADecoder_Create sets it (sla_decoder.c: DEC_WIDE_WALK_DEFAULT)
 
 
@@ -1500,6 +1652,112 @@ class Decoder:
                 else:
                     out[b, :, first:].zero_()
         return out, [n for _, n, _ in got], [rc for rc, _, _ in got]
+
+    def index_resident(self, srcs, stream=None):
+        """[Index] of .sla streams whose bytes are in device memory (sla_hip_index_build_resident): the header gather and
+        the chain walk on the device, wide for streams of at least the option "wide_walk".  Each serialises to the bytes
+        Index.build gives a host copy."""
+        import torch
+        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        out = []
+        self._index_walk = None              # last_walk() speaks of the last stream walked here
+        for ptr, size in self._resident_sources(srcs):
+            h = C.c_void_p()
+            self._check(self._lib.sla_hip_index_build_resident(self._h, C.c_void_p(ptr or None), size, C.c_void_p(st.cuda_stream),
+                                                               C.byref(h)), "sla_hip_index_build_resident")
+            out.append(Index(h))
+        return out
+
+    def decode_windows_indexed_into(self, srcs, indexes, starts, outs, sample_format, zero_fill=True, stream=None):
+        """decode_windows_into from block indexes, QUEUED (sla_hip_decode_windows_indexed): the call returns once its work
+        is enqueued behind `stream`; work queued on `stream` afterwards sees outs and the outcomes written.  indexes[i] is
+        the Index of srcs[i] (None refuses the item).  Returns an int32 device tensor [B][2]: (result code, samples) per
+        window, what decode_windows_into returns for the same bytes.  Nothing here waits for the device."""
+        import torch
+        if sample_format not in self._FORMAT_DTYPE:
+            raise ValueError("unknown sample format %r" % (sample_format,))
+        if len(outs) != len(srcs) or len(starts) != len(srcs) or len(indexes) != len(srcs):
+            raise ValueError("%d sources, %d indexes, %d starts, %d outputs" % (len(srcs), len(indexes), len(starts), len(outs)))
+        want = getattr(torch, self._FORMAT_DTYPE[sample_format])
+        ps = self._resident_sources(srcs)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        items = (IndexedWindowItem * max(len(ps), 1))()
+        for i, ((ptr, size), out) in enumerate(zip(ps, outs)):
+            if not isinstance(out, torch.Tensor) or out.dim() != 2:
+                raise ValueError("output %d: need a 2-D torch tensor [channel][sample]" % i)
+            if out.dtype != want:
+                raise ValueError("output %d: dtype %s, the format wants %s" % (i, out.dtype, want))
+            if out.device.type != "cuda" or out.device.index != self.device_index:
+                raise ValueError("output %d: on %s, the decoder's device is cuda:%d" % (i, out.device, self.device_index))
+            x = indexes[i]
+            nch = x.header.wave_format.num_channels if x is not None and x.header is not None and x.data_size == size else 0
+            if out.shape[0] < nch:
+                raise ValueError("output %d: %d rows for a file of %d channels" % (i, out.shape[0], nch))
+            if out.shape[1] > 0xFFFFFFFF or min(out.stride()) < 0 or (out.shape[1] > 1 and out.stride(1) == 0) \
+                    or (nch > 1 and out.stride(0) == 0):
+                raise ValueError("output %d: unsupported shape %s / strides %s" % (i, tuple(out.shape), out.stride()))
+            start = int(starts[i])
+            if not 0 <= start <= 0xFFFFFFFF:
+                raise ValueError("window %d: start %d out of range" % (i, start))
+            items[i].data = C.cast(C.c_void_p(ptr or None), u8p)
+            items[i].data_size = size
+            items[i].index = x.handle if x is not None else None
+            items[i].dst = out.data_ptr() or (out.untyped_storage().data_ptr() + out.storage_offset() * out.element_size()) or None
+            items[i].channel_stride = out.stride(0)
+            items[i].sample_stride = max(out.stride(1), 1)
+            items[i].start = start
+            items[i].length = out.shape[1]
+        with torch.cuda.stream(st):
+            outcomes = torch.empty((max(len(ps), 1), 2), dtype=torch.int32, device=torch.device("cuda", self.device_index))
+        rc = self._lib.sla_hip_decode_windows_indexed(self._h, items, len(ps), sample_format, DEC_ZERO_FILL if zero_fill else 0,
+                                                      C.c_void_p(outcomes.data_ptr()), C.c_void_p(st.cuda_stream))
+        self._check(rc, "sla_hip_decode_windows_indexed")
+        return outcomes[:len(ps)]
+
+    def decode_windows_indexed(self, srcs, indexes, starts, length, dtype=None, layout="planar", right_justify=False):
+        """decode_windows_tensor from block indexes, queued on the current stream: one window of `length` samples per
+        source -> (tensor, outcomes); the tensor's shape is decode_windows_tensor's, from the indexes' headers, outcomes an
+        int32 device tensor [B][2] of (result code, samples).  Rows no header covers, and windows refused outright, are
+        zeroed by stream-ordered torch ops: nothing here waits for the device."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype == torch.float32:
+            fmt = PCM_F32
+        elif dtype == torch.int16:
+            fmt = PCM_S16
+        elif dtype == torch.int32:
+            fmt = PCM_S32 if right_justify else PCM_S32_LEFT
+        else:
+            raise ValueError("dtype must be float32, int16 or int32, not %s" % (dtype,))
+        if layout not in ("planar", "interleaved"):
+            raise ValueError("layout must be 'planar' or 'interleaved', not %r" % (layout,))
+        ps = self._resident_sources(srcs)
+        if len(starts) != len(ps) or len(indexes) != len(ps):
+            raise ValueError("%d sources, %d indexes, %d starts" % (len(ps), len(indexes), len(starts)))
+        L = int(length)
+        if L < 0 or L > 0xFFFFFFFF:
+            raise ValueError("length %d out of range" % L)
+        nchs = [x.header.wave_format.num_channels if x is not None and x.header is not None and x.data_size == size else 0
+                for x, (_, size) in zip(indexes, ps)]
+        B, Cn = len(ps), max(nchs, default=0)
+        dev = torch.device("cuda", self.device_index)
+        shape = (B, Cn, L) if layout == "planar" else (B, L, Cn)
+        out = torch.empty(shape, dtype=dtype, device=dev)
+        if out.numel() == 0:
+            scratch = torch.empty(1, dtype=dtype, device=dev)
+            outs = [scratch.as_strided((Cn, L), (1, 1)) for _ in range(B)]
+        else:
+            outs = [out[b] if layout == "planar" else out[b].t() for b in range(B)]
+        outcomes = self.decode_windows_indexed_into(ps, indexes, starts, outs, fmt, zero_fill=True)
+        if out.numel():
+            # the zero fill covers the rows a header gave; rows no header covers are zeroed here, and a window refused
+            # outright (INVALID_ARGUMENT: nothing of it was written) by a mask from its outcome, all on the stream
+            for b in range(B):
+                if nchs[b] < Cn:
+                    (out[b, nchs[b]:] if layout == "planar" else out[b, :, nchs[b]:]).zero_()
+            refused = (outcomes[:, 0] == 2).view(B, 1, 1)
+            out.masked_fill_(refused, 0)
+        return out, outcomes
 
     def set_option(self, name, value):
         """a handle option (sla_hip_decoder_set_option): "wide_walk" -- resident streams of at least that many bytes have

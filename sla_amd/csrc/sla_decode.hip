@@ -1016,6 +1016,7 @@ void k_dec_gather(const sla_hip_dec_gather* __restrict__ table, uint32_t num_ent
 #include "kernels/walk_wide.inc"
 #include "kernels/salvage.inc"
 #include "kernels/verify.inc"
+#include "kernels/judge.inc"
 
 }  // namespace
 
@@ -1418,5 +1419,20 @@ extern "C" int sla_hip_launch_verify_blocks(const int32_t* d_planes, uint64_t pl
   a.report = (unsigned long long*)d_report;
   a.num_channels = num_channels; a.mid_side = mid_side; a.shift = shift;
   hipLaunchKernelGGL(k_verify_blocks, dim3(num_blocks), dim3(256), 0, (hipStream_t)stream, a);
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_dec_judge(const uint8_t* d_image, uint64_t image_bytes, const sla_hip_dec_block* d_blocks,
+                                        const sla_hip_dec_info* d_info, uint32_t num_blocks, const sla_hip_dec_judge_item* d_items,
+                                        uint32_t num_items, uint32_t crc_check, uint32_t lms_ok, sla_hip_dec_emit* d_emit,
+                                        uint32_t num_emit, sla_hip_window_outcome* d_outcomes, uint32_t num_outcomes,
+                                        sla_hip_stream_t stream)
+{
+  if (d_items == nullptr || d_outcomes == nullptr || (num_emit > 0 && d_emit == nullptr)
+      || (num_blocks > 0 && (d_image == nullptr || d_blocks == nullptr || d_info == nullptr))) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_items == 0) { return 0; }
+  // one wave per item, four items per workgroup
+  hipLaunchKernelGGL(k_dec_judge, dim3((num_items + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_image, image_bytes, d_blocks, d_info,
+                     num_blocks, d_items, num_items, crc_check, lms_ok, d_emit, num_emit, d_outcomes, num_outcomes);
   return hip_rc(hipGetLastError());
 }

@@ -54,7 +54,23 @@ struct SLADecoder {
   dbuf_t                    d_wide; hbuf_t h_wide;      /* the wide walk of long resident files: its scratch; info words and rerun results home */
   uint32_t                  wide_walk, wide_nodes;      /* options "wide_walk" (bytes, 0 = off) and "wide_walk_nodes" (0 = by file size) */
   uint64_t                  walk_stats[4];              /* sla_hip_decoder_last_walk */
+  /* sla_hip_decode_windows_indexed: a ring of page-locked staging slots for a pass's tables, each guarded by an event that
+   * the handle's stream passes once the slot's upload is done; the closing event; work queued and not known to have run */
+  struct { hbuf_t h; hipEvent_t ev; int busy; } q_slot[SLA_HIP_DEC_QUEUE_SLOTS];
+  uint32_t                  q_next;
+  hipEvent_t                ev_close;
+  int                       queued;
+  dbuf_t                    d_qtab;                     /* the same: judge and emit table of a pass */
 };
+
+/* Every entry point but sla_hip_decode_windows_indexed opens with this: what that call left queued on the handle's stream
+ * runs to its end before host staging that no event guards is written again. */
+static int drain(struct SLADecoder* d)
+{
+  if (!d->queued) { return 0; }
+  d->queued = 0;
+  return (hipStreamSynchronize(d->stream) == hipSuccess) ? 0 : -1;
+}
 
 static double now_ms(void)
 {
@@ -66,6 +82,7 @@ static double now_ms(void)
 static int dbuf_reserve(dbuf_t* b, size_t bytes)
 {
   if (bytes <= b->cap) { return 0; }
+  /* (work that sla_hip_decode_windows_indexed left queued may still use the old buffer: hipFree waits for the device) */
   if (b->ptr != NULL) { (void)hipFree(b->ptr); b->ptr = NULL; b->cap = 0; }
   bytes += bytes / 4 + 256;
   if (hipMalloc(&b->ptr, bytes) != hipSuccess) { b->ptr = NULL; return -1; }
@@ -155,6 +172,9 @@ void SLADecoder_Destroy(struct SLADecoder* d)
   hbuf_free(&d->h_src); hbuf_free(&d->h_hdr);
   dbuf_free(&d->d_wide); hbuf_free(&d->h_wide);
   { int k; for (k = 0; k < 3; k++) { if (d->ev_src[k] != NULL) { (void)hipEventDestroy(d->ev_src[k]); } } }
+  { uint32_t k; for (k = 0; k < SLA_HIP_DEC_QUEUE_SLOTS; k++) { hbuf_free(&d->q_slot[k].h); if (d->q_slot[k].ev != NULL) { (void)hipEventDestroy(d->q_slot[k].ev); } } }
+  dbuf_free(&d->d_qtab);
+  if (d->ev_close != NULL) { (void)hipEventDestroy(d->ev_close); }
   if (d->h_blocks != NULL) { (void)hipHostFree(d->h_blocks); }
   if (d->h_info != NULL) { (void)hipHostFree(d->h_info); }
   if (d->h_crcf != NULL) { (void)hipHostFree(d->h_crcf); }
@@ -329,6 +349,7 @@ static SLAApiResult decode_run(struct SLADecoder* d, const uint8_t* data, uint32
   float kernel_ms = 0.0f;
   double t0 = now_ms(), t_up = 0.0, t_walk = 0.0, t1;
 
+  if (drain(d) != 0) { return SLA_APIRESULT_NG; }
   memset(d->timing, 0, sizeof(d->timing));
   if (one_block_size == NULL) {
     if ((ret = file_format(d, data, data_size, &f)) != SLA_APIRESULT_OK) { return ret; }
@@ -953,24 +974,33 @@ static int wav_emit_run(struct SLADecoder* d, const dev_out_t* dev, const sla_hi
 /* The decode kernels of a pass, once each over its nb blocks: the table (nb rows, then nb block ends) is in d->d_blocks,
  * the image in d->d_image, d->d_info is cleared.  The block infos come home to d->h_info[first ...]; waited for, the
  * kernels' time is added to *kernel_ms. */
+static int pass_kernels_run(struct SLADecoder* d, const dec_format_t* f, uint32_t nb, uint32_t first, uint64_t img_bytes, uint64_t span,
+                            float* kernel_ms, int queued);
 static int pass_kernels(struct SLADecoder* d, const dec_format_t* f, uint32_t nb, uint32_t first, uint64_t img_bytes, uint64_t span,
                         float* kernel_ms)
+{
+  return pass_kernels_run(d, f, nb, first, img_bytes, span, kernel_ms, 0);
+}
+/* queued: the kernels only, on the handle's stream -- nothing comes home, nothing is waited for, no event is recorded */
+static int pass_kernels_run(struct SLADecoder* d, const dec_format_t* f, uint32_t nb, uint32_t first, uint64_t img_bytes, uint64_t span,
+                            float* kernel_ms, int queued)
 {
   const sla_hip_dec_block* db = (const sla_hip_dec_block*)d->d_blocks.ptr;
   const sla_hip_dec_info* di = (const sla_hip_dec_info*)d->d_info.ptr;
   int32_t* planes = (int32_t*)d->d_planes.ptr;
   const uint32_t C = f->C;
-  BCHK(hipEventRecord(d->ev[0], d->stream));
+  if (!queued) { BCHK(hipEventRecord(d->ev[0], d->stream)); }
   BRC(sla_hip_launch_dec_bits_x((const uint32_t*)d->d_image.ptr, img_bytes, db, nb, C, f->bps, f->lshift, f->ms, f->order, f->ntaps,
                                 d->cfg.enable_crc_check == 1, planes, span, (sla_hip_dec_info*)d->d_info.ptr,
                                 (sla_hip_dec_chan*)d->d_chan.ptr, (int32_t*)d->d_kint.ptr, d->stream,
                                 (const uint64_t*)(db + nb)));
-  BCHK(hipMemcpyAsync(d->h_info + first, d->d_info.ptr, sizeof(sla_hip_dec_info) * nb, hipMemcpyDeviceToHost, d->stream));
+  if (!queued) { BCHK(hipMemcpyAsync(d->h_info + first, d->d_info.ptr, sizeof(sla_hip_dec_info) * nb, hipMemcpyDeviceToHost, d->stream)); }
   if (lms_order_ok(f->lms)) {
     BRC(sla_hip_launch_dec_lms(planes, span, db, di, nb, C, f->lms, d->stream));
     BRC(sla_hip_launch_dec_ltm(planes, span, db, di, (const sla_hip_dec_chan*)d->d_chan.ptr, nb, C, f->ntaps, d->cfg.max_num_block_samples, d->stream));
     BRC(sla_hip_launch_dec_lattice(planes, span, db, di, nb, C, (const int32_t*)d->d_kint.ptr, f->order, 1, d->stream));
   }
+  if (queued) { return 0; }
   BCHK(hipEventRecord(d->ev[1], d->stream));
   BCHK(hipStreamSynchronize(d->stream));
   ev_add_ms(kernel_ms, d->ev[0], d->ev[1]);
@@ -1127,6 +1157,7 @@ static int batch_run(struct SLADecoder* d, sla_hip_decode_item* items, uint32_t 
   float kernel_ms = 0.0f;
   double t0 = now_ms(), t_walk = 0.0, t_up = 0.0, t_down = 0.0, t;
 
+  if (drain(d) != 0) { return SLA_APIRESULT_NG; }
   memset(d->timing, 0, sizeof(d->timing));
   if (res) { memset(d->walk_stats, 0, sizeof(d->walk_stats)); }
   memset(&cl, 0, sizeof(cl));
@@ -1298,6 +1329,7 @@ static int call_open(struct SLADecoder* d, call_mem_t* m, uint32_t num_items, in
 {
   uint32_t i;
   *t_hdr = 0.0;
+  if (drain(d) != 0) { return -1; }
   for (i = 0; i < num_items; i++) {
     m->src[i] = m->dv[i].data; m->size[i] = m->dv[i].data_size;
     if (resident && m->ok[i]) { m->ok[i] = (uint8_t)src_region_ok(m->dv[i].data, m->dv[i].data_size); }
@@ -1627,7 +1659,7 @@ int sla_hip_resident_headers(struct SLADecoder* d, const uint8_t* const* d_data,
   ok = (uint8_t*)calloc(num, 1);
   if (ok == NULL) { return SLA_APIRESULT_NG; }
   for (i = 0; i < num; i++) { ok[i] = (uint8_t)src_region_ok(d_data[i], data_size[i]); }
-  if (order_behind(d, stream) != 0 || res_fetch_headers(d, d_data, data_size, ok, num) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+  if (drain(d) != 0 || order_behind(d, stream) != 0 || res_fetch_headers(d, d_data, data_size, ok, num) != 0) { rc = SLA_APIRESULT_NG; goto out; }
   for (i = 0; i < num; i++) {
     memset(&headers[i], 0, sizeof(headers[i]));
     results[i] = ok[i] ? (int32_t)SLADecoder_DecodeHeader((const uint8_t*)d->h_hdr.ptr + (size_t)i * RES_HDR_SLOT, data_size[i], &headers[i])
@@ -1853,6 +1885,303 @@ int sla_hip_decode_windows_resident(struct SLADecoder* d, sla_hip_decode_window_
 
 out:
   call_close(d, &after, t0, t_gather, t_walk, kernel_ms, t_down, passes);
+  free(m.base);
+  return rc;
+}
+
+/* ------------------------------------------------------------------------------------------------------------
+ * The block index from device bytes (include/sla_hip.h; the host builder and everything else of sla_hip_index is
+ * sla_dec_index.c): the header gather, then the whole-file walk with capacity = the header's num_samples, no cap on the
+ * block length and no CRC rows, in count and in write mode -- wide for a long stream, on a lane after an overflow.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define IDX_MAX_BLOCK_SAMPLES 65535u     /* the format's: a 16-bit field */
+
+/* one walk of wf (a host struct) queued on the handle's stream: wide, or on one lane; write: its wf->max_rows rows go to
+ * d->d_blocks (rows, then ends) and d->d_crcf */
+static int idx_walk_launch(struct SLADecoder* d, const sla_hip_dec_walk_file* wf, int wide, int write)
+{
+  sla_hip_dec_block* db = write ? (sla_hip_dec_block*)d->d_blocks.ptr : NULL;
+  uint64_t* dend = write ? (uint64_t*)(db + wf->max_rows) : NULL;
+  uint32_t* dcrc = write ? (uint32_t*)d->d_crcf.ptr : NULL;
+  if (wide) {
+    BRC(sla_hip_launch_dec_walk_wide(wf, IDX_MAX_BLOCK_SAMPLES, 0, (sla_hip_dec_walk_result*)d->d_wres.ptr, db, dend, dcrc,
+                                     slai_dec_wide_capacity(d->wide_nodes, wf->data_size), d->d_wide.ptr, d->stream));
+  } else {
+    memcpy(d->h_src.ptr, wf, sizeof(*wf));
+    BCHK(hipMemcpyAsync(d->d_src.ptr, d->h_src.ptr, sizeof(*wf), hipMemcpyHostToDevice, d->stream));
+    BRC(sla_hip_launch_dec_walk((const sla_hip_dec_walk_file*)d->d_src.ptr, 1, IDX_MAX_BLOCK_SAMPLES, 0, (sla_hip_dec_walk_result*)d->d_wres.ptr,
+                                db, dend, dcrc, d->stream));
+  }
+  return 0;
+}
+
+int sla_hip_index_build_resident(struct SLADecoder* d, const uint8_t* d_data, uint32_t data_size, sla_hip_stream_t stream,
+                                 sla_hip_index** index)
+{
+  const uint32_t head_bytes = (data_size < SLA_HEADER_SIZE) ? data_size : SLA_HEADER_SIZE, zero = 0;
+  uint8_t head[SLA_HEADER_SIZE], ok = 1;
+  sla_hip_dec_walk_file wf;
+  sla_hip_dec_walk_result count, *wr;
+  sla_hip_index* x;
+  uint32_t nb, b;
+  int wide;
+  if (d == NULL || d_data == NULL || index == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  *index = NULL;
+  if (!src_region_ok(d_data, data_size)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (drain(d) != 0 || order_behind(d, stream) != 0 || res_fetch_headers(d, &d_data, &data_size, &ok, 1) != 0) { return SLA_APIRESULT_NG; }
+  memcpy(head, d->h_hdr.ptr, head_bytes);
+  if ((x = slai_index_new(head, head_bytes, data_size, 0)) == NULL) { return SLA_APIRESULT_NG; }
+  if (!slai_index_has_header(x) || x->info.header.num_samples == 0) { *index = x; return 0; }
+
+  memset(&wf, 0, sizeof(wf));
+  wf.src = d_data; wf.data_size = data_size; wf.total = x->info.header.num_samples; wf.capacity = wf.total;
+  free(x);
+  wide = (d->wide_walk != 0 && data_size >= d->wide_walk);
+  memset(d->walk_stats, 0, sizeof(d->walk_stats));
+  if (hbuf_reserve(&d->h_src, sizeof(wf) + sizeof(*wr)) != 0 || dbuf_reserve(&d->d_src, sizeof(wf)) != 0
+      || dbuf_reserve(&d->d_wres, sizeof(*wr)) != 0 || (wide && res_wide_reserve(d, &wf, &zero, 1) != 0)) { return SLA_APIRESULT_NG; }
+  wr = (sla_hip_dec_walk_result*)((uint8_t*)d->h_src.ptr + sizeof(wf));
+  /* ---- count mode; a wide walk whose nodes overflow goes to the lane */
+  for (;;) {
+    if (idx_walk_launch(d, &wf, wide, 0) != 0) { return SLA_APIRESULT_NG; }
+    HIPCHK(hipMemcpyAsync(wr, d->d_wres.ptr, sizeof(*wr), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    if (!wide || wr->reserved != SLA_HIP_DEC_WIDE_OVERFLOW) { break; }
+    wide = 0; d->walk_stats[1] = 1;
+  }
+  d->walk_stats[0] = (uint64_t)wide;                   /* sla_hip_decoder_last_walk: walked wide; overflowed and went to the lane */
+  count = *wr;
+  nb = count.num_blocks;
+  /* ---- write mode, checked against the count */
+  if (nb > 0) {
+    if (dbuf_reserve(&d->d_blocks, (sizeof(sla_hip_dec_block) + sizeof(uint64_t)) * (size_t)nb + 16) != 0
+        || dbuf_reserve(&d->d_crcf, sizeof(uint32_t) * (size_t)nb + 16) != 0 || host_tables_reserve(d, nb) != 0) { return SLA_APIRESULT_NG; }
+    wf.first = 0; wf.max_rows = nb;
+    if (idx_walk_launch(d, &wf, wide, 1) != 0) { return SLA_APIRESULT_NG; }
+    HIPCHK(hipMemcpyAsync(wr, d->d_wres.ptr, sizeof(*wr), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemcpyAsync(d->h_blocks, d->d_blocks.ptr, sizeof(sla_hip_dec_block) * (size_t)nb, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    if (memcmp(wr, &count, sizeof(count)) != 0) { return SLA_APIRESULT_NG; }
+  }
+  if ((x = slai_index_new(head, head_bytes, data_size, nb)) == NULL) { return SLA_APIRESULT_NG; }
+  for (b = 0; b < nb; b++) {
+    x->rows[b].byte_off = (uint32_t)d->h_blocks[b].byte_off; x->rows[b].byte_len = d->h_blocks[b].byte_len;
+    x->rows[b].smp_off = d->h_blocks[b].smp_off; x->rows[b].num_samples = d->h_blocks[b].num_samples;
+  }
+  x->info.stop = count.stop; x->info.extent = count.extent; x->info.num_blocks = nb;
+  *index = x;
+  return 0;
+}
+
+/* ------------------------------------------------------------------------------------------------------------
+ * sla_hip_decode_windows_indexed (include/sla_hip.h): sla_hip_decode_windows_resident with the chain from the caller's
+ * indexes and the examination on the device (k_dec_judge), so that nothing comes home and nothing is waited for.  The
+ * per-item checks, the header pass, the grouping and the pass caps, layout and reserve, the gather, the decode kernels, the
+ * emit entries and the emit launch are that call's code.  Its own: the rows laid out on the host (slai_index_window), a
+ * pass's tables in one slot of the staging ring, the judge between decode and emit.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define Q_NO_EMIT 0xFFFFFFFFu
+
+/* The next slot of the ring with room for `bytes`: the oldest, waited for when its upload is still in flight -- one of the
+ * two places this call may wait.  Idle slots grow along, so that a later call of the same shape allocates nothing. */
+static void* q_claim(struct SLADecoder* d, size_t bytes)
+{
+  const uint32_t s = d->q_next % SLA_HIP_DEC_QUEUE_SLOTS;
+  uint32_t k;
+  for (k = 0; k < SLA_HIP_DEC_QUEUE_SLOTS; k++) {
+    if (d->q_slot[k].ev == NULL && hipEventCreateWithFlags(&d->q_slot[k].ev, hipEventDisableTiming) != hipSuccess) { d->q_slot[k].ev = NULL; return NULL; }
+    if (k == s && d->q_slot[k].busy) {
+      if (hipEventSynchronize(d->q_slot[k].ev) != hipSuccess) { return NULL; }
+      d->q_slot[k].busy = 0;
+    }
+    if (d->q_slot[k].busy && hipEventQuery(d->q_slot[k].ev) == hipSuccess) { d->q_slot[k].busy = 0; }
+    if (!d->q_slot[k].busy && hbuf_reserve(&d->q_slot[k].h, bytes) != 0) { return NULL; }
+  }
+  d->q_next++;
+  return d->q_slot[s].h.ptr;
+}
+/* the claimed slot's uploads are queued: its guard */
+static int q_guard(struct SLADecoder* d)
+{
+  const uint32_t s = (d->q_next - 1) % SLA_HIP_DEC_QUEUE_SLOTS;
+  BCHK(hipEventRecord(d->q_slot[s].ev, d->stream));
+  d->q_slot[s].busy = 1;
+  return 0;
+}
+
+/* One pass queued: files[0, nf) share the launch parameters (nf may be 0); loose[0, nloose) are items that reached no pass,
+ * judged with no rows here (their result is the host's, m->hold[item]).  m->wres[item] is the item's plan: num_blocks kept,
+ * stop, the byte and sample range, and -- in `skipped` and `reserved` -- the first row and the number of rows of its index. */
+static int idx_pass(struct SLADecoder* d, const sla_hip_indexed_window_item* items, const call_mem_t* m, bfile_t* files, uint32_t nf,
+                    const uint32_t* loose, uint32_t nloose, uint32_t format, uint32_t zero_fill, sla_hip_window_outcome* d_outcomes,
+                    uint32_t num_items)
+{
+  const uint32_t nj = nf + nloose;
+  dec_format_t f;
+  sla_hip_dec_gather* gt;
+  sla_hip_dec_block* tb;
+  uint64_t* tend;
+  sla_hip_dec_judge_item* jt;
+  sla_hip_dec_emit* et;
+  pass_t p;
+  stage_t st;
+  size_t bytes, o_rows, o_judge;
+  uint8_t* slot;
+  uint32_t i, k = 0, ng = 0, ne = 0, max_bytes = 0, max_lim = 0, nb;
+
+  memset(&p, 0, sizeof(p)); memset(&f, 0, sizeof(f));
+  p.span = 1;
+  if (nf > 0) {
+    f = files[0].f;
+    if (pass_begin(d, files, nf, &p) != 0) { return -1; }
+  } else if (dbuf_reserve(&d->d_planes, 256) != 0) { return -1; }
+  nb = p.nb;
+  o_rows = sizeof(*gt) * (size_t)nf;
+  o_judge = o_rows + (sizeof(*tb) + sizeof(*tend)) * (size_t)nb;
+  bytes = o_judge + (sizeof(*jt) + sizeof(*et)) * (size_t)nj;
+  if (dbuf_reserve(&d->d_src, o_rows + 16) != 0 || dbuf_reserve(&d->d_qtab, (sizeof(*jt) + sizeof(*et)) * (size_t)nj) != 0 || res_events(d) != 0
+      || (slot = (uint8_t*)q_claim(d, bytes + 16)) == NULL) { return -1; }
+  gt = (sla_hip_dec_gather*)slot; tb = (sla_hip_dec_block*)(slot + o_rows); tend = (uint64_t*)(tb + nb);
+  jt = (sla_hip_dec_judge_item*)(slot + o_judge); et = (sla_hip_dec_emit*)(jt + nj);
+  memset(slot, 0, bytes);
+
+  /* ---- the tables, straight from the indexes */
+  for (i = 0; i < nf; i++) {
+    const uint32_t item = files[i].item;
+    const sla_hip_indexed_window_item* it = &items[item];
+    const sla_hip_dec_window_result* r = &m->wres[item];
+    const sla_hip_index_block* rows = it->index->rows + r->skipped;
+    const uint32_t rest = files[i].f.total - it->start, whole = (it->length < rest) ? it->length : rest;
+    const uint32_t done = (r->stop == SLA_APIRESULT_OK) ? whole : 0;
+    uint32_t b;
+    if (files[i].bytes > 0) {
+      gt[ng].src = it->data + r->first_byte; gt[ng].dst_off = files[i].img_off; gt[ng].bytes = files[i].bytes;
+      if (files[i].bytes > max_bytes) { max_bytes = files[i].bytes; }
+      ng++;
+    }
+    jt[i].first = k; jt[i].nb = files[i].nb; jt[i].stop = r->stop; jt[i].ok_samples = whole; jt[i].outcome = item;
+    jt[i].fill_end = zero_fill ? it->length : 0;
+    for (b = 0; b < r->reserved; b++) {
+      if (rows[b].num_samples == 0) { continue; }                   /* passed over, as the window walk does */
+      /* every row lies whole inside the gathered range: an index guarantees it (rows ascend without overlap) */
+      if (rows[b].byte_off < r->first_byte || (uint64_t)rows[b].byte_off + rows[b].byte_len > r->end_byte) { return -1; }
+      tb[k].byte_off = files[i].img_off + (rows[b].byte_off - r->first_byte); tb[k].byte_len = rows[b].byte_len;
+      tb[k].smp_off = (uint32_t)files[i].plane_off + (rows[b].smp_off - r->first_sample); tb[k].num_samples = rows[b].num_samples;
+      tend[k] = files[i].img_off + files[i].bytes;
+      k++;
+    }
+    if (k - jt[i].first != files[i].nb) { return -1; }
+    jt[i].emit = emit_entry(et + ne, &m->dv[item], zero_fill, files[i].plane_off + (it->start - r->first_sample), done, f.C, f.ms,
+                            32u - f.bps + f.lshift, f.bps, &max_lim) ? ne++ : Q_NO_EMIT;
+  }
+  for (i = 0; i < nloose; i++) {
+    const uint32_t item = loose[i];
+    sla_hip_dec_judge_item* j = &jt[nf + i];
+    j->stop = (uint32_t)m->hold[item]; j->outcome = item; j->fill_end = zero_fill ? items[item].length : 0;
+    j->emit = (zero_fill && m->state[item] == DEV_PENDING && emit_entry(et + ne, &m->dv[item], 1, 0, 0, m->chans[item], 0, 0, 32, &max_lim))
+              ? ne++ : Q_NO_EMIT;
+  }
+
+  /* ---- queued: the tables over, the slot's guard, gather, decode kernels, judge, emit */
+  st.gt = gt; st.up_bytes = sizeof(*gt) * (size_t)ng; st.d_gt = (const sla_hip_dec_gather*)d->d_src.ptr;
+  if (nb > 0) {
+    BCHK(hipMemcpyAsync(d->d_blocks.ptr, tb, (sizeof(*tb) + sizeof(*tend)) * (size_t)nb, hipMemcpyHostToDevice, d->stream));
+    BCHK(hipMemsetAsync(d->d_info.ptr, 0, sizeof(sla_hip_dec_info) * nb, d->stream));
+  }
+  BCHK(hipMemcpyAsync(d->d_qtab.ptr, jt, (sizeof(*jt) + sizeof(*et)) * (size_t)nj, hipMemcpyHostToDevice, d->stream));
+  if (ng > 0 && stage_gather(d, &st, ng, max_bytes, p.img_bytes) != 0) { return -1; }
+  if (q_guard(d) != 0) { return -1; }
+  if (nb > 0 && pass_kernels_run(d, &f, nb, 0, p.img_bytes, p.span, NULL, 1) != 0) { return -1; }
+  BRC(sla_hip_launch_dec_judge((const uint8_t*)d->d_image.ptr, p.img_bytes, (const sla_hip_dec_block*)d->d_blocks.ptr,
+                               (const sla_hip_dec_info*)d->d_info.ptr, nb, (const sla_hip_dec_judge_item*)d->d_qtab.ptr, nj,
+                               d->cfg.enable_crc_check == 1, (uint32_t)lms_order_ok(f.lms),
+                               (sla_hip_dec_emit*)((sla_hip_dec_judge_item*)d->d_qtab.ptr + nj), ne, d_outcomes, num_items, d->stream));
+  BRC(sla_hip_launch_dec_emit_batch((const int32_t*)d->d_planes.ptr, p.span, (const sla_hip_dec_emit*)((sla_hip_dec_judge_item*)d->d_qtab.ptr + nj),
+                                    ne, max_lim, format, d->stream));
+  return 0;
+}
+
+int sla_hip_decode_windows_indexed(struct SLADecoder* d, const sla_hip_indexed_window_item* items, uint32_t num_items,
+                                   uint32_t sample_format, uint32_t flags, sla_hip_window_outcome* d_outcomes, sla_hip_stream_t stream)
+{
+  const uint32_t zero_fill = (flags & SLA_HIP_DEC_ZERO_FILL) ? 1u : 0u;
+  const uint64_t esize = pcm_esize(sample_format);
+  const double t0 = now_ms();
+  call_mem_t m;
+  bfile_t* files;
+  fmt_mark_t after;
+  uint32_t *loose, nf = 0, nloose = 0, i, p0;
+  int rc = 0;
+  if (d == NULL || d_outcomes == NULL || (items == NULL && num_items > 0) || sample_format > SLA_HIP_PCM_F32
+      || (flags & ~SLA_HIP_DEC_ZERO_FILL) != 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_items > 0 && !slai_device_region_ok(d_outcomes, 1, num_items, 0, 1, sizeof(*d_outcomes), -1)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  memset(d->timing, 0, sizeof(d->timing));
+  if (num_items == 0) { return 0; }
+  if (call_mem_new(&m, num_items) != 0) { return SLA_APIRESULT_NG; }
+  files = m.files;
+  loose = m.done;                                   /* (an array of the call that this route does not otherwise use) */
+
+  /* ---- the per-item checks of the resident calls, on the host; the header is the index's */
+  for (i = 0; i < num_items; i++) {
+    const sla_hip_indexed_window_item* it = &items[i];
+    sla_hip_decode_device_item* dv = &m.dv[i];
+    dv->data = it->data; dv->dst = it->dst; dv->channel_stride = it->channel_stride; dv->sample_stride = it->sample_stride;
+    dv->data_size = it->data_size; dv->capacity = it->length;
+    m.state[i] = DEV_REFUSED;
+    if (it->index == NULL || it->index->info.data_size != it->data_size || !src_region_ok(it->data, it->data_size)) { continue; }
+    m.chans[i] = slai_index_has_header(it->index) ? it->index->info.header.wave_format.num_channels : 0;
+    if (dst_region_ok(dv, m.chans[i], esize)) { m.state[i] = DEV_PENDING; }
+  }
+  if (order_behind(d, stream) != 0) { free(m.base); return SLA_APIRESULT_NG; }
+
+  /* ---- headers in item order, as in sla_hip_decode_windows_resident; every window's rows planned from its index */
+  for (i = 0; i < num_items; i++) {
+    const sla_hip_indexed_window_item* it = &items[i];
+    sla_hip_dec_window_result* r = &m.wres[i];
+    dec_format_t f;
+    SLAApiResult ret;
+    int verdict;
+    uint32_t row0, nrows, kept, stop;
+    m.hold[i] = SLA_APIRESULT_INVALID_ARGUMENT;
+    if (m.state[i] == DEV_REFUSED) { continue; }
+    if ((ret = file_format(d, it->index->head, it->data_size, &f)) != SLA_APIRESULT_OK) { m.hold[i] = ret; continue; }
+    if (it->start > f.total) { m.state[i] = DEV_REFUSED; continue; }
+    if ((verdict = format_verdict(&f)) >= 0) { m.hold[i] = verdict; continue; }
+    m.hold[i] = SLA_APIRESULT_OK;
+    if (it->start == f.total || it->length == 0) { continue; }       /* OK, no samples: nothing is decoded */
+    slai_index_window(it->index, f.total, it->start, it->length, d->cfg.max_num_block_samples, &row0, &nrows, &kept, &stop);
+    r->num_blocks = kept; r->stop = stop; r->skipped = row0; r->reserved = nrows;
+    if (kept > 0) {
+      const sla_hip_index_block* a = &it->index->rows[row0];
+      const sla_hip_index_block* z = &it->index->rows[row0 + nrows - 1];
+      r->first_byte = a->byte_off; r->first_sample = a->smp_off;
+      r->end_byte = z->byte_off + z->byte_len; r->end_sample = z->smp_off + z->num_samples;
+    }
+    files[nf].item = i; files[nf].f = f; files[nf].nb = kept; files[nf].walk_err = (SLAApiResult)stop;
+    files[nf].extent = r->end_sample - r->first_sample; files[nf].bytes = r->end_byte - r->first_byte;
+    m.state[i] = DEV_DECODED;
+    nf++;
+  }
+  fmt_mark(d, &after);
+  for (i = 0; i < num_items; i++) { if (m.state[i] != DEV_DECODED) { loose[nloose++] = i; } }
+
+  /* ---- passes, by sla_hip_decode_windows_resident's grouping and caps; the first takes the loose items along */
+  qsort(files, nf, sizeof(*files), slai_dec_file_cmp);
+  for (p0 = 0; p0 < nf || nloose > 0; ) {
+    const uint32_t p1 = (p0 < nf) ? pass_cut(files, p0, nf) : p0;
+    d->queued = 1;
+    if (idx_pass(d, items, &m, files + p0, p1 - p0, loose, nloose, sample_format, zero_fill, d_outcomes, num_items) != 0) { rc = SLA_APIRESULT_NG; break; }
+    nloose = 0;
+    p0 = p1;
+  }
+
+  /* ---- the caller's stream behind the handle's closing event */
+  if (d->queued) {
+    if ((d->ev_close == NULL && hipEventCreateWithFlags(&d->ev_close, hipEventDisableTiming) != hipSuccess)
+        || hipEventRecord(d->ev_close, d->stream) != hipSuccess || hipStreamWaitEvent((hipStream_t)stream, d->ev_close, 0) != hipSuccess) { rc = SLA_APIRESULT_NG; }
+  }
+  d->wave_format = after.wf; d->encode_param = after.ep; d->status_flag = after.flag;
+  d->timing[4] = (float)(now_ms() - t0);
   free(m.base);
   return rc;
 }

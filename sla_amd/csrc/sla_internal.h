@@ -124,6 +124,25 @@ void     slai_dec_layout(slai_dec_file* files, uint32_t nf, uint64_t* img_bytes,
 uint32_t slai_dec_wide_capacity(uint32_t option, uint32_t data_size);
 uint32_t slai_dec_pick_wide(const slai_dec_file* files, uint32_t nf, uint32_t threshold, uint32_t pick[SLAI_DEC_WIDE_MAX]);
 
+/* ---- sla_dec_index.c: the block index of a stream (sla_hip_index; no device calls) --------- */
+#define SLAI_INDEX_HEAD 44u              /* bytes kept of a stream's head: the 43 of the header, padded */
+struct sla_hip_index {
+  sla_hip_index_summary info;
+  uint8_t              head[SLAI_INDEX_HEAD];
+  sla_hip_index_block* rows;             /* info.num_blocks of them, in the same allocation */
+};
+/* an index of `head_bytes` (<= 43) header bytes of a stream of data_size bytes with room for num_blocks rows: info's
+ * data_size, header_bytes, header_result and header are set, the rest is zero; NULL when memory is short */
+sla_hip_index* slai_index_new(const uint8_t* head, uint32_t head_bytes, uint32_t data_size, uint32_t num_blocks);
+/* 1 when the header was delivered, so that a chain is walked */
+int      slai_index_has_header(const sla_hip_index* index);
+/* The planned rows of the window [start, start + length) (clipped to `total`) of an index: k_dec_walk_window's rules over
+ * the index's rows instead of the bytes.  *row0 / *nrows: the run of index rows from the first kept one to the last (rows
+ * of no samples inside it are passed over, *kept counts the others); *stop: OK when the window's end was reached, BUF at a
+ * block of more than max_block_samples samples, else -- the rows ran out -- the index's stop code (DATA when that is OK). */
+void     slai_index_window(const sla_hip_index* index, uint32_t total, uint32_t start, uint32_t length, uint32_t max_block_samples,
+                           uint32_t* row0, uint32_t* nrows, uint32_t* kept, uint32_t* stop);
+
 /* ---- sla_decoder.c: caller-owned device memory of the batch calls --------- */
 /* 1 when [0, C) x [0, n) of esize-byte elements at p (element (c, i) at c * channel_stride + i * sample_stride) is aligned,
  * its byte extent does not overflow, the runtime reports p as device memory (of `device` when >= 0) and the region lies
