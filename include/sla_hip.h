@@ -594,7 +594,12 @@ int sla_hip_launch_dec_bits(const uint32_t* d_image, uint64_t image_bytes,
 /* dec_bits over blocks of several files concatenated in one image: d_block_end[b] (device, one per block) is the byte
  * end of block b's file in the image, and the block's reader treats it as the end of the stream -- zeros past it, the
  * same give-up limit -- so that it decodes exactly as its file would on its own.  NULL: every block is bounded by
- * image_bytes (sla_hip_launch_dec_bits). */
+ * image_bytes (sla_hip_launch_dec_bits).
+ * The launch gives every wave `lanes` blocks, a number it takes from the size of the launch alone:
+ *   lanes = ceil(num_blocks / 1024), at least 1, at most 64 / num_channels
+ * (one block per wave up to 1024 blocks: every SIMD of the chip gets a wave before a wave takes a second block;
+ * lanes * num_channels <= 64 rows of LDS staging).  sla_hip_dec_bits_lanes is that rule, a pure host function. */
+uint32_t sla_hip_dec_bits_lanes(uint32_t num_blocks, uint32_t num_channels);
 int sla_hip_launch_dec_bits_x(const uint32_t* d_image, uint64_t image_bytes,
                               const sla_hip_dec_block* d_blocks, uint32_t num_blocks,
                               uint32_t num_channels, uint32_t bits_per_sample, uint32_t offset_lshift,

@@ -368,6 +368,9 @@ def lib():
                                                 C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sla_hip_launch_dec_finish_batch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
                                                       C.c_void_p, C.c_void_p]
+        if hasattr(L, "sla_hip_dec_bits_lanes"):             # (SLA_HIP_LIB may name an older build in an A/B run)
+            L.sla_hip_dec_bits_lanes.argtypes = [C.c_uint32, C.c_uint32]
+            L.sla_hip_dec_bits_lanes.restype = C.c_uint32
         if hasattr(L, "sla_hip_decode_batch_resident"):      # (SLA_HIP_LIB may name an older build in an A/B run)
             L.sla_hip_decode_batch_resident.argtypes = [C.c_void_p, C.POINTER(DecodeDeviceItem), C.c_uint32, C.c_uint32,
                                                         C.c_uint32, C.c_void_p]
@@ -488,7 +491,7 @@ EXPORTED_SYMBOLS = [
     "SLALPCSynthesizer_SynthesizeByParcorCoefInt32", "SLALongTermSynthesizer_SynthesizeInt32", "SLALMSFilter_SynthesizeInt32",
     "SLAEmphasisFilter_DeEmphasisInt32", "sla_hip_launch_dec_deemphasis",
     # batch decode (include/sla_hip.h)
-    "sla_hip_decode_batch", "sla_hip_launch_dec_bits_x", "sla_hip_launch_dec_finish_batch",
+    "sla_hip_decode_batch", "sla_hip_launch_dec_bits_x", "sla_hip_launch_dec_finish_batch", "sla_hip_dec_bits_lanes",
     # batch decode into device memory (include/sla_hip.h)
     "sla_hip_decode_batch_device", "sla_hip_launch_dec_emit_batch",
     # batch decode of streams that are in device memory (include/sla_hip.h)

@@ -1023,6 +1023,15 @@ void k_dec_gather(const sla_hip_dec_gather* __restrict__ table, uint32_t num_ent
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
+// blocks per wave of k_dec_bits: enough waves for every SIMD of the chip before a wave takes a second block
+extern "C" uint32_t sla_hip_dec_bits_lanes(uint32_t num_blocks, uint32_t num_channels)
+{
+  uint32_t lanes = (num_blocks + 1023) / 1024;
+  if (lanes < 1) { lanes = 1; }
+  if (lanes > 64 / num_channels) { lanes = 64 / num_channels; }     // lanes * channels rows of LDS staging
+  return lanes;
+}
+
 extern "C" int sla_hip_launch_dec_bits(const uint32_t* d_image, uint64_t image_bytes,
                                        const sla_hip_dec_block* d_blocks, uint32_t num_blocks,
                                        uint32_t num_channels, uint32_t bits_per_sample, uint32_t offset_lshift,
@@ -1059,10 +1068,7 @@ extern "C" int sla_hip_launch_dec_bits_x(const uint32_t* d_image, uint64_t image
   dec_bits_args a;
   a.image = d_image; a.image_bytes = image_bytes; a.block_end = d_block_end; a.blocks = d_blocks; a.num_blocks = num_blocks;
   a.bps = bits_per_sample; a.lshift = offset_lshift; a.mid_side = mid_side; a.order = parcor_order; a.ntaps = longterm_order;
-  // enough waves for every SIMD of the chip before a wave takes a second block
-  uint32_t lanes = (num_blocks + 1023) / 1024;
-  if (lanes < 1) { lanes = 1; }
-  if (lanes > 64 / num_channels) { lanes = 64 / num_channels; }     // lanes * channels rows of LDS staging
+  const uint32_t lanes = sla_hip_dec_bits_lanes(num_blocks, num_channels);
   a.lanes = lanes;
   a.planes = d_planes; a.stride = plane_stride; a.info = d_info; a.chan = d_chan; a.kint = d_kint;
   const dim3 grid((num_blocks + lanes - 1) / lanes), block(64);

@@ -33,6 +33,7 @@ import numpy as np
 import pytest
 
 import crafted_catalogue as CC
+from decbitsmodel import kint_of, unfold
 import slalibs as S
 import slastream as SS
 import waveforms as W
@@ -43,23 +44,6 @@ IDS = [c.name for c in CASES]
 
 def params():
     return S.make_params(cap=CC.CAP)
-
-
-def unfold(codes):
-    u = np.asarray(codes, np.uint64) & np.uint64(SS.M32)
-    return ((u >> np.uint64(1)).astype(np.int64) ^ -(u & np.uint64(1)).astype(np.int64)).astype(np.int32)
-
-
-def kint_of(chan):
-    k = [0]
-    for o, c in enumerate(chan.codes, start=1):
-        q = 16 if o < 4 else 8
-        v = SS.fold(c) & ((1 << q) - 1)
-        s = (v >> 1) ^ -(v & 1)                                   # the code as read back from its q-bit field
-        w = (s << (16 - q)) & SS.M32
-        w = w - (1 << 32) if w >> 31 else w
-        k.append(w >> chan.rshift)
-    return np.array(k, np.int32)
 
 
 def synthesis_chain(oracle, case):

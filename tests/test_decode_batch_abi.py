@@ -60,3 +60,17 @@ def test_launchers_reject_null_pointers(L):
     assert L.sla_hip_launch_dec_bits_x(None, 0, None, 0, 1, 16, 0, 0, 8, 1, 0, None, 0, None, None, None, None,
                                        None) == INVALID_ARGUMENT
     assert L.sla_hip_launch_dec_finish_batch(None, 0, 1, None, 0, 0, None, None) == INVALID_ARGUMENT
+
+
+def test_dec_bits_lanes_follow_the_rule(L):
+    """blocks per wave of k_dec_bits (sla_hip_dec_bits_lanes, the function the launcher calls):
+    ceil(num_blocks / 1024), at least 1, at most 64 // channels -- 3, 5, 6 and 7 channels do not divide 64"""
+    caps = {1: 64, 2: 32, 3: 21, 4: 16, 5: 12, 6: 10, 7: 9, 8: 8}
+    for nch in range(1, 9):
+        assert caps[nch] == 64 // nch
+        for nb in (1, 1024, 1025, 2048, 2049, 64512, 64513, 10 ** 6):
+            want = min(max(-(-nb // 1024), 1), caps[nch])
+            assert L.sla_hip_dec_bits_lanes(nb, nch) == want, (nb, nch)
+    assert L.sla_hip_dec_bits_lanes(1024, 1) == 1 and L.sla_hip_dec_bits_lanes(1025, 1) == 2
+    assert L.sla_hip_dec_bits_lanes(64512, 1) == 63 and L.sla_hip_dec_bits_lanes(64513, 1) == 64
+    assert L.sla_hip_dec_bits_lanes(10 ** 6, 3) == 21 and L.sla_hip_dec_bits_lanes(10 ** 6, 7) == 9

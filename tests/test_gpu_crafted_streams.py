@@ -108,3 +108,34 @@ def test_lms_orders_off_the_list_are_refused_like_the_oracle(oracle, decoders):
         assert want[0] == 8
         for dec in decoders:
             assert same(dec.decode_whole(data, 3000), want), lms
+
+
+# (case, blocks the call must hold at least): a one-channel case also with three blocks per wave
+WAVE_SHARING = [("rice_over_64_bits_per_sample_1ch", 1025), ("rice_gamma_boundary_and_int32_extremes", 1025),
+                ("rice_gamma_boundary_and_int32_extremes", 2049), ("lengths_lms4", 1025), ("lengths_lms4", 2049),
+                ("format_32bit_ms_raw_33bit_side", 1025), ("format_8_channels", 1025)]
+
+
+@pytest.mark.parametrize("name,blocks", WAVE_SHARING, ids=["%s-%d" % w for w in WAVE_SHARING])
+def test_decode_batch_with_several_blocks_per_wave(oracle, hip, decoders, name, blocks):
+    """the whole decoder where k_dec_bits gives a wave two or three blocks: one crafted file so many times in one call
+    that its pass holds more than 1024 (2048) blocks.  One pass, so one k_dec_bits launch; every item must equal the
+    oracle's decode of the file, with the CRC check on and off.
+    (What this can see is limited: a block whose reader does not end where its size field says sends its file to the
+    single-file path, one block per wave, which then decodes it correctly.  A k_dec_bits fault that moves used_bytes is
+    therefore invisible from here; tests/test_gpu_dec_bits_lanes.py calls the launcher itself and sees it.)"""
+    case = CC.by_name()[name]
+    reps = -(-blocks // len(case.blocks))
+    total = reps * len(case.blocks)
+    assert total >= blocks
+    lanes = hip.lib().sla_hip_dec_bits_lanes(total, case.fmt.num_channels)
+    assert lanes >= 2 and (blocks < 2049 or lanes >= 3)
+    want = oracle_decode(oracle, case.data, case.num_samples)
+    assert want[0] == 0
+    data = np.frombuffer(case.data, np.uint8)
+    for crc, dec in zip((1, 0), decoders):
+        got = dec.decode_batch([data] * reps)
+        assert dec.last_timing()[5] == 1                       # all blocks went through one launch
+        assert len(got) == reps
+        bad = [i for i, g in enumerate(got) if not same(g, want)]
+        assert not bad, (name, "crc", crc, "items", len(bad), "first", bad[0], got[bad[0]][0])
