@@ -15,8 +15,9 @@
  *
  * Differences a caller can observe:
  *   - SLADecoder_Create returns NULL when no HIP device is usable (there is no CPU fallback) and for
- *     capacities the kernels do not cover: more than 8 channels, blocks above 16384 samples (long-term
- *     synthesis keeps a block in LDS), more than 5 long-term taps; a stream whose LMS filters are not 4, 8,
+ *     capacities the kernels do not cover: more than 8 channels, blocks above 65535 samples (the format's
+ *     16-bit block length; above 40896 the long-term synthesis slides the block through a ring of LDS instead
+ *     of holding it there whole, sla_hip_launch_dec_ltm), more than 5 long-term taps; a stream whose LMS filters are not 4, 8,
  *     16 or 32 coefficients long fails with SLA_APIRESULT_FAILED_TO_SYNTHESIZE at its first compressed block;
  *   - a block whose header announces more samples than max_num_block_samples is refused with
  *     SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE (the reference writes past its work buffers);
@@ -38,7 +39,7 @@ struct SLAStreamingDecoder;            /* opaque: a decoder + fragment queue + b
 /* Capacity of a handle (layout = reference src/include/public/SLADecoder.h:16-24). */
 struct SLADecoderConfig {
   uint32_t max_num_channels;           /* 1..8 planes                                            */
-  uint32_t max_num_block_samples;      /* <= 16384 here                                          */
+  uint32_t max_num_block_samples;      /* <= 65535, the format's 16-bit field                    */
   uint32_t max_parcor_order;           /* PARCOR coefficients per channel, <= 255                */
   uint32_t max_longterm_order;         /* long-term taps, <= 5                                   */
   uint32_t max_lms_order_per_filter;   /* LMS coefficients per cascade stage                     */

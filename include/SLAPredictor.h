@@ -35,7 +35,8 @@
  *     block, as src/SLAEncoder.c:594-659 does.  A second Predict on a handle that was not reset returns
  *     SLAPREDICTOR_APIRESULT_NG instead of continuing the previous block.  (The emphasis filter carries its
  *     previous sample across calls like the reference.)
- *   - limits: num_samples <= 16384 per call (analysis window in LDS), LMS coefficients 4/8/16/32, taps 1/3/5.
+ *   - limits: num_samples <= 16384 per call (analysis window in LDS; SLALongTermSynthesizer_SynthesizeInt32 takes up to
+ *     65535, with a pitch of at most 1023 above 40896), LMS coefficients 4/8/16/32, taps 1/3/5.
  */
 #ifndef SLAPREDICTOR_H_INCLUDED
 #define SLAPREDICTOR_H_INCLUDED

@@ -610,6 +610,16 @@ int sla_hip_launch_dec_bits_x(const uint32_t* d_image, uint64_t image_bytes,
 int sla_hip_launch_dec_lms(int32_t* d_planes, uint64_t plane_stride, const sla_hip_dec_block* d_blocks,
                            const sla_hip_dec_info* d_info, uint32_t num_blocks, uint32_t num_channels,
                            uint32_t lms_order, sla_hip_stream_t stream);
+/* dec_ltm: one 64-lane workgroup per (block, channel), in place on [smp_off, smp_off + num_samples); only
+ * [pitch + longterm_order / 2, num_samples) of compressed blocks with a pitch is written.  Which kernel runs is decided by
+ * max_block_samples (>= the longest block of the table) alone:
+ *   max_block_samples * 4 <= SLA_HIP_LDS_BUDGET (40 896 samples)  the whole block staged in that much dynamic LDS;
+ *   above                                                           the block slides through a fixed 16 KiB ring of LDS in
+ *                                                                   chunks of sla_hip_dec_ltm_window() samples (a pure host
+ *                                                                   function), any block length the 16-bit field can hold.
+ * Both compute the same samples, taps at or past the current sample (pitch 1 or 2 with 3 to 5 taps) reading input that is
+ * not yet synthesised; the ring kernel leaves a channel whose pitch exceeds the format's 10 bits (1023) untouched. */
+uint32_t sla_hip_dec_ltm_window(void);
 int sla_hip_launch_dec_ltm(int32_t* d_planes, uint64_t plane_stride, const sla_hip_dec_block* d_blocks,
                            const sla_hip_dec_info* d_info, const sla_hip_dec_chan* d_chan,
                            uint32_t num_blocks, uint32_t num_channels, uint32_t longterm_order,

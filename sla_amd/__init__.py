@@ -371,6 +371,9 @@ def lib():
         if hasattr(L, "sla_hip_dec_bits_lanes"):             # (SLA_HIP_LIB may name an older build in an A/B run)
             L.sla_hip_dec_bits_lanes.argtypes = [C.c_uint32, C.c_uint32]
             L.sla_hip_dec_bits_lanes.restype = C.c_uint32
+        if hasattr(L, "sla_hip_dec_ltm_window"):             # (the same)
+            L.sla_hip_dec_ltm_window.argtypes = []
+            L.sla_hip_dec_ltm_window.restype = C.c_uint32
         if hasattr(L, "sla_hip_decode_batch_resident"):      # (SLA_HIP_LIB may name an older build in an A/B run)
             L.sla_hip_decode_batch_resident.argtypes = [C.c_void_p, C.POINTER(DecodeDeviceItem), C.c_uint32, C.c_uint32,
                                                         C.c_uint32, C.c_void_p]
@@ -492,6 +495,7 @@ EXPORTED_SYMBOLS = [
     "SLAEmphasisFilter_DeEmphasisInt32", "sla_hip_launch_dec_deemphasis",
     # batch decode (include/sla_hip.h)
     "sla_hip_decode_batch", "sla_hip_launch_dec_bits_x", "sla_hip_launch_dec_finish_batch", "sla_hip_dec_bits_lanes",
+    "sla_hip_dec_ltm_window",
     # batch decode into device memory (include/sla_hip.h)
     "sla_hip_decode_batch_device", "sla_hip_launch_dec_emit_batch",
     # batch decode of streams that are in device memory (include/sla_hip.h)
@@ -1170,10 +1174,22 @@ WIDE_WALK_DEFAULT = 16000000     # the handle option "wide_walk" as SLADecoder_C
 
 
 class Decoder:
-    """Python face of ``struct SLADecoder`` (reference src/include/public/SLADecoder.h)."""
+    """Python face of ``struct SLADecoder`` (reference src/include/public/SLADecoder.h).
+
+    max_num_block_samples: up to 16384 -- what the encoder and the reference's tool write, the default -- or, with
+    long_blocks=True, up to 65535, the longest block the format's 16-bit field can hold (the reference's library writes such
+    blocks when asked).  Every route decodes them; above 40896 the long-term synthesis of ALL blocks of the handle slides
+    through a ring of LDS (sla_hip_launch_dec_ltm) instead of holding the block there whole, and the streaming buffers
+    grow with the capacity, which is why the larger capacity is asked for by name: without long_blocks a capacity above
+    16384 is refused as it always was."""
+
+    LONG_BLOCKS_FROM = 16384      # capacities above this need long_blocks=True
 
     def __init__(self, max_num_channels=8, max_num_block_samples=16384, max_parcor_order=48,
-                 max_longterm_order=5, max_lms_order_per_filter=32, enable_crc_check=1):
+                 max_longterm_order=5, max_lms_order_per_filter=32, enable_crc_check=1, long_blocks=False):
+        if max_num_block_samples > self.LONG_BLOCKS_FROM and not long_blocks:
+            raise RuntimeError("max_num_block_samples %d: capacities above %d (up to the format's 65535) need long_blocks=True"
+                               % (max_num_block_samples, self.LONG_BLOCKS_FROM))
         self._lib = lib()
         cfg = SLADecoderConfig(max_num_channels, max_num_block_samples, max_parcor_order,
                                max_longterm_order, max_lms_order_per_filter, enable_crc_check, 0)
@@ -1925,7 +1941,8 @@ class Decoder:
 def streaming_decode(data, decode_interval_hz=120.0, feed=None, max_bit_per_sample=24, crc=1,
                      capacity=(8, 16384, 48, 5, 40)):
     """Drive SLAStreamingDecoder_* the way the reference CLI does (src/main.c:277-420): header, then per call
-    append the estimated number of bytes (or `feed(i)` bytes), decode, collect.  Returns (rc, pcm [C][n], calls)."""
+    append the estimated number of bytes (or `feed(i)` bytes), decode, collect.  Returns (rc, pcm [C][n], calls).
+    capacity: (channels, block samples <= 65535, PARCOR order, long-term taps, LMS order) of the handle."""
     L = lib()
     buf = np.frombuffer(bytes(data), np.uint8)
     h = SLAHeaderInfo()

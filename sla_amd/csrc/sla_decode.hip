@@ -13,6 +13,7 @@
 //                        (SLACoder_GetDataArray), :406-427 (initial parameters)
 //   k_dec_lms            src/SLAPredictor.c:1334-1463 (SLALMSFilter_SynthesizeInt32)
 //   k_dec_ltm            src/SLAPredictor.c:1034-1119 (SLALongTermSynthesizer_SynthesizeInt32)
+//   k_dec_ltm_far        the same for blocks that do not fit LDS (up to the format's 65535 samples)
 //   k_dec_lattice        src/SLAPredictor.c:610-740 (SLALPCSynthesizer_SynthesizeByParcorCoefInt32),
 //                        :1768-1791 (SLAEmphasisFilter_DeEmphasisInt32)
 //   k_dec_finish         src/SLAUtility.c:415-433 (mid/side -> left/right), src/SLADecoder.c:540-547 (left-justify)
@@ -508,6 +509,71 @@ void k_dec_ltm(int32_t* __restrict__ planes, uint64_t stride, const sla_hip_dec_
     __syncthreads();                                       // one wave: orders the LDS writes before the next step's reads
   }
   for (uint32_t s = delay + lane; s < n; s += 64) { io[s] = s_blk[s]; }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_dec_ltm_far: the same synthesis for blocks that do not fit LDS.  The block passes through a ring of
+// DEC_LTM_RING samples in chunks of DEC_LTM_CHUNK: sample s lives in slot s & (DEC_LTM_RING - 1).  While the chunk
+// [c0, c1) is synthesised the ring holds the outputs back to c0 - DEC_LTM_HIST (delay = pitch + taps/2 <= 1023 + 2)
+// and the raw input up to c1 + DEC_LTM_LOOK (a tap reaches at most s + 1: 5 taps at pitch 1), a span of at most
+// HIST + CHUNK + LOOK <= RING samples, so no two live samples share a slot.  The steps inside a chunk are k_dec_ltm's:
+// min(d, 64) independent outputs each, one sample per step for d < 1, whose taps at s and s + 1 find the ring's slots
+// still holding input.  A step is cut at the chunk's end, which changes no value: every output is defined by the
+// recurrence alone.
+// Bounds: every LDS index is masked to the ring, so no num_samples, pitch or tap taken from the stream can leave it
+// (the ring's size is fixed at compile time and does not depend on n or the handle).  Global memory is touched at
+// io[s] with s < n for loads and delay <= s < n for stores only: the loops' own conditions, with `need`, c1 <= n.
+// A tap position at >= n is never read (it counts as 0), at < 0 cannot occur (s >= delay).
+// ---------------------------------------------------------------------------------------------
+#define DEC_LTM_CHUNK 2048u
+#define DEC_LTM_RING  4096u
+#define DEC_LTM_HIST  1025u              // 10-bit pitch + taps / 2
+#define DEC_LTM_LOOK  2u
+static_assert((DEC_LTM_RING & (DEC_LTM_RING - 1u)) == 0 && DEC_LTM_HIST + DEC_LTM_CHUNK + DEC_LTM_LOOK <= DEC_LTM_RING,
+              "live span of k_dec_ltm_far must fit its ring");
+
+__global__ __launch_bounds__(64)
+void k_dec_ltm_far(int32_t* __restrict__ planes, uint64_t stride, const sla_hip_dec_block* __restrict__ blocks,
+                   const sla_hip_dec_info* __restrict__ info, const sla_hip_dec_chan* __restrict__ chan,
+                   uint32_t num_channels, uint32_t ntaps)
+{
+  __shared__ __attribute__((aligned(16))) int32_t s_ring[DEC_LTM_RING];
+  constexpr uint32_t M = DEC_LTM_RING - 1u;
+  const uint32_t j = blockIdx.x;
+  const uint32_t bi = j / num_channels, ch = j - bi * num_channels;
+  const sla_hip_dec_block b = blocks[bi];
+  if (info[bi].type != 0 || (b.flags & SLA_HIP_DEC_HEADER_ONLY)) { return; }
+  const sla_hip_dec_chan ci = chan[j];
+  const uint32_t n = b.num_samples;
+  const uint32_t delay = ci.pitch + (ntaps >> 1);
+  if (ci.pitch == 0 || delay >= n || delay > DEC_LTM_HIST) { return; }       // (a pitch is a 10-bit field: the last never holds)
+  int32_t* io = planes + (uint64_t)ch * stride + b.smp_off;
+  const uint32_t lane = threadIdx.x;
+  const int32_t d = (int32_t)ci.pitch - (int32_t)((ntaps - 1) >> 1);
+  const uint32_t step = (d < 1) ? 1u : ((d > 64) ? 64u : (uint32_t)d);
+  uint32_t loaded = 0;                                       // [0, loaded) has been brought into the ring
+  for (uint32_t c0 = 0; c0 < n; c0 += DEC_LTM_CHUNK) {
+    const uint32_t c1 = (n - c0 > DEC_LTM_CHUNK) ? c0 + DEC_LTM_CHUNK : n;
+    const uint32_t need = (n - c1 > DEC_LTM_LOOK) ? c1 + DEC_LTM_LOOK : n;
+    for (uint32_t s = loaded + lane; s < need; s += 64) { s_ring[s & M] = io[s]; }
+    loaded = need;
+    __syncthreads();
+    const uint32_t first = (c0 > delay) ? c0 : delay;
+    for (uint32_t s0 = first; s0 < c1; s0 += step) {
+      const uint32_t s = s0 + lane;
+      if (lane < step && s < c1) {
+        int64_t acc = (int64_t)1 << 30;
+        for (uint32_t k = 0; k < ntaps; k++) {
+          const uint32_t at = s - delay + k;
+          acc += (int64_t)ci.ltm_coef[k] * (int64_t)((at < n) ? s_ring[at & M] : 0);
+        }
+        s_ring[s & M] = (int32_t)((uint32_t)s_ring[s & M] + (uint32_t)(int32_t)(acc >> 31));
+      }
+      __syncthreads();                                       // one wave: orders the LDS writes before the next step's reads
+    }
+    for (uint32_t s = first + lane; s < c1; s += 64) { io[s] = s_ring[s & M]; }
+    __syncthreads();                                         // the next chunk's look-ahead lands in the slots of c0 and c0 + 1, read just above
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1109,6 +1175,8 @@ extern "C" int sla_hip_launch_dec_lms(int32_t* d_planes, uint64_t plane_stride, 
   return hip_rc(hipGetLastError());
 }
 
+extern "C" uint32_t sla_hip_dec_ltm_window(void) { return DEC_LTM_CHUNK; }
+
 extern "C" int sla_hip_launch_dec_ltm(int32_t* d_planes, uint64_t plane_stride, const sla_hip_dec_block* d_blocks,
                                       const sla_hip_dec_info* d_info, const sla_hip_dec_chan* d_chan,
                                       uint32_t num_blocks, uint32_t num_channels, uint32_t longterm_order,
@@ -1116,9 +1184,13 @@ extern "C" int sla_hip_launch_dec_ltm(int32_t* d_planes, uint64_t plane_stride, 
 {
   if (d_planes == nullptr || d_blocks == nullptr || d_info == nullptr || d_chan == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if (num_channels == 0 || num_channels > 8 || longterm_order > 5) { return SLA_APIRESULT_INVALID_ARGUMENT; }
-  if ((size_t)max_block_samples * sizeof(int32_t) > SLA_HIP_LDS_BUDGET) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
   if (num_blocks == 0 || longterm_order == 0) { return 0; }
   const size_t lds = (size_t)max_block_samples * sizeof(int32_t);
+  if (lds > SLA_HIP_LDS_BUDGET) {                            // a block may not fit LDS: the ring kernel, whatever the blocks' lengths
+    hipLaunchKernelGGL(k_dec_ltm_far, dim3(num_blocks * num_channels), dim3(64), 0, (hipStream_t)stream, d_planes, plane_stride,
+                       d_blocks, d_info, d_chan, num_channels, longterm_order);
+    return hip_rc(hipGetLastError());
+  }
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)k_dec_ltm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) { return hip_rc(e); }

@@ -17,7 +17,7 @@
 #include <string.h>
 #include <time.h>
 
-#define DEC_MAX_BLOCK_SAMPLES 16384u
+#define DEC_MAX_BLOCK_SAMPLES 65535u     /* the format's: a 16-bit field */
 #define DEC_MIN_BLOCK_HEADER  11u        /* SLA_MINIMUM_BLOCK_HEADER_SIZE, reference src/include/private/SLAInternal.h:35 */
 #define STATUS_WAVE_FORMAT    1u
 #define STATUS_ENCODE_PARAM   2u

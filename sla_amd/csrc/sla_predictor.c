@@ -431,7 +431,9 @@ SLAPredictorApiResult SLALongTermSynthesizer_SynthesizeInt32(
   if (l == NULL || residual == NULL || ltm_coef == NULL || output == NULL) { return SLAPREDICTOR_APIRESULT_INVALID_ARGUMENT; }
   if (pitch_period == 0) { memmove(output, residual, sizeof(int32_t) * num_samples); return SLAPREDICTOR_APIRESULT_OK; }
   if (num_taps > l->max_taps || !(num_taps & 1u)) { return SLAPREDICTOR_APIRESULT_EXCEED_MAX_ORDER; }
-  if (pitch_period > l->max_period || l->used || num_samples > 16384) { return SLAPREDICTOR_APIRESULT_NG; }
+  if (pitch_period > l->max_period || l->used || num_samples > 65535u) { return SLAPREDICTOR_APIRESULT_NG; }
+  /* past the LDS budget the ring kernel runs (sla_hip_launch_dec_ltm): its history covers the format's 10-bit pitches */
+  if (sizeof(int32_t) * (size_t)num_samples > SLA_HIP_LDS_BUDGET && pitch_period > 1023u) { return SLAPREDICTOR_APIRESULT_NG; }
   if (num_samples == 0) { return SLAPREDICTOR_APIRESULT_OK; }
   l->used = 1;
   return (synth_once(1, residual, num_samples, output, 0, pitch_period, ltm_coef, num_taps, NULL, 0, 0, 0) == 0)
