@@ -309,6 +309,36 @@ int sla_hip_launch_lpc_rerun(const int32_t* d_pcm, uint64_t plane_stride, uint32
                              uint32_t max_cands_per_group, const sla_hip_lpc_cand* d_cands,
                              double* d_out, uint32_t* d_rerun_counter, sla_hip_stream_t stream);
 
+/* The far-window LPC stage: sla_hip_launch_lpc -- same arguments, same outputs in both of its forms, bit for bit -- for windows
+ * that do not fit the LDS: max_window up to SLA_HIP_LPC_FAR_MAX_WINDOW, orders 1 to 255, any number of candidates per group
+ * (no LDS bound on them).  The windows are staged as doubles into d_scratch (scratch_slots x max_window doubles; groups beyond
+ * the slots are taken in passes of scratch_slots groups, group g in slot g % scratch_slots) and the reference's serial chains
+ * (src/SLAPredictor.c:331-388) run on them out of the L2: one thread per (candidate, lag), a window's chains spread over as many
+ * workgroups as they fill; Levinson-Durbin (and, with d_code / d_kint / d_rshift, the quantiser) with one lane per candidate.
+ * Search form (d_code == NULL): d_window_pool may be NULL when every group is SLA_HIP_NO_WINDOW.  Block form: one candidate per
+ * group; d_window_pool must be given.  Both forms stage through the scratch (the chains take a pointer to doubles).
+ * Returns SLA_APIRESULT_INVALID_ARGUMENT before any launch for a NULL d_pcm, d_groups, d_cands, d_out or d_scratch,
+ * scratch_slots == 0, order outside 1..255, max_window == 0 or above SLA_HIP_LPC_FAR_MAX_WINDOW, max_cands_per_group == 0, some
+ * but not all of d_code / d_kint / d_rshift, or a block form with max_cands_per_group != 1 or without d_window_pool.
+ * A group's num_samples must not exceed max_window and a candidate must lie inside its group's window (one that does not is
+ * analysed as empty; nothing is read or written outside the slots).  Slots of groups not in the launch are not touched.
+ * extra->d_span: first kernel in to last kernel out.  Slower per chain than k_lpc wherever both apply: the encoder takes it
+ * only for encode parameters above 16 384 samples. */
+#define SLA_HIP_LPC_FAR_MAX_WINDOW 65535u
+int sla_hip_launch_lpc_far(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                           const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                           uint32_t max_cands_per_group,
+                           const sla_hip_lpc_cand* d_cands, const double* d_window_pool,
+                           double* d_out, int32_t* d_code, int32_t* d_kint, uint32_t* d_rshift,
+                           double* d_scratch, uint32_t scratch_slots, sla_hip_stream_t stream);
+int sla_hip_launch_lpc_far_x(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                             const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                             uint32_t max_cands_per_group,
+                             const sla_hip_lpc_cand* d_cands, const double* d_window_pool,
+                             double* d_out, int32_t* d_code, int32_t* d_kint, uint32_t* d_rshift,
+                             double* d_scratch, uint32_t scratch_slots, sla_hip_stream_t stream,
+                             const sla_hip_launch_extra* extra);
+
 /* Partition search without serial chains (reference src/SLAPredictor.c:1615-1649 + :331-388).
  * The search analyses the un-windowed samples: integers times a power of two.  As long as the energy of
  * a group's window stays below `exact_limit` (= 2^51 units^2, unit = the common power-of-two factor of
@@ -1262,6 +1292,31 @@ int sla_hip_launch_verify_blocks(const int32_t* d_planes, uint64_t plane_stride,
                                  uint64_t* d_report, sla_hip_stream_t stream);
 
 /* ---- (2) whole-file driver ---------------------------------------------- */
+
+/* Long blocks: encode parameters with max_num_block_samples of 16 385 to 65 535 (the format's 16-bit block length; the
+ * reference's library writes such blocks as soon as the parameter asks for them).  SLAEncoder_SetEncodeParameter accepts up to
+ * min(the handle's capacity, 65 535), SLAEncoder_EncodeBlock blocks up to the handle's capacity once such a parameter is set.
+ * While such a parameter is set the handle takes, WHATEVER its options say (they are neither changed nor consulted, and hold
+ * again for the next ordinary parameter), the routes that are exact and host-planned at any block length:
+ *   search          sla_hip_launch_lpc_far, search form: one group per (super-frame, channel) with all its candidates
+ *   planner         the host's (sla_plan.c: up to 66 nodes); k_plan is sized for 17
+ *   block tables    built on the host: no "device_plan", "device_expand", "search_early", no kept tables, no speculation, one chunk
+ *   block stage     sla_hip_launch_lpc_far, block form; no "block_cert" (the certificate's constants were validated for n <= 16 384)
+ *                   and no fused lattice; the lattice, tail, Rice and pack kernels are general in the block length
+ *   long-term stage the exact route (no "ltm_cert" / "ltm_int"): transforms of 65 536 and 131 072 points through the global scratch
+ *   silence         through the mask (no "silence_runs")
+ * and the sla_hip_last_* reports say so (no tile sums, no device plan, no device tables, no certificate).  Output is the
+ * reference's, byte for byte.  Slower per sample than ordinary parameters (profiles/long_enc.json).
+ * Calls that take long blocks:      SLAEncoder_EncodeWhole (never streamed over worker lanes), SLAEncoder_EncodeBlock,
+ *                                   sla_hip_analyze_device with sla_hip_pack or sla_hip_pack_device, sla_hip_encode_batch (no lanes).
+ * Calls that refuse them, with SLA_APIRESULT_EXCEED_HANDLE_CAPACITY before anything is launched: sla_hip_encode_batch_device,
+ *                                   sla_hip_encode_batch_resident, sla_hip_encode_wav_batch, sla_hip_encode_wav_batch_resident,
+ *                                   sla_hip_analyze_batch_device, sla_hip_pack_resident, sla_hip_shard_analyze,
+ *                                   sla_hip_shard_analyze_no_silence, sla_hip_verify_last_image, and each of the four calls above while
+ *                                   option "verify" is on.
+ * A handle of a capacity above 16 384 that is given an ordinary parameter is an ordinary handle, except that its long-term FFT
+ * follows the capacity, as the reference's does: above 32 768 points (capacity above 16 384) sla_hip_ltm_cert_supported is 0
+ * and its long-term stage takes the exact route at every parameter.  The per-call SLAPredictor API keeps its 16 384 samples. */
 
 /* Per-block results of the last analyze call, copied into caller arrays
  * (layout identical to the oracle's trace so tests can diff them). */

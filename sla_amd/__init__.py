@@ -467,7 +467,7 @@ EXPORTED_SYMBOLS = [
     "sla_hip_launch_lpc_f64", "sla_hip_launch_lattice_raw", "sla_hip_launch_tail_stages", "sla_hip_launch_emphasis_i32",
     "sla_hip_launch_emphasis_f64", "sla_hip_use_tuning", "sla_hip_launch_lattice_groups", "sla_hip_launch_ltm_solve",
     "sla_hip_launch_ltm_cert_x", "sla_hip_ltm_fast_twiddles", "sla_hip_ltm_cert_eps_rel", "sla_hip_ltm_cert_supported", "sla_hip_last_ltm_cert",
-    "sla_hip_launch_ltm_acf_int", "sla_hip_launch_acf_blocks",
+    "sla_hip_launch_ltm_acf_int", "sla_hip_launch_acf_blocks", "sla_hip_launch_lpc_far", "sla_hip_launch_lpc_far_x",
     "sla_hip_encoder_set_option", "sla_hip_shard_scan", "sla_hip_shard_scan_counts", "sla_hip_shard_bounds", "sla_hip_shard_analyze", "sla_hip_shard_analyze_no_silence", "sla_hip_shard_header",
     # include/SLAPredictor.h, include/SLACoder.h (per-call API of the reference, encode side)
     "SLALPCCalculator_Create", "SLALPCCalculator_Destroy", "SLALPCCalculator_CalculatePARCORCoefDouble",
@@ -572,10 +572,20 @@ class Trace:
 
 
 class Encoder:
-    """Python face of ``struct SLAEncoder`` (reference src/include/public/SLAEncoder.h)."""
+    """Python face of ``struct SLAEncoder`` (reference src/include/public/SLAEncoder.h).
+
+    max_num_block_samples: up to 16384 -- what the reference's tool writes, the default -- or, with long_blocks=True, up to
+    65535, the longest block the format's 16-bit field can hold.  Encode parameters above 16384 take the long-block routes
+    (include/sla_hip.h: the far-window LPC stage, host planner, exact long-term stage; slower per sample) and the handle's
+    FFT and scratch grow with the capacity, which is why the larger capacity is asked for by name, as with Decoder."""
+
+    LONG_BLOCKS_FROM = 16384      # capacities above this need long_blocks=True
 
     def __init__(self, max_num_channels=8, max_num_block_samples=16384, max_parcor_order=48,
-                 max_longterm_order=5, max_lms_order_per_filter=40):
+                 max_longterm_order=5, max_lms_order_per_filter=40, long_blocks=False):
+        if max_num_block_samples > self.LONG_BLOCKS_FROM and not long_blocks:
+            raise RuntimeError("max_num_block_samples %d: capacities above %d (up to the format's 65535) need long_blocks=True"
+                               % (max_num_block_samples, self.LONG_BLOCKS_FROM))
         self._lib = lib()
         cfg = SLAEncoderConfig(max_num_channels, max_num_block_samples, max_parcor_order,
                                max_longterm_order, max_lms_order_per_filter, 0)

@@ -407,6 +407,58 @@ static int launch_lpc_impl(const int32_t* d_pcm, uint64_t plane_stride, uint32_t
   return hip_rc(hipGetLastError());
 }
 
+// The far-window LPC stage (kernels/lpc_far.inc): sla_hip_launch_lpc's semantics for windows of up to 65 535 samples.
+extern "C" int sla_hip_launch_lpc_far_x(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                                        const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                                        uint32_t max_cands_per_group,
+                                        const sla_hip_lpc_cand* d_cands, const double* d_window_pool,
+                                        double* d_out, int32_t* d_code, int32_t* d_kint, uint32_t* d_rshift,
+                                        double* d_scratch, uint32_t scratch_slots,
+                                        sla_hip_stream_t stream, const sla_hip_launch_extra* extra)
+{
+  if (d_pcm == nullptr || d_groups == nullptr || d_cands == nullptr || d_out == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (order < 1 || order > 255 || max_window == 0 || max_window > SLA_HIP_LPC_FAR_MAX_WINDOW || max_cands_per_group == 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if ((d_code != nullptr) != (d_kint != nullptr) || (d_code != nullptr) != (d_rshift != nullptr)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (d_code != nullptr && (max_cands_per_group != 1 || d_window_pool == nullptr)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (d_scratch == nullptr || scratch_slots == 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_groups == 0) { return 0; }
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t chains = (uint64_t)max_cands_per_group * (order + 1);
+  const uint64_t chunks = (chains + FAR_THREADS - 1) / FAR_THREADS;
+  const size_t per_cand = sizeof(double) * (3 * (size_t)order + 5);      // r[order + 1], a[order + 2], v[order + 2]
+  uint32_t per_wg = (uint32_t)(FAR_FINISH_LDS / per_cand);
+  if (per_wg > 64) { per_wg = 64; }
+  if (per_wg > max_cands_per_group) { per_wg = max_cands_per_group; }
+  const uint64_t fchunks = ((uint64_t)max_cands_per_group + per_wg - 1) / per_wg;
+  const uint32_t pass = (num_groups < scratch_slots) ? num_groups : scratch_slots;
+  if (chunks * pass > 0x7FFFFFFFull || fchunks * num_groups > 0x7FFFFFFFull) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
+  for (uint32_t g_lo = 0; g_lo < num_groups; g_lo += pass) {
+    const uint32_t ng = (num_groups - g_lo < pass) ? (num_groups - g_lo) : pass;
+    hipLaunchKernelGGL(k_lpc_far_stage, dim3(ng), dim3(FAR_THREADS), 0, st, d_pcm, plane_stride, mid_side, d_groups, g_lo, d_window_pool,
+                       d_scratch, max_window, d_rshift, (g_lo == 0) ? span_of(extra) : nullptr);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { return hip_rc(e); }
+    hipLaunchKernelGGL(k_lpc_far_chains, dim3((uint32_t)(chunks * ng)), dim3(FAR_THREADS), 0, st, d_groups, g_lo, d_cands, order,
+                       (const double*)d_scratch, max_window, (uint32_t)chunks, d_out);
+    e = hipGetLastError();
+    if (e != hipSuccess) { return hip_rc(e); }
+  }
+  hipLaunchKernelGGL(k_lpc_far_finish, dim3((uint32_t)(fchunks * num_groups)), dim3(64), per_wg * per_cand, st, d_groups, d_cands, order,
+                     per_wg, (uint32_t)fchunks, max_window, d_out, d_code, d_kint, (const uint32_t*)d_rshift, span_of(extra));
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_lpc_far(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                                      const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                                      uint32_t max_cands_per_group,
+                                      const sla_hip_lpc_cand* d_cands, const double* d_window_pool,
+                                      double* d_out, int32_t* d_code, int32_t* d_kint, uint32_t* d_rshift,
+                                      double* d_scratch, uint32_t scratch_slots, sla_hip_stream_t stream)
+{
+  return sla_hip_launch_lpc_far_x(d_pcm, plane_stride, mid_side, order, d_groups, num_groups, max_window, max_cands_per_group, d_cands, d_window_pool,
+                                  d_out, d_code, d_kint, d_rshift, d_scratch, scratch_slots, stream, nullptr);
+}
+
 extern "C" uint32_t sla_hip_search_exact_lags(uint32_t order)
 {
   const uint32_t nb = (order + 1 + 3) / 4;

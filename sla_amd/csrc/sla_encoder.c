@@ -32,6 +32,11 @@
 #define STATUS_WAVE_FORMAT   (1u << 0)
 #define STATUS_ENCODE_PARAM  (1u << 1)
 #define MAX_ANALYSIS_WINDOW  16384u     /* LDS-resident window: 128 KiB of doubles */
+/* Encode parameters above it ("long blocks", up to the format's 16-bit block length) take the far-window LPC stage
+ * (sla_hip_launch_lpc_far: windows in global scratch slots) and the host-planned, exact routes of the other stages: long_begin */
+#define MAX_FAR_WINDOW       SLA_HIP_LPC_FAR_MAX_WINDOW
+#define FAR_SLOTS            64u        /* scratch windows of the search, and as many again of the block stage (512 KiB each) */
+#define LONG_PARAMS(e)       ((e)->encode_param.max_num_block_samples > MAX_ANALYSIS_WINDOW)
 
 typedef struct { void* ptr; size_t cap; } devbuf_t;
 typedef struct { void* ptr; size_t cap; } pinbuf_t;
@@ -224,6 +229,13 @@ struct SLAEncoder {
   float    timing[12];
   int      wall_clock_khz;          /* rate of the device's constant clock (cached) */
   float    kernel_ms[4];            /* last analysis: on-device execution spans of k_lpc_blocks, k_lattice, k_ltm_acf, k_tail, summed over chunks */
+
+  /* long blocks (LONG_PARAMS): the options a call runs with whatever the handle's say (long_begin / long_end keep the handle's
+   * own in long_saved meanwhile), the far stage's scratch windows, and what the last analysis was */
+  devbuf_t d_far_scratch;
+  int      long_depth, long_last;
+  struct { int device_plan, device_expand, search_early, table_cache, block_cert, ltm_cert, search_exact, fuse_lattice, stream_mode,
+               alt_streams, prelaunch, one_stream, chunks_forced; uint32_t silence_runs, ltm_int, chunks, batch_lanes, lpc_blocks_chains; } long_saved;
 };
 
 #define SPAN_SLOT(e, chunk, kernel) ((unsigned long long*)(e)->d_spans.ptr + ((size_t)(chunk) * 4 + (kernel)) * 2)
@@ -554,6 +566,7 @@ void SLAEncoder_Destroy(struct SLAEncoder* e)
   if (e->d_ver_kint.ptr != NULL) { (void)hipFree(e->d_ver_kint.ptr); }
   if (e->h_ver.ptr != NULL) { (void)hipHostFree(e->h_ver.ptr); }
   if (e->d_rice.ptr != NULL) { (void)hipFree(e->d_rice.ptr); }
+  if (e->d_far_scratch.ptr != NULL) { (void)hipFree(e->d_far_scratch.ptr); }
   if (e->h_rice.ptr != NULL) { (void)hipHostFree(e->h_rice.ptr); }
   free(e->w_job_blk.ptr); free(e->w_job_ch.ptr); free(e->w_job_grp.ptr); free(e->w_grp_of_slot.ptr);
   free(e->w_parts.ptr); free(e->w_nparts.ptr); free(e->w_status.ptr);
@@ -598,8 +611,8 @@ SLAApiResult SLAEncoder_SetEncodeParameter(struct SLAEncoder* e, const struct SL
       || ep->lms_order_per_filter > e->cfg.max_lms_order_per_filter
       || ep->max_num_block_samples > e->cfg.max_num_block_samples
       || ep->max_num_block_samples < SLAI_MIN_BLOCK) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
-  /* device limits of this implementation: the analysis window lives in LDS */
-  if (ep->max_num_block_samples > MAX_ANALYSIS_WINDOW || ep->parcor_order < 1) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
+  /* the format's block length is a 16-bit field; above MAX_ANALYSIS_WINDOW the handle takes the long-block routes (long_begin) */
+  if (ep->max_num_block_samples > MAX_FAR_WINDOW || ep->parcor_order < 1) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
   e->encode_param = *ep;
   e->status_flag |= STATUS_ENCODE_PARAM;
   e->analysed = 0; e->image_valid = 0;
@@ -937,7 +950,7 @@ static int build_tables(struct SLAEncoder* e, actx_t* a, const slai_silence* sil
       uint32_t cpg;
       if (a->sf[i].shape == 0xFFFFFFFFu) { continue; }
       sh = &a->shapes[a->sf[i].shape];
-      cpg = search_cands_per_group(a->max_window, order);
+      cpg = LONG_PARAMS(e) ? sh->ncand : search_cands_per_group(a->max_window, order);      /* (long blocks: the far stage has no LDS to fit) */
       if (cpg == 0) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
       if (cpg > sh->ncand) { cpg = sh->ncand; }
       total_groups += C * ((sh->ncand + cpg - 1) / cpg);
@@ -960,7 +973,7 @@ static int build_tables(struct SLAEncoder* e, actx_t* a, const slai_silence* sil
     f->grp_lo = f->grp_hi = a->nsgroups;
     if (f->shape == 0xFFFFFFFFu) { continue; }
     sh = &a->shapes[f->shape];
-    cpg = search_cands_per_group(a->max_window, order);
+    cpg = LONG_PARAMS(e) ? sh->ncand : search_cands_per_group(a->max_window, order);
     if (cpg > sh->ncand) { cpg = sh->ncand; }
     f->slot_base = a->nslots;
     for (ch = 0; ch < C; ch++) {
@@ -1495,6 +1508,7 @@ static int pipeline_reserve(struct SLAEncoder* e, const actx_t* a)
   if (sizeof(double) * (size_t)fft_size > SLA_HIP_LDS_BUDGET) {
     RCCHK(dev_reserve(&e->d_acf_scratch, sizeof(double) * (size_t)fft_size * 512));
   }
+  if (LONG_PARAMS(e)) { RCCHK(dev_reserve(&e->d_far_scratch, sizeof(double) * (size_t)MAX_FAR_WINDOW * 2 * FAR_SLOTS)); }
   if (e->user_res1 != NULL && e->user_stride != e->stride) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if (e->user_res1 == NULL) {
     RCCHK(dev_reserve(&e->d_res1, sizeof(int32_t) * (size_t)C * e->stride));
@@ -1589,6 +1603,12 @@ static int search_launch(struct SLAEncoder* e, actx_t* a, uint32_t c)
       RCCHK(sla_hip_launch_lpc_rerun(e->pcm_dev, e->stride, ms, order, (const sla_hip_lpc_group*)e->d_groups.ptr + k->grp_lo, ng,
                                      a->max_window, a->max_cpg, (const sla_hip_lpc_cand*)e->d_cands.ptr, (double*)e->d_lpc_out.ptr,
                                      (uint32_t*)e->d_or.ptr + 2, e->stream));
+    } else if (LONG_PARAMS(e)) {
+      /* long blocks: the far stage over the whole-candidate groups, one per (super-frame, channel), same slots as the slices */
+      HIPCHK(hipEventRecord(ev[EV_SEARCH_S], e->stream));
+      RCCHK(sla_hip_launch_lpc_far(e->pcm_dev, e->stride, ms, order, dx, nx, a->max_window, a->max_xcands,
+                                   (const sla_hip_lpc_cand*)e->d_cands.ptr, NULL, (double*)e->d_lpc_out.ptr, NULL, NULL, NULL,
+                                   (double*)e->d_far_scratch.ptr, FAR_SLOTS, e->stream));
     } else {
       sla_hip_lpc_group* dg = (sla_hip_lpc_group*)e->d_groups.ptr + k->grp_lo;
       RCCHK(search_groups_ready(e, a));
@@ -1837,7 +1857,7 @@ static int blocks_launch(struct SLAEncoder* e, actx_t* a, uint32_t c, int mode)
     const blk_t* blk = &e->blk[b];
     uint32_t woff = 0;
     if (blk->type == SLAI_BLK_SILENT) { continue; }
-    if (blk->nsmpl > MAX_ANALYSIS_WINDOW) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
+    if (blk->nsmpl > (LONG_PARAMS(e) ? MAX_FAR_WINDOW : MAX_ANALYSIS_WINDOW)) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
     RCCHK(window_offset(e, blk->nsmpl, &woff));
     if (e->win_dirty) { return SLA_APIRESULT_NG; }      /* every length was tabulated in pipeline_prepare */
     for (ch = 0; ch < C; ch++) {
@@ -1897,6 +1917,12 @@ static int blocks_launch(struct SLAEncoder* e, actx_t* a, uint32_t c, int mode)
                                              (uint32_t*)e->d_rshift.ptr, (uint32_t*)e->d_cert_flag.ptr,
                                              (uint32_t*)e->d_fb_list.ptr + k->bg_lo, (uint32_t*)e->d_fb_count.ptr + c,
                                              e->block_cert_safety, bps, bs, &xb));
+    } else if (LONG_PARAMS(e)) {
+      /* long blocks: the far stage's block form, in the second half of its scratch (the search's half may still be read) */
+      RCCHK(sla_hip_launch_lpc_far_x(e->pcm_dev, e->stride, ms, order, dg, ng, max_window, 1,
+                                     (const sla_hip_lpc_cand*)e->d_bcands.ptr, (const double*)e->d_winpool.ptr,
+                                     (double*)e->d_blk_out.ptr, (int32_t*)e->d_code.ptr, (int32_t*)e->d_kint.ptr,
+                                     (uint32_t*)e->d_rshift.ptr, (double*)e->d_far_scratch.ptr + (size_t)MAX_FAR_WINDOW * FAR_SLOTS, FAR_SLOTS, bs, &xb));
     } else {
       RCCHK(sla_hip_launch_lpc_x(e->pcm_dev, e->stride, ms, order, dg, ng, max_window, 1,
                                  (const sla_hip_lpc_cand*)e->d_bcands.ptr, (const double*)e->d_winpool.ptr,
@@ -2302,6 +2328,7 @@ static int run_pipeline(struct SLAEncoder* e, int preset_blocks)
   e->expanded_chunks = 0;
   e->image_valid = 0;                /* a new analysis: whatever image a pack left belongs to other tables */
   memset(e->ltm_stat, 0, sizeof(e->ltm_stat));
+  e->long_last = LONG_PARAMS(e);
   e->ltm_cert_now = (e->ltm_cert && e->device_ltm && sla_hip_ltm_cert_supported(slai_fft_plan_size(e->fft)));
   e->cert_now = (e->block_cert && !(e->fuse_lattice && e->encode_param.parcor_order <= SLA_HIP_FUSED_LATTICE_MAX_ORDER) && !e->tune.lpc_blocks_chains
                  && sla_hip_search_exact_lags(e->encode_param.parcor_order) != 0);
@@ -2535,6 +2562,45 @@ static int enter(struct SLAEncoder* e)
   return 0;
 }
 
+/* Long blocks (encode parameters above MAX_ANALYSIS_WINDOW samples): every public call that encodes them runs between
+ * long_begin and long_end, which put the handle on the routes that are exact and host-planned at any block length, whatever its
+ * options say -- the search and the chosen blocks through the far-window LPC stage (search_launch, blocks_launch), the host
+ * planner and host-built block tables (k_plan and k_expand are sized for 17 nodes and 16 384 samples), no kept tables and no
+ * speculation, no certificates (the block stage's constants and the long-term stage's transforms were validated up to 16 384
+ * samples / 32 768 points), silence through the mask, one chunk, no worker lanes -- and give the handle its own options back.
+ * The tables a long-block call leaves on the device are never taken for an ordinary file's. */
+static void long_begin(struct SLAEncoder* e)
+{
+  if (!LONG_PARAMS(e) || e->long_depth++ > 0) { return; }
+  e->long_saved.device_plan = e->device_plan; e->long_saved.device_expand = e->device_expand; e->long_saved.search_early = e->search_early;
+  e->long_saved.table_cache = e->table_cache; e->long_saved.block_cert = e->block_cert; e->long_saved.ltm_cert = e->ltm_cert;
+  e->long_saved.search_exact = e->search_exact; e->long_saved.fuse_lattice = e->fuse_lattice; e->long_saved.stream_mode = e->stream_mode;
+  e->long_saved.alt_streams = e->alt_streams; e->long_saved.prelaunch = e->prelaunch; e->long_saved.one_stream = e->one_stream;
+  e->long_saved.chunks_forced = e->chunks_forced; e->long_saved.silence_runs = e->silence_runs; e->long_saved.ltm_int = e->tune.ltm_int;
+  e->long_saved.chunks = e->chunks; e->long_saved.batch_lanes = e->batch_lanes; e->long_saved.lpc_blocks_chains = e->tune.lpc_blocks_chains;
+  e->device_plan = 0; e->device_expand = 0; e->search_early = 0; e->table_cache = 0; e->block_cert = 0; e->ltm_cert = 0;
+  e->search_exact = 0; e->fuse_lattice = 0; e->stream_mode = 0; e->alt_streams = 0; e->prelaunch = 0; e->one_stream = 0;
+  e->chunks_forced = 0; e->silence_runs = 0; e->tune.ltm_int = 0; e->chunks = 1; e->batch_lanes = 1; e->tune.lpc_blocks_chains = 0;
+  e->tab_valid = 0; e->spec_valid = 0;
+  sla_hip_use_tuning(&e->tune);
+}
+
+static void long_end(struct SLAEncoder* e)
+{
+  if (!LONG_PARAMS(e) || e->long_depth == 0 || --e->long_depth > 0) { return; }
+  e->device_plan = e->long_saved.device_plan; e->device_expand = e->long_saved.device_expand; e->search_early = e->long_saved.search_early;
+  e->table_cache = e->long_saved.table_cache; e->block_cert = e->long_saved.block_cert; e->ltm_cert = e->long_saved.ltm_cert;
+  e->search_exact = e->long_saved.search_exact; e->fuse_lattice = e->long_saved.fuse_lattice; e->stream_mode = e->long_saved.stream_mode;
+  e->alt_streams = e->long_saved.alt_streams; e->prelaunch = e->long_saved.prelaunch; e->one_stream = e->long_saved.one_stream;
+  e->chunks_forced = e->long_saved.chunks_forced; e->silence_runs = e->long_saved.silence_runs; e->tune.ltm_int = e->long_saved.ltm_int;
+  e->chunks = e->long_saved.chunks; e->batch_lanes = e->long_saved.batch_lanes; e->tune.lpc_blocks_chains = e->long_saved.lpc_blocks_chains;
+  e->tab_valid = 0; e->spec_valid = 0; e->groups_valid = 0;
+  sla_hip_use_tuning(&e->tune);
+}
+
+/* the public encode routes that do not take long blocks (include/sla_hip.h lists them): refused before anything is launched */
+#define LONG_REFUSE(e) do { if ((e) != NULL && ((e)->status_flag & STATUS_ENCODE_PARAM) && LONG_PARAMS(e)) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; } } while (0)
+
 int sla_hip_encoder_set_option(struct SLAEncoder* e, const char* name, double value)
 {
   const long iv = (long)value;
@@ -2614,13 +2680,27 @@ static int check_ready(const struct SLAEncoder* e)
   return 0;
 }
 
+static int analyze_device_impl(struct SLAEncoder* e, const int32_t* d_pcm, uint64_t plane_stride,
+                               uint32_t num_samples, sla_hip_stream_t stream, float* timing_ms);
+
 int sla_hip_analyze_device(struct SLAEncoder* e, const int32_t* d_pcm, uint64_t plane_stride,
                            uint32_t num_samples, sla_hip_stream_t stream, float* timing_ms)
 {
-  const double t_start = now_ms();
   int rc;
   if (e == NULL || d_pcm == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   RCCHK(check_ready(e));
+  if (LONG_PARAMS(e) && e->verify) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }      /* (option "verify": not with long blocks) */
+  long_begin(e);
+  rc = analyze_device_impl(e, d_pcm, plane_stride, num_samples, stream, timing_ms);
+  long_end(e);
+  return rc;
+}
+
+static int analyze_device_impl(struct SLAEncoder* e, const int32_t* d_pcm, uint64_t plane_stride,
+                               uint32_t num_samples, sla_hip_stream_t stream, float* timing_ms)
+{
+  const double t_start = now_ms();
+  int rc;
   if (plane_stride < num_samples) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   RCCHK(enter(e));
   if (stream != NULL) { HIPCHK(hipStreamSynchronize((hipStream_t)stream)); }   /* producer of d_pcm */
@@ -2727,6 +2807,7 @@ int sla_hip_shard_analyze(struct SLAEncoder* e, const int32_t* d_pcm, uint64_t p
 {
   int rc;
   if (e == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  LONG_REFUSE(e);
   e->file_or_word = file_or_word;
   rc = sla_hip_analyze_device(e, d_pcm, plane_stride, num_samples, NULL, timing_ms);
   e->file_or_word = 0;
@@ -2740,6 +2821,7 @@ int sla_hip_shard_analyze_no_silence(struct SLAEncoder* e, const int32_t* d_pcm,
 {
   int rc;
   if (e == NULL || file_or_word == 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  LONG_REFUSE(e);
   e->file_or_word = file_or_word; e->skip_prepass = 1;
   rc = sla_hip_analyze_device(e, d_pcm, plane_stride, num_samples, NULL, timing_ms);
   e->file_or_word = 0; e->skip_prepass = 0;
@@ -2778,7 +2860,7 @@ int sla_hip_last_counters(const struct SLAEncoder* e, uint32_t* counters)
 {
   if (e == NULL || counters == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   counters[0] = e->fallback_groups; counters[1] = e->host_planned;
-  counters[2] = (uint32_t)e->timing[11]; counters[3] = (uint32_t)e->device_plan;
+  counters[2] = (uint32_t)e->timing[11]; counters[3] = (uint32_t)(e->device_plan && !e->long_last);
   counters[4] = e->tail_launches; counters[5] = (uint32_t)e->device_ltm;
   return 0;
 }
@@ -3132,6 +3214,7 @@ int sla_hip_verify_last_image(struct SLAEncoder* e, const int32_t* d_pcm, uint64
   const uint64_t* rep;
   int rc;
   if (e == NULL || d_pcm == NULL || counters == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  LONG_REFUSE(e);
   if (!e->image_valid) { return SLA_APIRESULT_PARAMETER_NOT_SET; }
   if (plane_stride < e->img_samples) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   RCCHK(enter(e));
@@ -3470,6 +3553,7 @@ int sla_hip_pack_resident(struct SLAEncoder* e, uint8_t* d_data, uint32_t data_s
   pack_seg_t seg;
   int rc;
   if (e == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  LONG_REFUSE(e);
   if (!e->analysed) { return SLA_APIRESULT_PARAMETER_NOT_SET; }
   if (d_data == NULL || output_size == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if (data_size < SLA_HEADER_SIZE) { return SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE; }
@@ -3878,7 +3962,7 @@ static int encode_whole_streamed(struct SLAEncoder* e, const int32_t* const* inp
   uint32_t piece, K, L, r, t, started = 0;
   int rc = 0;
   struct SLAHeaderInfo hinfo;
-  if (!e->stream_mode || e->is_lane || C == 0) { return -1; }
+  if (!e->stream_mode || e->is_lane || C == 0 || LONG_PARAMS(e)) { return -1; }      /* (long blocks: never streamed) */
   piece = e->stream_piece / C;
   piece = (piece + 63u) & ~63u;
   if (piece < e->encode_param.max_num_block_samples * 2u) { piece = (e->encode_param.max_num_block_samples * 2u + 63u) & ~63u; }
@@ -3931,6 +4015,7 @@ SLAApiResult SLAEncoder_EncodeWhole(struct SLAEncoder* e, const int32_t* const* 
   if (e == NULL || input == NULL || data == NULL || output_size == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if ((rc = check_ready(e)) != 0) { return (SLAApiResult)rc; }
   if (data_size < SLA_HEADER_SIZE) { return SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE; }
+  if (LONG_PARAMS(e) && e->verify) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }      /* (option "verify": not with long blocks) */
   if (enter(e) != 0) { return SLA_APIRESULT_NG; }
   {
     const double t0 = now_ms();
@@ -4283,6 +4368,7 @@ int sla_hip_analyze_batch_device(struct SLAEncoder* e, const int32_t* d_pcm, uin
   int rc = 0;
   if (e == NULL || d_pcm == NULL || (num_files != 0 && (file_start == NULL || file_samples == NULL))) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   RCCHK(check_ready(e));
+  LONG_REFUSE(e);
   if (plane_stride < span || span > BATCH_MAX_SPAN) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   for (i = 0; i < num_files; i++) {
     if (file_start[i] % SLA_HIP_PREPASS_TILE != 0 || (uint64_t)file_start[i] + file_samples[i] > span
@@ -4437,12 +4523,24 @@ static int encode_batch_on_lanes(struct SLAEncoder* e, sla_hip_batch_item* items
   return (rc > 0) ? rc : (rc < 0 ? SLA_APIRESULT_NG : 0);
 }
 
+static int encode_batch_impl(struct SLAEncoder* e, sla_hip_batch_item* items, uint32_t num_items);
+
 int sla_hip_encode_batch(struct SLAEncoder* e, sla_hip_batch_item* items, uint32_t num_items)
 {
-  uint32_t first = 0, i, ch;
   int rc;
   if (e == NULL || (items == NULL && num_items != 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if ((rc = check_ready(e)) != 0) { return rc; }
+  if (LONG_PARAMS(e) && e->verify) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }      /* (option "verify": not with long blocks) */
+  long_begin(e);
+  rc = encode_batch_impl(e, items, num_items);
+  long_end(e);
+  return rc;
+}
+
+static int encode_batch_impl(struct SLAEncoder* e, sla_hip_batch_item* items, uint32_t num_items)
+{
+  uint32_t first = 0, i, ch;
+  int rc;
   RCCHK(enter(e));
   verify_clear(e);
   memset(e->sil_stat, 0, sizeof(e->sil_stat));
@@ -4485,6 +4583,7 @@ static int encode_batch_device_impl(struct SLAEncoder* e, sla_hip_encode_device_
   int rc;
   if (e == NULL || (items == NULL && num_items != 0) || sample_format > SLA_HIP_PCM_F32) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if ((rc = check_ready(e)) != 0) { return rc; }
+  LONG_REFUSE(e);
   for (i = 0; i < num_items; i++) {
     if (items[i].num_samples > BATCH_MAX_SPAN - SLA_HIP_PREPASS_TILE) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
   }
@@ -4619,6 +4718,7 @@ static int encode_wav_impl(struct SLAEncoder* e, sla_hip_wav_item* items, uint32
   int rc = 0;
   if (e == NULL || (items == NULL && num_items != 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if (!(e->status_flag & STATUS_ENCODE_PARAM)) { return SLA_APIRESULT_PARAMETER_NOT_SET; }
+  LONG_REFUSE(e);
   if (num_items == 0) { return 0; }
   RCCHK(enter(e));
   if (resident == 2 && !device_bytes_ok(d_arena, arena_bytes, e->device)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
@@ -4756,10 +4856,12 @@ SLAApiResult SLAEncoder_EncodeBlock(struct SLAEncoder* e, const int32_t* const* 
   int rc;
   if (e == NULL || input == NULL || data == NULL || output_size == NULL) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if (!(e->status_flag & STATUS_WAVE_FORMAT) || !(e->status_flag & STATUS_ENCODE_PARAM)) { return SLA_APIRESULT_PARAMETER_NOT_SET; }
-  if (num_samples > e->cfg.max_num_block_samples || num_samples > MAX_ANALYSIS_WINDOW) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
+  /* (a block longer than MAX_ANALYSIS_WINDOW needs the long-block routes, which follow the encode parameter) */
+  if (num_samples > e->cfg.max_num_block_samples || num_samples > (LONG_PARAMS(e) ? MAX_FAR_WINDOW : MAX_ANALYSIS_WINDOW)) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
   if (data_size <= SLA_BLOCK_HEADER_SIZE) { return SLA_APIRESULT_INSUFFICIENT_DATA_SIZE; }
   if ((rc = check_ready(e)) != 0) { return (SLAApiResult)rc; }
   if (num_samples == 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (LONG_PARAMS(e) && e->verify) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
   C = e->wave_format.num_channels;
   if (enter(e) != 0) { return SLA_APIRESULT_NG; }
   if ((rc = upload_pcm(e, input, num_samples)) != 0) { return (rc > 0) ? (SLAApiResult)rc : SLA_APIRESULT_NG; }
@@ -4781,7 +4883,9 @@ SLAApiResult SLAEncoder_EncodeBlock(struct SLAEncoder* e, const int32_t* const* 
   if (blocks_push(e, 0, num_samples, slai_range_is_zero((const uint64_t*)e->h_nz.ptr, 0, num_samples) ? SLAI_BLK_SILENT : SLAI_BLK_COMPRESS) != 0) {
     return SLA_APIRESULT_NG;
   }
+  long_begin(e);
   rc = run_pipeline(e, 1);
+  long_end(e);
   if (rc != 0) { return (rc > 0) ? (SLAApiResult)rc : SLA_APIRESULT_NG; }
   e->analysed = 1;
   /* pack into a scratch image (header + block) and hand back the block bytes only */

@@ -14,6 +14,8 @@
 //   k_search_cert (search)                where the order of summation provably cannot matter, certified where it can; :253-328
 //   k_lpc (lpc_chains)                    src/SLAPredictor.c:331-388 in the reference's serial order + :253-328: the rerun of windows
 //                                         the certificate could not decide, and the per-call predictor API
+//   k_lpc_far_stage / _chains / _finish   the same, for windows of up to 65 535 samples: the window in a global scratch slot (L2),
+//   (lpc_far)                             the chains of lpc_chains.inc on it; search and chosen blocks of long-block parameters
 //   k_plan (search)                       src/SLAPredictor.c:416-468 (code length), :1521-1581 (Dijkstra), :1652-1692 (partition),
 //                                         certified against libm's last bits
 //   k_expand_scan / _write (expand)       src/SLAEncoder.c:846-869 (the block table of the partitions)
@@ -97,6 +99,7 @@ __device__ __forceinline__ uint32_t umax_wave(uint32_t v)
 #include "kernels/prepass.inc"
 #include "kernels/zero_runs.inc"
 #include "kernels/lpc_chains.inc"
+#include "kernels/lpc_far.inc"
 #include "kernels/lattice_wave.inc"
 #include "kernels/blocks.inc"
 #include "kernels/search.inc"
