@@ -382,6 +382,44 @@ int sla_hip_launch_search_exact_early(const int32_t* d_pcm, uint64_t plane_strid
                                 sla_hip_stream_t stream, const sla_hip_launch_extra* extra,
                                 const uint32_t* d_early, void* prepass_done /* hipEvent_t */);
 
+/* The tile-sum search for windows of up to SLA_HIP_LPC_FAR_MAX_WINDOW samples (64 tiles): sla_hip_launch_search_exact's exact
+ * form -- the same tile kernels, the same group and candidate rules, the same strict limit (energy < exact_limit is exact) --
+ * without a certificate: a group whose energy reaches the limit gets NaN in r[0] of every candidate's slot and nothing else
+ * written, and the caller reruns it through sla_hip_launch_lpc_far_rerun.  The exactness argument does not depend on the
+ * number of tiles: every partial sum of any order of summation is bounded by the window's energy.
+ * d_tile_sums: num_groups * SLA_HIP_XTILES_FAR * 2 * sla_hip_search_exact_lags(order) doubles of scratch, per tile
+ * P[lags] | X[lags] as above with that stride.  k_search_finish_far spreads a group's candidates over workgroups of 256, each
+ * of which stages the running prefix of the group's P over the tiles and its X in LDS: a candidate's r[lag] is
+ * prefix[last + 1] - prefix[first] - X[last].  Any max_cands_per_group.  For windows of at most 16 384 samples every output
+ * word equals sla_hip_launch_search_exact's with cert_safety = 0.
+ * Returns SLA_APIRESULT_INVALID_ARGUMENT for a NULL d_pcm, d_groups, d_cands, d_tile_sums or d_out, max_window == 0 or
+ * max_cands_per_group == 0, and SLA_APIRESULT_EXCEED_HANDLE_CAPACITY for orders above 51 (or 0) or max_window above
+ * SLA_HIP_LPC_FAR_MAX_WINDOW, before any launch.  num_groups == 0 is success.  A group's num_samples must not exceed
+ * max_window; a candidate that leaves its window is analysed as empty.  Slots of groups not in the launch are not touched.
+ * extra->clear_ptr as sla_hip_launch_search_exact_x; extra->d_span: the execution span of k_search_finish_far. */
+#define SLA_HIP_XTILES_FAR 64u
+int sla_hip_launch_search_far(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                              const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                              uint32_t max_cands_per_group,
+                              const sla_hip_lpc_cand* d_cands, double* d_tile_sums, double* d_out,
+                              double exact_limit, sla_hip_stream_t stream);
+int sla_hip_launch_search_far_x(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                                const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                                uint32_t max_cands_per_group,
+                                const sla_hip_lpc_cand* d_cands, double* d_tile_sums, double* d_out,
+                                double exact_limit, sla_hip_stream_t stream, const sla_hip_launch_extra* extra);
+/* sla_hip_launch_lpc_far's search form restricted to the groups that sla_hip_launch_search_far flagged (NaN in r[0] of the
+ * group's first slot): every candidate of such a group is analysed as sla_hip_launch_lpc_far analyses it, everything else keeps
+ * its result word for word.  *d_rerun_counter (may be NULL) is incremented by the number of groups analysed.  The verdict on a
+ * group is taken from its first slot by the kernels that run BEFORE any slot's r[0] is rewritten (they hand it on in r[0] of
+ * every candidate's own slot, which the last kernel decides by); r[0] of the other slots of an unflagged group must not be NaN.
+ * Arguments, scratch and refusals as sla_hip_launch_lpc_far's search form. */
+int sla_hip_launch_lpc_far_rerun(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                                 const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                                 uint32_t max_cands_per_group, const sla_hip_lpc_cand* d_cands,
+                                 double* d_out, double* d_scratch, uint32_t scratch_slots,
+                                 uint32_t* d_rerun_counter, sla_hip_stream_t stream);
+
 /* The scalar tail of the partition search on the device: estimated code length per candidate, adjacency
  * matrix, shortest path (reference src/SLAPredictor.c:416-468, 1521-1581, 1615-1692).  d_groups: the groups of
  * sla_hip_launch_search_exact, num_channels consecutive entries per super-frame; d_lpc_out: their (or
@@ -1307,6 +1345,14 @@ int sla_hip_launch_verify_blocks(const int32_t* d_planes, uint64_t plane_stride,
  *   silence         through the mask (no "silence_runs")
  * and the sla_hip_last_* reports say so (no tile sums, no device plan, no device tables, no certificate).  Output is the
  * reference's, byte for byte.  Slower per sample than ordinary parameters (profiles/long_enc.json).
+ * Option "long_tile_search" (0 or 1, default 0; consulted only while such a parameter is set): with 1 and an order of at most 51
+ * the search takes 64-tile sums -- sla_hip_launch_search_far over the same groups, at the ordinary route's limit ("exact_bits",
+ * the samples' unit, mid/side), then sla_hip_launch_lpc_far_rerun for the groups at or over it -- and sla_hip_last_counters
+ * reports [2] = 1 and [0] = the groups rerun as chains; the planner, the other stages and the other reports are as above, and so
+ * are the bytes.  16-bit material has no group over the limit and its search all but disappears (profiles/long_search.json);
+ * loud material wider than 16 bits (a 65 535-sample window above about -31 dBFS rms at 24 bits) has every group over it and
+ * keeps the chains' cost: there is no certificate for 64 tiles.  Orders above 51 keep the far chains ([2] = 0).  The calls
+ * that reach the search: SLAEncoder_EncodeWhole, sla_hip_analyze_device with either pack, sla_hip_encode_batch.
  * Calls that take long blocks:      SLAEncoder_EncodeWhole (never streamed over worker lanes), SLAEncoder_EncodeBlock,
  *                                   sla_hip_analyze_device with sla_hip_pack or sla_hip_pack_device, sla_hip_encode_batch (no lanes).
  * Calls that refuse them, with SLA_APIRESULT_EXCEED_HANDLE_CAPACITY before anything is launched: sla_hip_encode_batch_device,

@@ -309,8 +309,15 @@ def lib():
         if hasattr(L, "sla_hip_launch_acf_blocks"):          # (SLA_HIP_LIB may name an older build in an A/B run)
             L.sla_hip_launch_acf_blocks.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "sla_hip_launch_search_far"):          # (SLA_HIP_LIB may name an older build in an A/B run)
+            far = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                   C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]      # .. d_cands, d_tile_sums, d_out, exact_limit, stream
+            L.sla_hip_launch_search_far.argtypes = far
+            L.sla_hip_launch_search_far_x.argtypes = far + [C.c_void_p]
+            L.sla_hip_launch_lpc_far_rerun.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.sla_hip_last_expand.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-        if hasattr(L, "sla_hip_last_verify"):                # (SLA_HIP_LIB may name an older build in an A/B run)
+        if hasattr(L, "sla_hip_last_verify"):               # (SLA_HIP_LIB may name an older build in an A/B run)
             L.sla_hip_last_verify.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
             L.sla_hip_verify_last_image.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
             L.sla_hip_launch_verify_blocks.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
@@ -468,6 +475,7 @@ EXPORTED_SYMBOLS = [
     "sla_hip_launch_emphasis_f64", "sla_hip_use_tuning", "sla_hip_launch_lattice_groups", "sla_hip_launch_ltm_solve",
     "sla_hip_launch_ltm_cert_x", "sla_hip_ltm_fast_twiddles", "sla_hip_ltm_cert_eps_rel", "sla_hip_ltm_cert_supported", "sla_hip_last_ltm_cert",
     "sla_hip_launch_ltm_acf_int", "sla_hip_launch_acf_blocks", "sla_hip_launch_lpc_far", "sla_hip_launch_lpc_far_x",
+    "sla_hip_launch_search_far", "sla_hip_launch_search_far_x", "sla_hip_launch_lpc_far_rerun",
     "sla_hip_encoder_set_option", "sla_hip_shard_scan", "sla_hip_shard_scan_counts", "sla_hip_shard_bounds", "sla_hip_shard_analyze", "sla_hip_shard_analyze_no_silence", "sla_hip_shard_header",
     # include/SLAPredictor.h, include/SLACoder.h (per-call API of the reference, encode side)
     "SLALPCCalculator_Create", "SLALPCCalculator_Destroy", "SLALPCCalculator_CalculatePARCORCoefDouble",

@@ -408,13 +408,16 @@ static int launch_lpc_impl(const int32_t* d_pcm, uint64_t plane_stride, uint32_t
 }
 
 // The far-window LPC stage (kernels/lpc_far.inc): sla_hip_launch_lpc's semantics for windows of up to 65 535 samples.
-extern "C" int sla_hip_launch_lpc_far_x(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
-                                        const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
-                                        uint32_t max_cands_per_group,
-                                        const sla_hip_lpc_cand* d_cands, const double* d_window_pool,
-                                        double* d_out, int32_t* d_code, int32_t* d_kint, uint32_t* d_rshift,
-                                        double* d_scratch, uint32_t scratch_slots,
-                                        sla_hip_stream_t stream, const sla_hip_launch_extra* extra)
+// RERUN: only the groups flagged in d_out (sla_hip_launch_lpc_far_rerun; kernels/lpc_far.inc: far_flagged).  The passes of
+// unflagged groups are launched all the same and return at their start, as the LDS kernel's rerun does.
+template <bool RERUN>
+static int launch_lpc_far_impl(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                               const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                               uint32_t max_cands_per_group,
+                               const sla_hip_lpc_cand* d_cands, const double* d_window_pool,
+                               double* d_out, int32_t* d_code, int32_t* d_kint, uint32_t* d_rshift,
+                               double* d_scratch, uint32_t scratch_slots,
+                               sla_hip_stream_t stream, const sla_hip_launch_extra* extra, uint32_t* d_rerun_counter)
 {
   if (d_pcm == nullptr || d_groups == nullptr || d_cands == nullptr || d_out == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
   if (order < 1 || order > 255 || max_window == 0 || max_window > SLA_HIP_LPC_FAR_MAX_WINDOW || max_cands_per_group == 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
@@ -434,18 +437,40 @@ extern "C" int sla_hip_launch_lpc_far_x(const int32_t* d_pcm, uint64_t plane_str
   if (chunks * pass > 0x7FFFFFFFull || fchunks * num_groups > 0x7FFFFFFFull) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
   for (uint32_t g_lo = 0; g_lo < num_groups; g_lo += pass) {
     const uint32_t ng = (num_groups - g_lo < pass) ? (num_groups - g_lo) : pass;
-    hipLaunchKernelGGL(k_lpc_far_stage, dim3(ng), dim3(FAR_THREADS), 0, st, d_pcm, plane_stride, mid_side, d_groups, g_lo, d_window_pool,
-                       d_scratch, max_window, d_rshift, (g_lo == 0) ? span_of(extra) : nullptr);
+    hipLaunchKernelGGL(k_lpc_far_stage<RERUN>, dim3(ng), dim3(FAR_THREADS), 0, st, d_pcm, plane_stride, mid_side, d_groups, g_lo, d_window_pool,
+                       d_scratch, max_window, d_rshift, (g_lo == 0) ? span_of(extra) : nullptr, (const double*)d_out, order, d_rerun_counter);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { return hip_rc(e); }
-    hipLaunchKernelGGL(k_lpc_far_chains, dim3((uint32_t)(chunks * ng)), dim3(FAR_THREADS), 0, st, d_groups, g_lo, d_cands, order,
+    hipLaunchKernelGGL(k_lpc_far_chains<RERUN>, dim3((uint32_t)(chunks * ng)), dim3(FAR_THREADS), 0, st, d_groups, g_lo, d_cands, order,
                        (const double*)d_scratch, max_window, (uint32_t)chunks, d_out);
     e = hipGetLastError();
     if (e != hipSuccess) { return hip_rc(e); }
   }
-  hipLaunchKernelGGL(k_lpc_far_finish, dim3((uint32_t)(fchunks * num_groups)), dim3(64), per_wg * per_cand, st, d_groups, d_cands, order,
+  hipLaunchKernelGGL(k_lpc_far_finish<RERUN>, dim3((uint32_t)(fchunks * num_groups)), dim3(64), per_wg * per_cand, st, d_groups, d_cands, order,
                      per_wg, (uint32_t)fchunks, max_window, d_out, d_code, d_kint, (const uint32_t*)d_rshift, span_of(extra));
   return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_lpc_far_x(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                                        const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                                        uint32_t max_cands_per_group,
+                                        const sla_hip_lpc_cand* d_cands, const double* d_window_pool,
+                                        double* d_out, int32_t* d_code, int32_t* d_kint, uint32_t* d_rshift,
+                                        double* d_scratch, uint32_t scratch_slots,
+                                        sla_hip_stream_t stream, const sla_hip_launch_extra* extra)
+{
+  return launch_lpc_far_impl<false>(d_pcm, plane_stride, mid_side, order, d_groups, num_groups, max_window, max_cands_per_group, d_cands, d_window_pool,
+                                    d_out, d_code, d_kint, d_rshift, d_scratch, scratch_slots, stream, extra, nullptr);
+}
+
+extern "C" int sla_hip_launch_lpc_far_rerun(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                                            const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                                            uint32_t max_cands_per_group, const sla_hip_lpc_cand* d_cands,
+                                            double* d_out, double* d_scratch, uint32_t scratch_slots,
+                                            uint32_t* d_rerun_counter, sla_hip_stream_t stream)
+{
+  return launch_lpc_far_impl<true>(d_pcm, plane_stride, mid_side, order, d_groups, num_groups, max_window, max_cands_per_group, d_cands, nullptr,
+                                   d_out, nullptr, nullptr, nullptr, d_scratch, scratch_slots, stream, nullptr, d_rerun_counter);
 }
 
 extern "C" int sla_hip_launch_lpc_far(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
@@ -582,6 +607,59 @@ extern "C" int sla_hip_launch_search_exact(const int32_t* d_pcm, uint64_t plane_
                                            double exact_limit, double cert_safety, uint32_t* d_any_exact, sla_hip_stream_t stream)
 {
   return sla_hip_launch_search_exact_x(d_pcm, plane_stride, mid_side, order, d_groups, num_groups, max_window, max_cands_per_group, d_cands, d_tile_sums, d_out, exact_limit, cert_safety, d_any_exact, stream, nullptr);
+}
+
+// The tile-sum search for windows of up to 64 tiles: the tile kernels of launch_search_exact_impl with the far stride, then
+// k_search_finish_far (kernels/search_far.inc).  Exact form only: no certificate, no form beside the prepass.
+extern "C" int sla_hip_launch_search_far_x(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                                           const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                                           uint32_t max_cands_per_group,
+                                           const sla_hip_lpc_cand* d_cands, double* d_tile_sums, double* d_out,
+                                           double exact_limit, sla_hip_stream_t stream, const sla_hip_launch_extra* extra)
+{
+  if (d_pcm == nullptr || d_groups == nullptr || d_cands == nullptr || d_tile_sums == nullptr || d_out == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  const uint32_t lags = sla_hip_search_exact_lags(order);
+  if (lags == 0 || max_window > SLA_HIP_LPC_FAR_MAX_WINDOW) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
+  if (max_window == 0 || max_cands_per_group == 0) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_groups == 0) { return 0; }
+  hipStream_t st = (hipStream_t)stream;
+  clear_list cl = {{nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}};
+  if (extra != nullptr) { for (int i = 0; i < 3; i++) { cl.ptr[i] = extra->clear_ptr[i]; cl.words[i] = extra->clear_words[i]; } }
+  const uint32_t tiles = (max_window + SLA_HIP_XTILE - 1) / SLA_HIP_XTILE;       // waves per group, <= SLA_HIP_XTILES_FAR
+  const uint64_t waves = (uint64_t)num_groups * tiles;
+  const uint64_t fchunks = ((uint64_t)max_cands_per_group + XFF_THREADS - 1) / XFF_THREADS;
+  if (waves > 0x7FFFFFFFull || fchunks * num_groups > 0x7FFFFFFFull) { return SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
+  const dim3 grid((uint32_t)((waves + 3) / 4)), block(256);
+  const uint32_t* no_early = nullptr;
+  switch (lags) {
+    case 12: hipLaunchKernelGGL((k_acf_tiles<3, SLA_HIP_XTILES_FAR>), grid, block, 0, st, d_pcm, plane_stride, mid_side, d_groups, num_groups, tiles, d_tile_sums, cl, no_early); break;
+#define SLA_ACFT(NBB, TOPP) hipLaunchKernelGGL((k_acf_tiles_lds<NBB, TOPP, SLA_HIP_XTILES_FAR>), grid, block, 0, st, d_pcm, plane_stride, mid_side, d_groups, num_groups, tiles, d_tile_sums, cl, no_early)
+    case 20: if (order == 16) { SLA_ACFT(5, 17); } else { SLA_ACFT(5, 20); } break;
+    case 36: if (order == 32) { SLA_ACFT(9, 33); } else { SLA_ACFT(9, 36); } break;
+    default: if (order == 48) { SLA_ACFT(13, 49); } else { SLA_ACFT(13, 52); } break;
+#undef SLA_ACFT
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { return hip_rc(e); }
+  const size_t lds = sizeof(double) * (size_t)(order + 1) * (XFF_PSTRIDE + SLA_HIP_XTILES_FAR);      // 53 KiB at order 51
+  const dim3 fgrid((uint32_t)(fchunks * num_groups)), fblock(XFF_THREADS);
+#define SLA_FINISH_FAR(PP) do { \
+    e = ensure_dynamic_lds((const void*)k_search_finish_far<PP>, lds); \
+    if (e != hipSuccess) { return hip_rc(e); } \
+    hipLaunchKernelGGL((k_search_finish_far<PP>), fgrid, fblock, lds, st, order, lags, (uint32_t)fchunks, d_groups, d_cands, \
+                       (const double*)d_tile_sums, d_out, exact_limit, span_of(extra)); } while (0)
+  if (order <= 16) { SLA_FINISH_FAR(16); } else if (order <= 32) { SLA_FINISH_FAR(32); } else if (order <= 48) { SLA_FINISH_FAR(48); } else { SLA_FINISH_FAR(64); }
+#undef SLA_FINISH_FAR
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_search_far(const int32_t* d_pcm, uint64_t plane_stride, uint32_t mid_side, uint32_t order,
+                                         const sla_hip_lpc_group* d_groups, uint32_t num_groups, uint32_t max_window,
+                                         uint32_t max_cands_per_group,
+                                         const sla_hip_lpc_cand* d_cands, double* d_tile_sums, double* d_out,
+                                         double exact_limit, sla_hip_stream_t stream)
+{
+  return sla_hip_launch_search_far_x(d_pcm, plane_stride, mid_side, order, d_groups, num_groups, max_window, max_cands_per_group, d_cands, d_tile_sums, d_out, exact_limit, stream, nullptr);
 }
 
 extern "C" int sla_hip_launch_plan_early(const sla_hip_lpc_group* d_groups, uint32_t num_superframes, uint32_t num_channels,

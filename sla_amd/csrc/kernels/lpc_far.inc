@@ -19,14 +19,31 @@
 #define FAR_THREADS 256u
 #define FAR_FINISH_LDS (60u * 1024u)      // r[], a[], v[] of the candidates one finish workgroup takes
 
+// RERUN (sla_hip_launch_lpc_far_rerun, search form): only the groups that k_search_finish_far flagged -- NaN in r[0] of the group's
+// first slot -- are analysed.  k_lpc_far_finish stores r0 into that very word while its other workgroups of the same group are
+// still starting, so only the stage and chains kernels look at it: every one of them runs before the call's one finish launch,
+// and no kernel in front of that writes r[0] of any slot.  The chains kernel hands the verdict on -- the lag-0 thread of every
+// candidate of a flagged group stores the NaN into r[0] of ITS candidate's slot -- and a finish lane decides from its own slot.
+__device__ __forceinline__ bool far_flagged(const double* __restrict__ out, const sla_hip_lpc_group& g, uint32_t order)
+{
+  const double r0 = out[(uint64_t)g.slot_first * (order + 2)];
+  return r0 != r0;
+}
+
+template <bool RERUN>
 __global__ __launch_bounds__(FAR_THREADS)
 void k_lpc_far_stage(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ms,
                      const sla_hip_lpc_group* __restrict__ groups, uint32_t g_lo,
                      const double* __restrict__ window_pool, double* __restrict__ scratch, uint32_t slot_doubles,
-                     uint32_t* __restrict__ out_rshift, unsigned long long* span)
+                     uint32_t* __restrict__ out_rshift, unsigned long long* span,
+                     const double* __restrict__ out, uint32_t order, uint32_t* __restrict__ rerun_counter)
 {
   __shared__ uint32_t s_maxabs;
   span_begin(span);
+  if (RERUN) {
+    if (!far_flagged(out, groups[g_lo + blockIdx.x], order)) { return; }
+    if (threadIdx.x == 0 && rerun_counter != nullptr) { atomicAdd(rerun_counter, 1u); }
+  }
   if (threadIdx.x == 0) { s_maxabs = 0; }
   __syncthreads();
   const sla_hip_lpc_group g = groups[g_lo + blockIdx.x];
@@ -63,6 +80,7 @@ void k_lpc_far_stage(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t 
   }
 }
 
+template <bool RERUN>
 __global__ __launch_bounds__(FAR_THREADS)
 void k_lpc_far_chains(const sla_hip_lpc_group* __restrict__ groups, uint32_t g_lo, const sla_hip_lpc_cand* __restrict__ cands,
                       uint32_t order, const double* __restrict__ scratch, uint32_t slot_doubles, uint32_t chunks,
@@ -70,6 +88,7 @@ void k_lpc_far_chains(const sla_hip_lpc_group* __restrict__ groups, uint32_t g_l
 {
   const uint32_t gi = blockIdx.x / chunks, chunk = blockIdx.x - gi * chunks;
   const sla_hip_lpc_group g = groups[g_lo + gi];
+  if (RERUN && !far_flagged(out, g, order)) { return; }
   const uint32_t nlag = g.cand_count * order;
   const uint32_t q = chunk * FAR_THREADS + threadIdx.x;
   if (q >= nlag + g.cand_count) { return; }
@@ -84,8 +103,11 @@ void k_lpc_far_chains(const sla_hip_lpc_group* __restrict__ groups, uint32_t g_l
   double r;
   if (lag == 0) { r = chain_lag0(xs, n); } else { r = (lag < n) ? chain_lag(xs, n, lag) : 0.0; }
   out[((uint64_t)g.slot_first + cidx) * (order + 2) + 1 + lag] = r;
+  // (slot 0 of a flagged group holds the NaN already: no thread of this launch changes what far_flagged reads)
+  if (RERUN && lag == 0 && cidx != 0) { out[((uint64_t)g.slot_first + cidx) * (order + 2)] = __longlong_as_double(0x7FF8000000000000ll); }
 }
 
+template <bool RERUN>
 __global__ __launch_bounds__(64)
 void k_lpc_far_finish(const sla_hip_lpc_group* __restrict__ groups, const sla_hip_lpc_cand* __restrict__ cands,
                       uint32_t order, uint32_t per_wg, uint32_t chunks, uint32_t max_window, double* __restrict__ out,
@@ -106,8 +128,10 @@ void k_lpc_far_finish(const sla_hip_lpc_group* __restrict__ groups, const sla_hi
     double* a = rc + O1;
     double* v = a + O2;
     double* o = out + slot * O2;
-    for (uint32_t i = 0; i < O1; i++) { rc[i] = o[1 + i]; }      // the chains left r[] where the coefficients go
-    levinson_out(rc, a, v, o, order, n);
+    if (!RERUN || o[0] != o[0]) {                                // (RERUN: this candidate's own word, see far_flagged)
+      for (uint32_t i = 0; i < O1; i++) { rc[i] = o[1 + i]; }    // the chains left r[] where the coefficients go
+      levinson_out(rc, a, v, o, order, n);
+    }
     // coefficient quantiser (chosen blocks: one candidate per group), as in k_lpc; the thread reads its own stores
     if (out_code != nullptr) {
       const uint32_t rshift = out_rshift[slot];

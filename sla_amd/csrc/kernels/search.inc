@@ -205,7 +205,9 @@ __device__ __forceinline__ void clear_words(const clear_list& cl)
   }
 }
 
-template <int NB>
+// XT: the stride of tile_sums in tiles per group -- SLA_HIP_XTILES, or SLA_HIP_XTILES_FAR for windows of up to 64 tiles
+// (sla_hip_launch_search_far).  A compile-time constant: nothing else of the kernel depends on it.
+template <int NB, uint32_t XT = SLA_HIP_XTILES>
 __global__ __launch_bounds__(256)
 void k_acf_tiles(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ms,
                  const sla_hip_lpc_group* __restrict__ groups, uint32_t num_groups, uint32_t tiles_per_group,
@@ -276,7 +278,7 @@ void k_acf_tiles(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ms,
       }
     }
   }
-  double* dst = tile_sums + ((uint64_t)gi * SLA_HIP_XTILES + tile) * (2 * LAGS);
+  double* dst = tile_sums + ((uint64_t)gi * XT + tile) * (2 * LAGS);
   {
     constexpr int M = (LAGS <= 16) ? 16 : (LAGS <= 32) ? 32 : 64;
     double tv[M];
@@ -321,7 +323,7 @@ __device__ __forceinline__ double side_f64(int32_t a, int32_t b) { return ((doub
 // in k_acf_tiles, from an edge buffer (filled from the values the wave stages anyway).  TOP: see acf_tile_fma.  (The first LDS port of round 3 kept the forward walk and re-defined P and X by
 // the position of a pair's LATER sample; it was three times slower and was dropped.)
 // ---------------------------------------------------------------------------------------------
-template <int NB, int TOP>
+template <int NB, int TOP, uint32_t XT = SLA_HIP_XTILES>      // XT: see k_acf_tiles
 __global__ __launch_bounds__(256, (NB >= 13) ? 3 : 1)
 void k_acf_tiles_lds(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t ms,
                      const sla_hip_lpc_group* __restrict__ groups, uint32_t num_groups, uint32_t tiles_per_group,
@@ -438,7 +440,7 @@ void k_acf_tiles_lds(const int32_t* __restrict__ pcm, uint64_t stride, uint32_t 
     { double2* t = E; E = En; En = t; t = O; O = On; On = t; }
   }
   // lag slots >= TOP of P and X are not written: k_search_finish and k_search_cert use lag <= order < TOP
-  double* dst = tile_sums + ((uint64_t)gi * SLA_HIP_XTILES + tile) * (2 * LAGS);
+  double* dst = tile_sums + ((uint64_t)gi * XT + tile) * (2 * LAGS);
   acf_reduce_store<(int)LAGS, TOP>(acc, lane, dst, TOP);
   // pairs that straddle t1: X[lag] = sum over j < lag of x[t1 - lag + j] x[t1 + j], a chain of dependent multiply-adds.
   if constexpr (TOP == 17 || TOP == 33) {

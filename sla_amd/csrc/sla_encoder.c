@@ -37,6 +37,9 @@
 #define MAX_FAR_WINDOW       SLA_HIP_LPC_FAR_MAX_WINDOW
 #define FAR_SLOTS            64u        /* scratch windows of the search, and as many again of the block stage (512 KiB each) */
 #define LONG_PARAMS(e)       ((e)->encode_param.max_num_block_samples > MAX_ANALYSIS_WINDOW)
+/* option "long_tile_search": (super-frame, channel) groups whose 64-tile sums one pass of sla_hip_launch_search_far keeps (53 KiB
+ * each at 52 lags: 13.6 MB); a file with more groups takes them in passes over the same buffer, in stream order */
+#define FAR_TILE_GROUPS      256u
 
 typedef struct { void* ptr; size_t cap; } devbuf_t;
 typedef struct { void* ptr; size_t cap; } pinbuf_t;
@@ -234,6 +237,7 @@ struct SLAEncoder {
    * own in long_saved meanwhile), the far stage's scratch windows, and what the last analysis was */
   devbuf_t d_far_scratch;
   int      long_depth, long_last;
+  int      long_tile_search;        /* option: 1 = the long-block search takes 64-tile sums where they are exact (search_launch); default 0 */
   struct { int device_plan, device_expand, search_early, table_cache, block_cert, ltm_cert, search_exact, fuse_lattice, stream_mode,
                alt_streams, prelaunch, one_stream, chunks_forced; uint32_t silence_runs, ltm_int, chunks, batch_lanes, lpc_blocks_chains; } long_saved;
 };
@@ -709,6 +713,7 @@ typedef struct {
   shape_t* shapes; uint32_t nshapes;
   uint32_t ncands, nsgroups, nslots, max_window, max_cpg, nxg, max_xcands;
   int exact;                                      /* this run searches with tile sums            */
+  int far_tiles;                                  /* long blocks: with 64-tile sums (option "long_tile_search"), chains for the flagged groups */
   uint32_t blocks_bound, lchunks_bound;
   uint32_t nbg, nlc, njobs, ltm_done;                      /* running counters of the block stage */
   uint32_t *job_blk, *job_ch, *job_grp, *grp_of_slot;      /* (these seven live in the handle: SLAEncoder.w_*) */
@@ -1219,6 +1224,8 @@ static void decide_routes(struct SLAEncoder* e, actx_t* a, uint32_t or_word, int
   a->or_word = or_word;
   a->exact = (e->search_exact && SLAI_SEARCH_DELTA == SLA_HIP_XTILE && maxb <= SLA_HIP_XTILE * SLA_HIP_XTILES
               && sla_hip_search_exact_lags(order) != 0 && or_word != 0);
+  a->far_tiles = (LONG_PARAMS(e) && e->long_tile_search && SLAI_SEARCH_DELTA == SLA_HIP_XTILE && maxb <= SLA_HIP_XTILE * SLA_HIP_XTILES_FAR
+                  && sla_hip_search_exact_lags(order) != 0 && or_word != 0);
   /* Block tables on the device (k_expand).  Where the mask has no all-zero word (or the caller vouched for that) no run of
    * zeros reaches SLA's minimum block length and no block inside a searched super-frame can be SILENT; whole SILENT
    * super-frames are in the table the kernel reads.  With silence (round 4) the kernel reads the device's copy of the mask
@@ -1474,6 +1481,10 @@ static int pipeline_reserve(struct SLAEncoder* e, const actx_t* a)
   if (e->search_exact && sla_hip_search_exact_lags(order) != 0) {      /* (whether the search may use them is decided once the prepass is in) */
     RCCHK(dev_reserve(&e->d_tile_sums, sizeof(double) * ((size_t)a->nxg + 1) * SLA_HIP_XTILES * 2 * sla_hip_search_exact_lags(order)));
   }
+  if (LONG_PARAMS(e) && e->long_tile_search && sla_hip_search_exact_lags(order) != 0) {
+    const size_t gcap = ((size_t)a->nxg < FAR_TILE_GROUPS) ? (size_t)a->nxg + 1 : FAR_TILE_GROUPS;
+    RCCHK(dev_reserve(&e->d_tile_sums, sizeof(double) * gcap * SLA_HIP_XTILES_FAR * 2 * sla_hip_search_exact_lags(order)));
+  }
   /* blocks */
   RCCHK(pin_reserve(&e->h_bgroups, sizeof(sla_hip_lpc_group) * nslots));
   RCCHK(pin_reserve(&e->h_bcands, sizeof(sla_hip_lpc_cand) * nslots));
@@ -1603,6 +1614,26 @@ static int search_launch(struct SLAEncoder* e, actx_t* a, uint32_t c)
       RCCHK(sla_hip_launch_lpc_rerun(e->pcm_dev, e->stride, ms, order, (const sla_hip_lpc_group*)e->d_groups.ptr + k->grp_lo, ng,
                                      a->max_window, a->max_cpg, (const sla_hip_lpc_cand*)e->d_cands.ptr, (double*)e->d_lpc_out.ptr,
                                      (uint32_t*)e->d_or.ptr + 2, e->stream));
+    } else if (a->far_tiles) {
+      /* long blocks, option "long_tile_search": 64-tile sums over the same whole-candidate groups, FAR_TILE_GROUPS of them per pass
+       * over one buffer; the groups at or over the exactness limit (the ordinary route's limit: unit of the samples, mid/side) are
+       * flagged and take the far chains behind it.  Where even 4 x the longest window is under the limit (|x| < 2 in the search's
+       * unit: 16-bit material) no group can be flagged and the rerun's launches are left out. */
+      const int ntz = __builtin_ctz(a->or_word);
+      const double limit = ldexp(1.0, e->exact_bits + 2 * (ntz - 31 - (int)ms));
+      uint32_t g_lo;
+      HIPCHK(hipEventRecord(ev[EV_SEARCH_S], e->stream));
+      for (g_lo = 0; g_lo < nx; g_lo += FAR_TILE_GROUPS) {
+        const uint32_t n = (nx - g_lo < FAR_TILE_GROUPS) ? (nx - g_lo) : FAR_TILE_GROUPS;
+        RCCHK(sla_hip_launch_search_far(e->pcm_dev, e->stride, ms, order, dx + g_lo, n, a->max_window, a->max_xcands,
+                                        (const sla_hip_lpc_cand*)e->d_cands.ptr, (double*)e->d_tile_sums.ptr, (double*)e->d_lpc_out.ptr,
+                                        limit, e->stream));
+      }
+      if (!(limit >= 4.0 * (double)a->max_window)) {
+        RCCHK(sla_hip_launch_lpc_far_rerun(e->pcm_dev, e->stride, ms, order, dx, nx, a->max_window, a->max_xcands,
+                                           (const sla_hip_lpc_cand*)e->d_cands.ptr, (double*)e->d_lpc_out.ptr,
+                                           (double*)e->d_far_scratch.ptr, FAR_SLOTS, (uint32_t*)e->d_or.ptr + 2, e->stream));
+      }
     } else if (LONG_PARAMS(e)) {
       /* long blocks: the far stage over the whole-candidate groups, one per (super-frame, channel), same slots as the slices */
       HIPCHK(hipEventRecord(ev[EV_SEARCH_S], e->stream));
@@ -2543,7 +2574,7 @@ static int run_pipeline(struct SLAEncoder* e, int preset_blocks)
     e->timing[9] = (float)a.nchunks;
     e->tail_launches = (e->single_tail) ? 1u : a.nchunks;
     e->timing[10] = (float)e->fallback_groups;
-    e->timing[11] = (float)a.exact;
+    e->timing[11] = (float)(a.exact || a.far_tiles);
   }
   TRACE("Rice parameters stored", 0);
   actx_free(&a);
@@ -2620,6 +2651,7 @@ int sla_hip_encoder_set_option(struct SLAEncoder* e, const char* name, double va
   else if (strcmp(name, "chunks") == 0)            { OPT_RANGE(1, 8); e->chunks = (uint32_t)iv; e->split_count = 0; e->chunks_forced = 1; }
   else if (strcmp(name, "search_exact") == 0)      { OPT_RANGE(0, 1); e->search_exact = (int)iv; }
   else if (strcmp(name, "exact_bits") == 0)        { OPT_RANGE(1, 53); e->exact_bits = (int)iv; }
+  else if (strcmp(name, "long_tile_search") == 0)  { OPT_RANGE(0, 1); e->long_tile_search = (int)iv; }
   else if (strcmp(name, "cert_safety") == 0)       { if ((value != 0.0 && value < 64.0) || value > 1e30) { return SLA_APIRESULT_INVALID_ARGUMENT; } e->cert_safety = value; }
   else if (strcmp(name, "upload24") == 0)          { OPT_RANGE(0, 1); e->upload24 = (int)iv; }
   else if (strcmp(name, "block_cert") == 0)        { OPT_RANGE(0, 1); e->block_cert = (int)iv; }

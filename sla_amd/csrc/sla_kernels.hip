@@ -16,6 +16,8 @@
 //                                         the certificate could not decide, and the per-call predictor API
 //   k_lpc_far_stage / _chains / _finish   the same, for windows of up to 65 535 samples: the window in a global scratch slot (L2),
 //   (lpc_far)                             the chains of lpc_chains.inc on it; search and chosen blocks of long-block parameters
+//   k_search_finish_far (search_far)      the partition search of such windows from the tile sums of k_acf_tiles[_lds] at a stride of
+//                                         64 tiles: prefix sums over the tiles in LDS, exact windows only (option "long_tile_search")
 //   k_plan (search)                       src/SLAPredictor.c:416-468 (code length), :1521-1581 (Dijkstra), :1652-1692 (partition),
 //                                         certified against libm's last bits
 //   k_expand_scan / _write (expand)       src/SLAEncoder.c:846-869 (the block table of the partitions)
@@ -103,6 +105,7 @@ __device__ __forceinline__ uint32_t umax_wave(uint32_t v)
 #include "kernels/lattice_wave.inc"
 #include "kernels/blocks.inc"
 #include "kernels/search.inc"
+#include "kernels/search_far.inc"
 #include "kernels/expand.inc"
 #include "kernels/lattice.inc"
 #include "kernels/tail.inc"
