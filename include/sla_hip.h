@@ -1302,6 +1302,152 @@ int sla_hip_decode_windows_indexed(struct SLADecoder* decoder, const sla_hip_ind
                                    uint32_t sample_format, uint32_t flags, sla_hip_window_outcome* d_outcomes,
                                    sla_hip_stream_t stream);
 
+/* ---- Cut and join resident streams without re-encoding ----
+ * Every block resets its filters and its coder and carries its own CRC16, so a new .sla stream is made from parts of old ones
+ * by copying whole blocks byte for byte; only the blocks a cut passes through are decoded, and what remains of them is stored
+ * as a RAW block (SILENT where the source block was).  Needs a decoder handle and the sources' block indexes only.
+ *
+ * THE LAYOUT RULE (sla_hip_splice_plan; pure host code, no device, no byte of any stream).  An output stream is the
+ * concatenation of num_segments >= 1 segments; a segment names a stream, its index and the samples [start, start + length).
+ * For every index row with samples that overlaps the segment, in order, with [a, b) the overlap:
+ *   the whole row lies inside the segment   its byte_len bytes, verbatim;
+ *   otherwise, byte_len == 11               an 11-byte SILENT block of b - a samples (only a SILENT block is 11 bytes long);
+ *   otherwise                               a RAW block of n = b - a samples, 11 + ceil(n * W / 8) bytes, W the sum over the
+ *                                           channels of bit_per_sample - offset_lshift (+ 1 for channel 1 under mid/side).
+ * A segment inside one block gives one such block; adjacent partial blocks of two segments are not merged; length 0
+ * contributes nothing; an output of no samples is the 43 header bytes with num_blocks 0.  Header: num_samples = the sum of
+ * the lengths, num_blocks = blocks emitted, max_block_size = the largest of them, max_bit_per_second = the largest
+ * (8 * bytes * sampling_rate mod 2^32) / samples over them, every other field the first segment's, the CRC slai_write_header's.
+ * Refusals, in this order (then *layout is zero): INVALID_ARGUMENT for a NULL argument, no segments, a segment with a NULL
+ * index, index->data_size != data_size, a header result other than OK, or header bytes 14, 19..28 or 33..34 (channels; rate,
+ * bits, offset_lshift, the three orders, the channel process method; max_num_block_samples) that differ from the first
+ * segment's; INVAILD_CHPROCESSMETHOD for mid/side with other than 2 channels, INVALID_HEADER_FORMAT for 0 or more than 8
+ * channels, 0 or more than 32 bits or offset_lshift >= bits; for the first segment with length > 0 that reaches past its
+ * index's extent the index's stop code (INSUFFICIENT_DATA_SIZE when that is OK); EXCEED_HANDLE_CAPACITY when bytes, samples or
+ * blocks do not fit 32 bits.  `data` is not looked at.
+ * The cost, plainly: edge blocks are stored uncompressed -- at most two per segment, each shorter than one block and never
+ * larger than its PCM at the file's depth plus the 11 header bytes (and one bit per frame under mid/side). */
+typedef struct sla_hip_splice_segment {
+  const uint8_t* data;            /* in : a whole .sla stream in device memory, any byte alignment */
+  const sla_hip_index* index;     /* in : its block index */
+  uint32_t data_size;             /* in  */
+  uint32_t start;                 /* in : first sample */
+  uint32_t length;                /* in : samples */
+  uint32_t reserved;
+} sla_hip_splice_segment;         /* 32 bytes */
+typedef struct sla_hip_splice_item {
+  const sla_hip_splice_segment* segments;     /* in  */
+  uint8_t* data;                  /* per-buffer mode: in, the destination (device); arena mode: out */
+  uint32_t num_segments;          /* in  */
+  uint32_t data_size;             /* per-buffer mode: in, the destination's capacity */
+  uint32_t output_size;           /* out */
+  int32_t  result;                /* out: SLAApiResult */
+} sla_hip_splice_item;            /* 32 bytes */
+typedef struct sla_hip_splice_layout {
+  uint64_t verbatim_bytes;        /* bytes of the blocks copied as they are */
+  uint32_t bytes;                 /* the output stream, header included */
+  uint32_t num_samples;
+  uint32_t num_blocks;
+  uint32_t edge_blocks;           /* blocks written anew (RAW or SILENT) */
+  uint32_t max_block_size;
+  uint32_t max_bit_per_second;
+  uint8_t  header[48];            /* the 43 header bytes; the rest zero */
+} sla_hip_splice_layout;          /* 80 bytes */
+int sla_hip_splice_plan(const sla_hip_splice_item* item, sla_hip_splice_layout* layout);
+
+/* The streams sla_hip_splice_plan lays out, written to device memory.  Synchronous: it returns when every write has completed.
+ * Item i gets result and output_size; a delivered item has exactly [data, data + output_size) written, byte for byte what the
+ * layout rule says, the edge blocks holding the decoded samples of their range; a refused or failed item has NOTHING written
+ * and output_size 0, the clean items of the same call are delivered.
+ * Per-buffer mode (d_arena NULL) and arena mode are sla_hip_encode_batch_resident's: a destination of any byte alignment with
+ * capacity data_size, INVALID_ARGUMENT for one that is NULL, not memory of the device or not inside its allocation,
+ * INSUFFICIENT_BUFFER_SIZE for one that is too small; in arena mode the delivered streams lie back to back from a running
+ * cursor in delivery order (passes by launch parameters as the decode calls sort them, items ascending inside a pass: a call
+ * whose items share one format lies in item order), a stream that does not fit gets INSUFFICIENT_BUFFER_SIZE, data NULL and
+ * the cursor stays, a failed item takes no space and gets data NULL; an arena that is not device memory inside one allocation
+ * returns INVALID_ARGUMENT and touches no item.
+ * Per item also: sla_hip_splice_plan's refusals; INVALID_ARGUMENT for a segment source that is NULL, not device memory or not
+ * inside its allocation (sla_hip_decode_windows_indexed's source check, made before anything is read); the handle's
+ * EXCEED_HANDLE_CAPACITY for a format it was not created for; INSUFFICIENT_BUFFER_SIZE for an edge block longer than the
+ * handle's max_num_block_samples; EXCEED_HANDLE_CAPACITY for an item with more edge samples than one pass holds (2^28).
+ * The host reads no byte of any stream: AN INDEX IS THE CALLER'S PROMISE, checked on the device.  Every verbatim block's ten
+ * chain-header bytes are compared with its row (sync code, size field + 6 == byte_len, sample count; a row of 11 bytes must be
+ * of type 1, a longer one must not), with enable_crc_check its CRC16 is recomputed; edge blocks are gathered, decoded by the
+ * decode kernels and judged by k_dec_judge, and every folded sample they keep must fit its channel's width.  Any failure
+ * gives the item DETECT_DATA_CORRUPTION, or for an edge block the judge's code; several failures: the first in output order.
+ * With enable_crc_check 0 a damaged verbatim block is copied as it is.  Whatever the index says, nothing outside
+ * [data, data + data_size) of a source is read.
+ * Ordering behind `stream` as in sla_hip_decode_windows_indexed; the handle's wave format and encode parameter are afterwards
+ * those of the last item whose header was accepted.
+ * How it runs, per pass (items of one set of launch parameters): one gather of the edge blocks into the pass image, the decode
+ * kernels, k_dec_judge one row per item, k_splice_check over every block; the verdicts come home in the pass's one wait; the
+ * host places the clean items and uploads the delivery tables; k_splice_edges writes the edge blocks from the planes,
+ * k_splice_copy the headers and the verbatim runs (touching rows are one entry).
+ * sla_hip_decoder_last_timing: [2] the execution span of k_splice_edges and [3] of k_splice_copy, summed over the passes, [4]
+ * the call, [5] the passes, zeros elsewhere.
+ * Returns 0; INVALID_ARGUMENT (no item touched) for a NULL decoder, NULL items with num_items > 0 or a bad arena; NG on a
+ * device or allocation failure. */
+int sla_hip_splice_resident(struct SLADecoder* decoder, sla_hip_splice_item* items, uint32_t num_items, uint8_t* d_arena,
+                            uint64_t arena_bytes, sla_hip_stream_t stream);
+
+/* The check kernel of sla_hip_splice_resident (k_splice_check): one wave per entry, as described there.  d_verdicts: one
+ * 64-bit word per item, set to all ones by the caller; a failing entry lowers word `verdict` to (ordinal << 8) | code.
+ * edge == SLA_HIP_SPLICE_NO_EDGE: a verbatim block (src: its first byte in the source; byte_len, num_samples: its row).
+ * Otherwise an edge block: d_outcomes[edge] is what k_dec_judge gave its row, the samples kept are [plane_off, plane_off + keep)
+ * of every plane (an entry that names rows or samples outside the tables is judged NG).  Entries with byte_len < 11 fail.
+ * INVALID_ARGUMENT before any launch for a NULL table, plane, outcome or verdict pointer, num_channels 0 or > 8, width 0 or
+ * > 32, mid_side with num_channels != 2. */
+#define SLA_HIP_SPLICE_NO_EDGE 0xFFFFFFFFu
+typedef struct sla_hip_splice_check {
+  const uint8_t* src;             /* device: the block's sync code in its source */
+  uint64_t plane_off;             /* edge: the first kept sample in the planes */
+  uint32_t byte_len;              /* the row's */
+  uint32_t num_samples;           /* the row's */
+  uint32_t verdict;               /* the item's word of d_verdicts */
+  uint32_t ordinal;               /* the block's position in its output */
+  uint32_t edge;                  /* SLA_HIP_SPLICE_NO_EDGE, or the block's outcome in d_outcomes */
+  uint32_t keep;                  /* edge: samples kept */
+} sla_hip_splice_check;           /* 40 bytes */
+int sla_hip_launch_splice_check(const sla_hip_splice_check* d_table, uint32_t num_entries, uint32_t crc_check,
+                                const int32_t* d_planes, uint64_t plane_stride, uint32_t num_channels, uint32_t width,
+                                uint32_t mid_side, const sla_hip_window_outcome* d_outcomes, uint32_t num_outcomes,
+                                uint64_t* d_verdicts, uint32_t num_verdicts, sla_hip_stream_t stream);
+
+/* The edge kernel (k_splice_edges): entry k writes one whole block to [dst, dst + len) at any byte alignment -- sync code,
+ * size field, CRC16 over [8, len), sample count, type, and for a RAW block (silent == 0) the frames of samples
+ * [plane_off, plane_off + num_samples) of the planes (decoded, right-justified, mid/side still folded): per frame and channel the
+ * zig-zag fold in `width` bits (+ 1 for channel 1 with mid_side; a 33-bit field is a zero bit and the 32 bits of the fold, as
+ * slai_pack_block writes it), zero bits up to the byte boundary; len = 11 + ceil(num_samples * W / 8).  silent != 0: the 11 bytes
+ * of a SILENT block.  No byte outside [dst, dst + len) is written, not even with its old value: entries may lie back to back
+ * and beside ranges sla_hip_launch_splice_copy writes.  An entry with a NULL dst, num_samples 0 or > 65535, or samples outside
+ * [0, plane_stride) is skipped.
+ * INVALID_ARGUMENT before any launch for a NULL table or planes, num_channels 0 or > 8, width 0 or > 32, mid_side with
+ * num_channels != 2. */
+typedef struct sla_hip_splice_edge {
+  uint8_t* dst;                   /* device, any alignment: the block's first byte */
+  uint64_t plane_off;             /* the block's first sample in the planes */
+  uint32_t num_samples;
+  uint32_t silent;
+} sla_hip_splice_edge;            /* 24 bytes */
+int sla_hip_launch_splice_edges(const int32_t* d_planes, uint64_t plane_stride, const sla_hip_splice_edge* d_table,
+                                uint32_t num_entries, uint32_t num_channels, uint32_t width, uint32_t mid_side,
+                                sla_hip_stream_t stream);
+
+/* The copy kernel (k_splice_copy): entry k writes exactly [dst, dst + bytes) from [src, src + bytes), device to device at any
+ * pair of byte alignments.  No byte outside the destination range is written, not even with its old value; heads and tails go
+ * out as guarded byte stores, the interior as 16-byte stores to aligned chunks, each made from the two aligned 16-byte words
+ * of the source that hold it (loads touch only aligned 16-byte words that hold at least one byte of the source range).
+ * Source and destination ranges must not overlap.  Entries with a NULL pointer are skipped.  max_bytes: the largest `bytes`
+ * (sizes the grid).  INVALID_ARGUMENT before any launch for a NULL table. */
+typedef struct sla_hip_splice_copy {
+  const uint8_t* src;             /* device, any alignment */
+  uint8_t* dst;                   /* device, any alignment */
+  uint32_t bytes;
+  uint32_t reserved;
+} sla_hip_splice_copy;            /* 24 bytes */
+int sla_hip_launch_splice_copy(const sla_hip_splice_copy* d_table, uint32_t num_entries, uint32_t max_bytes,
+                               sla_hip_stream_t stream);
+
 /* Decode-and-compare of blocks (option "verify" of the encoder; kernel k_verify_blocks): for every block of the table and
  * every channel, the decoded plane samples [smp_off, smp_off + num_samples) -- what dec_bits / dec_lms / dec_ltm /
  * dec_lattice left, right-justified, mid/side still folded -- are finished as sla_hip_launch_dec_finish_batch finishes them

@@ -164,6 +164,44 @@ class WindowOutcome(C.Structure):
     _fields_ = [("result", C.c_int32), ("output_num_samples", C.c_uint32)]
 
 
+class SpliceSegment(C.Structure):
+    """sla_hip_splice_segment (include/sla_hip.h): samples [start, start + length) of one resident stream"""
+    _fields_ = [("data", C.c_void_p), ("index", C.c_void_p), ("data_size", C.c_uint32), ("start", C.c_uint32),
+                ("length", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SpliceItem(C.Structure):
+    """sla_hip_splice_item (include/sla_hip.h): one output stream of sla_hip_splice_resident"""
+    _fields_ = [("segments", C.POINTER(SpliceSegment)), ("data", C.c_void_p), ("num_segments", C.c_uint32),
+                ("data_size", C.c_uint32), ("output_size", C.c_uint32), ("result", C.c_int32)]
+
+
+class SpliceLayout(C.Structure):
+    """sla_hip_splice_layout (include/sla_hip.h): what sla_hip_splice_plan returns"""
+    _fields_ = [("verbatim_bytes", C.c_uint64), ("bytes", C.c_uint32), ("num_samples", C.c_uint32), ("num_blocks", C.c_uint32),
+                ("edge_blocks", C.c_uint32), ("max_block_size", C.c_uint32), ("max_bit_per_second", C.c_uint32),
+                ("header", C.c_uint8 * 48)]
+
+
+class SpliceCheck(C.Structure):
+    """sla_hip_splice_check (include/sla_hip.h): one entry of sla_hip_launch_splice_check"""
+    _fields_ = [("src", C.c_void_p), ("plane_off", C.c_uint64), ("byte_len", C.c_uint32), ("num_samples", C.c_uint32),
+                ("verdict", C.c_uint32), ("ordinal", C.c_uint32), ("edge", C.c_uint32), ("keep", C.c_uint32)]
+
+
+class SpliceEdge(C.Structure):
+    """sla_hip_splice_edge (include/sla_hip.h): one entry of sla_hip_launch_splice_edges"""
+    _fields_ = [("dst", C.c_void_p), ("plane_off", C.c_uint64), ("num_samples", C.c_uint32), ("silent", C.c_uint32)]
+
+
+class SpliceCopy(C.Structure):
+    """sla_hip_splice_copy (include/sla_hip.h): one entry of sla_hip_launch_splice_copy"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SPLICE_NO_EDGE = 0xFFFFFFFF
+
+
 class DecJudgeItem(C.Structure):
     """sla_hip_dec_judge_item (include/sla_hip.h): one item of sla_hip_launch_dec_judge"""
     _fields_ = [("first", C.c_uint32), ("nb", C.c_uint32), ("stop", C.c_uint32), ("ok_samples", C.c_uint32),
@@ -447,8 +485,48 @@ def lib():
                                                          C.c_uint32, C.c_void_p, C.c_void_p]
             L.sla_hip_launch_dec_judge.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                                    C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        if hasattr(L, "sla_hip_splice_resident"):            # (SLA_HIP_LIB may name an older build in an A/B run)
+            L.sla_hip_splice_plan.argtypes = [C.POINTER(SpliceItem), C.POINTER(SpliceLayout)]
+            L.sla_hip_splice_resident.argtypes = [C.c_void_p, C.POINTER(SpliceItem), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+            L.sla_hip_launch_splice_check.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                      C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+            L.sla_hip_launch_splice_edges.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                      C.c_uint32, C.c_void_p]
+            L.sla_hip_launch_splice_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         _lib = L
     return _lib
+
+
+def _splice_item(segments):
+    """a SpliceItem (and the array it points to) of [(src, Index, start, length)]; src: None, a (ptr, size) pair or a 1-D uint8
+    CUDA tensor; the segment's data_size is the source's, or the index's where there is no source"""
+    segs = (SpliceSegment * max(len(segments), 1))()
+    for k, (src, index, start, length) in enumerate(segments):
+        if src is None:
+            ptr, size = None, (index.data_size if index is not None else 0)
+        elif isinstance(src, (tuple, list)):
+            ptr, size = (int(src[0]) or None), int(src[1])
+        else:
+            if src.dim() != 1 or str(src.dtype) != "torch.uint8" or not src.is_contiguous() or src.device.type != "cuda":
+                raise ValueError("segment %d: need a 1-D contiguous uint8 CUDA tensor or a (ptr, size) pair" % k)
+            ptr, size = (src.data_ptr() or None), src.numel()
+        if not (0 <= int(start) <= 0xFFFFFFFF and 0 <= int(length) <= 0xFFFFFFFF and 0 <= size <= 0xFFFFFFFF):
+            raise ValueError("segment %d: start %d, length %d, %d bytes" % (k, start, length, size))
+        segs[k].data, segs[k].index, segs[k].data_size = ptr, (index.handle if index is not None else None), size
+        segs[k].start, segs[k].length = int(start), int(length)
+    item = SpliceItem()
+    item.segments = C.cast(segs, C.POINTER(SpliceSegment)) if len(segments) else None
+    item.num_segments = len(segments)
+    return item, segs
+
+
+def splice_plan(segments):
+    """(result code, SpliceLayout) of the output stream made of [(src, Index, start, length)] (sla_hip_splice_plan: the layout
+    rule of Decoder.splice_resident, pure host code); src may be None, or a (ptr, size) pair that is never dereferenced"""
+    item, keep = _splice_item(segments)
+    lay = SpliceLayout()
+    rc = lib().sla_hip_splice_plan(C.byref(item), C.byref(lay))
+    return int(rc), lay
 
 
 def wav_info(data):
@@ -535,6 +613,9 @@ EXPORTED_SYMBOLS = [
     "sla_hip_index_build", "sla_hip_index_build_resident", "sla_hip_index_info", "sla_hip_index_blocks", "sla_hip_index_destroy",
     "sla_hip_index_serialized_bytes", "sla_hip_index_serialize", "sla_hip_index_deserialize", "sla_hip_launch_dec_judge",
     "sla_hip_decode_windows_indexed",
+    # cutting and joining resident streams (include/sla_hip.h)
+    "sla_hip_splice_plan", "sla_hip_splice_resident", "sla_hip_launch_splice_check", "sla_hip_launch_splice_edges",
+    "sla_hip_launch_splice_copy",
 ]
 
 
@@ -1795,6 +1876,60 @@ class Decoder:
             refused = (outcomes[:, 0] == 2).view(B, 1, 1)
             out.masked_fill_(refused, 0)
         return out, outcomes
+
+    def splice_resident(self, outputs, outs=None, arena=None, stream=None):
+        """new .sla streams from parts of resident ones, without re-encoding (sla_hip_splice_resident): outputs[i] is a list of
+        segments (src, Index, start, length), src a 1-D uint8 CUDA tensor or a (ptr, size) pair; whole blocks are copied
+        byte for byte, the blocks a cut passes through are decoded and stored as RAW (SILENT) blocks.  outs: one 1-D uint8
+        CUDA tensor per output (its capacity), arena: one such tensor the streams are packed into back to back, neither:
+        tensors of splice_plan's size.  Returns [(result code, uint8 tensor of the stream -- a view of outs[i] / the arena --
+        or None)].  Synchronous."""
+        import torch
+        if outs is not None and arena is not None:
+            raise ValueError("outs and arena exclude each other")
+        n = len(outputs)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        dev = torch.device("cuda", self.device_index)
+        items = (SpliceItem * max(n, 1))()
+        keep = []
+        for i, segments in enumerate(outputs):
+            item, segs = _splice_item(list(segments))
+            keep.append(segs)
+            items[i].segments, items[i].num_segments = item.segments, item.num_segments
+        if arena is None:
+            if outs is None:
+                with torch.cuda.stream(st):
+                    outs = [torch.empty(max(int(splice_plan(list(s))[1].bytes), 1), dtype=torch.uint8, device=dev) for s in outputs]
+            if len(outs) != n:
+                raise ValueError("%d outputs, %d destinations" % (n, len(outs)))
+            for i, o in enumerate(outs):
+                if o.dim() != 1 or o.dtype != torch.uint8 or not o.is_contiguous() or o.device != dev or o.numel() > 0xFFFFFFFF:
+                    raise ValueError("destination %d: need a 1-D contiguous uint8 tensor on %s" % (i, dev))
+                items[i].data, items[i].data_size = (o.data_ptr() or None), o.numel()
+        elif arena.dim() != 1 or arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.device != dev:
+            raise ValueError("arena: need a 1-D contiguous uint8 tensor on %s" % dev)
+        rc = self._lib.sla_hip_splice_resident(self._h, items, n, C.c_void_p(arena.data_ptr()) if arena is not None else None,
+                                               arena.numel() if arena is not None else 0, C.c_void_p(st.cuda_stream))
+        self._check(rc, "sla_hip_splice_resident")
+        got = []
+        for i in range(n):
+            size = int(items[i].output_size)
+            if items[i].result != 0:
+                got.append((int(items[i].result), None))
+            elif arena is not None:
+                off = int(items[i].data) - arena.data_ptr()
+                got.append((0, arena[off:off + size]))
+            else:
+                got.append((0, outs[i][:size]))
+        return got
+
+    def cut_resident(self, src, index, start, length):
+        """samples [start, start + length) of one resident stream as a new stream: (result code, uint8 tensor or None)"""
+        return self.splice_resident([[(src, index, start, length)]])[0]
+
+    def join_resident(self, srcs, indexes):
+        """whole resident streams of one format, one after the other, as one stream: (result code, uint8 tensor or None)"""
+        return self.splice_resident([[(s, x, 0, x.extent) for s, x in zip(srcs, indexes)]])[0]
 
     def set_option(self, name, value):
         """a handle option (sla_hip_decoder_set_option): "wide_walk" -- resident streams of at least that many bytes have

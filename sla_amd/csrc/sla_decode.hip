@@ -1083,6 +1083,7 @@ void k_dec_gather(const sla_hip_dec_gather* __restrict__ table, uint32_t num_ent
 #include "kernels/salvage.inc"
 #include "kernels/verify.inc"
 #include "kernels/judge.inc"
+#include "kernels/splice.inc"
 
 }  // namespace
 
@@ -1512,5 +1513,50 @@ extern "C" int sla_hip_launch_dec_judge(const uint8_t* d_image, uint64_t image_b
   // one wave per item, four items per workgroup
   hipLaunchKernelGGL(k_dec_judge, dim3((num_items + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_image, image_bytes, d_blocks, d_info,
                      num_blocks, d_items, num_items, crc_check, lms_ok, d_emit, num_emit, d_outcomes, num_outcomes);
+  return hip_rc(hipGetLastError());
+}
+
+static bool splice_format_ok(uint32_t num_channels, uint32_t width, uint32_t mid_side)
+{
+  return num_channels >= 1 && num_channels <= 8 && width >= 1 && width <= 32 && !(mid_side && num_channels != 2);
+}
+
+extern "C" int sla_hip_launch_splice_check(const sla_hip_splice_check* d_table, uint32_t num_entries, uint32_t crc_check,
+                                           const int32_t* d_planes, uint64_t plane_stride, uint32_t num_channels, uint32_t width,
+                                           uint32_t mid_side, const sla_hip_window_outcome* d_outcomes, uint32_t num_outcomes,
+                                           uint64_t* d_verdicts, uint32_t num_verdicts, sla_hip_stream_t stream)
+{
+  if (d_table == nullptr || d_planes == nullptr || d_outcomes == nullptr || d_verdicts == nullptr
+      || !splice_format_ok(num_channels, width, mid_side)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_entries == 0) { return 0; }
+  // one wave per entry, four entries per workgroup
+  hipLaunchKernelGGL(k_splice_check, dim3((num_entries + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_table, num_entries, crc_check,
+                     d_planes, plane_stride, num_channels, width, mid_side ? 1u : 0u, d_outcomes, num_outcomes,
+                     (unsigned long long*)d_verdicts, num_verdicts);
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_splice_edges(const int32_t* d_planes, uint64_t plane_stride, const sla_hip_splice_edge* d_table,
+                                           uint32_t num_entries, uint32_t num_channels, uint32_t width, uint32_t mid_side,
+                                           sla_hip_stream_t stream)
+{
+  if (d_table == nullptr || d_planes == nullptr || !splice_format_ok(num_channels, width, mid_side)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_entries == 0) { return 0; }
+  // one workgroup per block; longer tables grid-stride
+  hipLaunchKernelGGL(k_splice_edges, dim3((num_entries < 65535u) ? num_entries : 65535u), dim3(256), 0, (hipStream_t)stream, d_planes,
+                     plane_stride, d_table, num_entries, num_channels, width, mid_side ? 1u : 0u);
+  return hip_rc(hipGetLastError());
+}
+
+extern "C" int sla_hip_launch_splice_copy(const sla_hip_splice_copy* d_table, uint32_t num_entries, uint32_t max_bytes,
+                                          sla_hip_stream_t stream)
+{
+  if (d_table == nullptr) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (num_entries == 0 || max_bytes == 0) { return 0; }
+  // a workgroup row covers 4096 bytes of an entry (256 lanes x 16); longer entries grid-stride
+  uint64_t gx = ((uint64_t)max_bytes + 15 + 4095) / 4096;
+  if (gx > 1024) { gx = 1024; }
+  const dim3 grid((uint32_t)gx, (num_entries < 65535u) ? num_entries : 65535u), block(256);
+  hipLaunchKernelGGL(k_splice_copy, grid, block, 0, (hipStream_t)stream, d_table, num_entries);
   return hip_rc(hipGetLastError());
 }

@@ -61,6 +61,7 @@ struct SLADecoder {
   hipEvent_t                ev_close;
   int                       queued;
   dbuf_t                    d_qtab;                     /* the same: judge and emit table of a pass */
+  dbuf_t                    d_splice; hbuf_t h_splice;  /* sla_hip_splice_resident: a pass's judge, check and verdict tables; its staging */
 };
 
 /* Every entry point but sla_hip_decode_windows_indexed opens with this: what that call left queued on the handle's stream
@@ -174,6 +175,7 @@ void SLADecoder_Destroy(struct SLADecoder* d)
   { int k; for (k = 0; k < 3; k++) { if (d->ev_src[k] != NULL) { (void)hipEventDestroy(d->ev_src[k]); } } }
   { uint32_t k; for (k = 0; k < SLA_HIP_DEC_QUEUE_SLOTS; k++) { hbuf_free(&d->q_slot[k].h); if (d->q_slot[k].ev != NULL) { (void)hipEventDestroy(d->q_slot[k].ev); } } }
   dbuf_free(&d->d_qtab);
+  dbuf_free(&d->d_splice); hbuf_free(&d->h_splice);
   if (d->ev_close != NULL) { (void)hipEventDestroy(d->ev_close); }
   if (d->h_blocks != NULL) { (void)hipHostFree(d->h_blocks); }
   if (d->h_info != NULL) { (void)hipHostFree(d->h_info); }
@@ -2183,6 +2185,275 @@ int sla_hip_decode_windows_indexed(struct SLADecoder* d, const sla_hip_indexed_w
   d->wave_format = after.wf; d->encode_param = after.ep; d->status_flag = after.flag;
   d->timing[4] = (float)(now_ms() - t0);
   free(m.base);
+  return rc;
+}
+
+/* ------------------------------------------------------------------------------------------------------------
+ * sla_hip_splice_resident (include/sla_hip.h): new streams from parts of resident ones.  The layout is sla_splice.c's; here
+ * the blocks it names are collected per item (sp_visit), the items sorted by launch parameters and cut into passes by the
+ * edge blocks they decode, and per pass: gather + decode kernels + k_dec_judge on the edge blocks (each its own one-block
+ * file of the pass layout), k_splice_check on every block, the one wait for the verdicts, placement, k_splice_edges and
+ * k_splice_copy.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  const uint8_t* src;           /* the block's sync code in its source */
+  uint64_t out_off;             /* where it lies in its output */
+  uint32_t byte_len, num_samples;      /* its row */
+  uint32_t first, n, kind;      /* the kept samples of the row; SLAI_SPLICE_* */
+  uint32_t ordinal;             /* its position in the output */
+} sp_block_t;
+typedef struct { sp_block_t* v; uint32_t n, cap, ordinal; int oom; const sla_hip_splice_item* it; } sp_list_t;
+
+static void sp_visit(void* ctx, uint32_t seg, const sla_hip_index_block* row, uint32_t first, uint32_t n, uint32_t kind,
+                     uint64_t out_off, uint32_t out_len)
+{
+  sp_list_t* l = (sp_list_t*)ctx;
+  sp_block_t* b;
+  (void)out_len;
+  if (l->oom) { return; }
+  if (l->n == l->cap) {
+    const uint32_t cap = l->cap * 2 + 256;
+    sp_block_t* v = (sp_block_t*)realloc(l->v, sizeof(*v) * (size_t)cap);
+    if (v == NULL || cap < l->cap) { l->oom = 1; return; }
+    l->v = v; l->cap = cap;
+  }
+  b = &l->v[l->n++];
+  b->src = l->it->segments[seg].data + row->byte_off; b->out_off = out_off;
+  b->byte_len = row->byte_len; b->num_samples = row->num_samples;
+  b->first = first; b->n = n; b->kind = kind; b->ordinal = l->ordinal++;
+}
+
+#define SP_ALIGN(x) (((x) + 15u) & ~(size_t)15)
+
+/* One pass: grp[0, ng) are accepted items of one set of launch parameters (grp[].first / .nb: their blocks in bl).  Returns
+ * -1 on a device or allocation failure. */
+static int splice_pass(struct SLADecoder* d, sla_hip_splice_item* items, const sla_hip_splice_layout* lay, const bfile_t* grp,
+                       uint32_t ng, const sp_block_t* bl, uint8_t* d_arena, uint64_t arena_bytes, uint64_t* arena_used)
+{
+  const dec_format_t f = grp[0].f;
+  const uint32_t width = f.bps - f.lshift;
+  bfile_t* ef = NULL;
+  sla_hip_dec_gather* gt; sla_hip_dec_block* tb; uint64_t* tend; sla_hip_dec_judge_item* jt; sla_hip_splice_check* ck; uint64_t* vw;
+  sla_hip_splice_edge* et; sla_hip_splice_copy* ct; uint8_t* hd;
+  uint8_t *hs, *ds;
+  size_t o_tb, o_jt, o_ck, o_vw, o_oc, up_bytes, o_dl, o_ct, o_hd, dl_bytes;
+  uint32_t ne = 0, nblk = 0, i, k, e, max_bytes = 0, nd = 0, nc = 0, net = 0, max_copy = 0;
+  pass_t p;
+  stage_t st;
+  int rc = -1;
+
+  for (i = 0; i < ng; i++) {
+    nblk += grp[i].nb;
+    for (k = 0; k < grp[i].nb; k++) { if (bl[grp[i].first + k].kind != SLAI_SPLICE_VERBATIM) { ne++; } }
+  }
+  memset(&p, 0, sizeof(p)); p.span = 1;
+  if (ne > 0) {
+    if ((ef = (bfile_t*)calloc(ne, sizeof(*ef))) == NULL) { return -1; }
+    for (i = 0, e = 0; i < ng; i++) {
+      for (k = 0; k < grp[i].nb; k++) {
+        const sp_block_t* b = &bl[grp[i].first + k];
+        if (b->kind == SLAI_SPLICE_VERBATIM) { continue; }
+        ef[e].item = e; ef[e].f = f; ef[e].bytes = b->byte_len; ef[e].nb = 1; ef[e].extent = b->num_samples;
+        e++;
+      }
+    }
+    if (pass_begin(d, ef, ne, &p) != 0) { goto out; }
+  } else if (dbuf_reserve(&d->d_planes, 256) != 0) { goto out; }
+
+  /* ---- staging: gather table | rows, ends | judge items | check table | verdict words; on the device the first goes to
+   *      d_src, the second to d_blocks, the rest to d_splice with the judge's outcomes behind them */
+  o_tb = SP_ALIGN(sizeof(*gt) * (size_t)ne);
+  o_jt = o_tb + SP_ALIGN((sizeof(*tb) + sizeof(*tend)) * (size_t)ne);
+  o_ck = o_jt + SP_ALIGN(sizeof(*jt) * (size_t)ne);
+  o_vw = o_ck + SP_ALIGN(sizeof(*ck) * (size_t)nblk);
+  up_bytes = o_vw + SP_ALIGN(sizeof(*vw) * (size_t)ng);
+  o_oc = up_bytes - o_jt;
+  /* behind them, host only: the verdict words that come home; the delivery tables: edge entries | copy entries | headers */
+  o_dl = SP_ALIGN(up_bytes + sizeof(*vw) * (size_t)ng);
+  o_ct = SP_ALIGN(sizeof(*et) * (size_t)ne);
+  o_hd = o_ct + SP_ALIGN(sizeof(*ct) * ((size_t)nblk + ng));
+  dl_bytes = o_hd + 48u * (size_t)ng;
+  if (hbuf_reserve(&d->h_splice, o_dl + dl_bytes) != 0 || dbuf_reserve(&d->d_src, o_tb + 16) != 0
+      || dbuf_reserve(&d->d_splice, o_oc + sizeof(sla_hip_window_outcome) * (size_t)ne + 16) != 0 || res_events(d) != 0) { goto out; }
+  hs = (uint8_t*)d->h_splice.ptr; ds = (uint8_t*)d->d_splice.ptr;
+  memset(hs, 0, up_bytes);
+  gt = (sla_hip_dec_gather*)hs; tb = (sla_hip_dec_block*)(hs + o_tb); tend = (uint64_t*)(tb + ne);
+  jt = (sla_hip_dec_judge_item*)(hs + o_jt); ck = (sla_hip_splice_check*)(hs + o_ck); vw = (uint64_t*)(hs + o_vw);
+  for (i = 0, e = 0, nblk = 0; i < ng; i++) {
+    vw[i] = ~(uint64_t)0;
+    for (k = 0; k < grp[i].nb; k++, nblk++) {
+      const sp_block_t* b = &bl[grp[i].first + k];
+      sla_hip_splice_check* c = &ck[nblk];
+      c->src = b->src; c->byte_len = b->byte_len; c->num_samples = b->num_samples; c->verdict = i; c->ordinal = b->ordinal;
+      c->edge = SLA_HIP_SPLICE_NO_EDGE;
+      if (b->kind == SLAI_SPLICE_VERBATIM) { continue; }
+      gt[e].src = b->src; gt[e].dst_off = ef[e].img_off; gt[e].bytes = b->byte_len;
+      if (b->byte_len > max_bytes) { max_bytes = b->byte_len; }
+      tb[e].byte_off = ef[e].img_off; tb[e].byte_len = b->byte_len; tb[e].smp_off = (uint32_t)ef[e].plane_off; tb[e].num_samples = b->num_samples;
+      tend[e] = ef[e].img_off + b->byte_len;
+      jt[e].first = e; jt[e].nb = 1; jt[e].outcome = e; jt[e].emit = Q_NO_EMIT;
+      c->edge = e; c->plane_off = ef[e].plane_off + b->first; c->keep = b->n;
+      e++;
+    }
+  }
+
+  /* ---- queued: tables over, gather, decode kernels, judge, check; the verdicts home in the pass's one wait */
+  if (ne > 0) {
+    st.gt = gt; st.up_bytes = sizeof(*gt) * (size_t)ne; st.d_gt = (const sla_hip_dec_gather*)d->d_src.ptr;
+    if (hipMemcpyAsync(d->d_blocks.ptr, tb, (sizeof(*tb) + sizeof(*tend)) * (size_t)ne, hipMemcpyHostToDevice, d->stream) != hipSuccess
+        || hipMemsetAsync(d->d_info.ptr, 0, sizeof(sla_hip_dec_info) * ne, d->stream) != hipSuccess) { goto out; }
+  }
+  if (hipMemcpyAsync(ds, hs + o_jt, o_oc, hipMemcpyHostToDevice, d->stream) != hipSuccess) { goto out; }
+  if (ne > 0) {
+    if (stage_gather(d, &st, ne, max_bytes, p.img_bytes) != 0 || pass_kernels_run(d, &f, ne, 0, p.img_bytes, p.span, NULL, 1) != 0
+        || sla_hip_launch_dec_judge((const uint8_t*)d->d_image.ptr, p.img_bytes, (const sla_hip_dec_block*)d->d_blocks.ptr,
+                                    (const sla_hip_dec_info*)d->d_info.ptr, ne, (const sla_hip_dec_judge_item*)ds, ne,
+                                    d->cfg.enable_crc_check == 1, (uint32_t)lms_order_ok(f.lms), NULL, 0,
+                                    (sla_hip_window_outcome*)(ds + o_oc), ne, d->stream) != 0) { goto out; }
+  }
+  if (sla_hip_launch_splice_check((const sla_hip_splice_check*)(ds + (o_ck - o_jt)), nblk, d->cfg.enable_crc_check == 1,
+                                  (const int32_t*)d->d_planes.ptr, p.span, f.C, width, f.ms,
+                                  (const sla_hip_window_outcome*)(ds + o_oc), ne, (uint64_t*)(ds + (o_vw - o_jt)), ng, d->stream) != 0
+      || hipMemcpyAsync(hs + up_bytes, ds + (o_vw - o_jt), sizeof(*vw) * (size_t)ng, hipMemcpyDeviceToHost, d->stream) != hipSuccess
+      || hipStreamSynchronize(d->stream) != hipSuccess) { goto out; }
+  vw = (uint64_t*)(hs + up_bytes);
+
+  /* ---- verdicts, placement; the delivery tables of the clean items */
+  for (i = 0; i < ng; i++) {
+    sla_hip_splice_item* it = &items[grp[i].item];
+    const uint32_t bytes = lay[grp[i].item].bytes;
+    if (vw[i] != ~(uint64_t)0) { it->result = (int32_t)(vw[i] & 0xFFu); vw[i] = 0; continue; }
+    if (d_arena != NULL) {
+      if (bytes > arena_bytes - *arena_used) { it->result = SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE; vw[i] = 0; continue; }
+      it->data = d_arena + *arena_used; *arena_used += bytes;
+    }
+    it->result = SLA_APIRESULT_OK; it->output_size = bytes;
+    vw[i] = 1; nd++;
+  }
+  if (nd == 0) { rc = 0; goto out; }
+  if (dbuf_reserve(&d->d_ftab, dl_bytes + 16) != 0) { goto out; }
+  et = (sla_hip_splice_edge*)(hs + o_dl); ct = (sla_hip_splice_copy*)(hs + o_dl + o_ct); hd = hs + o_dl + o_hd;
+  memset(et, 0, dl_bytes);
+  for (i = 0, e = 0; i < ng; i++) {
+    const sla_hip_splice_item* it = &items[grp[i].item];
+    uint32_t run = 0;                    /* 1: ct[nc - 1] is a verbatim run that the next verbatim block may extend */
+    if (vw[i] == 0) { for (k = 0; k < grp[i].nb; k++) { if (bl[grp[i].first + k].kind != SLAI_SPLICE_VERBATIM) { e++; } } continue; }
+    memcpy(hd + 48u * (size_t)i, lay[grp[i].item].header, 48);
+    ct[nc].src = (const uint8_t*)d->d_ftab.ptr + o_hd + 48u * (size_t)i; ct[nc].dst = it->data; ct[nc].bytes = SLA_HEADER_SIZE;
+    if (max_copy < SLA_HEADER_SIZE) { max_copy = SLA_HEADER_SIZE; }
+    nc++;
+    for (k = 0; k < grp[i].nb; k++) {
+      const sp_block_t* b = &bl[grp[i].first + k];
+      if (b->kind != SLAI_SPLICE_VERBATIM) {
+        et[net].dst = it->data + b->out_off; et[net].plane_off = ef[e].plane_off + b->first; et[net].num_samples = b->n;
+        et[net].silent = (b->kind == SLAI_SPLICE_SILENT) ? 1u : 0u;
+        net++; e++; run = 0;
+        continue;
+      }
+      if (run && ct[nc - 1].src + ct[nc - 1].bytes == b->src && ct[nc - 1].bytes <= 0xFFFFFFFFu - b->byte_len) {
+        ct[nc - 1].bytes += b->byte_len;
+      } else {
+        ct[nc].src = b->src; ct[nc].dst = it->data + b->out_off; ct[nc].bytes = b->byte_len;
+        nc++; run = 1;
+      }
+      if (ct[nc - 1].bytes > max_copy) { max_copy = ct[nc - 1].bytes; }
+    }
+  }
+  if (hipMemcpyAsync(d->d_ftab.ptr, et, dl_bytes, hipMemcpyHostToDevice, d->stream) != hipSuccess
+      || hipEventRecord(d->ev_src[0], d->stream) != hipSuccess
+      || (net > 0 && sla_hip_launch_splice_edges((const int32_t*)d->d_planes.ptr, p.span, (const sla_hip_splice_edge*)d->d_ftab.ptr, net,
+                                                 f.C, width, f.ms, d->stream) != 0)
+      || hipEventRecord(d->ev_src[1], d->stream) != hipSuccess
+      || sla_hip_launch_splice_copy((const sla_hip_splice_copy*)((const uint8_t*)d->d_ftab.ptr + o_ct), nc, max_copy, d->stream) != 0
+      || hipEventRecord(d->ev_src[2], d->stream) != hipSuccess
+      || hipStreamSynchronize(d->stream) != hipSuccess) { goto out; }
+  /* sla_hip_decoder_last_timing: [2] the span of k_splice_edges, [3] of k_splice_copy, summed over the passes */
+  ev_add_ms(&d->timing[2], d->ev_src[0], d->ev_src[1]); ev_add_ms(&d->timing[3], d->ev_src[1], d->ev_src[2]);
+  rc = 0;
+out:
+  free(ef);
+  return rc;
+}
+
+int sla_hip_splice_resident(struct SLADecoder* d, sla_hip_splice_item* items, uint32_t num_items, uint8_t* d_arena, uint64_t arena_bytes,
+                            sla_hip_stream_t stream)
+{
+  const double t0 = now_ms();
+  sla_hip_splice_layout* lay;
+  bfile_t* grp;
+  sp_list_t list;
+  uint64_t arena_used = 0;
+  uint32_t i, s, k, ng = 0, p0;
+  int rc = 0;
+  if (d == NULL || (items == NULL && num_items > 0)) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (d_arena != NULL && !((arena_bytes <= 1) ? slai_device_region_ok(d_arena, 1, (uint32_t)arena_bytes, 0, 1, 1, -1)
+                                              : slai_device_region_ok(d_arena, 1, 2, 0, arena_bytes - 1, 1, -1))) { return SLA_APIRESULT_INVALID_ARGUMENT; }
+  if (drain(d) != 0) { return SLA_APIRESULT_NG; }
+  memset(d->timing, 0, sizeof(d->timing));
+  if (num_items == 0) { return 0; }
+  lay = (sla_hip_splice_layout*)calloc(num_items, sizeof(*lay));
+  grp = (bfile_t*)calloc(num_items, sizeof(*grp));
+  memset(&list, 0, sizeof(list));
+  if (lay == NULL || grp == NULL) { free(lay); free(grp); return SLA_APIRESULT_NG; }
+
+  /* ---- per item, on the host: the layout, the source and destination checks, the handle's capacity, the pass caps */
+  for (i = 0; i < num_items; i++) {
+    sla_hip_splice_item* it = &items[i];
+    const uint32_t b0 = list.n;
+    uint64_t smp = 0, bytes = 0;
+    dec_format_t f;
+    SLAApiResult ret;
+    it->output_size = 0;
+    if (d_arena != NULL) { it->data = NULL; }
+    list.it = it; list.ordinal = 0;
+    if ((it->result = slai_splice_walk(it, &lay[i], sp_visit, &list)) != SLA_APIRESULT_OK) { list.n = b0; continue; }
+    if (list.oom) { rc = SLA_APIRESULT_NG; goto out; }
+    it->result = SLA_APIRESULT_INVALID_ARGUMENT;
+    for (s = 0; s < it->num_segments; s++) { if (!src_region_ok(it->segments[s].data, it->segments[s].data_size)) { break; } }
+    if (s < it->num_segments) { list.n = b0; continue; }
+    if (d_arena == NULL && (it->data == NULL || !((it->data_size <= 1) ? slai_device_region_ok(it->data, 1, it->data_size, 0, 1, 1, -1)
+                                                                        : slai_device_region_ok(it->data, 1, 2, 0, (uint64_t)it->data_size - 1, 1, -1)))) {
+      list.n = b0; continue;
+    }
+    if ((ret = file_format(d, it->segments[0].index->head, it->segments[0].data_size, &f)) != SLA_APIRESULT_OK) { it->result = ret; list.n = b0; continue; }
+    it->result = SLA_APIRESULT_OK;
+    for (k = b0; k < list.n; k++) {
+      const sp_block_t* b = &list.v[k];
+      if (b->kind == SLAI_SPLICE_VERBATIM) { continue; }
+      if (b->num_samples > d->cfg.max_num_block_samples) { it->result = SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE; break; }
+      smp += ((uint64_t)b->num_samples + SLAI_DEC_BATCH_ALIGN) * f.C; bytes += (uint64_t)b->byte_len + 4;
+    }
+    if (it->result == SLA_APIRESULT_OK && (smp > SLA_HIP_DEC_BATCH_PASS || bytes > DEC_BATCH_PASS_BYTES)) { it->result = SLA_APIRESULT_EXCEED_HANDLE_CAPACITY; }
+    if (it->result == SLA_APIRESULT_OK && d_arena == NULL && lay[i].bytes > it->data_size) { it->result = SLA_APIRESULT_INSUFFICIENT_BUFFER_SIZE; }
+    if (it->result != SLA_APIRESULT_OK) { list.n = b0; continue; }
+    grp[ng].item = i; grp[ng].f = f; grp[ng].first = b0; grp[ng].nb = list.n - b0;
+    grp[ng].extent = (uint32_t)(smp / f.C); grp[ng].bytes = (uint32_t)bytes;
+    ng++;
+  }
+  if (order_behind(d, stream) != 0) { rc = SLA_APIRESULT_NG; goto out; }
+
+  /* ---- passes: equal launch parameters, items ascending, cut where the edge blocks of one more item would exceed a cap */
+  qsort(grp, ng, sizeof(*grp), slai_dec_file_cmp);
+  for (p0 = 0; p0 < ng; ) {
+    uint64_t smp = 0, bytes = 0;
+    uint32_t p1 = p0;
+    while (p1 < ng && slai_dec_same_launch(&grp[p1].f, &grp[p0].f)) {
+      const uint64_t s1 = (uint64_t)grp[p1].extent * grp[p1].f.C, b1 = grp[p1].bytes;
+      if (p1 > p0 && (smp + s1 > SLA_HIP_DEC_BATCH_PASS || bytes + b1 > DEC_BATCH_PASS_BYTES)) { break; }
+      smp += s1; bytes += b1; p1++;
+    }
+    if (splice_pass(d, items, lay, grp + p0, p1 - p0, list.v, d_arena, arena_bytes, &arena_used) != 0) {
+      /* a device failure: what this and the later passes would have delivered is not there */
+      for (i = p0; i < ng; i++) { items[grp[i].item].result = SLA_APIRESULT_NG; items[grp[i].item].output_size = 0; if (d_arena != NULL) { items[grp[i].item].data = NULL; } }
+      rc = SLA_APIRESULT_NG;
+      break;
+    }
+    p0 = p1;
+    d->timing[5] += 1.0f;
+  }
+out:
+  d->timing[4] = (float)(now_ms() - t0);
+  free(list.v); free(lay); free(grp);
   return rc;
 }
 

@@ -143,6 +143,18 @@ int      slai_index_has_header(const sla_hip_index* index);
 void     slai_index_window(const sla_hip_index* index, uint32_t total, uint32_t start, uint32_t length, uint32_t max_block_samples,
                            uint32_t* row0, uint32_t* nrows, uint32_t* kept, uint32_t* stop);
 
+/* ---- sla_splice.c: the layout rule of sla_hip_splice_resident (no device calls) --------- */
+#define SLAI_SPLICE_VERBATIM     0u      /* the block's bytes as they are */
+#define SLAI_SPLICE_SILENT       1u      /* an 11-byte SILENT block of the kept samples */
+#define SLAI_SPLICE_RAW          2u      /* a RAW block of the kept samples */
+#define SLAI_SPLICE_SILENT_BYTES 11u
+/* called for every emitted block in output order: segment, its index row, the kept samples [first, first + n) of the row,
+ * the kind, and where the block lies in the output stream */
+typedef void (*slai_splice_visit)(void* ctx, uint32_t segment, const sla_hip_index_block* row, uint32_t first, uint32_t n,
+                                  uint32_t kind, uint64_t out_off, uint32_t out_len);
+/* sla_hip_splice_plan with a visitor (NULL: none); on a refusal *layout is zero and the blocks visited so far are void */
+int      slai_splice_walk(const sla_hip_splice_item* item, sla_hip_splice_layout* layout, slai_splice_visit visit, void* ctx);
+
 /* ---- sla_decoder.c: caller-owned device memory of the batch calls --------- */
 /* 1 when [0, C) x [0, n) of esize-byte elements at p (element (c, i) at c * channel_stride + i * sample_stride) is aligned,
  * its byte extent does not overflow, the runtime reports p as device memory (of `device` when >= 0) and the region lies
