@@ -14,9 +14,14 @@ its amplitudes a few bits under the field width.
 Sources: crafted files of short blocks (1 to 300 samples, tests/slastream.py): COMPRESS, RAW and SILENT blocks in mono,
 stereo with and without mid/side and 8 channels, 8 / 16 / 24 / 32 bits, offset_lshift 0 and 3; three files per format
 for the joins.  `cases()` lists the cuts every test of the splice runs.
+
+`check_code` and `check_verdicts` are the rule of the check kernel (sla_hip_launch_splice_check) as the header states it,
+entry by entry, in unbounded integers: the yardstick of tests/test_gpu_splice_check.py, held against the judge's model, the
+RAW writer and the oracle's decoder by tests/test_splice_check_model.py.
 """
 import functools
 from dataclasses import dataclass, field
+from typing import Optional
 
 import numpy as np
 
@@ -174,6 +179,71 @@ def splice(segments):
 def expected_pcm(segments):
     """the concatenated source windows, left-justified [C][sum of lengths]"""
     return np.concatenate([pcm_of(c)[:, s:s + l] for c, s, l in segments], axis=1)
+
+
+# ---- the check kernel's rule (sla_hip_launch_splice_check), from the contract text of include/sla_hip.h -------------------
+NG, NO_EDGE = 1, 0xFFFFFFFF
+ALL_ONES = (1 << 64) - 1
+
+
+@dataclass
+class CheckEntry:
+    """sla_hip_splice_check.  src: the block's first byte as an offset into `memory`, None for a NULL pointer"""
+    src: Optional[int]
+    byte_len: int
+    num_samples: int
+    verdict: int = 0
+    ordinal: int = 0
+    edge: int = NO_EDGE
+    plane_off: int = 0
+    keep: int = 0
+
+
+def fits(s, w):
+    """whether the sample s can be stored in a RAW field of w bits: the field holds the two's complement range of w bits"""
+    return -(1 << (w - 1)) <= s < (1 << (w - 1))
+
+
+def check_code(entry, memory, planes, stride, C, width, ms, outcomes, crc_check, crc16=SS.crc16):
+    """the code of one entry, 0 when it is clean.  memory: the bytes entry.src counts in; planes: [C][stride] integers;
+    outcomes: the result codes the judge left, one per edge block; crc16: SS.crc16, or a faster routine held against it"""
+    if entry.src is None or entry.byte_len < 11:
+        return CORRUPT                                               # 1.
+    is_edge = entry.edge != NO_EDGE
+    if is_edge:                                                      # 2. the tables, then the judge's word
+        if entry.edge >= len(outcomes) or entry.plane_off > stride or entry.keep > stride - entry.plane_off:
+            return NG
+        if outcomes[entry.edge] != 0:
+            return int(outcomes[entry.edge])
+    h = bytes(memory[entry.src:entry.src + 11])                      # 3. the chain header against the row, and the type
+    typ = h[10] >> 6
+    if h[0:2] != b"\xff\xff" or (int.from_bytes(h[2:6], "big") + 6) % (1 << 32) != entry.byte_len:
+        return CORRUPT
+    if int.from_bytes(h[8:10], "big") != entry.num_samples or (typ == 1) != (entry.byte_len == 11):
+        return CORRUPT
+    if not is_edge:                                                  # 4.
+        if crc_check and crc16(bytes(memory[entry.src + 8:entry.src + entry.byte_len])) != int.from_bytes(h[6:8], "big"):
+            return CORRUPT
+        return 0
+    if typ != 1:                                                     # 5. what k_splice_edges would have to store
+        for c in range(C):
+            w = width + (1 if (ms and c == 1) else 0)
+            if w >= 32:
+                continue
+            for s in planes[c][entry.plane_off:entry.plane_off + entry.keep]:
+                if not fits(int(s), w):
+                    return CORRUPT
+    return 0
+
+
+def check_verdicts(entries, initial_words, num_verdicts, memory, planes, stride, C, width, ms, outcomes, crc_check, crc16=SS.crc16):
+    """the verdict buffer after one launch over `entries`: every failing entry whose word exists lowers it"""
+    words = [int(w) for w in initial_words]
+    for e in entries:
+        code = check_code(e, memory, planes, stride, C, width, ms, outcomes, crc_check, crc16)
+        if code != 0 and e.verdict < num_verdicts:
+            words[e.verdict] = min(words[e.verdict], (e.ordinal << 8) | (code & 0xFF))
+    return words
 
 
 @functools.lru_cache(maxsize=None)

@@ -4,7 +4,9 @@ MI355X): new .sla streams cut and joined from resident ones without re-encoding.
 The yardstick is tests/splicemodel.py, byte for byte: every cut and join of its catalogue in one call -- eight formats, so
 eight passes -- in per-buffer mode at odd destination alignments between canaries and in arena mode; the outputs decoded by
 decode_resident_tensor against decode_windows_tensor of the sources; an encoder-made stream; a cut inside a block of 65 535
-samples; and the failures: each leaves its destination untouched while the other items of the call are delivered."""
+samples; and the failures: each leaves its destination untouched while the other items of the call are delivered --
+stale indexes, indexes forged through the sidecar format, items with two failures (the first in output order decides) and
+40 items of one pass of which every third fails."""
 import numpy as np
 import pytest
 
@@ -263,5 +265,164 @@ def test_failures_leave_their_destination_untouched(hip):
             empty = SM.splice([(A, 0, 0)]).data
             assert got[3][1].data_ptr() == arena.data_ptr() + len(model_good) and len(empty) == 43
             check_buffer(buf, at, [model_good + empty])
+        finally:
+            dec.close()
+
+
+# ---- forged sidecars, several failures in one item, many items (tests/test_gpu_splice_check.py has the check kernel alone) ----
+
+ROWS_AT = 76               # a sidecar: 32 bytes of fixed fields (num_blocks at 28), 44 of the header, 16 per row, the CRC16
+
+
+def forged(hip, x, edit):
+    """the index of x's sidecar with edit(rows) applied to its rows [[byte_off, byte_len, smp_off, num_samples]] and the
+    checksum made right again: what a caller can hand in without ever having walked the stream"""
+    import ctypes as C
+    L = hip.lib()
+    L.slai_crc16.argtypes = [C.c_void_p, C.c_size_t]
+    L.slai_crc16.restype = C.c_uint32
+    blob = x.to_bytes()
+    rows = [[int(v) for v in r] for r in x.blocks()]
+    assert len(blob) == ROWS_AT + 16 * len(rows) + 2
+    edit(rows)
+    body = bytearray(blob[:ROWS_AT])
+    body[28:32] = len(rows).to_bytes(4, "little")
+    for r in rows:
+        body += b"".join(v.to_bytes(4, "little") for v in r)
+    a = np.frombuffer(bytes(body), np.uint8)
+    crc = int(L.slai_crc16(a.ctypes.data, len(a)))
+    y = hip.Index.from_bytes(bytes(body) + bytes([crc & 0xFF, crc >> 8]))                 # the library accepts it
+    assert [tuple(int(v) for v in r) for r in y.blocks()] == [tuple(r) for r in rows] and (y.extent, y.data_size) == (x.extent, x.data_size)
+    return y
+
+
+def count_flipped(data, off):
+    """the block at `off` with another sample count in its chain header: an index made before fails on it, CRC check or not"""
+    return data[:off + 9] + bytes([data[off + 9] ^ 1]) + data[off + 10:]
+
+
+def test_forged_indexes_are_caught_on_the_device(hip):
+    A = SM.sources()["stereo16ms"][0]
+    assert [b.type for b in A.blocks[3:5]] == [SS.COMPRESS] * 2 and [b.type for b in A.blocks[7:9]] == [SS.COMPRESS] * 2
+    ends = np.cumsum([b.n for b in A.blocks]).tolist()
+    res = Resident(hip, {"A": A.data})
+    src, honest = res.at["A"]
+    assert honest.blocks()[8]["byte_len"] > 11
+
+    def merge(rows):
+        rows[3][1] += rows[4][1]
+        rows[3][3] += rows[4][3]
+        del rows[4]
+
+    def move_a_sample(rows):
+        rows[0][3] -= 1
+        rows[1][2] -= 1
+        rows[1][3] += 1
+
+    def start_late(rows):
+        rows[7][0] += 1
+        rows[7][1] -= 1
+
+    def claim_11_bytes(rows):
+        rows[8][1] = 11
+
+    # (the forgery, a cut that takes the forged rows verbatim, a cut that passes through them)
+    forgeries = [(merge, (ends[2], ends[4] - ends[2]), (ends[2] + 10, 50)), (move_a_sample, (0, ends[1]), (10, 50)),
+                 (start_late, (ends[6], ends[7] - ends[6]), (ends[6] + 5, 100)), (claim_11_bytes, (ends[6], ends[8] - ends[6]), (ends[7] + 2, 4))]
+    jobs = []
+    for edit, whole, through in forgeries:
+        y = forged(hip, honest, edit)
+        for s, l in (whole, through):
+            rc, lay = hip.splice_plan([(None, y, s, l)])
+            assert rc == OK and lay.edge_blocks == (0 if (s, l) == whole else 1), edit.__name__     # the layout rule has no objection
+            jobs += [(edit.__name__, y, s, l, CORRUPT), (edit.__name__, honest, s, l, OK)]
+    models = [SM.splice([(A, s, l)]).data for _, _, s, l, _ in jobs]
+    for crc in (1, 0):
+        dec = hip.Decoder(*CC.CAP, enable_crc_check=crc)
+        try:
+            buf, outs, at = buffers([len(m) + 40 for m in models])
+            got = dec.splice_resident([[(src, x, s, l)] for _, x, s, l, _ in jobs], outs=outs)
+            assert [rc for rc, _ in got] == [j[4] for j in jobs], crc
+            check_buffer(buf, at, [m if j[4] == OK else None for j, m in zip(jobs, models)])
+        finally:
+            dec.close()
+
+
+def test_the_first_failure_in_output_order_decides(hip):
+    HEADER_FORMAT = 10
+    A, B, Cc = SM.sources()["stereo16ms"]
+    N, offs = A.num_samples, A.offsets
+    assert A.blocks[0].type == A.blocks[10].type == SS.COMPRESS and len(A.blocks) == 11
+
+    def type3(data, k):
+        """block k with block type 3 and its CRC made right: the judge's INVALID_HEADER_FORMAT, not a corruption"""
+        off, end = offs[k], (offs[k + 1] if k + 1 < len(offs) else len(data))
+        d = bytearray(data)
+        d[off + 10] |= 0xC0
+        d[off + 6:off + 8] = SS.crc16(d[off + 8:end]).to_bytes(2, "big")
+        return bytes(d)
+
+    streams = {"A": A.data, "B": B.data, "C": Cc.data,
+               "edge_then_verbatim": count_flipped(type3(A.data, 0), offs[4]), "verbatim_then_edge": count_flipped(type3(A.data, 10), offs[4]),
+               "C_bad": count_flipped(Cc.data, Cc.offsets[2])}
+    res = Resident(hip, streams)
+    stale = {"edge_then_verbatim": "A", "verbatim_then_edge": "A", "C_bad": "C"}         # the indexes of the bytes before the damage
+
+    def seg(name, s, l):
+        return (res.at[name][0], res.at[stale.get(name, name)][1], s, l)
+
+    two = [seg("A", 0, N), seg("B", 0, B.num_samples)]
+    jobs = [([seg("edge_then_verbatim", 10, N - 10)], HEADER_FORMAT, None),             # block 0 is an edge: the judge's code
+            ([seg("edge_then_verbatim", 0, N)], CORRUPT, None),                         # copied whole, a type of 3 is the decoder's to find
+            ([seg("verbatim_then_edge", 0, N - 10)], CORRUPT, None),                    # block 4 comes before the edge block 10
+            ([seg("verbatim_then_edge", ends_of(A)[4], N - 10 - ends_of(A)[4])], HEADER_FORMAT, None),
+            (two + [seg("C_bad", 0, Cc.num_samples)], CORRUPT, None),
+            (two, OK, SM.splice([(A, 0, N), (B, 0, B.num_samples)]).data),
+            (two + [seg("C", 0, Cc.num_samples)], OK, SM.splice([(A, 0, N), (B, 0, B.num_samples), (Cc, 0, Cc.num_samples)]).data)]
+    for crc in (1, 0):
+        dec = hip.Decoder(*CC.CAP, enable_crc_check=crc)
+        try:
+            buf, outs, at = buffers([len(A.data) + len(B.data) + len(Cc.data) + 4096] * len(jobs))      # room for the RAW edges
+            got = dec.splice_resident([j[0] for j in jobs], outs=outs)
+            assert [rc for rc, _ in got] == [j[1] for j in jobs], crc
+            check_buffer(buf, at, [j[2] for j in jobs])
+        finally:
+            dec.close()
+
+
+def ends_of(case):
+    return np.cumsum([b.n for b in case.blocks]).tolist()
+
+
+def test_forty_items_every_third_one_failing(hip):
+    """one format, one pass, about 300 entries of the check kernel: an item's failure is its own"""
+    A = SM.sources()["mono16"][0]
+    N, ends = A.num_samples, ends_of(A)
+    damaged = {"bad%d" % k: count_flipped(A.data, A.offsets[k]) for k in range(len(A.blocks))}
+    res = Resident(hip, dict(damaged, A=A.data))
+    honest = res.at["A"][1]
+    cuts = [(0, N), (3, N - 5), (10, 50), (ends[1], ends[6] - ends[1]), (ends[1] + 1, ends[6] - ends[1] - 2), (299, 1), (ends[5] + 3, 100)]
+    items, models, want = [], [], []
+    for i in range(40):
+        if i % 3 == 0:
+            k = (5 * (i // 3) + 1) % len(A.blocks)                    # the failing block's ordinal: 1, 6, 0, 5, 10, 4, ...
+            items.append([(res.at["bad%d" % k][0], honest, 3, N - 5)])
+            models.append(None)
+            want.append(CORRUPT)
+        else:
+            s, l = cuts[i % len(cuts)]
+            items.append([(res.at["A"][0], honest, s, l)])
+            models.append(SM.splice([(A, s, l)]).data)
+            want.append(OK)
+    for crc in (1, 0):
+        dec = hip.Decoder(*CC.CAP, enable_crc_check=crc)
+        try:
+            buf, outs, at = buffers([len(SM.splice([(A, 3, N - 5)]).data) + 64] * len(items))           # what a failed item would take
+            got = dec.splice_resident(items, outs=outs)
+            assert dec.last_timing()[5] == 1
+            assert [rc for rc, _ in got] == want, crc
+            for (rc, out), m in zip(got, models):
+                assert m is None or out.cpu().numpy().tobytes() == m
+            check_buffer(buf, at, models)
         finally:
             dec.close()

@@ -56,6 +56,27 @@ def test_struct_sizes_and_symbols(L):
         assert hasattr(L, name), name
 
 
+def test_the_check_entry_matches_the_headers_struct():
+    """sla_hip_splice_check as include/sla_hip.h declares it: the fields in its order, pointers and uint64_t 8 bytes,
+    uint32_t 4, no padding -- 40 bytes -- and sla_amd.SpliceCheck field for field at the same offsets"""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "sla_hip.h")) as f:
+        text = f.read()
+    body = re.search(r"typedef struct sla_hip_splice_check \{(.*?)\} sla_hip_splice_check;", text, re.S).group(1)
+    fields = re.findall(r"^\s*(const uint8_t\*|uint64_t|uint32_t)\s+(\w+);", body, re.M)
+    assert [name for _, name in fields] == ["src", "plane_off", "byte_len", "num_samples", "verdict", "ordinal", "edge", "keep"]
+    pos = 0
+    for typ, name in fields:
+        size = 4 if typ == "uint32_t" else 8
+        assert pos % size == 0
+        field = getattr(sla_amd.SpliceCheck, name)
+        assert (field.offset, field.size) == (pos, size), name
+        pos += size
+    assert pos == C.sizeof(sla_amd.SpliceCheck) == 40 and len(sla_amd.SpliceCheck._fields_) == len(fields)
+    assert int(re.search(r"#define SLA_HIP_SPLICE_NO_EDGE (0x[0-9A-Fa-f]+)u", text).group(1), 16) == sla_amd.SPLICE_NO_EDGE == SM.NO_EDGE
+
+
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_plan_equals_the_model(L, case):
     _, segs = case
